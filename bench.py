@@ -4,6 +4,11 @@
     python bench.py --gpus 1 --steps 8 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --full          # + roofline, per-kernel table, CPU baseline, protocols, sweeps, exchange report
+    python bench.py --gpus 1 --dump-outputs DIR
+
+A plain run sets up, warms up, times the --steps steps and prints one JSON line (`value`, `ms_per_step`, ...); everything
+below except `metric` is measured with --full only.  --dump-outputs writes the last timed step's outputs (dump_outputs).
 
 metric   : train samples/sec (whole job) of the neighbor-fusion fine-tune -- frozen RoBERTa-base + CLIP ViT-B/16
            over every neighbor, OPT-1.3B with 4 gated cross-attention layers (flamingo), 16 neighbors x 4 tokens,
@@ -336,6 +341,31 @@ def pmc_traffic(B, lm_cfg, cfg, dtype):
     return None, None
 
 
+DUMP_SAMPLE = 1 << 22          # elements per sampled output: 16 MB of float32 each
+
+
+def _seeded_sample(x, seed):
+    """x flattened when it has at most DUMP_SAMPLE elements, else DUMP_SAMPLE of them at sorted indices drawn from a fixed seed"""
+    x = x.reshape(-1)
+    if x.numel() <= DUMP_SAMPLE:
+        return x
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, x.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+    return x[idx.to(x.device)]
+
+
+def dump_outputs(out_dir, loss, meter, logits, engine):
+    """What a caller of the timed step receives from its last run, as float32 .npy files (32 MB in all): the
+    differentiated loss, the summary cross-entropy of the running meter, the summary logits and the trainable parameters after the
+    optimizer step (the latter two as fixed seeded samples)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1), "summary_cross_entropy": torch.as_tensor(meter).reshape(1),
+              "logits_sample": _seeded_sample(logits, 1), "trainable_params_sample": _seeded_sample(engine.flat_param, 2)}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -357,6 +387,12 @@ def main():
     ap.add_argument("--no-protocol", action="store_true", help="skip `at_reference_protocol` (the reference's 4 x 4 and 2 x 16 batch protocols "
                     "through the trainer's train_loop, fused and literal)")
     ap.add_argument("--ref-batch", type=int, default=4, help="also report the step at the reference's default per-device batch (Arguments default 4, run_generation.py:124-126); 0 = skip")
+    ap.add_argument("--full", action="store_true", help="also run every diagnostic beside the headline figure: kernel timing (roofline, "
+                    "per-entry-point table), the CPU baseline, the reference's batch protocols and evaluate_loop, the reference batch, the batch "
+                    "sweep and the `exchange` report (each still subject to its own --no-* switch).  Off: set up, warm up, time the steps, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "(loss, summary cross-entropy, a fixed seeded sample of the summary logits and of the trainable parameters after the "
+                    "optimizer step) as DIR/<name>.npy in float32 (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -445,6 +481,7 @@ def main():
 
     n_steps_run = [0]
     last_meter = [0.0]
+    last_logits = [None]                              # kept only for --dump-outputs
 
     # the trainer's step (reference run_generation.py:466-485; mmgl_amd train_loop): besides the token loss that is differentiated,
     # the logits of the summary positions and their cross-entropy for the running meter.  The meter value stays a device scalar, as in
@@ -457,6 +494,8 @@ def main():
         out = model(**batch, logits_slice=summary)
         lg = out.logits.detach()
         last_meter[0] = _summary_cross_entropy(lg, batch["labels"][..., lin + 1:], 1)
+        if args.dump_outputs:
+            last_logits[0] = lg
         out.loss.backward()
         engine.finish_backward()
         engine.step()
@@ -466,7 +505,7 @@ def main():
 
     for _ in range(args.warmup):
         loss = step()
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     _lib.KernelTimer.reset()
     _lib.KernelTimer.enabled = timing
     _lib.KernelTimer.only = {roof_name}               # timed region: HIP events around the roofline kernel only
@@ -482,6 +521,9 @@ def main():
     dt = time.perf_counter() - t0
     _lib.KernelTimer.enabled = False
     roof = _lib.KernelTimer.summary().get(roof_name) if timing else None
+    if args.dump_outputs and rank == 0:                 # before any further step (--full) moves the parameters on
+        dump_outputs(args.dump_outputs, loss, last_meter[0], last_logits[0], engine)
+    last_logits[0] = None
     table_steps = 0
     if timing:                                        # per-entry-point table: two more steps with events around EVERY call (the
         _lib.KernelTimer.reset()                      # ~1700 event pairs per step cost 1-2 % of throughput, so not in `value`)
@@ -556,7 +598,7 @@ def main():
 
     protocol = None
     # (single-GPU diagnostics: the N > 1 lines of the scaling run carry `value`, `exchange` and the sweep only)
-    if not args.no_protocol and world == 1:
+    if args.full and not args.no_protocol and world == 1:
         protocol = {"through": "mmgl_amd.language_modelling.run_generation.train_loop (host micro-batches in pinned memory, H2D inside)"}
         for per_device, accum in ((4, 4), (2, 16)):
             # warm-up = one pass over the SAME micro-batches (the packed encoder buffers have data-dependent sizes: the first time a
@@ -597,15 +639,15 @@ def main():
                 "value": round(world * evaluate_loop.samples_per_sec, 3), "unit": "samples/s"}
 
     eval_line = None
-    if not args.no_protocol and world == 1 and cfg["kind"] == "flamingo":
+    if args.full and not args.no_protocol and world == 1 and cfg["kind"] == "flamingo":
         eval_line = {"through": "mmgl_amd.language_modelling.run_generation.evaluate_loop (incl. decode + BLEU / CIDEr scoring on the host)",
                      "grouped": at_eval(2, 64, True), "literal": at_eval(2, 32, False)}
 
     ref_line = None
-    if args.ref_batch and args.ref_batch < args.batch:
+    if args.full and args.ref_batch and args.ref_batch < args.batch:
         ref_line = at_batch(args.ref_batch, 4321, 3, 10)
     sweep = None
-    if not args.no_batch_sweep:
+    if args.full and not args.no_batch_sweep:
         sweep = {}
         for bsz in (4, 16, 32, 64):
             if bsz < args.batch:
@@ -614,7 +656,7 @@ def main():
 
     # ---- gradient-exchange report (outside the timed region; every rank runs the same collectives)
     exchange = None
-    if comm:
+    if args.full and comm:
         ones = torch.ones(1, device=device)
         dist.all_reduce(ones)                                         # = number of ranks RCCL actually connected
         bytes_per_step = engine.exchange_bytes / max(1, n_steps_run[0])
@@ -736,7 +778,7 @@ def main():
             line["batch_sweep"] = {"unit": "samples/s (whole job) by per-GPU batch", **sweep}
         if exchange is not None:
             line["exchange"] = exchange
-        if world == 1 and not args.no_cpu_baseline and cfg["kind"] == "flamingo":
+        if args.full and world == 1 and not args.no_cpu_baseline and cfg["kind"] == "flamingo":
             line["cpu_baseline"] = cpu_baseline(model, cfg, lm_cfg, batch, args.cpu_samples, all_threads_too=args.cpu_all_threads)
     else:
         line = None

@@ -24,6 +24,8 @@ import torch
 
 REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+from helpers import save_golden  # noqa: E402  (tests/helpers.py: fixtures above 1 MiB are split into continuation files)
 
 
 def _load(name, path):
@@ -41,9 +43,8 @@ def save(fname, meta, **groups):
             if isinstance(v, torch.Tensor):
                 v = v.detach().cpu().numpy()
             flat[f"{g}/{k}"] = np.asarray(v)
-    path = os.path.join(HERE, fname)
-    np.savez_compressed(path, **flat)
-    print(f"wrote {fname}: {os.path.getsize(path)/1024:.1f} KiB, {len(flat)} arrays")
+    paths = save_golden(os.path.join(HERE, fname), flat)
+    print(f"wrote {fname}: {sum(os.path.getsize(p) for p in paths)/1024:.1f} KiB in {len(paths)} file(s), {len(flat)} arrays")
 
 
 # --------------------------------------------------------------------------- tiny HF configs

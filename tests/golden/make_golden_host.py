@@ -13,6 +13,8 @@ REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
+from helpers import save_golden  # noqa: E402  (tests/helpers.py: fixtures above 1 MiB are split into continuation files)
 
 
 def _load(name, path):
@@ -118,9 +120,9 @@ def golden_data_with_images(ref, df, ids, tok):
         finally:
             os.chdir(cwd)
     assert n_img > 20, n_img
-    np.savez_compressed(os.path.join(HERE, "g6_data_images.npz"), **flat)
+    paths = save_golden(os.path.join(HERE, "g6_data_images.npz"), flat)
     print(f"wrote g6_data_images.npz: {len(flat)} arrays, {n_img} non-blank image slots, {sum(v == 'corrupt' for v in written.values())} corrupt "
-          f"files of {len(written)}, {os.path.getsize(os.path.join(HERE, 'g6_data_images.npz'))/1024:.1f} KiB")
+          f"files of {len(written)}, {sum(os.path.getsize(p) for p in paths)/1024:.1f} KiB in {len(paths)} file(s)")
 
 
 def golden_self_attention():

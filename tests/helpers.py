@@ -6,14 +6,46 @@ import numpy as np
 import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+MAX_FIXTURE_BYTES = 1 << 20    # every committed file stays below 1 MiB: a larger fixture is <stem>.npz + <stem>.part1.npz + ...
+
+
+def load_golden(name):
+    """The arrays of the fixture tests/golden/<name> (<stem>.npz) and of its continuation files <stem>.part1.npz, .part2.npz, ..."""
+    out, k, path = {}, 0, os.path.join(GOLDEN, name)
+    while os.path.exists(path):
+        with np.load(path, allow_pickle=False) as z:
+            out.update((n, z[n]) for n in z.files)
+        k += 1
+        path = os.path.join(GOLDEN, f"{name[:-4]}.part{k}.npz")
+    if not out:
+        raise FileNotFoundError(os.path.join(GOLDEN, name))
+    return out
+
+
+def save_golden(path, flat):
+    """np.savez_compressed of `flat` as <stem>.npz plus as many continuation files as keep every file below MAX_FIXTURE_BYTES
+    (consecutive runs of keys, in order); returns the paths written"""
+    import glob
+    stem = path[:-4]
+    for n in range(1, len(flat) + 1):
+        for old in glob.glob(stem + ".part*.npz"):
+            os.remove(old)
+        keys = list(flat)
+        chunks = [keys[i * len(keys) // n:(i + 1) * len(keys) // n] for i in range(n)]
+        paths = [path] + [f"{stem}.part{k}.npz" for k in range(1, n)]
+        for p, ks in zip(paths, chunks):
+            np.savez_compressed(p, **{key: flat[key] for key in ks})
+        if all(os.path.getsize(p) < MAX_FIXTURE_BYTES for p in paths):
+            return paths
+    raise ValueError(f"{path}: a single array is larger than {MAX_FIXTURE_BYTES} bytes compressed")
 
 
 class Fixture:
     def __init__(self, name):
-        z = np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+        z = load_golden(name)
         self.meta = json.loads(str(z["meta"]))
         self.groups = {}
-        for k in z.files:
+        for k in z:
             if k == "meta":
                 continue
             g, n = k.split("/", 1)
@@ -49,8 +81,8 @@ def elementwise_err(a: torch.Tensor, b: torch.Tensor, floor_frac: float = 1e-3, 
     return ((a - b).abs() / (b.abs() + floor)).max().item()
 
 
-def assert_close(a, b, tol, what=""):
-    e = rel_err(a, b)
+def assert_close(a, b, tol, what="", floor=1e-6):
+    e = rel_err(a, b, floor)
     assert e <= tol, f"{what}: rel err {e:.3e} > {tol:.1e}"
     return e
 

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN
+from helpers import GOLDEN, load_golden
 
 
 def data_args(**kw):
@@ -32,14 +32,14 @@ DATA_CASES = {
 def test_g6_dataset_items_bit_exact(case):
     from mmgl_amd.wikiweb2m import WikiWeb2M
     from mmgl_amd.wikiweb2m.synthetic import synthetic_id_list, synthetic_pages, synthetic_tokenizer
-    z = np.load(os.path.join(GOLDEN, "g6_data.npz"))
+    z = load_golden("g6_data.npz")
     df = synthetic_pages(4, seed=3)
     ids = synthetic_id_list(df)
     ds = WikiWeb2M(data_args(**DATA_CASES[case]), df, ids, synthetic_tokenizer(), None)
     assert len(ds) == len(ids)
     for i in range(len(ids)):
         item = ds[i]
-        want = {k.split("/", 2)[2]: z[k] for k in z.files if k.startswith(f"{case}/{i}/")}
+        want = {k.split("/", 2)[2]: z[k] for k in z if k.startswith(f"{case}/{i}/")}
         assert set(item) == set(want), (case, i, set(item) ^ set(want))
         for k, v in want.items():
             got = item[k].numpy()
@@ -67,7 +67,7 @@ def test_g6_dataset_items_with_image_neighbors_bit_exact(case, tmp_path):
     from mmgl_amd.wikiweb2m import WikiWeb2M
     from mmgl_amd.wikiweb2m.synthetic import (synthetic_id_list, synthetic_images, synthetic_pages, synthetic_pixel_values,
                                              synthetic_tokenizer)
-    z = np.load(os.path.join(GOLDEN, "g6_data_images.npz"))
+    z = load_golden("g6_data_images.npz")
     df = synthetic_pages(4, seed=3)
     ids = synthetic_id_list(df)
     written = synthetic_images(df, str(tmp_path / "images"), seed=11)
@@ -77,7 +77,7 @@ def test_g6_dataset_items_with_image_neighbors_bit_exact(case, tmp_path):
     n_img = 0
     for i in range(len(ids)):
         item = ds[i]
-        want = {k.split("/", 2)[2]: z[k] for k in z.files if k.startswith(f"{case}/{i}/")}
+        want = {k.split("/", 2)[2]: z[k] for k in z if k.startswith(f"{case}/{i}/")}
         assert set(item) == set(want), (case, i, set(item) ^ set(want))
         for k, v in want.items():
             got = item[k].numpy()

@@ -68,6 +68,17 @@ def _layer_cfg(meta):
                            num_hidden_layers=1, word_embed_proj_dim=meta["d"], do_layer_norm_before=meta["pre_ln"])
 
 
+def assert_grad_close(grads, golden, k, tol, what):
+    """d k_proj.bias is analytically zero (softmax ignores a per-row score shift): both sides are fp32 round-off, whose bits depend on
+    the host's thread count and vector width.  It must be zero to `tol` of the size the same attention's d q_proj.bias has, and its
+    error is measured on that scale; every other gradient against its own magnitude."""
+    floor = 1e-6
+    if k.endswith("k_proj.bias"):
+        floor = golden[k[:-len("k_proj.bias")] + "q_proj.bias"].abs().max().item()
+        assert grads[k].abs().max().item() <= tol * floor, f"{what}: not zero to {tol:.1e} of d q_proj.bias"
+    assert_close(grads[k], golden[k], tol, what, floor=floor)
+
+
 def test_g5_layer_fwd_bwd():
     for name in ("g5_layer_preln.npz", "g5_layer_postln.npz"):
         fx = Fixture(name)
@@ -82,7 +93,7 @@ def test_g5_layer_fwd_bwd():
         assert_close(hidden.grad, fx.grad["hidden"], TOL, "d hidden")
         assert_close(ne.grad, fx.grad["neighbor_embeds"], TOL, "d ne")
         for k in p:
-            assert_close(p[k].grad, fx.grad[k], TOL, f"{name} d {k}")
+            assert_grad_close({n: t.grad for n, t in p.items()}, fx.grad, k, TOL, f"{name} d {k}")
 
 
 def _lm_cfg(p, pre_ln, wise, heads=4):
@@ -124,7 +135,7 @@ def test_g1_wrapper_logits_loss_grads():
         assert_close(loss, fx.out["loss"], TOL, f"{name} loss")
         loss.backward()
         for k in fx.grad:
-            assert_close(p[k].grad, fx.grad[k], 1e-4, f"{name} d {k}")
+            assert_grad_close({n: p[n].grad for n in fx.grad}, fx.grad, k, 1e-4, f"{name} d {k}")
 
 
 def test_gates_zero_is_identity():

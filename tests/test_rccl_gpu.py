@@ -19,7 +19,7 @@ def test_bench_two_ranks_over_rccl():
     RCCL and reports what it connected."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "opt-125m", "--batch", "4", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-kernel-timing"], capture_output=True, text=True, env=env, timeout=900)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-kernel-timing"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["exchange"]["rccl_ranks"] == 2
@@ -66,7 +66,7 @@ def test_bench_one_rank_over_rccl_reports_the_exchange():
     (allreduce_ms_alone, step_ms_without_exchange) in the line."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-exchange", "--config", "opt-125m", "--batch", "4",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-timing", "--ref-batch", "0"], capture_output=True,
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-kernel-timing", "--ref-batch", "0"], capture_output=True,
                        text=True, env=env, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -86,20 +86,22 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     batches, the hook-launched exchange and the max-over-ranks timing of the scaling run, minus the xGMI wire."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MMGL_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "opt-125m", "--batch", "4", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-kernel-timing", "--ref-batch", "0"], capture_output=True, text=True, env=env,
-                       timeout=1200)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-kernel-timing", "--ref-batch", "0"], capture_output=True, text=True,
+                       env=env, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["parallelism"] == "dp2"
     assert line["exchange"]["exchange_bytes_per_step_per_gpu"] > 0
 
 
-def test_bench_eight_ranks_launched_as_the_driver_does_gloo():
-    """The N = 8 line of the scaling run, on the ONE GPU a test box has: the driver's own command line (`python -m
-    torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...`) with
-    MMGL_DIST_BACKEND=gloo, all eight ranks on device 0 -- eight different seeded batches, eight engines cutting the same >= 4
-    buckets (layout check at construction), hook-launched all-reduces in index order, barrier + max-over-ranks timing, ONE JSON line
-    from rank 0 as the LAST line of stdout (reference run_generation.py:265-266, 283, 317-319)."""
+def test_bench_two_ranks_launched_as_the_driver_does_gloo():
+    """The scaling run's launch on the ONE GPU a test box has: the driver's own command line (`python -m torch.distributed.run
+    --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`) with MMGL_DIST_BACKEND=gloo and
+    N = 2 ranks sharing device 0 (more ranks would put more processes on one GPU than a shared box admits) -- N different seeded
+    batches, N engines cutting the same >= 4 buckets (layout check at construction), hook-launched all-reduces in index order,
+    barrier + max-over-ranks timing, ONE JSON line from rank 0 as the LAST line of stdout (reference run_generation.py:265-266, 283,
+    317-319)."""
+    n = 2
     import socket
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -107,9 +109,9 @@ def test_bench_eight_ranks_launched_as_the_driver_does_gloo():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MMGL_DIST_BACKEND="gloo", OMP_NUM_THREADS="4")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port",
-           str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "opt-125m", "--batch", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-kernel-timing", "--no-protocol", "--no-batch-sweep", "--ref-batch", "0"]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port",
+           str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--config", "opt-125m", "--batch", "2", "--steps", "2", "--warmup", "1",
+           "--full", "--no-cpu-baseline", "--no-kernel-timing", "--no-protocol", "--no-batch-sweep", "--ref-batch", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1800)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -117,11 +119,11 @@ def test_bench_eight_ranks_launched_as_the_driver_does_gloo():
     assert len(json_lines) == 1, f"exactly one JSON line, from rank 0 (got {len(json_lines)})"
     assert lines[-1] == json_lines[0], "the JSON line is the last line of stdout"
     line = json.loads(json_lines[0])
-    assert line["n_gpus"] == 8 and line["config"]["parallelism"] == "dp8" and line["config"]["global_batch"] == 16
-    assert line["scaling"] == "weak" and line["value"] > 0 and line["samples_per_sec_per_gpu"] == pytest.approx(line["value"] / 8, rel=1e-3)
+    assert line["n_gpus"] == n and line["config"]["parallelism"] == f"dp{n}" and line["config"]["global_batch"] == 2 * n
+    assert line["scaling"] == "weak" and line["value"] > 0 and line["samples_per_sec_per_gpu"] == pytest.approx(line["value"] / n, rel=1e-3)
     ex = line["exchange"]
-    assert ex["rccl_ranks"] == 8 and ex["buckets"] >= 4 and ex["exchange_bytes_per_step_per_gpu"] > 0
-    assert ex["wire_bytes_per_step_per_gpu"] == int(2 * 7 / 8 * ex["exchange_bytes_per_step_per_gpu"])
+    assert ex["rccl_ranks"] == n and ex["buckets"] >= 4 and ex["exchange_bytes_per_step_per_gpu"] > 0
+    assert ex["wire_bytes_per_step_per_gpu"] == int(2 * (n - 1) / n * ex["exchange_bytes_per_step_per_gpu"])
     assert ex["first_bucket_fraction_of_gradient"] <= 0.25
 
 

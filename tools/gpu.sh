@@ -19,7 +19,7 @@ for task in "$@"; do
     tests)  timeout 2400 python -m pytest tests -m gpu -x -q ${a:+-k "$a"} > $O/tests.log 2>&1; echo "[tests] rc $? $(tail -1 $O/tests.log)";;
     file)   n=$(basename $a .py); timeout 1800 python -m pytest $a -m gpu -x -q ${b:+-k "$b"} > $O/tests_$n.log 2>&1; echo "[file $n] rc $? $(tail -1 $O/tests_$n.log)";;
     smoke)  timeout 600 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "[smoke] rc $? $(tail -1 $O/smoke.log)";;
-    bench)  c=${a:-opt-1.3b}; timeout 1500 python bench.py --config $c ${b//,/ } > $O/bench_$c.log 2>&1; rc=$?
+    bench)  c=${a:-opt-1.3b}; timeout 1500 python bench.py --full --config $c ${b//,/ } > $O/bench_$c.log 2>&1; rc=$?
             grep '^{"metric"' $O/bench_$c.log | tail -1 > $O/bench_$c.json
             python - $O/bench_$c.json $rc <<'PY'
 import json, sys

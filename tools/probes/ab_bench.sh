@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of the default bench line between the regular library and variants/lib_<name>.so:  tools/probes/ab_bench.sh <name> [bench args]
 v=$1; shift
-args="--no-cpu-baseline --no-protocol --no-batch-sweep --ref-batch 0 --steps 12 --warmup 3 $*"
+args="--full --no-cpu-baseline --no-protocol --no-batch-sweep --ref-batch 0 --steps 12 --warmup 3 $*"
 pick() { python -c "
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{\"metric\"')][-1])

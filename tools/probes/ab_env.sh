@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of the default bench line between two environment settings:  tools/probes/ab_env.sh VAR=a VAR=b [bench args]
 A=$1; B=$2; shift 2
-args="--no-cpu-baseline --no-protocol --no-batch-sweep --ref-batch 0 --steps 12 --warmup 3 $*"
+args="--full --no-cpu-baseline --no-protocol --no-batch-sweep --ref-batch 0 --steps 12 --warmup 3 $*"
 pick() { python -c "
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{\"metric\"')][-1])
