@@ -185,19 +185,10 @@ int mmgl_gated_residual_bwd(const void* dy, const void* x, const float* gate, vo
  */
 int mmgl_linear_fwd(const void* x, const void* W, const void* bias, void* y,
                     int M, int N, int K, int act, float out_scale, int dtype, void* stream);
-/* dx[M,K] = dyp[M,N] @ W[N,K]   where dyp = dy * out_scale * act'(y)   (y = forward OUTPUT; NULL if act none).
- * workspace (>= mmgl_linear_dgrad_workspace bytes) holds W^T and, with an activation, dyp. N must be a multiple of 8. */
-size_t mmgl_linear_dgrad_workspace(int M, int N, int K, int act, int dtype);
-int mmgl_linear_dgrad(const void* dy, const void* y, const void* W, void* dx, void* workspace, size_t workspace_bytes,
-                      int M, int N, int K, int act, float out_scale, int dtype, void* stream);
-/* dW[N,K] (+)= dyp^T @ x ; dbias[N] (+)= colsum(dyp) ; both in the activation dtype; accumulate!=0 adds to
- * the existing contents (gradient accumulation across micro-batches). dbias may be NULL.
- * workspace (>= mmgl_linear_wgrad_workspace bytes) holds dyp^T and x^T. */
-size_t mmgl_linear_wgrad_workspace(int M, int N, int K, int dtype);
-int mmgl_linear_wgrad(const void* dy, const void* y, const void* x, void* dW, void* dbias, void* workspace,
-                      size_t workspace_bytes, int M, int N, int K, int act, float out_scale, int accumulate,
-                      int dtype, void* stream);
-/* Whole backward of one linear in a single call: dyp is formed once, then dx / dW / dbias (each may be NULL).
+/* Whole backward of one linear in a single call: dyp = dy * out_scale * act'(y) is formed once (y = forward OUTPUT; NULL if act
+ * none), then dx[M,K] = dyp @ W, dW[N,K] (+)= dyp^T @ x, dbias[N] (+)= colsum(dyp), each in the activation dtype and each
+ * optional (NULL); accumulate != 0 adds dW / dbias to the existing contents (gradient accumulation across micro-batches).
+ * N must be a multiple of 8; the fp32 path needs dW whenever dbias is requested.
  * mask_dx != 0: x is itself the output of a ReLU (fc2 after fc1+ReLU, modelling_cross_attention.py:352-355) and that ReLU's
  * backward is folded into this call: dx is zeroed where x <= 0 (in the dgrad GEMM's epilogue for the large-shape kernel), so
  * the producing linear can be differentiated with act = none on the already-masked gradient. */
@@ -205,8 +196,6 @@ size_t mmgl_linear_bwd_workspace(int M, int N, int K, int act, int dtype);
 int mmgl_linear_bwd(const void* dy, const void* y, const void* x, const void* W, void* dx, void* dW, void* dbias,
                     void* workspace, size_t workspace_bytes, int M, int N, int K, int act, float out_scale,
                     int accumulate, int mask_dx, int dtype, void* stream);
-/* out[C,ld] = in[R,C]^T, ld = R rounded up to a whole 16-byte chunk (zero padded) */
-int mmgl_transpose(const void* in, void* out, int R, int C, int dtype, void* stream);
 
 /* LoRA-fused linear:  y = x W^T + bias + scale * (x A^T) B^T        A [r,K], Bm [N,r]
  * (peft semantics, lora_dropout = 0; replaces peft's LoRA Linear injected at
@@ -288,8 +277,9 @@ int mmgl_adamw_step(void* param, float* master, const void* grad, float* exp_avg
  *   bias [N], residual [M,N], zmask [M,N] may be NULL; act: 0 none, 1 relu, 2 gelu (erf), 3 quick_gelu, 4 gelu (tanh).
  * bf16 shapes with K % 128 == 0, K >= 256, N % 16 == 0 and enough 256x256 tiles run on the persistent ping-pong kernel
  * (gemm8p.hip; mmgl_gemm_nt_fast returns 1), other bf16 shapes with K % 64 == 0, N % 8 == 0 on the 128x128 kernel (gemm_mid.hip;
- * returns 2): both take strided operands and apply the whole epilogue in the kernel.  Anything else (returns 0) is composed from
- * mmgl_linear_fwd + the elementwise kernels.
+ * returns 2): both take strided operands and apply the whole epilogue in the kernel.  Anything else (returns 0) runs on gemm.hip's
+ * dense 128x128 kernel followed by the elementwise kernels.  mmgl_linear_fwd and the LoRA linears (no K-split scratch: the
+ * persistent kernel from a full chip of tiles on) and mmgl_linear_bwd's dgrad follow the same plan (gemm.hip: nt_route).
  * ldx / ldw / ldy: row strides in elements (residual and zmask share ldy); the composed path needs dense operands.
  * K may exceed ldx by less than 128 when columns ldx.. of W are zero (a contraction length padded to the kernels' K step: the
  * lm_head dgrad over a 50272-entry vocabulary): the tail of row r of x then reads the head of row r + 1 (nothing is read past

@@ -11,7 +11,7 @@ import torch  # imported first on purpose: the .so must bind to the HIP runtime 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMGL_LIB_PATH") or os.path.join(_HERE, "libmmgl_hip.so")     # override: timing experiments with ablated builds
 
-ABI_VERSION = 104         # = mmgl_version() of the library this binding was written against (csrc/lib.hip)
+ABI_VERSION = 105         # = mmgl_version() of the library this binding was written against (csrc/lib.hip)
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 _ERR_INVALID, _ERR_UNSUPPORTED, _ERR_HIP = 1, 2, 3
@@ -47,13 +47,8 @@ SIGNATURES = {
     "mmgl_gated_residual_bwd_workspace": (Z, [Z]),
     "mmgl_gated_residual_bwd": (I, [P, P, P, P, P, P, Z, Z, F, U, I, P]),
     "mmgl_linear_fwd": (I, [P, P, P, P, I, I, I, I, F, I, P]),
-    "mmgl_linear_dgrad_workspace": (Z, [I, I, I, I, I]),
-    "mmgl_linear_dgrad": (I, [P, P, P, P, P, Z, I, I, I, I, F, I, P]),
-    "mmgl_linear_wgrad_workspace": (Z, [I, I, I, I]),
-    "mmgl_linear_wgrad": (I, [P, P, P, P, P, P, Z, I, I, I, I, F, I, I, P]),
     "mmgl_linear_bwd_workspace": (Z, [I, I, I, I, I]),
     "mmgl_linear_bwd": (I, [P, P, P, P, P, P, P, P, Z, I, I, I, I, F, I, I, I, P]),
-    "mmgl_transpose": (I, [P, P, I, I, I, P]),
     "mmgl_lora_linear_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, F, I, P]),
     "mmgl_lora_linear_bwd_workspace": (Z, [I, I, I, I, I]),
     "mmgl_lora_linear_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, Z, I, I, I, I, F, I, I, P]),

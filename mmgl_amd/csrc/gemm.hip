@@ -180,16 +180,11 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const T* __restrict__ X, c
 // transposed copy of the weight (the persistent kernel of gemm8p.hip), smaller ones on the transposition-free 128x128 kernel
 inline bool big_tile_shape(int M, int N, int K) { return K % 64 == 0 && (size_t)cdiv(M, 256) * cdiv(N, 256) >= 512; }
 
-// the persistent ping-pong kernel (gemm8p.hip) takes every bf16 shape it supports; the 256x256 / 128x128 kernels of this file are
-// what the remaining shapes run on (K not a multiple of 128, accumulating outputs, fp32, few tiles)
-inline constexpr int tune_gemm_8p() { return 1; }
 // few-tile shapes (>= 24 tiles: below that even 8 splits leave most of the chip idle and the 128x128 kernel's 4x finer tiles win)
 inline bool gemm8p_use_splits(int M, int N, int K) {
     return cdiv(M, 256) * cdiv(N, 256) >= 24 && gemm8p_splits(M, N, K) > 0;
 }
-inline constexpr int tune_gemm_8p_min_tiles() { return 160; }
 
-inline constexpr int tune_gemm_mid() { return 1; }       // 1: gemm_mid_kernel takes the few-tile bf16 shapes (round 3: 38.4 -> 32.7 us at 2560x2048x2048)
 // Row split of an output of one to three rounds of 256x256 tiles plus a short remainder (the reference's batch: [2560, 8192] = 320
 // tiles on 256 CUs, a second round at a quarter of the chip): rows [0, m1) = the whole rounds on the persistent kernel, the tail rows
 // on the few-tile kernel -- 102.6 -> 78.3 us at 2560x8192x2048 (tools/probes/gemm_msplit.py).  0 = no split.
@@ -205,7 +200,7 @@ inline int gemm8p_row_split(int M, int N, int K, int ldx, int ldw, int ldy) {
     const int m1 = rounds * G / tn * 256;
     return (m1 > 0 && m1 < M && gemm_mid_supported(M - m1, N, K, ldx, ldw, ldy)) ? m1 : 0;
 }
-// launch_gemm8p with that split applied (no K-split scratch: the callers below bring none or use it for other plans)
+// launch_gemm8p with that split applied (K-split scratch, if any, serves an output without a row split)
 inline int launch_gemm8p_rows(const bf16* X, int ldx, const bf16* W, int ldw, bf16* Y, int ldy, const bf16* bias, const bf16* resid, const bf16* zmask,
                               int M, int N, int K, int act, float scale, hipStream_t st, float* part = nullptr, size_t part_bytes = 0) {
     const int m1 = gemm8p_row_split(M, N, K, ldx, ldw, ldy);
@@ -275,34 +270,20 @@ __global__ __launch_bounds__(256) void relu_mask_kernel(const T* __restrict__ dy
     }
 }
 
-inline constexpr bool tune_gemm_glds() { return true; }
-
 template <typename T> inline int pad_k(int k) { return (k + GT<T>::VN - 1) / GT<T>::VN * GT<T>::VN; }
 
+// gemm_nt_kernel on dense operands, act none / relu.  The only kernel for a second operand pair (the fused LoRA linear) and for an
+// accumulating output; every other NT GEMM is planned by nt_route below and reaches this launch as its TILE128 route.
 template <typename T>
-int launch_gemm(const T* X, const T* W, T* Y, const T* bias, int M, int N, int K, int act, float scale, int accumulate,
-                const T* X2, const T* W2, int K2, hipStream_t st, const T* zmask = nullptr, bool* zmask_done = nullptr) {
+int launch_nt128(const T* X, const T* W, T* Y, const T* bias, int M, int N, int K, int act, float scale, int accumulate,
+                 const T* X2, const T* W2, int K2, hipStream_t st) {
     constexpr int VN = GT<T>::VN;
     MMGL_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: M,N,K must be positive (got %d,%d,%d)", M, N, K);
     if (K % VN || N % 4 || (X2 && K2 % VN))
         MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "gemm: K (%d) must be a multiple of %d and N (%d) of 4", K, VN, N);
-    if constexpr (sizeof(T) == 2) {
-        // persistent ping-pong kernel (gemm8p.hip) whenever the shape gives it enough 256x256 tiles
-        if (!X2 && !accumulate && tune_gemm_8p() && gemm8p_supported(M, N, K, K, K, N) && cdiv(M, 256) * cdiv(N, 256) >= tune_gemm_8p_min_tiles()) {
-            if (zmask_done) *zmask_done = zmask != nullptr;
-            return launch_gemm8p_rows((const bf16*)X, K, (const bf16*)W, K, (bf16*)Y, N, (const bf16*)bias, nullptr, (const bf16*)zmask, M, N, K, act, scale, st);
-        }
-    }
-    if constexpr (sizeof(T) == 2) {
-        // 128x128 tiles, two workgroups per CU (gemm_mid.hip): outputs of too few 256x256 tiles for the persistent kernel
-        if (!X2 && !accumulate && tune_gemm_mid() && gemm_mid_supported(M, N, K, K, K, N)) {
-            if (zmask_done) *zmask_done = zmask != nullptr;
-            return launch_gemm_mid((const bf16*)X, K, (const bf16*)W, K, (bf16*)Y, N, (const bf16*)bias, nullptr, (const bf16*)zmask, M, N, K, act, scale, st);
-        }
-    }
     const int tiles_m = cdiv(M, BM), tiles_n = cdiv(N, BN);
     const size_t lds = 4 * TILE_BYTES;
-    const bool glds = (K % GT<T>::BK == 0) && (!X2 || K2 % GT<T>::BK == 0) && tune_gemm_glds();
+    const bool glds = (K % GT<T>::BK == 0) && (!X2 || K2 % GT<T>::BK == 0);
     const void* kern;
     if (glds) kern = act == MMGL_ACT_RELU ? (const void*)gemm_nt_kernel<T, MMGL_ACT_RELU, true> : (const void*)gemm_nt_kernel<T, MMGL_ACT_NONE, true>;
     else kern = act == MMGL_ACT_RELU ? (const void*)gemm_nt_kernel<T, MMGL_ACT_RELU, false> : (const void*)gemm_nt_kernel<T, MMGL_ACT_NONE, false>;
@@ -689,7 +670,7 @@ int launch_gemm_tx(bool tb, const bf16* Aop, int lda, const bf16* Bop, int ldb, 
         if (rc) return rc;
         return launch_gemm_tx(tb, Aop + (size_t)K1 * lda, lda, Bop + (size_t)K1 * ldb, ldb, nullptr, Out, RA, RB, K - K1, scale, 1, st, p2);
     }
-    if (tb && !ymask && tune_gemm_8p()) {
+    if (tb && !ymask) {
         // both operands k-major and enough (tile, K split) work items: the ping-pong weight-gradient kernel (gemm8p_tt.hip)
         const int s8 = gemm8p_tt_splits(RA, RB, K);
         if (s8 == 1 || (s8 > 1 && part)) {
@@ -705,7 +686,7 @@ int launch_gemm_tx(bool tb, const bf16* Aop, int lda, const bf16* Bop, int ldb, 
     const int tiles_a = cdiv(RA, 128), tiles_b = cdiv(RB, 128);
     const size_t lds = 4 * TX_TILE_BYTES;
     // LDS-DMA staging needs whole tiles along every k-major dimension and no ReLU mask (the mask is applied once, upstream)
-    const bool glds = !ymask && K % 64 == 0 && RA % 128 == 0 && (!tb || RB % 128 == 0) && tune_gemm_glds();
+    const bool glds = !ymask && K % 64 == 0 && RA % 128 == 0 && (!tb || RB % 128 == 0);
     dim3 grid(tiles_a * tiles_b), block(256);
 #define TX_LAUNCH(TBV, MK, GL)                                                                                              \
     do {                                                                                                                    \
@@ -732,100 +713,69 @@ int launch_relu_mask(const T* dy, const T* y, T* out, size_t n, float scale, hip
     return MMGL_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The GEMM plan: the one place that picks the kernel of an NT GEMM  Y[M,N] = epilogue(X[M,K] . W[N,K]^T)  -- mmgl_gemm_nt,
+// mmgl_linear_fwd, the dgrads that run as NT GEMMs against W^T, the LoRA internals and the fp32 path.
+//   P8       the persistent 256x256 kernel (gemm8p.hip), row split applied: outputs of GEMM8P_MIN_TILES tiles or more, and for
+//            callers that bring K-split scratch (k_splits) also the few-tile / remainder-of-a-round shapes of gemm8p_use_splits
+//   MID      the 128x128 two-per-CU kernel (gemm_mid.hip): the remaining bf16 shapes it supports (round 3: 38.4 -> 32.7 us at
+//            2560x2048x2048 against TILE128)
+//   TILE128  launch_nt128 on dense operands; an activation beyond ReLU, the zmask and the residual run as separate passes after it
+// P8 and MID take strided operands and apply the whole epilogue in the kernel.
+enum class NtRoute { P8, MID, TILE128 };
+
+NtRoute nt_route(int M, int N, int K, int ldx, int ldw, int ldy, int dtype, bool k_splits) {
+    if (dtype != MMGL_BF16) return NtRoute::TILE128;
+    if (gemm8p_supported(M, N, K, ldx, ldw, ldy) &&
+        (cdiv(M, 256) * cdiv(N, 256) >= GEMM8P_MIN_TILES || (k_splits && gemm8p_use_splits(M, N, K))))
+        return NtRoute::P8;
+    return gemm_mid_supported(M, N, K, ldx, ldw, ldy) ? NtRoute::MID : NtRoute::TILE128;
+}
+
+template <typename T> constexpr int dtype_of = sizeof(T) == 2 ? MMGL_BF16 : MMGL_F32;
+
+// part / part_bytes: K-split scratch of the P8 route (NULL: nothing is split)
+template <typename T>
+int launch_nt(NtRoute route, const T* X, int ldx, const T* W, int ldw, T* Y, int ldy, const T* bias, const T* resid, const T* zmask,
+              int M, int N, int K, int act, float scale, float* part, size_t part_bytes, hipStream_t st) {
+    if constexpr (sizeof(T) == 2) {
+        if (route == NtRoute::P8)
+            return launch_gemm8p_rows(X, ldx, W, ldw, Y, ldy, bias, resid, zmask, M, N, K, act, scale, st, part, part_bytes);
+        if (route == NtRoute::MID) return launch_gemm_mid(X, ldx, W, ldw, Y, ldy, bias, resid, zmask, M, N, K, act, scale, st);
+    }
+    if (ldx != K || ldw != K || ldy != N)
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "gemm_nt: strided operands (ld %d %d %d) need the bf16 fast path (K %% 128 == 0, N %% 16 == 0, "
+                  ">= %d tiles of 256x256); got M=%d N=%d K=%d dtype=%d", ldx, ldw, ldy, GEMM8P_MIN_TILES, M, N, K, dtype_of<T>);
+    int rc = launch_nt128<T>(X, W, Y, bias, M, N, K, act <= MMGL_ACT_RELU ? act : MMGL_ACT_NONE, scale, 0, nullptr, nullptr, 0, st);
+    const size_t n = (size_t)M * N;
+    if (!rc && act > MMGL_ACT_RELU) rc = mmgl_activation_fwd(Y, Y, n, act, dtype_of<T>, st);
+    if (!rc && zmask) rc = launch_relu_mask<T>(Y, zmask, Y, n, 1.f, st);
+    if (!rc && resid) rc = mmgl_gated_residual_fwd(resid, Y, nullptr, Y, n, 0.f, 0, dtype_of<T>, st);
+    return rc;
+}
+
+// dense operands, no K splits; an accumulating output runs on the 128x128 kernel
+template <typename T>
+int gemm_dense(const T* X, const T* W, T* Y, const T* bias, int M, int N, int K, int act, float scale, int accumulate, hipStream_t st) {
+    if (accumulate) return launch_nt128<T>(X, W, Y, bias, M, N, K, act, scale, accumulate, nullptr, nullptr, 0, st);
+    return launch_nt<T>(nt_route(M, N, K, K, K, N, dtype_of<T>, false), X, K, W, K, Y, N, bias, nullptr, nullptr, M, N, K, act, scale,
+                        nullptr, 0, st);
+}
+
 // bf16 backward workspace: [dyp M*N (only with an activation)] [bias column-sum partials] [W^T K*N (big-tile dgrad)]
 inline size_t bf16_wt_offset(int M, int N, int act) {
     return (act ? align_up((size_t)M * N * 2, 256) : 0) + align_up((size_t)COLSUM_SPLITS * N * sizeof(float), 256);
 }
-// ... [fp32 split-K partials of the weight gradient (small outputs only)]
+// ... [fp32 split-K partials of the dgrad / weight gradient]
 inline size_t bf16_part_offset(int M, int N, int K, int act) { return bf16_wt_offset(M, N, act) + align_up((size_t)K * N * 2, 256); }
-
-template <typename T>
-int linear_dgrad(const T* dy, const T* y, const T* W, T* dx, char* ws, int M, int N, int K, int act, float scale, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) {     // bf16: no transposes; dyp = dy*scale*(y>0) is materialised ONCE (masking inside the
-        // GEMM would re-read y for every output tile column: 16x the L2 traffic at fc1's shape)
-        const bf16* a = (const bf16*)dy;
-        float sc = scale;
-        if (act == MMGL_ACT_RELU) {
-            int rc = launch_relu_mask<T>(dy, y, (T*)ws, (size_t)M * N, scale, st);
-            if (rc) return rc;
-            a = (const bf16*)ws;
-            sc = 1.f;
-        }
-        if (big_tile_shape(M, K, N)) {
-            T* Wt = (T*)(ws + bf16_wt_offset(M, N, act));
-            int rc = launch_transpose<T>(W, nullptr, Wt, nullptr, N, K, 1.f, 0, st);
-            if (rc) return rc;
-            return launch_gemm<T>((const T*)a, Wt, dx, nullptr, M, K, N, MMGL_ACT_NONE, sc, 0, nullptr, nullptr, 0, st);
-        }
-        return launch_gemm_tx(false, (const bf16*)W, K, a, N, nullptr, (bf16*)dx, K, M, N, sc, 0, st);
-    }
-    // fp32 (parity path): W^T [K,N] | dyp [M,N] (only with an activation) in ws
-    if (N % GT<T>::VN) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "linear_dgrad: out_features %d must be a multiple of %d", N, GT<T>::VN);
-    T* Wt = (T*)ws;
-    T* dyp = (T*)(ws + align_up((size_t)K * ((size_t)(N + 7) / 8 * 8) * sizeof(T), 256));
-    int rc = launch_transpose<T>(W, nullptr, Wt, nullptr, N, K, 1.f, 0, st);
-    if (rc) return rc;
-    const T* a = dy;
-    float s = scale;
-    if (act == MMGL_ACT_RELU) {
-        size_t n = (size_t)M * N;
-        int blocks = (int)((n / GT<T>::VN + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(relu_mask_kernel<T>, dim3(blocks), dim3(256), 0, st, dy, y, dyp, n, scale);
-        MMGL_CHECK_LAUNCH("relu_mask");
-        a = dyp;
-        s = 1.f;
-    }
-    return launch_gemm<T>(a, Wt, dx, nullptr, M, K, N, MMGL_ACT_NONE, s, 0, nullptr, nullptr, 0, st);   // N % 8 == 0 checked by caller
-}
-
-template <typename T>
-int linear_wgrad(const T* dy, const T* y, const T* x, T* dW, T* dbias, char* ws, int M, int N, int K, int act, float scale,
-                 int accumulate, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) {     // bf16: both operands k-major straight from memory; ws = [dyp] | bias partials
-        const bf16* a = (const bf16*)dy;
-        float sc = scale;
-        char* part = ws;
-        if (act == MMGL_ACT_RELU) {
-            int rc = launch_relu_mask<T>(dy, y, (T*)ws, (size_t)M * N, scale, st);
-            if (rc) return rc;
-            a = (const bf16*)ws;
-            sc = 1.f;
-            part = ws + align_up((size_t)M * N * sizeof(T), 256);
-        }
-        int rc = launch_gemm_tx(true, (const bf16*)x, K, a, N, nullptr, (bf16*)dW, K, N, M, sc, accumulate, st,
-                                (float*)(ws + bf16_part_offset(M, N, K, act)));
-        if (rc || !dbias) return rc;
-        return launch_colsum<T>((const T*)a, nullptr, dbias, (float*)part, M, N, sc, accumulate, st);
-    }
-    // fp32 (parity path): dyp^T [N,M] | x^T [K,M] in ws
-    T* dyT = (T*)ws;
-    T* xT = (T*)(ws + align_up((size_t)N * ((size_t)(M + 7) / 8 * 8) * sizeof(T), 256));
-    int rc = launch_transpose<T>(dy, act == MMGL_ACT_RELU ? y : nullptr, dyT, dbias, M, N, scale, accumulate, st);
-    if (rc) return rc;
-    rc = launch_transpose<T>(x, nullptr, xT, nullptr, M, K, 1.f, 0, st);
-    if (rc) return rc;
-    return launch_gemm<T>(dyT, xT, dW, nullptr, N, K, pad_k<T>(M), MMGL_ACT_NONE, 1.f, accumulate, nullptr, nullptr, 0, st);
-}
-
-size_t dgrad_ws(int M, int N, int K, int act, size_t esz) {
-    const size_t Np = (size_t)(N + 7) / 8 * 8;
-    if (esz == 2) return bf16_part_offset(M, N, K, act) + split_partial_bytes(K, N, M);
-    return align_up((size_t)K * Np * esz, 256) + (act ? align_up((size_t)M * N * esz, 256) : 0);
-}
-size_t wgrad_ws(int M, int N, int K, size_t esz) {
-    const size_t Mp = (size_t)(M + 7) / 8 * 8;
-    if (esz == 2) return bf16_part_offset(M, N, K, 1) + split_partial_bytes(K, N, M);
-    return align_up((size_t)N * Mp * esz, 256) + align_up((size_t)K * Mp * esz, 256);
-}
 
 template <typename T>
 int lora_fwd(const T* x, const T* W, const T* bias, const T* A, const T* Bm, T* y, T* xa, int M, int N, int K, int r,
              float scale, hipStream_t st) {
     // xa = scale * x A^T ; y = [x | xa] . [W | Bm]^T + bias  (the LoRA term rides in the same accumulators)
-    int rc = launch_gemm<T>(x, A, xa, nullptr, M, r, K, MMGL_ACT_NONE, scale, 0, nullptr, nullptr, 0, st);
+    int rc = gemm_dense<T>(x, A, xa, nullptr, M, r, K, MMGL_ACT_NONE, scale, 0, st);
     if (rc) return rc;
-    return launch_gemm<T>(x, W, y, bias, M, N, K, MMGL_ACT_NONE, 1.f, 0, xa, Bm, r, st);
+    return launch_nt128<T>(x, W, y, bias, M, N, K, MMGL_ACT_NONE, 1.f, 0, xa, Bm, r, st);
 }
 
 template <typename T>
@@ -845,16 +795,16 @@ int lora_bwd(const T* dy, const T* x, const T* xa, const T* W, const T* A, const
     if ((rc = launch_transpose<T>(A, nullptr, At, nullptr, r, K, 1.f, 0, st))) return rc;
     if ((rc = launch_transpose<T>(Bm, nullptr, Bt, nullptr, N, r, 1.f, 0, st))) return rc;
     // dyb = scale * dy Bm            [M,r]
-    if ((rc = launch_gemm<T>(dy, Bt, dyb, nullptr, M, r, N, MMGL_ACT_NONE, scale, 0, nullptr, nullptr, 0, st))) return rc;
+    if ((rc = gemm_dense<T>(dy, Bt, dyb, nullptr, M, r, N, MMGL_ACT_NONE, scale, 0, st))) return rc;
     // dx = dy W + dyb A              [M,K]
-    if ((rc = launch_gemm<T>(dy, Wt, dx, nullptr, M, K, N, MMGL_ACT_NONE, 1.f, 0, dyb, At, r, st))) return rc;
+    if ((rc = launch_nt128<T>(dy, Wt, dx, nullptr, M, K, N, MMGL_ACT_NONE, 1.f, 0, dyb, At, r, st))) return rc;
     // dA = dyb^T x  [r,K] ; dB = dy^T xa [N,r]   (xa already carries `scale`)
     if ((rc = launch_transpose<T>(dyb, nullptr, dybT, nullptr, M, r, 1.f, 0, st))) return rc;
     if ((rc = launch_transpose<T>(x, nullptr, xT, nullptr, M, K, 1.f, 0, st))) return rc;
-    if ((rc = launch_gemm<T>(dybT, xT, dA, nullptr, r, K, pad_k<T>(M), MMGL_ACT_NONE, 1.f, accumulate, nullptr, nullptr, 0, st))) return rc;
+    if ((rc = gemm_dense<T>(dybT, xT, dA, nullptr, r, K, pad_k<T>(M), MMGL_ACT_NONE, 1.f, accumulate, st))) return rc;
     if ((rc = launch_transpose<T>(dy, nullptr, dyT, nullptr, M, N, 1.f, 0, st))) return rc;
     if ((rc = launch_transpose<T>(xa, nullptr, xaT, nullptr, M, r, 1.f, 0, st))) return rc;
-    return launch_gemm<T>(dyT, xaT, dB, nullptr, N, r, pad_k<T>(M), MMGL_ACT_NONE, 1.f, accumulate, nullptr, nullptr, 0, st);
+    return gemm_dense<T>(dyT, xaT, dB, nullptr, N, r, pad_k<T>(M), MMGL_ACT_NONE, 1.f, accumulate, st);
 }
 
 size_t lora_ws(int M, int N, int K, int r, size_t esz) {
@@ -878,47 +828,19 @@ extern "C" int mmgl_linear_fwd(const void* x, const void* W, const void* bias, v
     MMGL_CHECK_ARG(act == MMGL_ACT_NONE || act == MMGL_ACT_RELU, "mmgl_linear_fwd: unknown activation %d", act);
     hipStream_t st = (hipStream_t)stream;
     DT_SWITCH("mmgl_linear_fwd",
-              launch_gemm<bf16>((const bf16*)x, (const bf16*)W, (bf16*)y, (const bf16*)bias, M, N, K, act, out_scale, 0, nullptr, nullptr, 0, st),
-              launch_gemm<float>((const float*)x, (const float*)W, (float*)y, (const float*)bias, M, N, K, act, out_scale, 0, nullptr, nullptr, 0, st));
-}
-
-extern "C" size_t mmgl_linear_dgrad_workspace(int M, int N, int K, int act, int dtype) {
-    return dgrad_ws(M, N, K, act, dtype == MMGL_BF16 ? 2 : 4);
-}
-extern "C" size_t mmgl_linear_wgrad_workspace(int M, int N, int K, int dtype) { return wgrad_ws(M, N, K, dtype == MMGL_BF16 ? 2 : 4); }
-
-extern "C" int mmgl_linear_dgrad(const void* dy, const void* y, const void* W, void* dx, void* workspace, size_t workspace_bytes,
-                                 int M, int N, int K, int act, float out_scale, int dtype, void* stream) {
-    MMGL_CHECK_ARG(dy && W && dx && workspace && (act == MMGL_ACT_NONE || y), "mmgl_linear_dgrad: null pointer");
-    MMGL_CHECK_ARG(workspace_bytes >= mmgl_linear_dgrad_workspace(M, N, K, act, dtype), "mmgl_linear_dgrad: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    DT_SWITCH("mmgl_linear_dgrad",
-              linear_dgrad<bf16>((const bf16*)dy, (const bf16*)y, (const bf16*)W, (bf16*)dx, ws, M, N, K, act, out_scale, st),
-              linear_dgrad<float>((const float*)dy, (const float*)y, (const float*)W, (float*)dx, ws, M, N, K, act, out_scale, st));
-}
-
-extern "C" int mmgl_linear_wgrad(const void* dy, const void* y, const void* x, void* dW, void* dbias, void* workspace,
-                                 size_t workspace_bytes, int M, int N, int K, int act, float out_scale, int accumulate,
-                                 int dtype, void* stream) {
-    MMGL_CHECK_ARG(dy && x && dW && workspace && (act == MMGL_ACT_NONE || y), "mmgl_linear_wgrad: null pointer");
-    MMGL_CHECK_ARG(workspace_bytes >= mmgl_linear_wgrad_workspace(M, N, K, dtype), "mmgl_linear_wgrad: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    DT_SWITCH("mmgl_linear_wgrad",
-              linear_wgrad<bf16>((const bf16*)dy, (const bf16*)y, (const bf16*)x, (bf16*)dW, (bf16*)dbias, ws, M, N, K, act, out_scale, accumulate, st),
-              linear_wgrad<float>((const float*)dy, (const float*)y, (const float*)x, (float*)dW, (float*)dbias, ws, M, N, K, act, out_scale, accumulate, st));
+              gemm_dense<bf16>((const bf16*)x, (const bf16*)W, (bf16*)y, (const bf16*)bias, M, N, K, act, out_scale, 0, st),
+              gemm_dense<float>((const float*)x, (const float*)W, (float*)y, (const float*)bias, M, N, K, act, out_scale, 0, st));
 }
 
 // One call for the whole backward of a linear: dyp once, then dx / dW / dbias as requested (any of them may be NULL).
-extern "C" int mmgl_gemm_nt_fast(int M, int N, int K, int ldx, int ldw, int ldy, int dtype);
-
 template <typename T>
 int linear_bwd(const T* dy, const T* y, const T* x, const T* W, T* dx, T* dW, T* dbias, char* ws, int M, int N, int K, int act,
                float scale, int accumulate, hipStream_t st, bool mask_dx = false) {
     // mask_dx: x is the output of a ReLU; its backward (dx = 0 where x <= 0) is folded into this dgrad -- the epilogue of the
-    // 256x256 kernel, or one in-place pass after the other GEMM forms
+    // 256x256 / 128x128 kernels, or one in-place pass after the other GEMM forms
     if constexpr (sizeof(T) == 2) {
+        // bf16: no transposes on the dyp side; dyp = dy*scale*(y>0) is materialised ONCE (masking inside the GEMM would re-read y
+        // for every output tile column: 16x the L2 traffic at fc1's shape)
         const bf16* a = (const bf16*)dy;
         float sc = scale;
         char* part = ws;
@@ -931,23 +853,18 @@ int linear_bwd(const T* dy, const T* y, const T* x, const T* W, T* dx, T* dW, T*
         }
         int rc = MMGL_OK;
         if (dx) {
-            if ((big_tile_shape(M, K, N) || (N % 128 == 0 && mmgl_gemm_nt_fast(M, K, N, N, N, K, MMGL_BF16)))) {
+            const NtRoute route = nt_route(M, K, N, N, N, K, MMGL_BF16, true);
+            if (big_tile_shape(M, K, N) || (N % 128 == 0 && route != NtRoute::TILE128)) {
                 // (sending every M >= 1024 dgrad through W^T and the 128x128 NT kernel was tried: no gain in the batch-4 step)
                 // shapes the persistent kernel takes (a chip of 256x256 tiles, or K-split work items at the reference's small
-                // batch): dx = dyp . (W^T)^T as an NT GEMM; transposing the [N,K] weight costs a few percent of the GEMM
+                // batch): dx = dyp . (W^T)^T as an NT GEMM; transposing the [N,K] weight costs a few percent of the GEMM.  The K-split
+                // scratch tiles are the region the weight gradient's split partials use afterwards (same stream: the dgrad has
+                // consumed them by then)
                 T* Wt = (T*)(ws + bf16_wt_offset(M, N, act));
                 rc = launch_transpose<T>(W, nullptr, Wt, nullptr, N, K, 1.f, 0, st);
-                bool masked = false;
-                if (!rc && tune_gemm_8p() && gemm8p_supported(M, K, N, N, N, K) && gemm8p_use_splits(M, K, N)) {
-                    // few tiles, or a remainder of a round of tiles (the reference's batch): K-split work items, scratch tiles in
-                    // the region the weight gradient's split partials use afterwards (same stream: the dgrad has consumed them by then)
-                    rc = launch_gemm8p_rows((const bf16*)a, N, (const bf16*)Wt, N, (bf16*)dx, K, nullptr, nullptr, mask_dx ? (const bf16*)x : nullptr,
-                                       M, K, N, MMGL_ACT_NONE, sc, st, (float*)(ws + bf16_part_offset(M, N, K, act)), gemm8p_split_bytes(M, K, N));
-                    masked = mask_dx;
-                } else if (!rc)
-                    rc = launch_gemm<T>((const T*)a, Wt, dx, nullptr, M, K, N, MMGL_ACT_NONE, sc, 0, nullptr, nullptr, 0, st,
-                                        mask_dx ? x : nullptr, &masked);
-                if (!rc && mask_dx && !masked) rc = launch_relu_mask<T>(dx, x, dx, (size_t)M * K, 1.f, st);
+                if (!rc)
+                    rc = launch_nt<T>(route, (const T*)a, N, Wt, N, dx, K, nullptr, nullptr, mask_dx ? x : nullptr, M, K, N, MMGL_ACT_NONE, sc,
+                                      (float*)(ws + bf16_part_offset(M, N, K, act)), gemm8p_split_bytes(M, K, N), st);
             } else {
                 rc = launch_gemm_tx(false, (const bf16*)W, K, a, N, nullptr, (bf16*)dx, K, M, N, sc, 0, st);
                 if (!rc && mask_dx) rc = launch_relu_mask<T>(dx, x, dx, (size_t)M * K, 1.f, st);
@@ -958,21 +875,45 @@ int linear_bwd(const T* dy, const T* y, const T* x, const T* W, T* dx, T* dW, T*
         if (!rc && dbias) rc = launch_colsum<T>((const T*)a, nullptr, dbias, (float*)part, M, N, sc, accumulate, st);
         return rc;
     } else {
+        // fp32 (parity path): the 128x128 kernel on explicitly transposed operands
         int rc = MMGL_OK;
-        if (dx) rc = linear_dgrad<T>(dy, y, W, dx, ws, M, N, K, act, scale, st);
-        if (!rc && dx && mask_dx) rc = launch_relu_mask<T>(dx, x, dx, (size_t)M * K, 1.f, st);
+        if (dx) {
+            // ws: W^T [K,N] | dyp [M,N] (only with an activation)
+            if (N % GT<T>::VN) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_linear_bwd: out_features %d must be a multiple of %d", N, GT<T>::VN);
+            T* Wt = (T*)ws;
+            T* dyp = (T*)(ws + align_up((size_t)K * ((size_t)(N + 7) / 8 * 8) * sizeof(T), 256));
+            rc = launch_transpose<T>(W, nullptr, Wt, nullptr, N, K, 1.f, 0, st);
+            if (rc) return rc;
+            const T* a = dy;
+            float s = scale;
+            if (act == MMGL_ACT_RELU) {
+                if ((rc = launch_relu_mask<T>(dy, y, dyp, (size_t)M * N, scale, st))) return rc;
+                a = dyp;
+                s = 1.f;
+            }
+            rc = gemm_dense<T>(a, Wt, dx, nullptr, M, K, N, MMGL_ACT_NONE, s, 0, st);
+            if (!rc && mask_dx) rc = launch_relu_mask<T>(dx, x, dx, (size_t)M * K, 1.f, st);
+        }
         if (!rc && (dW || dbias)) {
             MMGL_CHECK_ARG(dW, "mmgl_linear_bwd: fp32 path needs dW when dbias is requested");
-            rc = linear_wgrad<T>(dy, y, x, dW, dbias, ws, M, N, K, act, scale, accumulate, st);
+            // ws: dyp^T [N,M] | x^T [K,M]
+            T* dyT = (T*)ws;
+            T* xT = (T*)(ws + align_up((size_t)N * ((size_t)(M + 7) / 8 * 8) * sizeof(T), 256));
+            if ((rc = launch_transpose<T>(dy, act == MMGL_ACT_RELU ? y : nullptr, dyT, dbias, M, N, scale, accumulate, st))) return rc;
+            if ((rc = launch_transpose<T>(x, nullptr, xT, nullptr, M, K, 1.f, 0, st))) return rc;
+            rc = gemm_dense<T>(dyT, xT, dW, nullptr, N, K, pad_k<T>(M), MMGL_ACT_NONE, 1.f, accumulate, st);
         }
         return rc;
     }
 }
 
 extern "C" size_t mmgl_linear_bwd_workspace(int M, int N, int K, int act, int dtype) {
-    const size_t esz = dtype == MMGL_BF16 ? 2 : 4;
-    const size_t a = dgrad_ws(M, N, K, act, esz), b = wgrad_ws(M, N, K, esz);
-    return a > b ? a : b;
+    // bf16: the layout above, with the dyp region whatever `act` is; fp32: the larger of the dgrad's and the weight gradient's
+    if (dtype == MMGL_BF16) return bf16_part_offset(M, N, K, 1) + split_partial_bytes(K, N, M);
+    const size_t Mp = (size_t)(M + 7) / 8 * 8, Np = (size_t)(N + 7) / 8 * 8;
+    const size_t dgrad = align_up((size_t)K * Np * 4, 256) + (act ? align_up((size_t)M * N * 4, 256) : 0);
+    const size_t wgrad = align_up((size_t)N * Mp * 4, 256) + align_up((size_t)K * Mp * 4, 256);
+    return dgrad > wgrad ? dgrad : wgrad;
 }
 
 extern "C" int mmgl_linear_bwd(const void* dy, const void* y, const void* x, const void* W, void* dx, void* dW, void* dbias,
@@ -1013,33 +954,17 @@ extern "C" int mmgl_lora_linear_bwd(const void* dy, const void* x, const void* x
               lora_bwd<float>((const float*)dy, (const float*)x, (const float*)xa, (const float*)W, (const float*)A, (const float*)Bm, (float*)dx, (float*)dA, (float*)dB, (float*)dyb, ws, M, N, K, r, scale, accumulate, st));
 }
 
-extern "C" int mmgl_transpose(const void* in, void* out, int R, int C, int dtype, void* stream) {
-    MMGL_CHECK_ARG(in && out && R > 0 && C > 0, "mmgl_transpose: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    DT_SWITCH("mmgl_transpose", launch_transpose<bf16>((const bf16*)in, nullptr, (bf16*)out, nullptr, R, C, 1.f, 0, st),
-              launch_transpose<float>((const float*)in, nullptr, (float*)out, nullptr, R, C, 1.f, 0, st));
-}
-
 // ------------------------------------------------------------------------------------------------------------------
-// General NT GEMM with a fused epilogue (the frozen path's linears and their dgrads): fast path = gemm8p.hip; every other
-// shape / dtype is composed from the kernels above plus the elementwise entry points.
-extern "C" int mmgl_activation_fwd(const void* x, void* y, size_t n, int act, int dtype, void* stream);
-extern "C" int mmgl_gated_residual_fwd(const void* residual, const void* x, const float* gate, void* y, size_t n, float p_drop,
-                                       uint64_t seed, int dtype, void* stream);
-
-static bool gemm_nt_on_8p(int M, int N, int K, int ldx, int ldw, int ldy, int dtype) {
-    return dtype == MMGL_BF16 && tune_gemm_8p() && gemm8p_supported(M, N, K, ldx, ldw, ldy) &&
-           (cdiv(M, 256) * cdiv(N, 256) >= tune_gemm_8p_min_tiles() || gemm8p_use_splits(M, N, K));
-}
+// General NT GEMM with a fused epilogue (the frozen path's linears and their dgrads), planned by nt_route with K splits.
 // 1: the persistent 256x256 kernel, 2: the 128x128 kernel (both: strided operands, whole epilogue in the kernel), 0: composed path
 extern "C" int mmgl_gemm_nt_fast(int M, int N, int K, int ldx, int ldw, int ldy, int dtype) {
-    if (gemm_nt_on_8p(M, N, K, ldx, ldw, ldy, dtype)) return 1;
-    return (dtype == MMGL_BF16 && tune_gemm_mid() && gemm_mid_supported(M, N, K, ldx, ldw, ldy)) ? 2 : 0;
+    const NtRoute r = nt_route(M, N, K, ldx, ldw, ldy, dtype, true);
+    return r == NtRoute::P8 ? 1 : r == NtRoute::MID ? 2 : 0;
 }
 
 extern "C" size_t mmgl_gemm_nt_workspace(int M, int N, int K, int ldx, int ldw, int ldy, int dtype) {
-    if (dtype != MMGL_BF16 || !tune_gemm_8p() || !gemm8p_supported(M, N, K, ldx, ldw, ldy)) return 0;
-    if (!gemm8p_use_splits(M, N, K)) return 0;              // few-tile outputs and remainders of a round of tiles (gemm8p_plan)
+    // few-tile outputs and remainders of a round of tiles (gemm8p_plan)
+    if (nt_route(M, N, K, ldx, ldw, ldy, dtype, true) != NtRoute::P8 || !gemm8p_use_splits(M, N, K)) return 0;
     return align_up(gemm8p_split_bytes(M, N, K), 256);
 }
 
@@ -1053,26 +978,12 @@ extern "C" int mmgl_gemm_nt(const void* x, int ldx, const void* W, int ldw, cons
     MMGL_CHECK_ARG(ldx + 127 >= K && ldw >= K && ldy >= N, "mmgl_gemm_nt: leading dimensions (%d, %d, %d) smaller than the rows (K=%d, N=%d)", ldx, ldw, ldy, K, N);
     hipStream_t st = (hipStream_t)stream;
     // few-tile shapes run as K-split work items when the caller brought mmgl_gemm_nt_workspace() bytes, unsplit otherwise
-    if (gemm_nt_on_8p(M, N, K, ldx, ldw, ldy, dtype))
-        return launch_gemm8p_rows((const bf16*)x, ldx, (const bf16*)W, ldw, (bf16*)y, ldy, (const bf16*)bias, (const bf16*)residual,
-                                  (const bf16*)zmask, M, N, K, act, out_scale, st, (float*)workspace, workspace_bytes);
-    if (dtype == MMGL_BF16 && tune_gemm_mid() && gemm_mid_supported(M, N, K, ldx, ldw, ldy))
-        return launch_gemm_mid((const bf16*)x, ldx, (const bf16*)W, ldw, (bf16*)y, ldy, (const bf16*)bias, (const bf16*)residual,
-                               (const bf16*)zmask, M, N, K, act, out_scale, st);
-    if (ldx != K || ldw != K || ldy != N)
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_gemm_nt: strided operands (ld %d %d %d) need the bf16 fast path (K %% 128 == 0, N %% 16 == 0, "
-                  ">= %d tiles of 256x256); got M=%d N=%d K=%d dtype=%d", ldx, ldw, ldy, tune_gemm_8p_min_tiles(), M, N, K, dtype);
-    int rc = mmgl_linear_fwd(x, W, bias, y, M, N, K, act <= 1 ? act : 0, out_scale, dtype, stream);
-    if (rc) return rc;
-    const size_t n = (size_t)M * N;
-    if (act >= 2 && (rc = mmgl_activation_fwd(y, y, n, act, dtype, stream))) return rc;
-    if (zmask) {
-        if (dtype == MMGL_BF16) rc = launch_relu_mask<bf16>((const bf16*)y, (const bf16*)zmask, (bf16*)y, n, 1.f, st);
-        else rc = launch_relu_mask<float>((const float*)y, (const float*)zmask, (float*)y, n, 1.f, st);
-        if (rc) return rc;
-    }
-    if (residual) rc = mmgl_gated_residual_fwd(residual, y, nullptr, y, n, 0.f, 0, dtype, stream);
-    return rc;
+    const NtRoute r = nt_route(M, N, K, ldx, ldw, ldy, dtype, true);
+    DT_SWITCH("mmgl_gemm_nt",
+              launch_nt<bf16>(r, (const bf16*)x, ldx, (const bf16*)W, ldw, (bf16*)y, ldy, (const bf16*)bias, (const bf16*)residual,
+                              (const bf16*)zmask, M, N, K, act, out_scale, (float*)workspace, workspace_bytes, st),
+              launch_nt<float>(r, (const float*)x, ldx, (const float*)W, ldw, (float*)y, ldy, (const float*)bias, (const float*)residual,
+                               (const float*)zmask, M, N, K, act, out_scale, (float*)workspace, workspace_bytes, st));
 }
 
 // ReLU mask as bits.  fc1 of a frozen FFN writes one bit per element of relu(x W1^T + b1) beside the activation; fc2's dgrad
@@ -1080,9 +991,7 @@ extern "C" int mmgl_gemm_nt(const void* x, int ldx, const void* W, int ldw, cons
 // tile instead of 256, and the activation need not be kept for the backward pass.  Only for shapes that run as whole 256x256
 // tiles on the persistent kernel (the bits are lane-private: both kernels must map tiles to lanes the same way).
 extern "C" size_t mmgl_gemm_nt_relu_bits_bytes(int M, int N, int K, int ldx, int ldw, int ldy, int dtype) {
-    if (dtype != MMGL_BF16 || !tune_gemm_8p() || !gemm8p_supported(M, N, K, ldx, ldw, ldy)) return 0;
-    if (cdiv(M, 256) * cdiv(N, 256) < tune_gemm_8p_min_tiles()) return 0;
-    return gemm8p_bits_bytes(M, N);
+    return nt_route(M, N, K, ldx, ldw, ldy, dtype, false) == NtRoute::P8 ? gemm8p_bits_bytes(M, N) : 0;
 }
 
 extern "C" int mmgl_gemm_nt_relu_bits(const void* x, int ldx, const void* W, int ldw, const void* bias, void* y, int ldy, void* bits_out,

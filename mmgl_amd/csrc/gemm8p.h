@@ -5,6 +5,9 @@
 // act codes: 0 none, 1 relu, 2 gelu (erf), 3 quick_gelu, 4 gelu (tanh)  (= mmgl_activation_fwd's)
 // row strides ldx / ldw / ldy in elements (resid and zmask share ldy)
 bool gemm8p_supported(int M, int N, int K, int ldx, int ldw, int ldy);
+// 256x256 output tiles from which the kernel runs without K splits (gemm8p_plan) and takes a GEMM whose caller brings no
+// K-split scratch (nt_route, gemm.hip)
+constexpr int GEMM8P_MIN_TILES = 160;
 int gemm8p_splits(int M, int N, int K);      // K splits for few-tile outputs (0 = none)
 int gemm8p_num_cu();                          // workgroups of a full launch (= CUs of the current device)
 size_t gemm8p_split_bytes(int M, int N, int K);   // fp32 partial tiles of the K-split path (caller's scratch)

@@ -666,7 +666,7 @@ void gemm8p_plan(int M, int N, int K, int* direct, int* nsplit) {
     const int tiles = cdiv(M, 256) * cdiv(N, 256), units = K / 128;
     *direct = tiles;
     *nsplit = 0;
-    if (tiles < 160) {
+    if (tiles < GEMM8P_MIN_TILES) {
         constexpr int min_units = 24;                     // K >= 3072 (tools: 2560 x 2048 x K sweep)
         if (units < min_units) return;
         // K in [3072, 4096) with >= 64 tiles (config 2's fc2 / fc1-dgrad at B = 16: 10240 x 768 x 3072 = 120 tiles): two K splits of

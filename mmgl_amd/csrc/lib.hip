@@ -16,4 +16,5 @@ extern "C" const char* mmgl_last_error(void) { return g_err; }
 // stale build would otherwise load and run with misaligned arguments).  101: mmgl_xattn_fwd lost p_drop / seed / offset.
 // 102: round 4 (tile counters bound to one stream; entry points added / removed with the kernel families).
 // 103: mmgl_comm_* / mmgl_allreduce_sum / mmgl_allgather / mmgl_broadcast.
-extern "C" int mmgl_version(void) { return 104; }
+// 105: the stand-alone dgrad, weight-gradient and transpose entry points removed (mmgl_linear_bwd covers them).
+extern "C" int mmgl_version(void) { return 105; }

@@ -823,7 +823,8 @@ def lora_qkv(x, w_qkv, b_qkv, lora_Aq, lora_Bq, lora_Av, lora_Bv, scale, q_scale
 
 def lora_linear(x, weight, bias, lora_A, lora_B, scale, out_scale=1.0):
     """x W^T + b + scale * (x A^T) B^T with a frozen base weight (peft LoRA semantics, lora_dropout = 0).
-    Large bf16 shapes: the base product runs on the persistent ping-pong GEMM with the low-rank update
+    A frozen base product the persistent ping-pong GEMM takes (bf16, enough 256x256 tiles or K-split work items:
+    mmgl_gemm_nt_fast == 1): _LoraLinearBig, the base product on that kernel with the low-rank update
     delta = (x A^T)(scale B)^T -- two skinny, HBM-bound GEMMs -- added in its epilogue; backward = the frozen dgrad GEMM plus
     the four skinny products autograd derives from the same pieces.  Everything else: one fused kernel (mmgl_lora_linear_*)
     that carries the rank-r term as a second operand pair in the same accumulators."""
@@ -831,19 +832,8 @@ def lora_linear(x, weight, bias, lora_A, lora_B, scale, out_scale=1.0):
     N, K = weight.shape
     if (not weight.requires_grad and (bias is None or not bias.requires_grad) and x.is_cuda
             and lib().mmgl_gemm_nt_fast(M, N, K, K, K, N, dtype_code(x)) == 1):
-        # the rank is zero-padded to 256 (autograd slices the gradients back): every product of the low-rank path -- x A^T,
-        # (x A^T) B^T, and in backward dy B, (dy B) A, (dy B)^T x, dy^T (x A^T) -- is then a 256-wide GEMM the large-tile kernels
-        # (and their K splits) carry, instead of a 16-wide one on a handful of workgroups
-        if x.dtype == torch.bfloat16 and K % 8 == 0 and N % 8 == 0:
-            return _LoraLinearBig.apply(x, weight, bias, lora_A, lora_B, float(scale), float(out_scale))
-        if out_scale != 1.0:
-            return lora_linear(x, weight, bias, lora_A, lora_B, scale) * out_scale
-        rp = (-lora_A.shape[0]) % 256
-        A_pad = F.pad(lora_A, (0, 0, 0, rp)) if rp else lora_A
-        B_pad = F.pad(lora_B, (0, rp)) if rp else lora_B
-        xa = linear(x, A_pad)                                      # [.., 256]
-        delta = linear(xa, B_pad, out_scale=scale)                 # [.., N]
-        return frozen_linear(x, weight, bias, residual=delta)
+        # (fast == 1 implies bf16, K % 128 == 0 and N % 16 == 0: every condition _LoraLinearBig's GEMMs need)
+        return _LoraLinearBig.apply(x, weight, bias, lora_A, lora_B, float(scale), float(out_scale))
     y = _LoraLinear.apply(x, weight, bias, lora_A, lora_B, float(scale))
     return y if out_scale == 1.0 else y * out_scale
 

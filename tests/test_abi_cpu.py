@@ -41,7 +41,7 @@ def test_library_is_not_older_than_its_sources():
         f"{_lib.LIB_PATH} is older than {newest}: run `python -m mmgl_amd._build` and read its output"
 
 
-def test_argument_validation_error_codes():
+def test_argument_validation_and_linear_bwd_workspace():
     from mmgl_amd import _lib
     L = _lib.lib()
     # null pointers / bad sizes are rejected before any launch (safe without a GPU)
@@ -52,7 +52,7 @@ def test_argument_validation_error_codes():
     assert L.mmgl_xattn_fwd(None, None, None, None, None, None, 0, 1, 8, 8, 64, 0, None) == 1
     assert L.mmgl_linear_fwd(None, None, None, None, 4, 4, 4, 0, 1.0, 1, None) == 1
     assert L.mmgl_xattn_bwd_workspace(4, 32, 640, 64, 64) > 4 * 32 * 640 * 4
-    assert L.mmgl_linear_wgrad_workspace(44, 8192, 768, 1) >= (8192 + 768) * 48 * 2
+    assert L.mmgl_linear_bwd_workspace(44, 8192, 768, 1, 1) >= (8192 + 768) * 48 * 2
     with pytest.raises(ValueError):
         _lib.check(2, "x")
     with pytest.raises(RuntimeError):
