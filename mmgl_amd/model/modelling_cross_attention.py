@@ -115,14 +115,14 @@ class MPTLearnedPositionalEmbedding(nn.Embedding):
         return F.embedding(positions, self.weight)
 
 
-def _lin(module: nn.Module, x, **kw):
+def _lin(module: nn.Module, x):
     """nn.Linear on the HIP GEMMs: frozen parameters -> ops.frozen_linear (dgrad only, cached W^T), else ops.linear.
     Anything that is not a plain nn.Linear (a LoRALinear wrapper, model/modelling_self_attention.py) runs its own forward."""
     if type(module) is not nn.Linear:
         return module(x)
     if module.weight.requires_grad or (module.bias is not None and module.bias.requires_grad):
         return ops.linear(x, module.weight, module.bias)
-    return ops.frozen_linear(x, module.weight, module.bias, **kw)
+    return ops.frozen_linear(x, module.weight, module.bias)
 
 
 class MPTAttention(nn.Module):
@@ -380,8 +380,7 @@ class MPTDecoderLayer(nn.Module):
             # fc1's ReLU backward rides in the epilogue of fc2's dgrad GEMM (mask_dx): no pass over [M, ffn], nothing kept twice
             frozen = not any(p.requires_grad for p in (*self.fc1.parameters(), *self.fc2.parameters()))
             lin = ops.frozen_linear if frozen else ops.linear
-            kw = dict(relu=True) if frozen else dict(act="relu")
-            x = lin(lin(x, self.fc1.weight, self.fc1.bias, bwd_premasked=True, **kw), self.fc2.weight, self.fc2.bias, mask_dx=True)
+            x = lin(lin(x, self.fc1.weight, self.fc1.bias, act="relu", bwd_premasked=True), self.fc2.weight, self.fc2.bias, mask_dx=True)
         else:
             x = _lin(self.fc2, self.activation_fn(_lin(self.fc1, x)))
         if pre and defer_residual:

@@ -5,7 +5,6 @@ entry point on torch's current stream and returns fresh tensors owned by autogra
 """
 import math
 import os
-import threading
 import weakref
 
 import torch
@@ -577,6 +576,35 @@ def gated_residual(residual, x, gate=None, p_drop=0.0, training=False, seed=None
 
 
 # ------------------------------------------------------------------------------------------ linear (+bias, scale, ReLU)
+_ACTS = {"none": _lib.ACT_NONE, "relu": _lib.ACT_RELU}      # the epilogues linear / frozen_linear differentiate
+
+
+def _act_code(op, act):
+    code = _ACTS.get(act)
+    if code is None:
+        raise ValueError(f"{op}: activation {act!r} is not fused (supported: none, relu)")
+    return code
+
+
+def _mfma_aligned(gemm, x, w, bias=None, residual=None, zmask=None, act=0, out_scale=1.0, out=None):
+    """gemm(x, w, bias, residual, zmask, act, out_scale, K, out) -- gemm_nt's signature -- for any feature counts K = w.shape[1],
+    N = w.shape[0].  The MFMA kernels move 16-byte chunks along K (8 bf16 / 4 fp32 elements) and 4 outputs per lane along N: an odd
+    count (the Laplacian-PE input width k = N_neighbors - 4, a tiny test vocabulary) is zero-padded -- x [..., K] and w along K, w,
+    bias, residual and zmask along N -- and the result is sliced back to N columns, into `out` when given.  Under autograd the pads
+    and the slice carry the gradients back."""
+    N, K = w.shape
+    kq = 8 if x.dtype == torch.bfloat16 else 4
+    if K % kq == 0 and N % 8 == 0:
+        return gemm(x, w, bias, residual, zmask, act, out_scale, K, out)
+    pk, pn = (-K) % kq, (-N) % 8
+    x = F.pad(x, (0, pk)) if pk else x
+    w = F.pad(w, (0, pk, 0, pn))
+    bias, residual, zmask = (F.pad(c, (0, pn)) if (pn and c is not None) else c for c in (bias, residual, zmask))
+    y = gemm(x, w, bias, residual, zmask, act, out_scale, K + pk, None)
+    y = y[..., :N] if pn else y
+    return y if out is None else out.copy_(y)
+
+
 class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, act, out_scale, mask_dx=False, premasked=False):
@@ -610,25 +638,18 @@ class _Linear(torch.autograd.Function):
         want_w = ctx.need[1] or ctx.need[2]
         dw = torch.empty_like(w) if want_w else None
         db = torch.empty(N, dtype=x2.dtype, device=x2.device) if ctx.need[2] else None
-        dx_done = None
-        if (dx is not None and N % 128 and act == _lib.ACT_NONE and not ctx.mask_dx and x2.dtype == torch.bfloat16 and K % 8 == 0
-                and N % 8 == 0):
-            # a contraction length that is no multiple of 128 (a trainable lm_head: N = vocab = 50272) has no large-tile dgrad
-            # in mmgl_linear_bwd; W^T zero-padded to the next multiple (built per call: the weight is being trained) puts it on
-            # the persistent kernel, dy read with its own row stride (frozen_dgrad's trick)
-            npad = N + (-N) % 128
-            if lib().mmgl_gemm_nt_fast(M, K, npad, N, npad, K, code):
-                wt = torch.zeros(K, npad, dtype=w.dtype, device=w.device)
-                wt[:, :N] = w.t()
-                gemm_nt(dy2, wt, out_scale=out_scale, K=npad, out=dx)
-                dx_done, dx = dx, None
+        dx_lin = dx
+        if dx is not None and act == _lib.ACT_NONE and not ctx.mask_dx and _dgrad_pad_to(dy2, w) > 1:
+            # a contraction length that is no multiple of 128 (a trainable lm_head: N = vocab = 50272) has no large-tile dgrad in
+            # mmgl_linear_bwd: frozen_dgrad's padded W^T puts it on the persistent kernel.  Built per call: the weight is being
+            # trained, and a cached 2048 x 50304 copy would keep 206 MB alive
+            frozen_dgrad(dy2, w, out=dx, out_scale=out_scale, wt=_padded_t(w, 128))
+            dx_lin = None
         ws = _ws(lib().mmgl_linear_bwd_workspace(M, N, K, act, code), x2.device)
-        _lib.call("mmgl_linear_bwd", dict(flops=2.0 * M * N * K * (int(dx is not None) + int(dw is not None)),
+        _lib.call("mmgl_linear_bwd", dict(flops=2.0 * M * N * K * (int(dx_lin is not None) + int(dw is not None)),
                                          bytes=float(M * K + N * K + M * N) * x2.element_size()),
-                  ptr(dy2), ptr(y), ptr(x2), ptr(w), ptr(dx), ptr(dw), ptr(db), ptr(ws), ws.numel(), M, N, K, act, out_scale, 0,
+                  ptr(dy2), ptr(y), ptr(x2), ptr(w), ptr(dx_lin), ptr(dw), ptr(db), ptr(ws), ws.numel(), M, N, K, act, out_scale, 0,
                   int(ctx.mask_dx), code, stream_ptr())
-        if dx_done is not None:
-            dx = dx_done
         if dx is not None:
             dx = dx.view(shape)
         dw = dw.to(wdt) if (dw is not None and ctx.need[1]) else None
@@ -644,22 +665,8 @@ def linear(x, weight, bias=None, act="none", out_scale=1.0, mask_dx=False, bwd_p
     its dx where h <= 0 inside the dgrad GEMM, the first one then skips the separate mask pass.  Use the two flags together."""
     if x.shape[-1] != weight.shape[1]:
         raise ValueError(f"linear: x has {x.shape[-1]} features, weight expects {weight.shape[1]}")
-    code = {"none": _lib.ACT_NONE, "relu": _lib.ACT_RELU}.get(act)
-    if code is None:
-        raise ValueError(f"linear: activation {act!r} is not fused (supported: none, relu)")
-    # The MFMA kernels move 16-byte chunks along K and 4 outputs per lane along N: odd feature counts (e.g. the
-    # Laplacian-PE input width k = N_neighbors - 4) are zero-padded here; autograd slices the gradients back.
-    K, N = weight.shape[1], weight.shape[0]
-    kq = 8 if x.dtype == torch.bfloat16 else 4
-    pk, pn = (-K) % kq, (-N) % 8
-    if pk or pn:
-        x = torch.nn.functional.pad(x, (0, pk)) if pk else x
-        weight = torch.nn.functional.pad(weight, (0, pk, 0, pn))
-        if bias is not None and pn:
-            bias = torch.nn.functional.pad(bias, (0, pn))
-        y = _Linear.apply(x, weight, bias, code, float(out_scale), bool(mask_dx), bool(bwd_premasked))
-        return y[..., :N] if pn else y
-    return _Linear.apply(x, weight, bias, code, float(out_scale), bool(mask_dx), bool(bwd_premasked))
+    return _mfma_aligned(lambda a, w, b, _r, _z, act_, scale, _K, _out: _Linear.apply(a, w, b, act_, scale, bool(mask_dx), bool(bwd_premasked)),
+                         x, weight, bias, act=_act_code("linear", act), out_scale=float(out_scale))
 
 
 class _LoraLinear(torch.autograd.Function):
@@ -709,6 +716,19 @@ def _wgrad_only(dy2, x2, w_like, scale):
     return dw
 
 
+def _lora_bwd(g, x2, xa, weight, A_pad, B_pad, dxa_scale, dB_scale, dx_scale, need_dx, need_dA, need_dB):
+    """Backward of a frozen base product plus a rank-padded low-rank term, from g = dy [M, N], x2 [M, K], xa = x2 A_pad^T and the
+    factors A_pad [256, K], B_pad [N, 256] as the forward used them: dxa = dxa_scale (g B_pad), dA = dxa^T x2, dB = dB_scale g^T xa,
+    and dx = dx_scale g W + dxa A_pad as ONE dgrad GEMM with the low-rank term in its epilogue.  Returns (dx, dA, dB), None where
+    not needed."""
+    dxa = gemm_nt(g, B_pad.t().contiguous(), out_scale=dxa_scale)                   # [M, 256]
+    dA = _wgrad_only(dxa, x2, A_pad, 1.0) if need_dA else None                       # [256, K]
+    dB = _wgrad_only(g, xa, B_pad, dB_scale) if need_dB else None                    # [N, 256]
+    dx = None
+    if need_dx:
+        low = gemm_nt(dxa, A_pad.t().contiguous())                                  # [M, K]
+        dx = frozen_dgrad(g, weight, out_scale=dx_scale, residual=low)
+    return dx, dA, dB
 
 
 class _LoraLinearBig(torch.autograd.Function):
@@ -741,14 +761,11 @@ class _LoraLinearBig(torch.autograd.Function):
         xshape, scale, r, adt, bdt, os_ = ctx.meta
         N = weight.shape[0]
         g = dy.reshape(-1, N).contiguous()
-        dxa = gemm_nt(g, B_pad.t().contiguous(), out_scale=scale * os_)                 # (dy B) * scale  [M, 256]
-        dB = _wgrad_only(g, xa, B_pad, scale * os_) if ctx.needs_input_grad[4] else None      # [N, 256]
-        dA = _wgrad_only(dxa, x2, A_pad, 1.0) if ctx.needs_input_grad[3] else None      # [256, K]
-        dx = None
-        if ctx.needs_input_grad[0]:
-            low = gemm_nt(dxa, A_pad.t().contiguous())                                  # (dy B) A  [M, K]
-            dx = frozen_dgrad(g, weight, out_scale=os_, residual=low).view(xshape)      # dy W * out_scale + ... in the epilogue
-        return (dx, None, None, None if dA is None else dA[:r].to(adt), None if dB is None else dB[:, :r].contiguous().to(bdt), None, None)
+        need = ctx.needs_input_grad
+        # the scale enters through (dy B) and dB; out_scale (attention's D^-1/2 on q_proj) also scales dy W
+        dx, dA, dB = _lora_bwd(g, x2, xa, weight, A_pad, B_pad, scale * os_, scale * os_, os_, need[0], need[3], need[4])
+        return (None if dx is None else dx.view(xshape), None, None, None if dA is None else dA[:r].to(adt),
+                None if dB is None else dB[:, :r].contiguous().to(bdt), None, None)
 
 
 class _LoraQKV(torch.autograd.Function):
@@ -789,21 +806,16 @@ class _LoraQKV(torch.autograd.Function):
         xshape, r, scale, q_scale, adt, bdt = ctx.meta
         d = w_qkv.shape[0] // 3
         g = dqkv.reshape(-1, 3 * d).contiguous()
-        dxa = gemm_nt(g, B_cat.t().contiguous())                                        # [M, 256]: (dq B_q) s qs | (dv B_v) s
         need = ctx.needs_input_grad
+        # the scales sit in B_cat already: dxa = (dq B_q) s qs | (dv B_v) s; dB [3d, 256] = s dqkv^T (x A_cat^T)
+        dx, dA, dB = _lora_bwd(g, x2, xa, w_qkv, A_cat, B_cat, 1.0, scale, 1.0, need[0], need[3] or need[5], need[4] or need[6])
         dAq = dAv = dBq = dBv = None
-        if need[3] or need[5]:
-            dA = _wgrad_only(dxa, x2, A_cat, 1.0)                                       # [256, K]
+        if dA is not None:
             dAq, dAv = dA[:r].to(adt), dA[r:2 * r].to(adt)
-        if need[4] or need[6]:
-            dB = _wgrad_only(g, xa, B_cat, scale)                                       # [3d, 256] = s dqkv^T (x A_cat^T)
+        if dB is not None:
             dBq = (dB[:d, :r].float() * q_scale).to(bdt)
             dBv = dB[2 * d:, r:2 * r].contiguous().to(bdt)
-        dx = None
-        if need[0]:
-            low = gemm_nt(dxa, A_cat.t().contiguous())                                  # [M, K]
-            dx = frozen_dgrad(g, w_qkv, residual=low).view(xshape)
-        return dx, None, None, dAq, dBq, dAv, dBv, None, None
+        return None if dx is None else dx.view(xshape), None, None, dAq, dBq, dAv, dBv, None, None
 
 
 def lora_qkv_supported(x, w_qkv, r):
@@ -1005,10 +1017,22 @@ _WT_CACHE = {}
 ACT_CODES = {"none": 0, "relu": 1, "gelu": 2, "quick_gelu": 3, "gelu_new": 4, "gelu_pytorch_tanh": 4, "gelu_fast": 4}
 
 
+def _padded_t(weight, pad_to=1):
+    """W^T as a contiguous tensor [in, out_padded] (out zero-padded up to a multiple of `pad_to`)."""
+    with torch.no_grad():
+        wt = weight.detach().t()
+        n = wt.shape[1]
+        npad = (n + pad_to - 1) // pad_to * pad_to
+        if npad == n:
+            return wt.contiguous()
+        full = wt.new_zeros(wt.shape[0], npad)
+        full[:, :n] = wt
+        return full
+
+
 def _transposed(weight, pad_to=1):
-    """W^T as a contiguous tensor [in, out_padded] (out zero-padded up to a multiple of `pad_to`), cached per weight OBJECT
-    (weakref-checked: an id or an address can be reused by a later tensor) and rebuilt when its storage / version / dtype
-    changes (load_state_dict, .bfloat16(), flattening)."""
+    """_padded_t(weight, pad_to) cached per weight OBJECT (weakref-checked: an id or an address can be reused by a later tensor)
+    and rebuilt when its storage / version / dtype changes (load_state_dict, .bfloat16(), flattening)."""
     key = (id(weight), pad_to)
     tag = (weight.data_ptr(), weight._version, weight.dtype, tuple(weight.shape))
     hit = _WT_CACHE.get(key)
@@ -1016,15 +1040,7 @@ def _transposed(weight, pad_to=1):
         if len(_WT_CACHE) > 4096:                             # drop entries of dead tensors
             for k in [k for k, h in _WT_CACHE.items() if h[0]() is None]:
                 del _WT_CACHE[k]
-        with torch.no_grad():
-            wt = weight.detach().t()
-            n = wt.shape[1]
-            npad = (n + pad_to - 1) // pad_to * pad_to
-            if npad != n:
-                full = wt.new_zeros(wt.shape[0], npad)
-                full[:, :n] = wt
-                wt = full
-            hit = (weakref.ref(weight), tag, wt.contiguous())
+        hit = (weakref.ref(weight), tag, _padded_t(weight, pad_to))
         _WT_CACHE[key] = hit
     return hit[2]
 
@@ -1084,15 +1100,19 @@ def relu_bits_bytes(M, N, K, ldx, ldw, ldy, dtype):
     return lib().mmgl_gemm_nt_relu_bits_bytes(M, N, K, ldx, ldw, ldy, _lib.BF16)
 
 
-def gemm_nt_relu_bits(x2, w, bias, out, K=None):
+def gemm_nt_relu_bits(x2, w, bias, out, K=None, bits=None):
     """out = relu(x2[:, :K] @ w^T + bias) plus one bit per element (out > 0), lane-private to the persistent GEMM's tiling:
-    (out, bits uint8 [nbytes]).  Callers check relu_bits_bytes() > 0 first.  No autograd."""
+    (out, bits uint8 [nbytes]).  Callers check relu_bits_bytes() > 0 first; `bits`: that many bytes of their own, else allocated
+    here.  No autograd."""
     M, N = x2.shape[0], w.shape[0]
     K = x2.shape[1] if K is None else K
     nb = relu_bits_bytes(M, N, K, x2.stride(0), w.stride(0), out.stride(0), x2.dtype)
     if not nb:
         raise ValueError("gemm_nt_relu_bits: shape not eligible (relu_bits_bytes == 0)")
-    bits = torch.empty(nb, dtype=torch.uint8, device=x2.device)
+    if bits is None:
+        bits = torch.empty(nb, dtype=torch.uint8, device=x2.device)
+    elif bits.numel() != nb:
+        raise ValueError(f"gemm_nt_relu_bits: bits hold {bits.numel()} bytes, the shape writes {nb}")
     _lib.call("mmgl_gemm_nt_relu_bits", dict(flops=2.0 * M * N * K, bytes=float(M * K + N * K + M * N) * x2.element_size(), tag=f"{M}x{N}x{K}+b+a1+bits"),
               ptr(x2), x2.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(out), out.stride(0), ptr(bits), M, N, K, 1.0, dtype_code(x2), stream_ptr())
     return out, bits
@@ -1107,51 +1127,35 @@ def gemm_nt_masked(x2, w, bits, out, K=None):
     return out
 
 
-def _gemm_nt_padded(x2, w, bias=None, zmask=None, act=0, K=None):
-    """gemm_nt for feature counts the MFMA kernels cannot address (K not a multiple of one 16-byte chunk, N not a multiple
-    of 8 -- tiny test vocabularies, the Laplacian-PE width): operands are zero-padded, the result sliced back."""
-    kq = 8 if x2.dtype == torch.bfloat16 else 4
-    Kx = x2.shape[1] if K is None else K
-    N = w.shape[0]
-    pk, pn = (-Kx) % kq, (-N) % 8
-    if not pk and not pn:
-        return gemm_nt(x2, w, bias, zmask=zmask, act=act, K=K)
-    x2 = F.pad(x2[:, :Kx], (0, pk)) if pk else x2
-    w = F.pad(w[:, :Kx], (0, pk, 0, pn))
-    bias = F.pad(bias, (0, pn)) if (bias is not None and pn) else bias
-    zmask = F.pad(zmask, (0, pn)) if (zmask is not None and pn) else zmask
-    y = gemm_nt(x2.contiguous(), w.contiguous(), bias, zmask=zmask, act=act, K=Kx + pk)
-    return y[:, :N].contiguous() if pn else y
-
-
-def frozen_dgrad(g, weight, zmask=None, out=None, bits=None, out_scale=1.0, residual=None):
-    """dx[M,K] = g[M,N] @ W[N,K] for a frozen W  ==  an NT GEMM against the cached W^T [K, Npad].  The contraction length is
-    padded to a multiple of 128 with zero columns of W^T (lm_head: N = vocab = 50272) and g is read with its own row stride.
-    No autograd."""
+def _dgrad_pad_to(g, weight):
+    """pad_to of the W^T operand of dx = g W (see _padded_t): 128 when the contraction N = weight.shape[0] is no multiple of 128
+    (lm_head: N = vocab = 50272) and the persistent kernel takes dx against W^T zero-padded to that multiple, g read with its own
+    row stride (its row tails meet the zero columns); else 1, dense operands."""
     N, K = weight.shape
-    pad = 128 if (g.dtype == torch.bfloat16 and N % 128) else 1
-    wt = _transposed(weight, pad) if weight.dtype == g.dtype else weight.detach().to(g.dtype).t().contiguous()
-    kk = wt.shape[1]
-    if kk != N and not lib().mmgl_gemm_nt_fast(g.shape[0], K, kk, g.stride(0), kk, K, dtype_code(g)):
-        wt, kk = wt[:, :N].contiguous(), N                # shape not on the fast path: dense operands
-    if out is None and zmask is not None and zmask.stride(0) != zmask.shape[1]:
-        # the mask (a ReLU output kept with a padded row pitch, see _ffn_pitch) shares the output's row stride in the epilogue
-        out = torch.empty(zmask.shape[0], zmask.stride(0), dtype=g.dtype, device=g.device)[:, :zmask.shape[1]]
-    if bits is not None:                                      # the ReLU mask as bits (see _FrozenLinear): `out` carries the row pitch
-        return gemm_nt_masked(g, wt, bits, out, K=kk)
-    if out is not None and kk % (8 if g.dtype == torch.bfloat16 else 4) == 0 and K % 8 == 0:
-        return gemm_nt(g, wt, zmask=zmask, residual=residual, out_scale=out_scale, K=kk, out=out)
-    if residual is not None or out_scale != 1.0:
-        if kk % (8 if g.dtype == torch.bfloat16 else 4) or K % 8:
-            raise ValueError("frozen_dgrad: out_scale / residual need 16-byte aligned feature counts")
-        return gemm_nt(g, wt, zmask=zmask, residual=residual, out_scale=out_scale, K=kk)
-    dx = _gemm_nt_padded(g, wt, zmask=zmask, K=kk)
-    if out is not None:
-        out.copy_(dx)
-        return out
-    return dx
+    if N % 128 == 0 or not (g.dtype == weight.dtype == torch.bfloat16):
+        return 1
+    npad = N + (-N) % 128
+    return 128 if lib().mmgl_gemm_nt_fast(g.shape[0], K, npad, g.stride(0), npad, K, _lib.BF16) else 1
 
 
+def frozen_dgrad(g, weight, zmask=None, out=None, bits=None, out_scale=1.0, residual=None, wt=None):
+    """dx[M,K] = g[M,N] @ W[N,K] for a frozen W  ==  an NT GEMM against W^T: the cached copy (zero-padded along N where
+    _dgrad_pad_to says so) unless the caller brings its own `wt`.  With the ReLU mask as bits (gemm_nt_masked: `out` carries their
+    row pitch), else through gemm_nt with its zmask / residual / out_scale epilogue.  No autograd."""
+    if wt is None:
+        if weight.dtype == g.dtype:
+            wt = _transposed(weight, _dgrad_pad_to(g, weight))
+        else:
+            wt = weight.detach().to(g.dtype).t().contiguous()
+    if out is None:
+        # zmask (a ReLU output kept with a padded row pitch, see _ffn_pitch) shares the output's row stride in the epilogue
+        K = wt.shape[0]
+        ld = K if zmask is None else zmask.stride(0)
+        out = g.new_empty(g.shape[0], ld)
+        out = out[:, :K] if ld != K else out
+    if bits is not None:
+        return gemm_nt_masked(g, wt, bits, out, K=wt.shape[1])
+    return _mfma_aligned(gemm_nt, g, wt, residual=residual, zmask=zmask, out_scale=out_scale, out=out)
 
 
 def _ffn_pitch(M, N, K, dtype):
@@ -1196,73 +1200,48 @@ def _row_strided(t2, cols, n_out):
     return t2.contiguous()
 
 
-# The ReLU mask bits fc1's forward produced travel from _FrozenLinear.forward to frozen_linear (its caller, a few lines below, which hangs
-# them on the output tensor) through this per-THREAD slot: autograd Functions can only return tensors.  A consumer that does not find
-# the attribute (a wrapper or view dropped it) falls back to the activation as the mask.
-_HANDOVER = threading.local()
-_HANDOVER.relu_bits = None
-
-
 class _FrozenLinear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, act, mask_dx, premasked, residual=None, relu_bits=None, relu_pitch=0, relu_rows=0):
+    def forward(ctx, x, weight, bias, act, mask_dx, premasked, pitch, relu_out, relu_in):
         require_cuda(x, weight)
         K, N = weight.shape[1], weight.shape[0]
         x2 = _row_strided(x.reshape(-1, K), K, N)
-        w = weight if weight.dtype == x.dtype else weight.to(x.dtype)
+        w = (weight if weight.dtype == x.dtype else weight.to(x.dtype)).contiguous()
         b = None if bias is None else (bias if bias.dtype == x.dtype else bias.to(x.dtype))
-        kq = 8 if x.dtype == torch.bfloat16 else 4
-        if K % kq == 0 and N % 8 == 0:
-            # the output is allocated in its final shape and returned as is (not a view made inside this Function): consumers
-            # such as the in-place rotary embedding may then modify it
-            pitch = _ffn_pitch(x2.shape[0], N, K, x.dtype) if (premasked and residual is None) else N
-            if pitch != N:                   # fc1 of a frozen FFN: the consumer (fc2, mask_dx) reads it with its row stride
-                out = torch.empty(*x.shape[:-1], pitch, dtype=x.dtype, device=x.device)[..., :N]
-                wc = w.contiguous()
-                M_ = x2.shape[0]
-                m1 = _round_split_rows(M_, N, x.device) if act == 1 else 0
-                if m1 and relu_bits_bytes(m1, N, K, x2.stride(0), K, pitch, x.dtype):
-                    # a 1.25-round output: whole rounds on the persistent kernel (mask bits), the short tail on the few-tile kernel
-                    # (its rows of the activation stay the mask of fc2's backward)
-                    y = out.reshape(-1, N)
-                    _, bits = gemm_nt_relu_bits(x2[:m1], wc, b, y[:m1])
-                    gemm_nt(x2[m1:], wc, b, act=1, out=y[m1:])
-                    _HANDOVER.relu_bits = (bits, pitch, m1)
-                elif act == 1 and relu_bits_bytes(M_, N, K, x2.stride(0), K, pitch, x.dtype):
-                    # the ReLU mask leaves as bits beside the activation: fc2's backward applies those (16 bytes per lane and
-                    # tile) instead of re-reading -- and keeping -- the [M, ffn] activation
-                    y, bits = gemm_nt_relu_bits(x2, wc, b, out.reshape(-1, N))
-                    _HANDOVER.relu_bits = (bits, pitch, M_)
-                else:
-                    y = gemm_nt(x2, wc, b, act=act, out=out.reshape(-1, N))
-            else:
-                out = torch.empty(*x.shape[:-1], N, dtype=x.dtype, device=x.device)
-                r2 = None if residual is None else residual.reshape(-1, N).contiguous()
-                y = gemm_nt(x2, w.contiguous(), b, residual=r2, act=act, out=out.view(-1, N))
+        # the output is allocated here, in its final shape, and returned as is: consumers such as the in-place rotary embedding may
+        # then modify it (a tensor the caller passed in would come back as a view of an input).  pitch != N: fc1 of a frozen FFN,
+        # which the consumer (fc2, mask_dx) reads with its row stride
+        out = torch.empty(*x.shape[:-1], pitch, dtype=x.dtype, device=x.device)
+        out = out[..., :N] if pitch != N else out
+        y = out.view(-1, N)
+        if relu_out is None:
+            _mfma_aligned(gemm_nt, x2, w, b, act=act, out=y)
         else:
-            out = None
-            y = _gemm_nt_padded(x2, w.contiguous(), b, act=act)
-            if residual is not None:
-                y = y + residual.reshape(-1, N)
-        ctx.has_resid = residual is not None
+            # fc1 planned by frozen_linear: the ReLU mask leaves as bits beside the activation -- fc2's backward applies those (16 bytes
+            # per lane and tile) instead of re-reading and keeping the [M, ffn] activation -- for the rows that run as whole rounds of
+            # the persistent kernel; a short tail runs on the few-tile kernel and its activation rows stay the mask
+            bits, _, rows = relu_out
+            gemm_nt_relu_bits(x2[:rows], w, b, y[:rows], bits=bits)
+            if rows < y.shape[0]:
+                gemm_nt(x2[rows:], w, b, act=act, out=y[rows:])
         # premasked: the consumer folds this layer's ReLU backward into its own dgrad (mask_dx there): differentiate as a plain
         # linear and keep nothing.  mask_dx: x2 is a ReLU output whose backward rides in this layer's dgrad epilogue -- as the
         # producer's mask bits when it left some and the dgrad's shape takes them (then x2 itself is not kept), else as x2.
         ctx.mask_bits = None
         xkeep = x2 if mask_dx else None
-        if mask_dx and relu_bits is not None:
-            mrows = relu_rows or x2.shape[0]                  # rows the bits cover (the rest: the activation rows themselves)
-            if x2.dtype == torch.bfloat16 and x2.stride(0) == relu_pitch and N % 128 == 0 and 0 < mrows <= x2.shape[0] and \
-                    relu_bits_bytes(mrows, K, N, N, N, relu_pitch, x2.dtype) == relu_bits.numel():
-                ctx.mask_bits = (relu_bits, relu_pitch, mrows)
+        if mask_dx and relu_in is not None:
+            bits, rpitch, mrows = relu_in                     # bits cover rows [0, mrows), the rest: the activation rows themselves
+            if x2.dtype == torch.bfloat16 and x2.stride(0) == rpitch and N % 128 == 0 and 0 < mrows <= x2.shape[0] and \
+                    relu_bits_bytes(mrows, K, N, N, N, rpitch, x2.dtype) == bits.numel():
+                ctx.mask_bits = relu_in
                 xkeep = None
                 if mrows < x2.shape[0]:      # a short tail, copied (a view would keep the [M, ffn] buffer) with the row pitch the dgrad's output has
-                    xkeep = torch.empty(x2.shape[0] - mrows, relu_pitch, dtype=x2.dtype, device=x2.device)[:, :K]
+                    xkeep = torch.empty(x2.shape[0] - mrows, rpitch, dtype=x2.dtype, device=x2.device)[:, :K]
                     xkeep.copy_(x2[mrows:])
-        ctx.save_for_backward(weight, y if (act == 1 and not premasked) else None, xkeep)
+        ctx.save_for_backward(weight, out if (act == 1 and not premasked) else None, xkeep)
         ctx.act = 0 if premasked else act
         ctx.xshape = x.shape
-        return out if out is not None else y.view(*x.shape[:-1], N)
+        return out
 
     @staticmethod
     def backward(ctx, dy):
@@ -1274,51 +1253,48 @@ class _FrozenLinear(torch.autograd.Function):
             gm = torch.empty_like(g)
             _lib.call("mmgl_relu_bwd", dict(bytes=3.0 * g.numel() * g.element_size()), ptr(g), ptr(y), ptr(gm), g.numel(), dtype_code(g), stream_ptr())
             g = gm
-        elif ctx.act:
-            raise RuntimeError("frozen_linear: only the ReLU epilogue is differentiable")
         if ctx.mask_bits is not None:
             bits, pitch, mrows = ctx.mask_bits
-            buf = torch.empty(g.shape[0], pitch, dtype=g.dtype, device=g.device)[:, :K]
-            if mrows < g.shape[0]:                            # whole rounds with the mask bits, the tail rows with their activation rows
-                frozen_dgrad(g[:mrows], weight, out=buf[:mrows], bits=bits)
-                frozen_dgrad(g[mrows:], weight, zmask=xmask, out=buf[mrows:])
-                dx = buf
-            else:
-                dx = frozen_dgrad(g, weight, out=buf, bits=bits)
+            dx = torch.empty(g.shape[0], pitch, dtype=g.dtype, device=g.device)[:, :K]
+            frozen_dgrad(g[:mrows], weight, out=dx[:mrows], bits=bits)
+            if mrows < g.shape[0]:                            # the tail rows with their activation rows as the mask
+                frozen_dgrad(g[mrows:], weight, zmask=xmask, out=dx[mrows:])
         else:
             dx = frozen_dgrad(g, weight, zmask=xmask)
-        return dx.reshape(ctx.xshape), None, None, None, None, None, (dy if ctx.has_resid else None), None, None, None
+        return dx.reshape(ctx.xshape), None, None, None, None, None, None, None, None
 
 
-def frozen_linear(x, weight, bias, relu=False, mask_dx=False, bwd_premasked=False, act=None, residual=None):
-    """act(x W^T + b) for a FROZEN nn.Linear (reference :194-199, :273, :352-355 inside the frozen LM layers, lm_head :826).
-    mask_dx / bwd_premasked: as in `linear` -- `h = frozen_linear(x, W1, b1, relu=True, bwd_premasked=True);
-    y = frozen_linear(h, W2, b2, mask_dx=True)` puts fc1's ReLU backward into the epilogue of fc2's dgrad GEMM.
-    residual: a differentiable [..., out_features] tensor added in the GEMM epilogue (the LoRA update of an adapted projection)."""
+def frozen_linear(x, weight, bias, act="none", mask_dx=False, bwd_premasked=False):
+    """act(x W^T + b) for a FROZEN nn.Linear (reference :194-199, :273, :352-355 inside the frozen LM layers, lm_head :826),
+    act "none" | "relu".  mask_dx / bwd_premasked: as in `linear` -- `h = frozen_linear(x, W1, b1, act="relu", bwd_premasked=True);
+    y = frozen_linear(h, W2, b2, mask_dx=True)` puts fc1's ReLU backward into the epilogue of fc2's dgrad GEMM."""
     if weight.requires_grad or (bias is not None and bias.requires_grad):
         raise ValueError("frozen_linear: weight and bias must be frozen (requires_grad=False)")
     if x.shape[-1] != weight.shape[1]:
         raise ValueError(f"frozen_linear: x has {x.shape[-1]} features, weight expects {weight.shape[1]}")
-    code = 1 if relu else ACT_CODES.get(act or "none")
-    if code is None:
-        raise ValueError(f"frozen_linear: activation {act!r} is not fused")
-    if code > 1 and torch.is_grad_enabled() and x.requires_grad:
-        raise ValueError("frozen_linear: GELU epilogues are forward-only (frozen encoders); use relu / none under autograd")
-    if bwd_premasked and code != 1:
+    code = _act_code("frozen_linear", act)
+    if bwd_premasked and code != _lib.ACT_RELU:
         raise ValueError("frozen_linear: bwd_premasked needs the ReLU epilogue")
-    if residual is not None and (code or residual.shape[:-1] != x.shape[:-1] or residual.shape[-1] != weight.shape[0]):
-        raise ValueError("frozen_linear: `residual` ([..., out_features], added in the GEMM epilogue) goes with no activation")
-    _HANDOVER.relu_bits = None
-    mb = getattr(x, "_mmgl_relu_bits", None) if mask_dx else None
-    y = _FrozenLinear.apply(x, weight, bias, code, bool(mask_dx), bool(bwd_premasked), residual, None if mb is None else mb[0], 0 if mb is None else mb[1],
-                            0 if mb is None else mb[2])
-    if _HANDOVER.relu_bits is not None:                      # fc1 of a frozen FFN left its ReLU mask as bits: hand them to the consumer
-        y._mmgl_relu_bits, _HANDOVER.relu_bits = _HANDOVER.relu_bits, None
+    N, K = weight.shape
+    pitch, relu_out = N, None
+    if bwd_premasked:
+        # fc1 of a frozen FFN: its row pitch, and the rows whose ReLU mask leaves as bits -- whole rounds of the persistent kernel
+        # when the rest is a short tail, else all of them where the shape runs as whole tiles.  The plan reads x's rows densely.
+        x = x.contiguous()
+        M = x.numel() // K
+        pitch = _ffn_pitch(M, N, K, x.dtype)
+        if pitch != N:
+            rows = _round_split_rows(M, N, x.device)
+            nb = relu_bits_bytes(rows, N, K, K, K, pitch, x.dtype) if rows else 0
+            if not nb:
+                rows, nb = M, relu_bits_bytes(M, N, K, K, K, pitch, x.dtype)
+            if nb:
+                relu_out = (torch.empty(nb, dtype=torch.uint8, device=x.device), pitch, rows)
+    y = _FrozenLinear.apply(x, weight, bias, code, bool(mask_dx), bool(bwd_premasked), pitch, relu_out,
+                            getattr(x, "_mmgl_relu_bits", None) if mask_dx else None)
+    if relu_out is not None:         # fc2 (mask_dx) finds them here; one that does not (a wrapper or view dropped it) masks with y
+        y._mmgl_relu_bits = relu_out
     return y
-
-
-def frozen_linear_relu(x, weight, bias):
-    return frozen_linear(x, weight, bias, relu=True)
 
 
 # ------------------------------------------------------------------------------------------ Llama-family elementwise ops

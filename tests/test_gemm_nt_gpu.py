@@ -130,7 +130,7 @@ def test_frozen_ffn_pair_mask_dx(M, d, ffn):
     W2 = (torch.randn(d, ffn, device="cuda", generator=g) * ffn ** -0.5).bfloat16()
     b2 = (torch.randn(d, device="cuda", generator=g) * 0.1).bfloat16()
     w = torch.randn(M, d, device="cuda", generator=g).bfloat16()
-    h = ops.frozen_linear(x, W1, b1, relu=True, bwd_premasked=True)
+    h = ops.frozen_linear(x, W1, b1, act="relu", bwd_premasked=True)
     if M >= 2560:                    # whole tiles of the persistent kernel: the ReLU mask travels as bits, h is not kept for backward
         assert getattr(h, "_mmgl_relu_bits", None) is not None
     y = ops.frozen_linear(h, W2, b2, mask_dx=True)
@@ -375,7 +375,7 @@ def test_dynamic_tile_schedule_ffn_relu_bits():
     w2 = (torch.randn(2048, 8192, device="cuda") * 0.02).bfloat16()
 
     def run():
-        y = ops.frozen_linear(ops.frozen_linear(x, w1, b1, relu=True, bwd_premasked=True), w2, None, mask_dx=True)
+        y = ops.frozen_linear(ops.frozen_linear(x, w1, b1, act="relu", bwd_premasked=True), w2, None, mask_dx=True)
         (g,) = torch.autograd.grad(y.float().square().mean(), x)
         return y.detach(), g
     y0, g0 = run()

@@ -145,15 +145,17 @@ def test_add_layer_norm_pair_dropout_matches_unfused(dtype):
         assert bool((xa.grad[drop] == 0).all()) and bool((xb.grad[drop] == 0).all())
 
 
+# (12, 7): operands zero-padded to the MFMA alignment; 3 x 48 rows, as mmgl_relu_bwd covers whole 16-byte chunks (M * N % 8 == 0)
+@pytest.mark.parametrize("T,K,N", [(50, 64, 96), (48, 12, 7)])
 @pytest.mark.parametrize("dtype", DTYPES)
-def test_frozen_linear_relu(dtype):
+def test_frozen_linear_relu(dtype, T, K, N):
     from mmgl_amd import ops
     g = torch.Generator().manual_seed(5)
-    x = dev(torch.randn(3, 50, 64, generator=g), dtype)
-    W = (torch.randn(96, 64, generator=g) * 0.2).to(dtype).cuda()
-    b = (torch.randn(96, generator=g) * 0.2).to(dtype).cuda()
-    w = torch.randn(3, 50, 96, generator=g).to(dtype).cuda()
-    y = ops.frozen_linear_relu(x, W, b)
+    x = dev(torch.randn(3, T, K, generator=g), dtype)
+    W = (torch.randn(N, K, generator=g) * 0.2).to(dtype).cuda()
+    b = (torch.randn(N, generator=g) * 0.2).to(dtype).cuda()
+    w = torch.randn(3, T, N, generator=g).to(dtype).cuda()
+    y = ops.frozen_linear(x, W, b, act="relu")
     (y * w).sum().backward()
     xr = x.detach().float().cpu().requires_grad_()
     yr = F.relu(F.linear(xr, W.float().cpu(), b.float().cpu()))
@@ -163,7 +165,7 @@ def test_frozen_linear_relu(dtype):
     assert_close(y.float(), yr, t, "y")
     assert_close(x.grad.float(), xr.grad, t, "dx")
     with pytest.raises(ValueError):
-        ops.frozen_linear_relu(x, W.clone().requires_grad_(), b)
+        ops.frozen_linear(x, W.clone().requires_grad_(), b, act="relu")
     x2 = x.detach().clone().requires_grad_()              # plain frozen linear: dgrad against the cached W^T
     (ops.frozen_linear(x2, W, b) * w).sum().backward()
     xr2 = x.detach().float().cpu().requires_grad_()
