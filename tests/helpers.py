@@ -75,10 +75,34 @@ def elementwise_err(a: torch.Tensor, b: torch.Tensor, floor_frac: float = 1e-3, 
     """max over elements of |a - b| / (|b| + floor_frac * max|b|): an element-wise relative error (rel_err above is a max-norm measure:
     a small element of a tensor with a large maximum can be wrong by many times its own size and pass).  The floor -- a fraction of the
     tensor's largest magnitude -- keeps elements that are analytically ~0 from dividing round-off by nothing."""
-    a = a.detach().double().cpu()
-    b = b.detach().double().cpu()
+    a = a.detach().double()
+    b = b.detach().double().to(a.device)      # on the device `a` lives on: a [40960, 8192] gradient is checked where it was computed
     floor = max(floor_frac * b.abs().max().item(), abs_floor)      # abs_floor: analytically-zero tensors (d k_proj.bias) are round-off on both sides
     return ((a - b).abs() / (b.abs() + floor)).max().item()
+
+
+def slice_err(a: torch.Tensor, b: torch.Tensor, keep, floor_frac: float = 1e-3) -> torch.Tensor:
+    """Per-slice max-norm relative error: for every index along the dims in `keep` (e.g. (0, 2) of a [B, T, H, D] tensor: one
+    (sample, head) slice), max|a - b| / max|b| over the slice's other elements.  Returns the errors indexed by the `keep` dims.
+    A whole-tensor maximum hides a defect confined to one chunk, trip, head or split; this measure does not.  The floor -- a fraction
+    of the WHOLE tensor's largest magnitude -- keeps an analytically-zero slice (dQ of a sample with one valid key) from dividing
+    round-off by nothing."""
+    a = a.detach().double()
+    b = b.detach().double().to(a.device)
+    red = [i for i in range(b.dim()) if i not in keep]
+    d = (a - b).abs().amax(dim=red)
+    m = b.abs().amax(dim=red)
+    return (d / m.clamp_min(max(floor_frac * float(m.max()), 1e-30))).cpu()
+
+
+def tile_err(a: torch.Tensor, b: torch.Tensor, tile: int = 256, floor_frac: float = 1e-3) -> float:
+    """Largest slice_err over the tile x tile blocks of a 2-D tensor (ragged edge blocks included): a weight gradient whose one
+    output tile or one K split is off shows here even when the tensor's maximum lies in another tile."""
+    R, C = b.shape
+    pr, pc = (-R) % tile, (-C) % tile
+    pad = lambda t: torch.nn.functional.pad(t.detach().double(), (0, pc, 0, pr))
+    a, b = pad(a), pad(b.to(a.device))
+    return float(slice_err(a.view(-1, tile, a.shape[1] // tile, tile), b.view(-1, tile, b.shape[1] // tile, tile), (0, 2), floor_frac).max())
 
 
 def assert_close(a, b, tol, what="", floor=1e-6):

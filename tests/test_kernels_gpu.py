@@ -316,7 +316,9 @@ def test_linear(M, N, K, dtype, act):
 
 
 @pytest.mark.parametrize("act", ["none", "relu"])
-@pytest.mark.parametrize("M,N,K", [(8192 - 64, 4096, 4096),      # big forward (ragged M), big dgrad, big wgrad (256 tiles)
+@pytest.mark.parametrize("M,N,K", [(8192 - 64, 4096, 4096),      # big forward (ragged M), big dgrad; M no multiple of 128: the weight
+                                                                 # gradient runs on the 128x128 gemm_tx kernel, not gemm8p_tt
+                                   (8192, 4096, 4096),           # big wgrad on gemm8p_tt, unsplit (256 tiles; by reading gemm8p_tt_splits)
                                    (8192, 2048, 2048),           # 64-tile weight gradient: split-K x4 + fp32 reduce
                                    (8192, 6504, 2048)])          # trainable lm_head-like: N no multiple of 128 / 256 -> zero-padded
                                                                  # contraction in dgrad, ragged last tile row in the weight gradient
