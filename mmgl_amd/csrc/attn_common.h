@@ -37,7 +37,17 @@ template <typename T, int D_, int NSB_, int WORK_ = 1> struct XC {
     // is at most 2-way conflicted.
     static constexpr int LD = DPAD + 16;
     static constexpr int RMIMG = SPAD * LD;
+    // K and V of one staged block as the forward / dQ kernels hold them: one row image, the other operand row-major (bf16) or a second
+    // row image (f32).  What those launches ask for per buffer, next to their key-mask bytes.
+    static constexpr size_t KV_BYTES = sizeof(T) * (ROWIMG + (TIMG ? RMIMG : ROWIMG));
 };
+
+// dtype and head_dim rules shared by the cross- and self-attention entry points (each checks its own sizes first)
+inline int attn_check(const char* who, int D, int dtype) {
+    MMGL_CHECK_ARG(dtype == MMGL_F32 || dtype == MMGL_BF16, "%s: dtype must be MMGL_F32 or MMGL_BF16", who);
+    if (!(D == 16 || D == 32 || D == 64 || D == 128)) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: head_dim %d not in {16,32,64,128}", who, D);
+    return MMGL_OK;
+}
 
 template <typename C> __device__ __forceinline__ int rf_idx(int sb, int dc, int lane) {
     return ((sb * C::NDC + dc) * 64 + lane) * 8;

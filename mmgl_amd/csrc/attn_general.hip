@@ -330,15 +330,6 @@ __global__ __launch_bounds__(256) void ag_mask_kernel(uint8_t* mask, size_t n, f
         mask[i] = (p > 0.f && mmgl_hash32(seed, i) < thr) ? 0 : 1;
 }
 
-template <typename K> int ag_lds(K kern, size_t bytes) {
-    if (bytes > 160 * 1024) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "attn_general: %zu B of LDS", bytes);
-    if (bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    return MMGL_OK;
-}
-
 int ag_check(const char* who, int B, int H, int T, int S, int D, int causal, float p, int dtype) {
     MMGL_CHECK_ARG(B > 0 && H > 0 && T > 0 && S > 0 && D > 0, "%s: bad sizes B=%d H=%d T=%d S=%d D=%d", who, B, H, T, S, D);
     if (D > 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: head_dim %d > 128", who, D);
@@ -362,10 +353,10 @@ extern "C" int mmgl_attn_general_fwd(const void* q, const void* k, const void* v
     const dim3 grid(B * H * cdiv(T, AG_ROWS));
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MMGL_BF16) {
-        if (int rc = ag_lds(ag_fwd_kernel<bf16>, lds)) return rc;
+        if (int rc = mmgl_set_lds(ag_fwd_kernel<bf16>, lds, "attn_general")) return rc;
         hipLaunchKernelGGL(ag_fwd_kernel<bf16>, grid, dim3(256), lds, st, a);
     } else {
-        if (int rc = ag_lds(ag_fwd_kernel<float>, lds)) return rc;
+        if (int rc = mmgl_set_lds(ag_fwd_kernel<float>, lds, "attn_general")) return rc;
         hipLaunchKernelGGL(ag_fwd_kernel<float>, grid, dim3(256), lds, st, a);
     }
     MMGL_CHECK_LAUNCH("attn_general_fwd");
@@ -389,13 +380,13 @@ extern "C" int mmgl_attn_general_bwd(const void* dout, const void* q, const void
     const size_t lds2 = ((size_t)(2 * AG_KC + 2 * AG_RB) * (D + 1) + 2 * AG_RB * AG_KC) * sizeof(float);
     const dim3 g1(B * H * cdiv(T, AG_ROWS)), g2(B * H * cdiv(S, AG_KC));
     if (dtype == MMGL_BF16) {
-        if (int rc = ag_lds(ag_bwd_dq_kernel<bf16>, lds1)) return rc;
-        if (int rc = ag_lds(ag_bwd_dkv_kernel<bf16>, lds2)) return rc;
+        if (int rc = mmgl_set_lds(ag_bwd_dq_kernel<bf16>, lds1, "attn_general")) return rc;
+        if (int rc = mmgl_set_lds(ag_bwd_dkv_kernel<bf16>, lds2, "attn_general")) return rc;
         hipLaunchKernelGGL(ag_bwd_dq_kernel<bf16>, g1, dim3(256), lds1, st, a);
         hipLaunchKernelGGL(ag_bwd_dkv_kernel<bf16>, g2, dim3(256), lds2, st, a);
     } else {
-        if (int rc = ag_lds(ag_bwd_dq_kernel<float>, lds1)) return rc;
-        if (int rc = ag_lds(ag_bwd_dkv_kernel<float>, lds2)) return rc;
+        if (int rc = mmgl_set_lds(ag_bwd_dq_kernel<float>, lds1, "attn_general")) return rc;
+        if (int rc = mmgl_set_lds(ag_bwd_dkv_kernel<float>, lds2, "attn_general")) return rc;
         hipLaunchKernelGGL(ag_bwd_dq_kernel<float>, g1, dim3(256), lds1, st, a);
         hipLaunchKernelGGL(ag_bwd_dkv_kernel<float>, g2, dim3(256), lds2, st, a);
     }

@@ -32,6 +32,12 @@ void mmgl_set_error(const char* fmt, ...);
         if (e_ != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "%s: %s", name, hipGetErrorString(e_)); \
     } while (0)
 
+// launch configuration (lib.hip).  mmgl_set_lds: call in front of every launch with dynamic LDS; raises the kernel's limit once per
+// (kernel, device) when the launch needs more than the 48 KiB default.  `who` names the caller in the error message.
+int mmgl_set_lds(const void* kernel, size_t bytes, const char* who);
+template <typename K> int mmgl_set_lds(K* kernel, size_t bytes, const char* who) { return mmgl_set_lds((const void*)kernel, bytes, who); }
+int mmgl_num_cu();                       // CUs of the current device
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -189,7 +189,7 @@ inline bool gemm8p_use_splits(int M, int N, int K) {
 // tiles on 256 CUs, a second round at a quarter of the chip): rows [0, m1) = the whole rounds on the persistent kernel, the tail rows
 // on the few-tile kernel -- 102.6 -> 78.3 us at 2560x8192x2048 (tools/probes/gemm_msplit.py).  0 = no split.
 inline int gemm8p_row_split(int M, int N, int K, int ldx, int ldw, int ldy) {
-    const int G = gemm8p_num_cu(), tm = cdiv(M, 256), tn = cdiv(N, 256);
+    const int G = mmgl_num_cu(), tm = cdiv(M, 256), tn = cdiv(N, 256);
     const int rounds = tm * tn / G, rem = tm * tn % G;
     // (round 5 tried the same split for ANY number of whole rounds plus a remainder of a third to a half of a round -- config 4 at
     // B = 64: [45056, 2048] = 5.5 rounds, the remainder as one round of the few-tile kernel: mmgl_gemm_nt 310.6 -> 307.8 ms per step,
@@ -287,8 +287,7 @@ int launch_nt128(const T* X, const T* W, T* Y, const T* bias, int M, int N, int 
     const void* kern;
     if (glds) kern = act == MMGL_ACT_RELU ? (const void*)gemm_nt_kernel<T, MMGL_ACT_RELU, true> : (const void*)gemm_nt_kernel<T, MMGL_ACT_NONE, true>;
     else kern = act == MMGL_ACT_RELU ? (const void*)gemm_nt_kernel<T, MMGL_ACT_RELU, false> : (const void*)gemm_nt_kernel<T, MMGL_ACT_NONE, false>;
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    if (int rc = mmgl_set_lds(kern, lds, "gemm_nt")) return rc;
     dim3 grid(tiles_m * tiles_n), block(256);
 #define NT_LAUNCH(A, G) hipLaunchKernelGGL((gemm_nt_kernel<T, A, G>), grid, block, lds, st, X, W, Y, bias, M, N, K, scale, accumulate, X2, W2, K2, tiles_m, tiles_n)
     if (glds) { if (act == MMGL_ACT_RELU) NT_LAUNCH(MMGL_ACT_RELU, true); else NT_LAUNCH(MMGL_ACT_NONE, true); }
@@ -691,8 +690,7 @@ int launch_gemm_tx(bool tb, const bf16* Aop, int lda, const bf16* Bop, int ldb, 
 #define TX_LAUNCH(TBV, MK, GL)                                                                                              \
     do {                                                                                                                    \
         auto kf = gemm_tx_kernel<TBV, MK, GL>;                                                                              \
-        hipError_t e = hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
-        if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));                      \
+        if (int rc = mmgl_set_lds(kf, lds, "gemm_tx")) return rc;                                                           \
         hipLaunchKernelGGL(kf, grid, block, lds, st, Aop, lda, Bop, ldb, ymask, Out, RA, RB, K, scale, accumulate, tiles_a, tiles_b); \
     } while (0)
     if (glds) { if (tb) TX_LAUNCH(true, false, true); else TX_LAUNCH(false, false, true); }

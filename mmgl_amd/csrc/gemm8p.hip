@@ -652,16 +652,6 @@ __global__ __launch_bounds__(256) void p8_splitk_finish_kernel(const float* __re
 //    320 tiles on 256 CUs): the remainder would occupy a quarter of the chip for a whole tile time; cut into K splits it takes a
 //    quarter of that.
 // N % 8 == 0 is implied by gemm8p_supported.
-static int p8_num_cu() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-    }
-    return n;
-}
-int gemm8p_num_cu() { return p8_num_cu(); }
 void gemm8p_plan(int M, int N, int K, int* direct, int* nsplit) {
     const int tiles = cdiv(M, 256) * cdiv(N, 256), units = K / 128;
     *direct = tiles;
@@ -682,7 +672,7 @@ void gemm8p_plan(int M, int N, int K, int* direct, int* nsplit) {
     constexpr int hybrid = 3;                             // smallest split count worth it
     // up to 12 whole rounds (round 4: Llama's 17408-row outputs with N = 4096 are 1088 tiles = 4.25 rounds -- o_proj, down_proj and,
     // in the backward pass, the dgrads of q|k|v and gate|up, K up to 22016: a fifth round at a quarter of the chip cost 15 % of each)
-    const int G = p8_num_cu(), rounds = tiles / G, r = tiles % G;
+    const int G = mmgl_num_cu(), rounds = tiles / G, r = tiles % G;
     if (!hybrid || rounds < 1 || rounds > 12 || r == 0) return;
     int s = G / r;
     if (s > 8) s = 8;
@@ -753,21 +743,7 @@ int launch_gemm8p(const bf16* X, int ldx, const bf16* W, int ldw, bf16* Y, int l
     if (bits_out && (act != 1 || resid || zmask)) MMGL_FAIL(MMGL_ERR_INVALID, "gemm8p: mask bits are written by the plain ReLU epilogue only");
     if (bits_in && (zmask || resid || act != 0)) MMGL_FAIL(MMGL_ERR_INVALID, "gemm8p: mask bits are applied by the plain epilogue only");
     if (bits_out || bits_in) part = nullptr;             // whole tiles only: the bits are indexed by (tile, wave, lane)
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess)
-            MMGL_FAIL(MMGL_ERR_HIP, "gemm8p: hipGetDeviceProperties failed");
-        n_cu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-        const void* ks[9] = {(const void*)gemm8p_kernel<0, false>, (const void*)gemm8p_kernel<0, true>, (const void*)gemm8p_kernel<1, false>,
-                             (const void*)gemm8p_kernel<1, true>,  (const void*)gemm8p_kernel<2, false>, (const void*)gemm8p_kernel<3, false>,
-                             (const void*)gemm8p_kernel<3, true>,  (const void*)gemm8p_kernel<4, true>,  (const void*)gemm8p_kernel<5, false>};
-        for (const void* kf : ks) {
-            hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, P8_LDS_ALLOC);
-            if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        }
-    }
+    const int n_cu = mmgl_num_cu();
     // the work plan (gemm8p_plan): whole tiles [0, direct), then K-split work items for the rest with fp32 scratch tiles in the
     // CALLER's memory (gemm8p_split_bytes), folded -- with the whole epilogue -- by p8_splitk_finish_kernel.  Without scratch
     // nothing is split.
@@ -792,7 +768,11 @@ int launch_gemm8p(const bf16* X, int ldx, const bf16* W, int ldw, bf16* Y, int l
         if (const char* e = getenv("MMGL_P8_TRACE_WG")) a.trace_wg = atoi(e);
 #endif
         const bool zr = resid || zmask || bits_in;
-#define P8_LAUNCH(A, Z) hipLaunchKernelGGL((gemm8p_kernel<A, Z>), dim3(grid), dim3(512), P8_LDS_ALLOC, st, a)
+#define P8_LAUNCH(A, Z)                                                                                     \
+    do {                                                                                                    \
+        if (int rc = mmgl_set_lds(gemm8p_kernel<A, Z>, P8_LDS_ALLOC, "gemm8p")) return rc;                  \
+        hipLaunchKernelGGL((gemm8p_kernel<A, Z>), dim3(grid), dim3(512), P8_LDS_ALLOC, st, a);              \
+    } while (0)
         switch (act) {
             case 0: if (zr) P8_LAUNCH(0, true); else P8_LAUNCH(0, false); break;
             case 1: if (zr) P8_LAUNCH(1, true); else P8_LAUNCH(1, false); break;
@@ -813,6 +793,7 @@ int launch_gemm8p(const bf16* X, int ldx, const bf16* W, int ldw, bf16* Y, int l
         a.part = part;
         a.trace = nullptr;
         const int items = rest * nsplit, g = items < n_cu ? items : n_cu;
+        if (int rc = mmgl_set_lds(gemm8p_kernel<5, false>, P8_LDS_ALLOC, "gemm8p (K split)")) return rc;
         hipLaunchKernelGGL((gemm8p_kernel<5, false>), dim3(g), dim3(512), P8_LDS_ALLOC, st, a);
         MMGL_CHECK_LAUNCH("gemm8p (K split)");
         int blocks = rest * 32;                                  // 8192 vectors per tile, 256 per block and trip

@@ -315,7 +315,7 @@ int gemm8p_tt_splits(int RA, int RB, int M) {
     // item to write them plus 0.06 per partial tile for the fold (256 KiB written and read back at ~5 TB/s, chip-wide).  A 768 x 768
     // gradient over 40960 rows (9 tiles) takes 20 splits (180 items of 16 steps) instead of 16 (144 of 20), a 3072 x 768 one 5
     // (180 x 64) instead of 8 (288 items = two rounds of 40); 64 tiles stay at 4 splits, outputs of >= 256 tiles unsplit.
-    const int tiles = (RA / 256) * (RB / 256), units = M / 128, G = gemm8p_num_cu();
+    const int tiles = (RA / 256) * (RB / 256), units = M / 128, G = mmgl_num_cu();
     int best = 0, best_cost = 0;
     for (int s = 1; s <= 32; ++s) {
         if (units % s || M / s < 256) continue;
@@ -334,16 +334,8 @@ int launch_gemm8p_tt(const bf16* A, int lda, const bf16* B, int ldb, bf16* Out, 
     T8Args a;
     a.A = A; a.B = B; a.Out = Out; a.part = part; a.RA = RA; a.RB = RB; a.Mk = M / nsplit; a.lda = lda; a.ldb = ldb; a.scale = scale;
     a.accumulate = accumulate; a.tiles_a = cdiv(RA, 256); a.tiles_b = cdiv(RB, 256); a.nsplit = nsplit; a.total = a.tiles_a * a.tiles_b * nsplit;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "gemm8p_tt: hipGetDeviceProperties failed");
-        n_cu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-        hipError_t e = hipFuncSetAttribute((const void*)gemm8p_tt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS);
-        if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    const int grid = a.total < n_cu ? a.total : n_cu;
+    if (int rc = mmgl_set_lds(gemm8p_tt_kernel, T8_LDS, "gemm8p_tt")) return rc;
+    const int n_cu = mmgl_num_cu(), grid = a.total < n_cu ? a.total : n_cu;
     hipLaunchKernelGGL(gemm8p_tt_kernel, dim3(grid), dim3(512), T8_LDS, st, a);
     MMGL_CHECK_LAUNCH("gemm8p_tt");
     return MMGL_OK;

@@ -228,12 +228,7 @@ int launch_gemm_mid(const bf16* X, int ldx, const bf16* W, int ldw, bf16* Y, int
     a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.scale = scale; a.act = act;
     a.tiles_m = cdiv(M, 128); a.tiles_n = cdiv(N, 128);
     constexpr int LDS = GM_NS * GM_STAGE;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_mid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute(gemm_mid): %s", hipGetErrorString(e));
-        configured = true;
-    }
+    if (int rc = mmgl_set_lds(gemm_mid_kernel, LDS, "gemm_mid")) return rc;
     hipLaunchKernelGGL(gemm_mid_kernel, dim3(a.tiles_m * a.tiles_n), dim3(256), LDS, st, a);
     MMGL_CHECK_LAUNCH("gemm_mid");
     return MMGL_OK;

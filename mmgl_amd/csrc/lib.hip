@@ -1,6 +1,8 @@
-// libmmgl_hip.so: error channel + version.
+// libmmgl_hip.so: error channel, launch configuration shared by every kernel family, version.
 #include "common.h"
 #include <string.h>
+#include <atomic>
+#include <mutex>
 
 static thread_local char g_err[512] = "";
 
@@ -12,6 +14,56 @@ void mmgl_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* mmgl_last_error(void) { return g_err; }
+
+// The dynamic-LDS limit is raised ONCE per (kernel, device), to the hardware maximum (the attribute is a launch limit, not an allocation: the
+// launch's own dynamic size decides occupancy): at the reference's batch the step is launch-bound and this call sat in front of every
+// launch above 48 KiB.  Lookup is lock-free; the first use of a (kernel, device) pair takes a mutex, so two threads
+// with different LDS sizes cannot leave the attribute below what the table says (it is never lowered: there is one value).
+// The value set is the 160 KiB of a CU minus the kernel's static LDS: two attn_general kernels carry 256 B that the compiler put there,
+// every other kernel with dynamic LDS has none and gets the whole maximum.
+int mmgl_set_lds(const void* kernel, size_t bytes, const char* who) {
+    constexpr size_t kMaxLds = 160 * 1024;
+    if (bytes > kMaxLds) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: needs %zu B of LDS (> 160 KiB)", who, bytes);
+    if (bytes <= 48 * 1024) return MMGL_OK;
+    constexpr int kSlots = 1024;                        // (kernel, device) pairs; under 200 kernels take dynamic LDS, few of them above 48 KiB
+    struct Slot { std::atomic<const void*> fn{nullptr}; int dev = -1; };
+    static Slot slots[kSlots];
+    static std::atomic<int> used{0};
+    static std::mutex mu;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const int n = used.load(std::memory_order_acquire);
+    for (int i = 0; i < n; ++i)
+        if (slots[i].fn.load(std::memory_order_relaxed) == kernel && slots[i].dev == dev) return MMGL_OK;
+    std::lock_guard<std::mutex> lock(mu);
+    const int n2 = used.load(std::memory_order_acquire);
+    for (int i = n; i < n2; ++i)
+        if (slots[i].fn.load(std::memory_order_relaxed) == kernel && slots[i].dev == dev) return MMGL_OK;
+    hipFuncAttributes fa;
+    hipError_t e = hipFuncGetAttributes(&fa, kernel);
+    if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMaxLds - fa.sharedSizeBytes));
+    if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "%s: raising the dynamic LDS limit: %s", who, hipGetErrorString(e));
+    if (n2 < kSlots) {                                  // a full table only costs the call again next time
+        slots[n2].dev = dev;
+        slots[n2].fn.store(kernel, std::memory_order_relaxed);
+        used.store(n2 + 1, std::memory_order_release);
+    }
+    return MMGL_OK;
+}
+
+// CUs of the current device (= workgroups of a full persistent launch), looked up once per device; 256 where there is no device to ask
+// (the planners that size K splits by it also run on a machine without one).
+int mmgl_num_cu() {
+    static std::atomic<int> cus[64];
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    std::atomic<int>& slot = cus[dev & 63];
+    if ((n = slot.load(std::memory_order_relaxed))) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    slot.store(n, std::memory_order_relaxed);
+    return n;
+}
+
 // ABI version: bumped whenever an exported signature changes (mmgl_amd/_lib.py refuses a library that reports another one -- a
 // stale build would otherwise load and run with misaligned arguments).  101: mmgl_xattn_fwd lost p_drop / seed / offset.
 // 102: round 4 (tile counters bound to one stream; entry points added / removed with the kernel families).

@@ -725,23 +725,14 @@ __global__ __launch_bounds__(128 * PAR) void selfattn_bwd_dkv_kernel(const T* __
 }
 
 // ============================================================================================ host
-template <typename K> int set_lds_sa(K kern, size_t bytes) {
-    if (bytes > 160 * 1024) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "selfattn: needs %zu B of LDS (> 160 KiB)", bytes);
-    if (bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    return MMGL_OK;
-}
-
 template <typename T, int D>
 int sa_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, void* out, float* lse, int B, int H, int T_,
            int ldq, int P, int ldk, hipStream_t st) {
     typedef SC<T, D> C;
     const int QB = 4 * 16 * C::QT, nqb = cdiv(T_, QB);
-    const size_t lds = 2 * (sizeof(T) * (C::ROWIMG + (C::TIMG ? C::RMIMG : C::ROWIMG)) + KT);
+    const size_t lds = 2 * (C::KV_BYTES + KT);
     auto kern = selfattn_fwd_kernel<T, D>;
-    int rc = set_lds_sa(kern, lds);
+    int rc = mmgl_set_lds(kern, lds, "selfattn");
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(B * H * nqb), dim3(256), lds, st, (const T*)q, (const T*)k, (const T*)v, valid, (T*)out, lse, B, H,
                        T_, nqb, ldq, P, ldk);
@@ -763,9 +754,9 @@ int sa_bwd(const void* dout, const void* q, const void* k, const void* v, const 
     {
         typedef XC<T, D, 4, 2> C;
         const int QB = 4 * 16 * C::QT, nqb = cdiv(T_, QB);
-        const size_t lds = 2 * (sizeof(T) * ((C::TIMG ? C::RMIMG : C::ROWIMG) + C::ROWIMG) + KT);
+        const size_t lds = 2 * (C::KV_BYTES + KT);
         auto kern = selfattn_bwd_dq_kernel<T, D>;
-        int rc = set_lds_sa(kern, lds);
+        int rc = mmgl_set_lds(kern, lds, "selfattn");
         if (rc) return rc;
         hipLaunchKernelGGL(kern, dim3(B * H * nqb), dim3(256), lds, st, (const T*)dout, (const T*)q, (const T*)k, (const T*)v, lse,
                            delta, valid, (T*)dq, B, H, T_, nqb, ldq, ldg, P, ldk);
@@ -783,13 +774,13 @@ int sa_bwd(const void* dout, const void* q, const void* k, const void* v, const 
         };
         if (lds_for(2) <= 160 * 1024) {
             auto kern = selfattn_bwd_dkv_kernel<T, D, 2>;
-            int rc = set_lds_sa(kern, lds_for(2));
+            int rc = mmgl_set_lds(kern, lds_for(2), "selfattn");
             if (rc) return rc;
             hipLaunchKernelGGL(kern, dim3(B * H * nkb), dim3(256), lds_for(2), st, (const T*)dout, (const T*)q, (const T*)k, (const T*)v,
                                lse, delta, valid, (T*)dk, (T*)dv, B, H, T_, nkb, ldq, ldgk, P, ldk);
         } else {
             auto kern = selfattn_bwd_dkv_kernel<T, D, 1>;
-            int rc = set_lds_sa(kern, lds_for(1));
+            int rc = mmgl_set_lds(kern, lds_for(1), "selfattn");
             if (rc) return rc;
             hipLaunchKernelGGL(kern, dim3(B * H * nkb), dim3(128), lds_for(1), st, (const T*)dout, (const T*)q, (const T*)k, (const T*)v,
                                lse, delta, valid, (T*)dk, (T*)dv, B, H, T_, nkb, ldq, ldgk, P, ldk);
@@ -805,9 +796,9 @@ int enc_fwd(const void* q, const void* k, const void* v, const int* cu, void* ou
     typedef SC<T, D> C;
     const int QB = 4 * 16 * C::QT;
     const int nqb = cdiv(max_len < q_rows ? max_len : q_rows, QB);
-    const size_t lds = 2 * (sizeof(T) * (C::ROWIMG + (C::TIMG ? C::RMIMG : C::ROWIMG)) + KT);
+    const size_t lds = 2 * (C::KV_BYTES + KT);
     auto kern = encattn_fwd_kernel<T, D>;
-    int rc = set_lds_sa(kern, lds);
+    int rc = mmgl_set_lds(kern, lds, "selfattn");
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(nseq * H * nqb), dim3(256), lds, st, (const T*)q, (const T*)k, (const T*)v, cu, (T*)out, nseq, H,
                        ld_in, ld_out, nqb, q_rows);
@@ -817,18 +808,18 @@ int enc_fwd(const void* q, const void* k, const void* v, const int* cu, void* ou
 
 int sa_check(const char* who, int B, int H, int T, int D, int dtype) {
     MMGL_CHECK_ARG(B > 0 && H > 0 && T > 0, "%s: B,H,T must be positive (got %d,%d,%d)", who, B, H, T);
-    MMGL_CHECK_ARG(dtype == MMGL_F32 || dtype == MMGL_BF16, "%s: dtype must be MMGL_F32 or MMGL_BF16", who);
-    if (!(D == 16 || D == 32 || D == 64 || D == 128)) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: head_dim %d not in {16,32,64,128}", who, D);
-    return MMGL_OK;
+    return attn_check(who, D, dtype);
 }
 
-#define SA_DISPATCH(FN, T, ...)                        \
+// the 16x16 kernels of this file, for what sa32_supported turns down: fp32, head_dim 16 / 32, more than 4096 keys
+#define SA_DISPATCH_D(FN, T, ...)                      \
     switch (D) {                                       \
         case 16: return FN<T, 16>(__VA_ARGS__);        \
         case 32: return FN<T, 32>(__VA_ARGS__);        \
         case 64: return FN<T, 64>(__VA_ARGS__);        \
         default: return FN<T, 128>(__VA_ARGS__);       \
     }
+#define SA_DISPATCH(FN, ...) do { if (dtype == MMGL_BF16) SA_DISPATCH_D(FN, bf16, __VA_ARGS__) SA_DISPATCH_D(FN, float, __VA_ARGS__) } while (0)
 
 }  // namespace
 
@@ -845,9 +836,8 @@ extern "C" int mmgl_selfattn_prefix_fwd(const void* q, const void* k, const void
     MMGL_CHECK_ARG(q && k && v && key_valid && out && lse && P >= 0, "mmgl_selfattn_prefix_fwd: bad arguments");
     if ((rc = sa_ld("mmgl_selfattn_prefix_fwd", ld_q, H, D)) || (rc = sa_ld("mmgl_selfattn_prefix_fwd", ld_kv, H, D))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16 && sa32_supported(D, T + P)) return sa32_fwd(q, k, v, key_valid, out, lse, B, H, T, P, D, ld_q, ld_kv, st);
-    if (dtype == MMGL_BF16) { SA_DISPATCH(sa_fwd, bf16, q, k, v, key_valid, out, lse, B, H, T, ld_q, P, ld_kv, st) }
-    SA_DISPATCH(sa_fwd, float, q, k, v, key_valid, out, lse, B, H, T, ld_q, P, ld_kv, st)
+    if (sa32_supported(dtype, D, T + P)) return sa32_fwd(q, k, v, key_valid, out, lse, B, H, T, P, D, ld_q, ld_kv, st);
+    SA_DISPATCH(sa_fwd, q, k, v, key_valid, out, lse, B, H, T, ld_q, P, ld_kv, st);
 }
 
 extern "C" int mmgl_selfattn_fwd(const void* q, const void* k, const void* v, const uint8_t* key_valid, void* out, float* lse,
@@ -871,13 +861,10 @@ extern "C" int mmgl_selfattn_prefix_bwd(const void* dout, const void* q, const v
     MMGL_CHECK_ARG(workspace_bytes >= mmgl_selfattn_bwd_workspace(B, H, T), "mmgl_selfattn_prefix_bwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     float* delta = (float*)workspace;
-    if (dtype == MMGL_BF16 && sa32_supported(D, T + P)) {
-        // dQ (+ delta) kernel, then the dK / dV kernel (head_dim 128: one workgroup per CU, 304 registers; Llama shape 1743 -> 1289 us
-        // against the 16x16 dK / dV kernel it replaced)
-        return sa32_bwd(dout, q, k, v, out, lse, key_valid, dq, dk, dv, delta, B, H, T, P, D, ld_q, ld_kv, ld_dq, ld_dkv, 3, st);
-    }
-    if (dtype == MMGL_BF16) { SA_DISPATCH(sa_bwd, bf16, dout, q, k, v, out, lse, key_valid, dq, dk, dv, delta, B, H, T, ld_q, ld_dq, P, ld_kv, ld_dkv, st) }
-    SA_DISPATCH(sa_bwd, float, dout, q, k, v, out, lse, key_valid, dq, dk, dv, delta, B, H, T, ld_q, ld_dq, P, ld_kv, ld_dkv, st)
+    // dQ (+ delta) kernel, then the dK / dV kernel (head_dim 128: one workgroup per CU, 304 registers; Llama shape 1743 -> 1289 us
+    // against the 16x16 dK / dV kernel it replaced)
+    if (sa32_supported(dtype, D, T + P)) return sa32_bwd(dout, q, k, v, out, lse, key_valid, dq, dk, dv, delta, B, H, T, P, D, ld_q, ld_kv, ld_dq, ld_dkv, st);
+    SA_DISPATCH(sa_bwd, dout, q, k, v, out, lse, key_valid, dq, dk, dv, delta, B, H, T, ld_q, ld_dq, P, ld_kv, ld_dkv, st);
 }
 
 extern "C" int mmgl_selfattn_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
@@ -896,7 +883,6 @@ extern "C" int mmgl_encattn_fwd(const void* q, const void* k, const void* v, con
     MMGL_CHECK_ARG(ld_in >= H * D && ld_out >= H * D && ld_in % 8 == 0 && ld_out % 8 == 0,
                    "mmgl_encattn_fwd: row strides (%d, %d) must be >= H*D = %d and multiples of 8 elements", ld_in, ld_out, H * D);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16 && sa32_supported(D, max_len)) return sa32_enc_fwd(q, k, v, cu_seqlens, out, nseq, H, D, ld_in, ld_out, max_len, q_rows, st);
-    if (dtype == MMGL_BF16) { SA_DISPATCH(enc_fwd, bf16, q, k, v, cu_seqlens, out, nseq, H, ld_in, ld_out, max_len, q_rows, st) }
-    SA_DISPATCH(enc_fwd, float, q, k, v, cu_seqlens, out, nseq, H, ld_in, ld_out, max_len, q_rows, st)
+    if (sa32_supported(dtype, D, max_len)) return sa32_enc_fwd(q, k, v, cu_seqlens, out, nseq, H, D, ld_in, ld_out, max_len, q_rows, st);
+    SA_DISPATCH(enc_fwd, q, k, v, cu_seqlens, out, nseq, H, ld_in, ld_out, max_len, q_rows, st);
 }

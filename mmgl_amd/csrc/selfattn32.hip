@@ -931,12 +931,7 @@ __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dk
 template <int D, bool CAUSAL> int launch_fwd(const SA32Args& a, int nblocks, hipStream_t st) {
     typedef G32<D> G;
     auto kern = sa32_fwd_kernel<D, CAUSAL>;
-    static bool configured = false;                 // per instantiation
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute(sa32_fwd): %s", hipGetErrorString(e));
-        configured = true;
-    }
+    if (int rc = mmgl_set_lds(kern, G::LDS, "sa32_fwd")) return rc;
     hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), G::LDS, st, a);
     MMGL_CHECK_LAUNCH("sa32_fwd");
     return MMGL_OK;
@@ -946,12 +941,7 @@ template <int D> int launch_bwd_dq(const SA32BwdArgs& a, hipStream_t st) {
     typedef G32<D> G;
     constexpr int LDS = SA32_NS_DQ * G::SLOTB + G::MAXT * 8;
     auto kern = sa32_bwd_dq_kernel<D>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute(sa32_bwd_dq): %s", hipGetErrorString(e));
-        configured = true;
-    }
+    if (int rc = mmgl_set_lds(kern, LDS, "sa32_bwd_dq")) return rc;
     hipLaunchKernelGGL(kern, dim3(a.B * a.H * a.nqb), dim3(256), LDS, st, a);
     MMGL_CHECK_LAUNCH("sa32_bwd_dq");
     return MMGL_OK;
@@ -960,12 +950,7 @@ template <int D> int launch_bwd_dq(const SA32BwdArgs& a, hipStream_t st) {
 template <int D> int launch_bwd_dkv(const SA32BwdArgs& a, hipStream_t st) {
     typedef GB32<D> GB;
     auto kern = sa32_bwd_dkv_kernel<D>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, GB::LDS);
-        if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute(sa32_bwd_dkv): %s", hipGetErrorString(e));
-        configured = true;
-    }
+    if (int rc = mmgl_set_lds(kern, GB::LDS, "sa32_bwd_dkv")) return rc;
     hipLaunchKernelGGL(kern, dim3(a.B * a.H * a.nkb), dim3(256), GB::LDS, st, a);
     MMGL_CHECK_LAUNCH("sa32_bwd_dkv");
     return MMGL_OK;
@@ -973,7 +958,7 @@ template <int D> int launch_bwd_dkv(const SA32BwdArgs& a, hipStream_t st) {
 
 }  // namespace
 
-bool sa32_supported(int D, int Tk) { return (D == 64 || D == 128) && Tk <= 64 * 64; }
+bool sa32_supported(int dtype, int D, int Tk) { return dtype == MMGL_BF16 && (D == 64 || D == 128) && Tk <= 64 * 64; }
 
 int sa32_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, void* out, float* lse, int B, int H, int T, int P,
              int D, int ldq, int ldk, hipStream_t st) {
@@ -998,16 +983,12 @@ int sa32_enc_fwd(const void* q, const void* k, const void* v, const int* cu, voi
 }
 
 int sa32_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse, const uint8_t* valid,
-             void* dq, void* dk, void* dv, float* delta, int B, int H, int T, int P, int D, int ldq, int ldk, int ldg, int ldgk, int parts,
+             void* dq, void* dk, void* dv, float* delta, int B, int H, int T, int P, int D, int ldq, int ldk, int ldg, int ldgk,
              hipStream_t st) {
     SA32BwdArgs a{};
     a.dout = (const bf16*)dout; a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (const bf16*)out; a.lse = lse;
     a.valid = valid; a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.delta = delta;
     a.B = B; a.H = H; a.T = T; a.P = P; a.nqb = cdiv(T, 128); a.nkb = cdiv(T + P, 128); a.ldq = ldq; a.ldk = ldk; a.ldg = ldg; a.ldgk = ldgk;
-    int rc = MMGL_OK;
-    if (parts & 1) rc = D == 64 ? launch_bwd_dq<64>(a, st) : launch_bwd_dq<128>(a, st);
-    if (rc == MMGL_OK && (parts & 2)) {
-        rc = D == 64 ? launch_bwd_dkv<64>(a, st) : launch_bwd_dkv<128>(a, st);
-    }
-    return rc;
+    if (int rc = D == 64 ? launch_bwd_dq<64>(a, st) : launch_bwd_dq<128>(a, st)) return rc;
+    return D == 64 ? launch_bwd_dkv<64>(a, st) : launch_bwd_dkv<128>(a, st);
 }

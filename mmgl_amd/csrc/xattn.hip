@@ -22,8 +22,6 @@
 // Both are "fragment linear": a fragment read is one conflict-free ds_read_b128 per lane.
 // fp32 activations skip the t image (LDS budget) and gather it from the row image with scalar reads.
 #include "attn_common.h"
-#include <atomic>
-#include <mutex>
 
 namespace {
 
@@ -1134,20 +1132,27 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
 }
 
 // ============================================================================================ host dispatch
-struct BwdPlan { int nsg, nchunk, rows_per_chunk; size_t delta_off, dk_off, dv_off, total; };
+// The backward kernels.  ONE_WAVE: xattn_bwd_fused_kernel, one pass over Q / dO, one wave holds all keys.  MULTI_WAVE:
+// xattn_bwd_fusedw_kernel, one pass with the keys split over NSB / 2 waves.  TWO_KERNEL: xattn_bwd_dq_kernel, then xattn_bwd_dkv_kernel
+// with 32 keys per wave.  (Round 5 removed a bf16-only 64-key dK / dV variant: since the one-pass kernels took every BASELINE shape it
+// only served bf16 with S > 128 or head_dim 16 / 32 with S > 64, which the generic kernel covers.)
+enum BwdRoute { ONE_WAVE, MULTI_WAVE, TWO_KERNEL };
 
-// (the two-kernel backward below the fused ones: 32 keys per dK/dV wave.  Round 5 removed its bf16-only 64-key variant,
-// xattn_bwd_dkv64_kernel: since the one-pass kernels took every BASELINE shape it only served bf16 with S > 128 or head_dim 16 / 32
-// with S > 64, which the generic kernel covers)
-inline constexpr bool use_fused_bwd() { return true; }
+// THE choice of backward kernel; bwd_plan sizes chunks and workspace by it and launch_bwd launches it.  Constant over the key range of
+// one NSB (32 / 64 / 128 / 256 keys), which is how launch_bwd<T, D, NSB> knows at compile time which kernel it has to instantiate.
+constexpr BwdRoute bwd_route(int S, int D, size_t esz) {
+    if (esz != 2) return TWO_KERNEL;
+    if (D <= 64 && S <= 64) return ONE_WAVE;
+    if ((D == 64 || D == 128) && S <= 128) return MULTI_WAVE;
+    return TWO_KERNEL;
+}
 
-// the multi-wave one-pass backward (xattn_bwd_fusedw_kernel): bf16, head_dim 64 / 128, up to 128 keys, and not the shapes the one-wave
-// fused kernel takes (D <= 64 with S <= 64)
-inline bool use_fusedw(int S, int D, size_t esz) { return esz == 2 && S <= 128 && (D == 128 || (D == 64 && S > 64)); }
+struct BwdPlan { BwdRoute route; int nsg, nchunk, rows_per_chunk; size_t delta_off, dk_off, dv_off, total; };
 
 BwdPlan bwd_plan(int B, int H, int T, int S, int D, size_t esz = 2) {
     BwdPlan p;
-    const bool fw = use_fusedw(S, D, esz);
+    p.route = bwd_route(S, D, esz);
+    const bool fw = p.route == MULTI_WAVE;
     p.nsg = fw ? 1 : (S + 31) / 32;
     long units = (long)B * H * p.nsg;
     // fusedw: one workgroup per CU (LDS); a chunk costs a set of fp32 dK / dV partials, so chunks only while (batch, head) pairs
@@ -1193,51 +1198,31 @@ void fwd_geometry(int B, int H, int T, int tile_rows, int& rows_per_wg, int& nch
     nchunk = (T + rows - 1) / rows;
 }
 
-// hipFuncSetAttribute ONCE per (kernel, device), to the hardware maximum (the attribute is a launch limit, not an allocation: the
-// launch's own dynamic size decides occupancy): at the reference's batch the step is launch-bound and this call sat in front of every
-// cross-attention launch above 48 KiB.  Lookup is lock-free; the first use of a (kernel, device) pair takes a mutex, so two threads
-// with different LDS sizes cannot leave the attribute below what the table says (it is never lowered: there is one value).
-template <typename K> int set_lds(K kern, size_t bytes) {
-    constexpr size_t kMaxLds = 160 * 1024;
-    if (bytes > kMaxLds) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "xattn: S*D needs %zu B of LDS (> 160 KiB)", bytes);
-    if (bytes <= 48 * 1024) return MMGL_OK;
-    struct Slot { std::atomic<const void*> fn{nullptr}; int dev = -1; };
-    static Slot slots[256];
-    static std::atomic<int> used{0};
-    static std::mutex mu;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const void* fn = (const void*)kern;
-    const int n = used.load(std::memory_order_acquire);
-    for (int i = 0; i < n; ++i)
-        if (slots[i].fn.load(std::memory_order_relaxed) == fn && slots[i].dev == dev) return MMGL_OK;
-    std::lock_guard<std::mutex> lock(mu);
-    const int n2 = used.load(std::memory_order_acquire);
-    for (int i = n; i < n2; ++i)
-        if (slots[i].fn.load(std::memory_order_relaxed) == fn && slots[i].dev == dev) return MMGL_OK;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    if (e != hipSuccess) MMGL_FAIL(MMGL_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    if (n2 < 256) {                                     // a full table only costs the call again next time
-        slots[n2].dev = dev;
-        slots[n2].fn.store(fn, std::memory_order_relaxed);
-        used.store(n2 + 1, std::memory_order_release);
-    }
-    return MMGL_OK;
-}
-
 template <typename T, int D, int NSB>
 int launch_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, void* out, float* lse, int B, int H,
                int T_, int S, hipStream_t st) {
     typedef XC<T, D, NSB> C;
     int rpw, nchunk;
     fwd_geometry(B, H, T_, 16 * C::QT, rpw, nchunk);
-    size_t lds = sizeof(T) * (C::ROWIMG + (C::TIMG ? C::RMIMG : C::ROWIMG)) + C::SPAD;
+    size_t lds = C::KV_BYTES + C::SPAD;
     auto kern = xattn_fwd_kernel<T, D, NSB>;
-    int rc = set_lds(kern, lds);
+    int rc = mmgl_set_lds(kern, lds, "xattn");
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(B * H * nchunk), dim3(256), lds, st, (const T*)q, (const T*)k, (const T*)v, valid,
                        (T*)out, lse, B, H, T_, S, rpw, nchunk);
     MMGL_CHECK_LAUNCH("xattn_fwd");
+    return MMGL_OK;
+}
+
+// dK / dV = sum over the plan's chunks of the fp32 partials
+template <typename T>
+int reduce_partials(const float* dkp, const float* dvp, void* dk, void* dv, int B, int H, int S, int D, int nchunk, hipStream_t st) {
+    size_t n4 = (size_t)B * S * H * D / 4;
+    int blocks = (int)((n4 + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(blocks), dim3(256), 0, st, dkp, (T*)dk, n4, n4, nchunk);
+    hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(blocks), dim3(256), 0, st, dvp, (T*)dv, n4, n4, nchunk);
+    MMGL_CHECK_LAUNCH("xattn_bwd_reduce");
     return MMGL_OK;
 }
 
@@ -1246,90 +1231,68 @@ int launch_bwd(const void* dout, const void* q, const void* k, const void* v, co
                void* dq, void* dk, void* dv, char* ws, int B, int H, int T_, int S, hipStream_t st) {
     typedef XC<T, D, NSB, 2> C;
     const BwdPlan p = bwd_plan(B, H, T_, S, D, sizeof(T));
+    constexpr BwdRoute ROUTE = bwd_route(16 * NSB, D, sizeof(T));     // the kernel this <T, D, NSB> instantiates
+    if (p.route != ROUTE)
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "xattn_bwd: S=%d D=%d is planned for route %d, its %d-key instantiation serves route %d", S, D,
+                  (int)p.route, 16 * NSB, (int)ROUTE);
     float* delta = (float*)(ws + p.delta_off);
     float* dkp = (float*)(ws + p.dk_off);
     float* dvp = (float*)(ws + p.dv_off);
-    if constexpr (sizeof(T) == 2 && (D == 128 || D == 64) && NSB <= 8 && !(D <= 64 && NSB <= 4)) {
+    if constexpr (ROUTE == MULTI_WAVE) {
         // one pass over Q / dO with the keys split over NSB / 2 waves (p.nsg == 1: a workgroup holds all keys)
         constexpr int NW = NSB / 2, LDT = C::DPAD + 16;
         const size_t lds = sizeof(bf16) * (C::RMIMG + 2 * 2 * 32 * LDT + NW * 2 * 32 * 48 + NW * 2 * 64 * 8) + (NW * 32 + 2 * 32) * sizeof(float) + C::SPAD;
         auto kern = xattn_bwd_fusedw_kernel<D, NSB>;
-        int rc = set_lds(kern, lds);
+        int rc = mmgl_set_lds(kern, lds, "xattn");
         if (rc) return rc;
         hipLaunchKernelGGL(kern, dim3(B * H * p.nchunk), dim3(64 * NW), lds, st, (const bf16*)dout, (const bf16*)q, (const bf16*)k,
                            (const bf16*)v, lse, valid, (bf16*)dq, (bf16*)dk, (bf16*)dv, dkp, dvp, B, H, T_, S, p.rows_per_chunk, p.nchunk);
         MMGL_CHECK_LAUNCH("xattn_bwd_fusedw");
-        if (p.nchunk > 1) {
-            size_t n4 = (size_t)B * S * H * D / 4;
-            int blocks = (int)((n4 + 255) / 256);
-            if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(blocks), dim3(256), 0, st, dkp, (T*)dk, n4, n4, p.nchunk);
-            hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(blocks), dim3(256), 0, st, dvp, (T*)dv, n4, n4, p.nchunk);
-            MMGL_CHECK_LAUNCH("xattn_bwd_reduce");
-        }
-        return MMGL_OK;
-    }
-    if constexpr (sizeof(T) == 2 && D <= 64 && NSB <= 4) {
-        if (use_fused_bwd()) {                                // one pass over Q / dO (p.nsg == 1 here: all keys in one wave)
-            constexpr int LDT = C::DPAD + 16, LDP = C::SPAD + 16;
-            const size_t lds = sizeof(bf16) * (C::RMIMG + C::ROWIMG + 2 * 32 * LDT + 2 * 32 * LDP) + C::SPAD;
-            auto kern = xattn_bwd_fused_kernel<D, NSB>;
-            int rc = set_lds(kern, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL(kern, dim3(B * H * p.nchunk), dim3(64), lds, st, (const bf16*)dout, (const bf16*)q, (const bf16*)k,
-                               (const bf16*)v, lse, valid, (bf16*)dq, (bf16*)dk, (bf16*)dv, dkp, dvp, B, H, T_, S, p.rows_per_chunk,
-                               p.nchunk);
-            MMGL_CHECK_LAUNCH("xattn_bwd_fused");
-            if (p.nchunk > 1) {
-                size_t n4 = (size_t)B * S * H * D / 4;
-                int blocks = (int)((n4 + 255) / 256);
-                if (blocks > 2048) blocks = 2048;
-                hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(blocks), dim3(256), 0, st, dkp, (T*)dk, n4, n4, p.nchunk);
-                hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(blocks), dim3(256), 0, st, dvp, (T*)dv, n4, n4, p.nchunk);
-                MMGL_CHECK_LAUNCH("xattn_bwd_reduce");
-            }
-            return MMGL_OK;
-        }
-    }
-    {
-        int rpw, nchunk;
-        fwd_geometry(B, H, T_, 16 * C::QT, rpw, nchunk);
-        size_t lds = sizeof(T) * (C::ROWIMG + (C::TIMG ? C::RMIMG : C::ROWIMG)) + C::SPAD;
-        auto kern = xattn_bwd_dq_kernel<T, D, NSB>;
-        int rc = set_lds(kern, lds);
+        return p.nchunk > 1 ? reduce_partials<T>(dkp, dvp, dk, dv, B, H, S, D, p.nchunk, st) : MMGL_OK;
+    } else if constexpr (ROUTE == ONE_WAVE) {
+        // one pass over Q / dO, one wave per workgroup holding all keys.  p.nsg (1 up to 32 keys, 2 up to 64) only enters the plan's
+        // chunk count here; the grid is B * H * nchunk
+        constexpr int LDT = C::DPAD + 16, LDP = C::SPAD + 16;
+        const size_t lds = sizeof(bf16) * (C::RMIMG + C::ROWIMG + 2 * 32 * LDT + 2 * 32 * LDP) + C::SPAD;
+        auto kern = xattn_bwd_fused_kernel<D, NSB>;
+        int rc = mmgl_set_lds(kern, lds, "xattn");
         if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3(B * H * nchunk), dim3(256), lds, st, (const T*)dout, (const T*)q, (const T*)k,
-                           (const T*)v, lse, valid, (T*)dq, delta, B, H, T_, S, rpw, nchunk);
-        MMGL_CHECK_LAUNCH("xattn_bwd_dq");
-    }
-    {
-        typedef XC<T, D, 2> C2;
-        constexpr int DLD = C2::DPAD + (sizeof(T) == 2 ? 8 : 4);
-        size_t lds = sizeof(T) * (2 * C2::ROWIMG + 2 * 32 * DLD);
-        auto kern = xattn_bwd_dkv_kernel<T, D>;
-        int rc = set_lds(kern, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3(B * H * p.nsg * p.nchunk), dim3(64), lds, st, (const T*)dout, (const T*)q,
-                           (const T*)k, (const T*)v, lse, delta, valid, dkp, dvp, B, H, T_, S, p.nsg, p.rows_per_chunk,
+        hipLaunchKernelGGL(kern, dim3(B * H * p.nchunk), dim3(64), lds, st, (const bf16*)dout, (const bf16*)q, (const bf16*)k,
+                           (const bf16*)v, lse, valid, (bf16*)dq, (bf16*)dk, (bf16*)dv, dkp, dvp, B, H, T_, S, p.rows_per_chunk,
                            p.nchunk);
-        MMGL_CHECK_LAUNCH("xattn_bwd_dkv");
+        MMGL_CHECK_LAUNCH("xattn_bwd_fused");
+        return p.nchunk > 1 ? reduce_partials<T>(dkp, dvp, dk, dv, B, H, S, D, p.nchunk, st) : MMGL_OK;
+    } else {
+        {
+            int rpw, nchunk;
+            fwd_geometry(B, H, T_, 16 * C::QT, rpw, nchunk);
+            size_t lds = C::KV_BYTES + C::SPAD;
+            auto kern = xattn_bwd_dq_kernel<T, D, NSB>;
+            int rc = mmgl_set_lds(kern, lds, "xattn");
+            if (rc) return rc;
+            hipLaunchKernelGGL(kern, dim3(B * H * nchunk), dim3(256), lds, st, (const T*)dout, (const T*)q, (const T*)k,
+                               (const T*)v, lse, valid, (T*)dq, delta, B, H, T_, S, rpw, nchunk);
+            MMGL_CHECK_LAUNCH("xattn_bwd_dq");
+        }
+        {
+            typedef XC<T, D, 2> C2;
+            constexpr int DLD = C2::DPAD + (sizeof(T) == 2 ? 8 : 4);
+            size_t lds = sizeof(T) * (2 * C2::ROWIMG + 2 * 32 * DLD);
+            auto kern = xattn_bwd_dkv_kernel<T, D>;
+            int rc = mmgl_set_lds(kern, lds, "xattn");
+            if (rc) return rc;
+            hipLaunchKernelGGL(kern, dim3(B * H * p.nsg * p.nchunk), dim3(64), lds, st, (const T*)dout, (const T*)q,
+                               (const T*)k, (const T*)v, lse, delta, valid, dkp, dvp, B, H, T_, S, p.nsg, p.rows_per_chunk,
+                               p.nchunk);
+            MMGL_CHECK_LAUNCH("xattn_bwd_dkv");
+        }
+        return reduce_partials<T>(dkp, dvp, dk, dv, B, H, S, D, p.nchunk, st);
     }
-    {
-        size_t n4 = (size_t)B * S * H * D / 4;
-        int blocks = (int)((n4 + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(blocks), dim3(256), 0, st, dkp, (T*)dk, n4, n4, p.nchunk);
-        hipLaunchKernelGGL(reduce_partials_kernel<T>, dim3(blocks), dim3(256), 0, st, dvp, (T*)dv, n4, n4, p.nchunk);
-        MMGL_CHECK_LAUNCH("xattn_bwd_reduce");
-    }
-    return MMGL_OK;
 }
 
 int check_shape(const char* who, int B, int H, int T, int S, int D, int dtype) {
     MMGL_CHECK_ARG(B > 0 && H > 0 && T > 0 && S > 0, "%s: B,H,T,S must be positive (got %d,%d,%d,%d)", who, B, H, T, S);
-    MMGL_CHECK_ARG(dtype == MMGL_F32 || dtype == MMGL_BF16, "%s: dtype must be MMGL_F32 or MMGL_BF16", who);
-    if (!(D == 16 || D == 32 || D == 64 || D == 128))
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: head_dim %d not in {16,32,64,128}", who, D);
+    if (int rc = attn_check(who, D, dtype)) return rc;
     if (S > 256) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: %d neighbor key tokens > 256 (single-pass kernel)", who, S);
     return MMGL_OK;
 }

@@ -15,6 +15,30 @@ from ._lib import dtype_code, lib, ptr, ptr_off, require_cuda, stream_ptr
 
 
 # ------------------------------------------------------------------------------------------ attention core
+def _check_mask(key_valid, shape):
+    if key_valid.shape != shape:
+        raise ValueError(f"Attention mask should be of size {tuple(shape)}, but is {tuple(key_valid.shape)}")
+
+
+def _key_valid(key_valid):
+    """key_valid [B, keys] (True = attend) as the contiguous uint8 the kernels read; after every check, so that a refused call does no
+    GPU work."""
+    if key_valid.dtype != torch.uint8:
+        key_valid = key_valid.to(torch.uint8)
+    return key_valid.contiguous()
+
+
+def _attn_args(op, q, k, v, key_valid, num_heads, extra_keys=None, tail=""):
+    """The argument checks of every attention op, raised the way the reference does: q [B,T,d], k and v [B,S,d] (with S = T + extra_keys
+    where the op fixes it), d a multiple of num_heads, key_valid [B,S]."""
+    if (q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]
+            or (extra_keys is not None and k.shape[1] != q.shape[1] + extra_keys)):
+        raise ValueError(f"{op}: incompatible shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)}{tail}")
+    if q.shape[2] % num_heads:
+        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {q.shape[2]} and `num_heads`: {num_heads}).")
+    _check_mask(key_valid, k.shape[:2])
+
+
 class _XAttnCore(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, key_valid, num_heads):
@@ -51,15 +75,8 @@ def xattn_core(q, k, v, key_valid, num_heads):
     """softmax(max(q k^T + M, finfo.min)) v per head.  q [B,T,d] is already scaled; k, v [B,S,d];
     key_valid [B,S] bool/uint8 (True = attend).  Mirrors the core of MPTAttention.forward
     (reference model/modelling_cross_attention.py:206-271)."""
-    if q.dim() != 3 or k.shape != v.shape or k.dim() != 3 or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
-        raise ValueError(f"xattn_core: incompatible shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)}")
-    if q.shape[2] % num_heads:
-        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {q.shape[2]} and `num_heads`: {num_heads}).")
-    if key_valid.shape != k.shape[:2]:
-        raise ValueError(f"Attention mask should be of size {tuple(k.shape[:2])}, but is {tuple(key_valid.shape)}")
-    if key_valid.dtype != torch.uint8:
-        key_valid = key_valid.to(torch.uint8)
-    return _XAttnCore.apply(q, k, v, key_valid.contiguous(), num_heads)
+    _attn_args("xattn_core", q, k, v, key_valid, num_heads)
+    return _XAttnCore.apply(q, k, v, _key_valid(key_valid), num_heads)
 
 
 # ------------------------------------------------------------------------------------------ general (unfused) attention core
@@ -108,12 +125,7 @@ def attn_general(q, k, v, key_valid, num_heads, causal=False, head_mask=None, p_
     before dropout (:246-254); the returned tensor is DETACHED (the reference keeps it in the graph, ":248 make sure that attn_weights
     keeps its gradient": differentiating through the returned probabilities is not supported here and autograd will say so) --, `p_drop` drops probabilities in training (:256; counter hash of (seed, index),
     regenerated in backward).  q [B,T,d] is already scaled; causal = the decoder's self-attention (S == T).  Returns (out, probs | None)."""
-    if q.dim() != 3 or k.shape != v.shape or k.dim() != 3 or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
-        raise ValueError(f"attn_general: incompatible shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)}")
-    if q.shape[2] % num_heads:
-        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {q.shape[2]} and `num_heads`: {num_heads}).")
-    if key_valid.shape != k.shape[:2]:
-        raise ValueError(f"Attention mask should be of size {tuple(k.shape[:2])}, but is {tuple(key_valid.shape)}")
+    _attn_args("attn_general", q, k, v, key_valid, num_heads)
     if head_mask is not None and tuple(head_mask.shape) != (num_heads,):
         raise ValueError(f"Head mask for a single layer should be of size {(num_heads,)}, but is {tuple(head_mask.shape)}")
     if head_mask is not None and head_mask.requires_grad and torch.is_grad_enabled():
@@ -121,12 +133,10 @@ def attn_general(q, k, v, key_valid, num_heads, causal=False, head_mask=None, p_
         # This kernel treats it as a constant -- refuse rather than hand back a silent zero gradient
         raise NotImplementedError("attn_general: head_mask.requires_grad is not supported (the kernel computes no gradient for the head "
                                   "mask); detach it, or differentiate a per-head scale applied outside the attention core")
-    if key_valid.dtype != torch.uint8:
-        key_valid = key_valid.to(torch.uint8)
     p = float(p_drop) if training else 0.0
     if p > 0.0 and seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    return _AttnGeneral.apply(q, k, v, key_valid.contiguous(), head_mask, num_heads, bool(causal), p, int(seed or 0), bool(output_attentions))
+    return _AttnGeneral.apply(q, k, v, _key_valid(key_valid), head_mask, num_heads, bool(causal), p, int(seed or 0), bool(output_attentions))
 
 
 def attn_dropout_mask(B, H, T, S, p_drop, seed, device):
@@ -137,35 +147,53 @@ def attn_dropout_mask(B, H, T, S, p_drop, seed, device):
 
 
 # ------------------------------------------------------------------------------------------ causal self-attention
-class _SelfAttnCore(torch.autograd.Function):
+# One pair of call helpers for every self-attention op.  q / k / v (and dq / dk / dv) are device pointers.  P is None: the plain entry
+# points mmgl_selfattn_fwd / _bwd, rows `ld` (`ldg` for the gradients) elements apart, 0 = packed.  P >= 0: mmgl_selfattn_prefix_fwd /
+# _bwd with P always-visible keys in front of the T causal ones, packed.  `like` gives dtype and device.
+def _selfattn_fwd(like, qp, kp, vp, key_valid, B, T, d, H, P, ld):
+    out = torch.empty(B, T, d, dtype=like.dtype, device=like.device)
+    lse = torch.empty(B, H, T, dtype=torch.float32, device=like.device)
+    work = dict(flops=2.0 * B * T * (T + 2 * (P or 0)) * d, bytes=4.0 * B * T * d * like.element_size())
+    if P is None:
+        _lib.call("mmgl_selfattn_fwd", work, qp, kp, vp, ptr(key_valid), ptr(out), ptr(lse), B, H, T, d // H, ld, dtype_code(like), stream_ptr())
+    else:
+        _lib.call("mmgl_selfattn_prefix_fwd", work, qp, kp, vp, ptr(key_valid), ptr(out), ptr(lse), B, H, T, P, d // H, 0, 0, dtype_code(like),
+                  stream_ptr())
+    return out, lse
+
+
+def _selfattn_bwd(like, dout, qp, kp, vp, out, lse, key_valid, dqp, dkp, dvp, B, T, d, H, P, ld, ldg):
+    dout = dout.contiguous()
+    nbytes = lib().mmgl_selfattn_bwd_workspace(B, H, T)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=like.device)
+    work = dict(flops=5.0 * B * T * (T + 2 * (P or 0)) * d, bytes=8.0 * B * T * d * like.element_size())
+    ptrs = (ptr(dout), qp, kp, vp, ptr(out), ptr(lse), ptr(key_valid), dqp, dkp, dvp, ptr(ws), nbytes)
+    if P is None:
+        _lib.call("mmgl_selfattn_bwd", work, *ptrs, B, H, T, d // H, ld, ldg, dtype_code(like), stream_ptr())
+    else:
+        _lib.call("mmgl_selfattn_prefix_bwd", work, *ptrs, B, H, T, P, d // H, 0, 0, 0, 0, dtype_code(like), stream_ptr())
+
+
+class _SelfAttn(torch.autograd.Function):
+    """Causal self-attention over separate q [B,T,d], k, v [B,P+T,d]; P is None for selfattn_core (see _selfattn_fwd)."""
+
     @staticmethod
-    def forward(ctx, q, k, v, key_valid, num_heads):
+    def forward(ctx, q, k, v, key_valid, num_heads, P):
         require_cuda(q, k, v, key_valid)
         B, T, d = q.shape
-        D = d // num_heads
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        out = torch.empty_like(q)
-        lse = torch.empty(B, num_heads, T, dtype=torch.float32, device=q.device)
-        _lib.call("mmgl_selfattn_fwd", dict(flops=2.0 * B * T * T * d, bytes=4.0 * B * T * d * q.element_size()),
-                  ptr(q), ptr(k), ptr(v), ptr(key_valid), ptr(out), ptr(lse), B, num_heads, T, D, 0, dtype_code(q), stream_ptr())
+        out, lse = _selfattn_fwd(q, ptr(q), ptr(k), ptr(v), key_valid, B, T, d, num_heads, P, 0)
         ctx.save_for_backward(q, k, v, key_valid, out, lse)
-        ctx.num_heads = num_heads
+        ctx.num_heads, ctx.P = num_heads, P
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, key_valid, out, lse = ctx.saved_tensors
-        H = ctx.num_heads
         B, T, d = q.shape
-        D = d // H
-        dout = dout.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        nbytes = lib().mmgl_selfattn_bwd_workspace(B, H, T)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-        _lib.call("mmgl_selfattn_bwd", dict(flops=5.0 * B * T * T * d, bytes=8.0 * B * T * d * q.element_size()),
-                  ptr(dout), ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(key_valid), ptr(dq), ptr(dk), ptr(dv), ptr(ws), nbytes,
-                  B, H, T, D, 0, 0, dtype_code(q), stream_ptr())
-        return dq, dk, dv, None, None
+        _selfattn_bwd(q, dout, ptr(q), ptr(k), ptr(v), out, lse, key_valid, ptr(dq), ptr(dk), ptr(dv), B, T, d, ctx.num_heads, ctx.P, 0, 0)
+        return dq, dk, dv, None, None, None
 
 
 class _SelfAttnFusedQKV(torch.autograd.Function):
@@ -177,14 +205,9 @@ class _SelfAttnFusedQKV(torch.autograd.Function):
         require_cuda(qkv, key_valid)
         B, T, d3 = qkv.shape
         d = d3 // 3
-        D = d // num_heads
         qkv = qkv.contiguous()
-        out = torch.empty(B, T, d, dtype=qkv.dtype, device=qkv.device)
-        lse = torch.empty(B, num_heads, T, dtype=torch.float32, device=qkv.device)
         es = qkv.element_size()
-        _lib.call("mmgl_selfattn_fwd", dict(flops=2.0 * B * T * T * d, bytes=4.0 * B * T * d * es),
-                  ptr(qkv), ptr_off(qkv, d * es), ptr_off(qkv, 2 * d * es), ptr(key_valid), ptr(out), ptr(lse), B, num_heads, T, D, d3,
-                  dtype_code(qkv), stream_ptr())
+        out, lse = _selfattn_fwd(qkv, ptr(qkv), ptr_off(qkv, d * es), ptr_off(qkv, 2 * d * es), key_valid, B, T, d, num_heads, None, d3)
         ctx.save_for_backward(qkv, key_valid, out, lse)
         ctx.num_heads = num_heads
         return out
@@ -192,18 +215,12 @@ class _SelfAttnFusedQKV(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         qkv, key_valid, out, lse = ctx.saved_tensors
-        H = ctx.num_heads
         B, T, d3 = qkv.shape
         d = d3 // 3
-        D = d // H
         es = qkv.element_size()
-        dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
-        nbytes = lib().mmgl_selfattn_bwd_workspace(B, H, T)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
-        _lib.call("mmgl_selfattn_bwd", dict(flops=5.0 * B * T * T * d, bytes=8.0 * B * T * d * es),
-                  ptr(dout), ptr(qkv), ptr_off(qkv, d * es), ptr_off(qkv, 2 * d * es), ptr(out), ptr(lse), ptr(key_valid),
-                  ptr(dqkv), ptr_off(dqkv, d * es), ptr_off(dqkv, 2 * d * es), ptr(ws), nbytes, B, H, T, D, d3, d3, dtype_code(qkv), stream_ptr())
+        _selfattn_bwd(qkv, dout, ptr(qkv), ptr_off(qkv, d * es), ptr_off(qkv, 2 * d * es), out, lse, key_valid,
+                      ptr(dqkv), ptr_off(dqkv, d * es), ptr_off(dqkv, 2 * d * es), B, T, d, ctx.num_heads, None, d3, d3)
         return dqkv, None, None
 
 
@@ -211,73 +228,23 @@ def selfattn_core_fused(qkv, key_valid, num_heads):
     """selfattn_core over a fused projection output: qkv [B,T,3d] = [q*scale | k | v] along the last dim."""
     if qkv.dim() != 3 or qkv.shape[2] % (3 * num_heads):
         raise ValueError(f"selfattn_core_fused: qkv{tuple(qkv.shape)} is not [B, T, 3*H*D] for H={num_heads}")
-    if key_valid.shape != qkv.shape[:2]:
-        raise ValueError(f"Attention mask should be of size {tuple(qkv.shape[:2])}, but is {tuple(key_valid.shape)}")
-    if key_valid.dtype != torch.uint8:
-        key_valid = key_valid.to(torch.uint8)
-    return _SelfAttnFusedQKV.apply(qkv, key_valid.contiguous(), num_heads)
+    _check_mask(key_valid, qkv.shape[:2])
+    return _SelfAttnFusedQKV.apply(qkv, _key_valid(key_valid), num_heads)
 
 
 def selfattn_core(q, k, v, key_valid, num_heads):
     """Causal self-attention softmax(mask(q k^T)) v with mask = (s <= t) & key_valid[b, s]; q is already scaled.
     The caller guarantees key_valid[:, 0] is all ones (see include/mmgl_hip.h).  (reference :203-271 self branch)"""
-    if q.dim() != 3 or q.shape != k.shape or k.shape != v.shape:
-        raise ValueError(f"selfattn_core: incompatible shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)}")
-    if q.shape[2] % num_heads:
-        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {q.shape[2]} and `num_heads`: {num_heads}).")
-    if key_valid.shape != q.shape[:2]:
-        raise ValueError(f"Attention mask should be of size {tuple(q.shape[:2])}, but is {tuple(key_valid.shape)}")
-    if key_valid.dtype != torch.uint8:
-        key_valid = key_valid.to(torch.uint8)
-    return _SelfAttnCore.apply(q, k, v, key_valid.contiguous(), num_heads)
-
-
-class _SelfAttnPrefix(torch.autograd.Function):
-    """Causal self-attention with P always-visible prefix keys in front of the T causal ones (mmgl_selfattn_prefix_fwd/_bwd)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, key_valid, num_heads, P):
-        require_cuda(q, k, v, key_valid)
-        B, T, d = q.shape
-        D = d // num_heads
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        out = torch.empty_like(q)
-        lse = torch.empty(B, num_heads, T, dtype=torch.float32, device=q.device)
-        _lib.call("mmgl_selfattn_prefix_fwd", dict(flops=2.0 * B * T * (T + 2 * P) * d, bytes=4.0 * B * T * d * q.element_size()),
-                  ptr(q), ptr(k), ptr(v), ptr(key_valid), ptr(out), ptr(lse), B, num_heads, T, P, D, 0, 0, dtype_code(q), stream_ptr())
-        ctx.save_for_backward(q, k, v, key_valid, out, lse)
-        ctx.num_heads, ctx.P = num_heads, P
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, key_valid, out, lse = ctx.saved_tensors
-        H, P = ctx.num_heads, ctx.P
-        B, T, d = q.shape
-        D = d // H
-        dout = dout.contiguous()
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        nbytes = lib().mmgl_selfattn_bwd_workspace(B, H, T)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-        _lib.call("mmgl_selfattn_prefix_bwd", dict(flops=5.0 * B * T * (T + 2 * P) * d, bytes=8.0 * B * T * d * q.element_size()),
-                  ptr(dout), ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(key_valid), ptr(dq), ptr(dk), ptr(dv), ptr(ws), nbytes,
-                  B, H, T, P, D, 0, 0, 0, 0, dtype_code(q), stream_ptr())
-        return dq, dk, dv, None, None, None
+    _attn_args("selfattn_core", q, k, v, key_valid, num_heads, 0)
+    return _SelfAttn.apply(q, k, v, _key_valid(key_valid), num_heads, None)
 
 
 def selfattn_core_prefix(q, k, v, key_valid, num_heads, prefix_len):
     """softmax(mask(q k^T)) v where k, v [B, P+T, d] carry P = prefix_len always-visible rows in front of the T causal ones:
     mask = (s <= t + P) & key_valid[b, s]; q [B, T, d] is already scaled.  The attention of an OPT layer under peft prefix tuning
     (reference model/modelling_self_attention.py:88-93: HF prepends the learned per-layer key/value prefix as past_key_values)."""
-    if q.dim() != 3 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2] or k.shape[1] != q.shape[1] + prefix_len:
-        raise ValueError(f"selfattn_core_prefix: incompatible shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} for a prefix of {prefix_len}")
-    if q.shape[2] % num_heads:
-        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {q.shape[2]} and `num_heads`: {num_heads}).")
-    if key_valid.shape != k.shape[:2]:
-        raise ValueError(f"Attention mask should be of size {tuple(k.shape[:2])}, but is {tuple(key_valid.shape)}")
-    if key_valid.dtype != torch.uint8:
-        key_valid = key_valid.to(torch.uint8)
-    return _SelfAttnPrefix.apply(q, k, v, key_valid.contiguous(), num_heads, int(prefix_len))
+    _attn_args("selfattn_core_prefix", q, k, v, key_valid, num_heads, prefix_len, f" for a prefix of {prefix_len}")
+    return _SelfAttn.apply(q, k, v, _key_valid(key_valid), num_heads, int(prefix_len))
 
 
 def _ws(nbytes, device):
