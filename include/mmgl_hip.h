@@ -381,6 +381,33 @@ int mmgl_allgather(void* comm, const void* in, void* out, size_t count_per_rank,
 int mmgl_broadcast(void* comm, void* buf, size_t count, int dtype, int root, void* stream);
 int mmgl_comm_destroy(void* comm);
 
+/* ---------------------------------------------------------------------------------------------
+ * Greedy generation with a key/value cache: the two kernels of a decode step (csrc/decode.hip).
+ * replaces: the sequential generation of the test protocol, language_modelling/run_generation.py:597-603
+ *   (model.module.generate(..., max_new_tokens=32)), which the reference's wrappers cannot serve: its self-attention
+ *   returns no cache (model/modelling_cross_attention.py:372), the decoder collects none (:629) and the causal LM hands
+ *   past_key_values = None on (:851-870).  Forward only.
+ *
+ * mmgl_gemm_skinny: y[M,N] = act((x[M,K] . W[N,K]^T + bias) * scale) + residual for 1 <= M <= 64 rows -- every linear of a decode
+ *   step (q, k|v, out_proj, fc1 + ReLU, fc2, lm_head on the last row).  x, W, y row-major with unit column stride and row strides
+ *   ldx, ldw, ldy; ldy may be a whole cache row (the k|v projection writes column `t` of the cache in place).  bias [N] and
+ *   residual [M, ldy] may be NULL.  act: MMGL_ACT_NONE / MMGL_ACT_RELU.  bf16 with K % 64 == 0, N % 8 == 0 and 16-byte aligned
+ *   rows streams W from HBM once into MFMA fragments; every other shape, and fp32, runs a plain one-wave-per-column kernel.
+ *   Deterministic (fixed-order fold of the K partials, no atomics).  M > 64: MMGL_ERR_UNSUPPORTED -- chunk the rows or call mmgl_gemm_nt.
+ *
+ * mmgl_attn_decode_fwd: out[b, h*D..] = softmax(q[b, h] . K[b, :, h]^T masked) V[b, :, h], one query row per (batch, head).
+ *   q         [B, H*D] row stride ldq, already scaled by D^-0.5
+ *   k, v      S rows of H*D per sample, row stride ldkv, sample stride batch_stride_kv (elements): column slabs of the cache rows
+ *             [B, capacity, 2 H D], or the projected neighbor tokens [B, S, H*D]
+ *   key_valid [B, S] uint8 with row stride ld_valid, 1 = attend.  Causality is the caller's: a cache holds only keys at or before
+ *             the query.  A sample with no valid key gets the uniform distribution over its S keys (as mmgl_xattn_fwd).
+ *   out       [B, H*D] dense
+ *   D in {16,32,64,128} (those of mmgl_xattn_fwd); any S >= 1; strides multiples of 16 bytes.  fp32 softmax. */
+int mmgl_gemm_skinny(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* residual, void* y, int ldy,
+                     int M, int N, int K, int act, float scale, int dtype, void* stream);
+int mmgl_attn_decode_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,
+                         const uint8_t* key_valid, int ld_valid, void* out, int B, int H, int S, int D, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

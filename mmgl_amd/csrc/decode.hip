@@ -1,0 +1,371 @@
+// Decode-step kernels: the weight-streaming GEMM for M = batch rows and single-query attention over a key/value cache.
+// Reached only from the generation path (ops.decode_linear / ops.attn_decode); no training or prefill caller routes here.
+//
+// mmgl_gemm_skinny, bf16 (skinny_mfma_kernel).  Y[M,N] = epi(X[M,K] . W[N,K]^T), 1 <= M <= 64.  The step is bound by the weight bytes:
+//   * W is the MFMA A operand (as everywhere in this library) and goes HBM -> VGPR as 16-byte lane loads in A-fragment shape, two per lane
+//     and 64-wide K unit ("pair"): lane (i, g) reads W[n0 + i][64 p + 16 g .. + 15], so the four lane groups of a row cover one whole
+//     128-byte line.  v_mfma_f32_16x16x32_bf16 accepts any k order that A and B share: MFMA t of a pair contracts k = 16 g + 8 t + (0..7).
+//     No LDS round trip for W; a ring of DW pairs per lane is in flight (issued DW iterations ahead of their use).
+//   * the K range is dealt over the workgroup's 4 waves pair by pair (slot s takes pairs s, s + NS, ...).  Each wave stages only the x
+//     columns of its own pairs: whole 128-byte lines (8 rows x 8 lanes x 16 B per instruction) into an XOR-swizzled [rows][8 x 16 B]
+//     LDS image, read back as B fragments with ds_read_b128.  x is at most 1 MiB and stays in L2.
+//   * a workgroup owns 16 weight rows.  Where N / 16 would leave CUs without work (N = 2048: 128 workgroups on 256 CUs) it owns 8 (HALF):
+//     lanes i >= 8 then hold the same 8 rows at the wave's SECOND K slot, and every A fragment feeds two MFMAs -- one against the x
+//     of slot 0 (rows 0..7 of that accumulator are the result), one against the x of slot 1 (rows 8..15) -- so no lane loads a byte
+//     twice and none idles.
+//   * the per-slot fp32 partials are folded through LDS in slot order by the epilogue threads: deterministic, no atomics, no
+//     inter-workgroup hand-off.  Epilogue as mmgl_gemm_nt: act((acc + bias) * scale) + residual, ldy free (rows go straight into the cache).
+// Any dtype / alignment the MFMA kernel does not take (fp32: a correctness path; K % 64, N % 8, unaligned rows) runs on
+// skinny_generic_kernel: one wave per output column, 8 rows of x per wave, fp32 accumulation, same epilogue.
+//
+// mmgl_attn_decode_fwd (attn_decode_kernel).  One query row per (batch, head) against S keys addressed in place in the [B, S, H*D] cache
+// rows.  D / VEC lanes share a key (16-byte K and V loads straight to registers, VEC = 8 bf16 / 4 fp32), so a wave covers 64 VEC / D
+// keys per instruction and the 4 waves of the workgroup interleave key blocks; U blocks are loaded before the first is used.  Every lane
+// group keeps its own online-softmax state (max, sum, partial O) in fp32; the states are merged by a fixed butterfly inside the wave and
+// in wave order through LDS.  A masked key scores -FLT_MAX: with a valid key in the row it weighs exp(-FLT_MAX - max) = 0, and a row of
+// masked keys only has every weight exp(0) = 1 -- the uniform distribution of the reference's finfo.min clamp.
+#include "common.h"
+#include "attn_common.h"      // make_rsrc / OOB: hardware-bounds-checked buffer loads
+#include <float.h>
+
+namespace {
+
+constexpr int SK_WAVES = 4;
+constexpr int SK_THREADS = SK_WAVES * WAVE;
+
+template <typename T> struct SkArgs {
+    const T* X; const T* W; const T* bias; const T* resid; T* Y;
+    int ldx, ldw, ldy, M, N, K, act;
+    float scale;
+};
+
+template <typename T>
+__device__ __forceinline__ void sk_store(const SkArgs<T>& a, int m, int n, float v) {
+    if (a.bias) v += Elem<T>::to_f(a.bias[n]);
+    v *= a.scale;
+    if (a.act == MMGL_ACT_RELU) v = fmaxf(v, 0.f);
+    const size_t o = (size_t)m * a.ldy + n;
+    if (a.resid) v += Elem<T>::to_f(a.resid[o]);
+    a.Y[o] = Elem<T>::from_f(v);
+}
+
+template <int MT, bool HALF>
+__global__ __launch_bounds__(SK_THREADS) void skinny_mfma_kernel(const SkArgs<bf16> a) {
+    constexpr int SL = HALF ? 2 : 1;               // K slots per wave
+    constexpr int ROWS = HALF ? 8 : 16;            // weight rows per workgroup
+    constexpr int NS = SK_WAVES * SL;              // K slots per workgroup
+    constexpr int MR = MT * 16;                    // x rows held (rows >= M are zeros)
+    constexpr int XL = MR / 8;                     // x loads per lane, slot and pair
+    constexpr int DW = 4;                          // W pairs in flight per lane
+    constexpr int DX = MT == 1 ? 4 : MT == 2 ? 2 : 1;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[NS * MR * 128];      // x staging; the fold reuses it
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int i = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * ROWS;
+    const int P = a.K >> 6;
+    const int iters = (P + NS - 1) / NS;
+    const int wslot = HALF ? w * 2 + (i >> 3) : w;
+    // branch-free loads (units past K and x rows past M fall outside the descriptors and read as zero): the compiler sees every VMEM
+    // op of the loop and waits with exact vmcnt counts, so the W ring stays in flight across iterations
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.W + (size_t)n0 * a.ldw, (uint32_t)(((size_t)(ROWS - 1) * a.ldw + a.K) * 2));
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.X, (uint32_t)(((size_t)(a.M - 1) * a.ldx + a.K) * 2));
+    const uint32_t woff = (uint32_t)((HALF ? (i & 7) : i) * a.ldw + 16 * g) * 2u;
+    const int xr_row = lane >> 3, xr_c = lane & 7;
+
+    bf16x8 wr[DW][2];
+    bf16x8 xr[DX][SL * XL];
+    auto load_w = [&](int it, bf16x8 (&dst)[2]) {
+        const int p = it * NS + wslot;
+        const uint32_t off = p < P ? woff + (uint32_t)p * 128u : OOB;
+        dst[0] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, off, 0, 2));            // aux 2: non-temporal
+        dst[1] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, off + 16u, 0, 2));
+    };
+    auto load_x = [&](int it, bf16x8 (&dst)[SL * XL]) {
+#pragma unroll
+        for (int sl = 0; sl < SL; ++sl) {
+            const int p = it * NS + w * SL + sl;
+#pragma unroll
+            for (int j = 0; j < XL; ++j) {
+                const int r = j * 8 + xr_row;
+                const uint32_t off = (p < P && r < a.M) ? ((uint32_t)r * (uint32_t)a.ldx + (uint32_t)p * 64u + (uint32_t)xr_c * 8u) * 2u : OOB;
+                dst[sl * XL + j] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
+            }
+        }
+    };
+#pragma unroll
+    for (int u = 0; u < DW; ++u) load_w(u, wr[u]);
+#pragma unroll
+    for (int u = 0; u < DX; ++u) load_x(u, xr[u]);
+
+    f32x4 acc0[MT], acc1[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) { acc0[mt] = vzero<f32x4>(); acc1[mt] = vzero<f32x4>(); }
+
+    unsigned char* xs = smem + (size_t)w * SL * MR * 128;          // this wave's staging image
+    for (int it0 = 0; it0 < iters; it0 += DW) {
+#pragma unroll
+        for (int u = 0; u < DW; ++u) {
+            const int it = it0 + u;
+            if (it < iters) {                                       // uniform over the workgroup
+#pragma unroll
+                for (int sl = 0; sl < SL; ++sl)
+#pragma unroll
+                    for (int j = 0; j < XL; ++j) {
+                        const int r = j * 8 + xr_row;
+                        *(bf16x8*)(xs + ((sl * MR + r) * 128) + ((xr_c ^ (r & 7)) << 4)) = xr[u % DX][sl * XL + j];
+                    }
+                __syncthreads();
+                load_x(it + DX, xr[u % DX]);
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) {
+                        const int row = mt * 16 + i;
+                        const int off = row * 128 + (((2 * g + t) ^ (i & 7)) << 4);
+                        const bf16x8 b0 = *(const bf16x8*)(xs + off);
+                        mma16(acc0[mt], wr[u][t], b0);
+                        if (HALF) {
+                            const bf16x8 b1 = *(const bf16x8*)(xs + MR * 128 + off);
+                            mma16(acc1[mt], wr[u][t], b1);
+                        }
+                    }
+                load_w(it + DW, wr[u]);
+                __syncthreads();
+            }
+        }
+    }
+
+    // fold: part[slot][m][ROWS] fp32, summed in slot order
+    float* part = (float*)smem;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        if (HALF) {
+            const int slot = 2 * w + (g >> 1);
+            *(f32x4*)&part[((size_t)slot * MR + mt * 16 + i) * 8 + 4 * (g & 1)] = g < 2 ? acc0[mt] : acc1[mt];
+        } else {
+            *(f32x4*)&part[((size_t)w * MR + mt * 16 + i) * 16 + 4 * g] = acc0[mt];
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < ROWS * a.M; idx += SK_THREADS) {
+        const int n = idx % ROWS, m = idx / ROWS;
+        float s = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) s += part[((size_t)sl * MR + m) * ROWS + n];
+        sk_store(a, m, n0 + n, s);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void skinny_generic_kernel(const SkArgs<T> a) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int n = blockIdx.x * 4 + w, m0 = blockIdx.y * 8;
+    if (n >= a.N) return;                           // whole waves leave; the kernel has no barrier
+    float acc[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[r] = 0.f;
+    const T* wrow = a.W + (size_t)n * a.ldw;
+    for (int k = lane; k < a.K; k += WAVE) {
+        const float wv = Elem<T>::to_f(wrow[k]);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int m = min(m0 + r, a.M - 1);
+            acc[r] += wv * Elem<T>::to_f(a.X[(size_t)m * a.ldx + k]);
+        }
+    }
+    float mine = 0.f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const float s = wave_sum(acc[r]);
+        if (lane == r) mine = s;
+    }
+    if (lane < 8 && m0 + lane < a.M) sk_store(a, m0 + lane, n, mine);
+}
+
+template <int MT, bool HALF> int launch_skinny_mfma(const SkArgs<bf16>& a, hipStream_t st) {
+    hipLaunchKernelGGL((skinny_mfma_kernel<MT, HALF>), dim3(a.N / (HALF ? 8 : 16)), dim3(SK_THREADS), 0, st, a);
+    MMGL_CHECK_LAUNCH("mmgl_gemm_skinny");
+    return MMGL_OK;
+}
+
+template <bool HALF> int launch_skinny_mt(const SkArgs<bf16>& a, hipStream_t st) {
+    if (a.M <= 16) return launch_skinny_mfma<1, HALF>(a, st);
+    if (a.M <= 32) return launch_skinny_mfma<2, HALF>(a, st);
+    return launch_skinny_mfma<4, HALF>(a, st);
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+template <typename T> int launch_skinny_generic(const SkArgs<T>& a, hipStream_t st) {
+    hipLaunchKernelGGL((skinny_generic_kernel<T>), dim3(cdiv(a.N, 4), cdiv(a.M, 8)), dim3(256), 0, st, a);
+    MMGL_CHECK_LAUNCH("mmgl_gemm_skinny");
+    return MMGL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ single-query attention
+template <typename T> struct Vec16;
+template <> struct Vec16<bf16> { typedef bf16x8 type; };
+template <> struct Vec16<float> { typedef f32x4 type; };
+
+constexpr int AD_WAVES = 4;
+constexpr int AD_UNROLL = 4;
+
+template <typename T, int D>
+__global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k,
+                                                                      const T* __restrict__ v, int ldkv, size_t bs_kv,
+                                                                      const uint8_t* __restrict__ valid, int ld_valid,
+                                                                      T* __restrict__ out, int H, int S) {
+    typedef typename Vec16<T>::type V;
+    constexpr int VEC = 16 / sizeof(T);
+    constexpr int LPK = D / VEC;                    // lanes per key
+    constexpr int KPI = WAVE / LPK;                 // keys per wave and load instruction
+    constexpr float NEG = -FLT_MAX;
+    __shared__ float sm_m[AD_WAVES], sm_l[AD_WAVES], sm_o[AD_WAVES][D];
+
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane % LPK, kk = lane / LPK;
+
+    float qf[VEC];
+    {
+        const V qv = *(const V*)(q + (size_t)b * ldq + h * D + c * VEC);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) qf[e] = Elem<T>::to_f(qv[e]);
+    }
+    // branch-free loads: keys past S fall outside the descriptors
+    const uint32_t slab = (uint32_t)(((size_t)(S - 1) * ldkv + D) * sizeof(T)), row_bytes = (uint32_t)(ldkv * sizeof(T));
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(k + b * bs_kv + h * D, slab);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(v + b * bs_kv + h * D, slab);
+    const uint8_t* mb = valid + (size_t)b * ld_valid;
+
+    float m = NEG, l = 0.f, acc[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
+
+    for (int base = w * KPI; base < S; base += AD_WAVES * KPI * AD_UNROLL) {          // wave-uniform trip count
+        V kr[AD_UNROLL], vr[AD_UNROLL];
+        uint8_t ok[AD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            const int s = base + u * AD_WAVES * KPI + kk;
+            const uint32_t off = s < S ? (uint32_t)s * row_bytes + (uint32_t)(c * 16) : OOB;
+            kr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+            vr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+            ok[u] = mb[min(s, S - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            const int s = base + u * AD_WAVES * KPI + kk;
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) dot += qf[e] * Elem<T>::to_f(kr[u][e]);
+#pragma unroll
+            for (int o = 1; o < LPK; o <<= 1) dot += __shfl_xor(dot, o);
+            if (s < S) {
+                const float sc = ok[u] ? dot : NEG;
+                const float mn = fmaxf(m, sc);
+                const float corr = __expf(m - mn), p = __expf(sc - mn);
+                l = l * corr + p;
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) acc[e] = acc[e] * corr + p * Elem<T>::to_f(vr[u][e]);
+                m = mn;
+            }
+        }
+    }
+    // merge the lane groups of the wave (fixed butterfly), then the waves in order
+#pragma unroll
+    for (int o = LPK; o < WAVE; o <<= 1) {
+        const float m2 = __shfl_xor(m, o), l2 = __shfl_xor(l, o);
+        const float mn = fmaxf(m, m2);
+        const float c1 = __expf(m - mn), c2 = __expf(m2 - mn);
+        l = l * c1 + l2 * c2;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] = acc[e] * c1 + __shfl_xor(acc[e], o) * c2;
+        m = mn;
+    }
+    if (lane < LPK) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) sm_o[w][c * VEC + e] = acc[e];
+        if (lane == 0) { sm_m[w] = m; sm_l[w] = l; }
+    }
+    __syncthreads();
+    if (tid < D) {
+        float mm = sm_m[0];
+#pragma unroll
+        for (int i = 1; i < AD_WAVES; ++i) mm = fmaxf(mm, sm_m[i]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int i = 0; i < AD_WAVES; ++i) {
+            const float ci = __expf(sm_m[i] - mm);
+            ll += sm_l[i] * ci;
+            o += sm_o[i][tid] * ci;
+        }
+        out[((size_t)b * H + h) * D + tid] = Elem<T>::from_f(o / ll);
+    }
+}
+
+template <typename T, int D>
+int launch_attn_decode(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t bs_kv, const uint8_t* valid, int ld_valid,
+                       void* out, int B, int H, int S, hipStream_t st) {
+    hipLaunchKernelGGL((attn_decode_kernel<T, D>), dim3(B * H), dim3(AD_WAVES * WAVE), 0, st, (const T*)q, ldq, (const T*)k, (const T*)v,
+                       ldkv, bs_kv, valid, ld_valid, (T*)out, H, S);
+    MMGL_CHECK_LAUNCH("mmgl_attn_decode_fwd");
+    return MMGL_OK;
+}
+
+template <typename T>
+int attn_decode_d(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t bs_kv, const uint8_t* valid, int ld_valid, void* out,
+                  int B, int H, int S, int D, hipStream_t st) {
+    switch (D) {
+        case 16: return launch_attn_decode<T, 16>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, S, st);
+        case 32: return launch_attn_decode<T, 32>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, S, st);
+        case 64: return launch_attn_decode<T, 64>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, S, st);
+        default: return launch_attn_decode<T, 128>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, S, st);
+    }
+}
+
+}  // namespace
+
+extern "C" int mmgl_gemm_skinny(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* residual, void* y, int ldy,
+                                int M, int N, int K, int act, float scale, int dtype, void* stream) {
+    MMGL_CHECK_ARG(M >= 1 && N >= 1 && K >= 1, "mmgl_gemm_skinny: bad sizes M=%d N=%d K=%d", M, N, K);
+    if (M > 64) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_gemm_skinny: M=%d > 64 rows (chunk the rows or use mmgl_gemm_nt)", M);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_gemm_skinny: bad dtype %d", dtype);
+    MMGL_CHECK_ARG(x && W && y, "mmgl_gemm_skinny: null pointer");
+    MMGL_CHECK_ARG(act == MMGL_ACT_NONE || act == MMGL_ACT_RELU, "mmgl_gemm_skinny: unknown activation %d", act);
+    MMGL_CHECK_ARG(ldx >= K && ldw >= K && ldy >= N, "mmgl_gemm_skinny: leading dimensions (%d, %d, %d) smaller than the rows (K=%d, N=%d)",
+                   ldx, ldw, ldy, K, N);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_F32) {
+        SkArgs<float> a{(const float*)x, (const float*)W, (const float*)bias, (const float*)residual, (float*)y, ldx, ldw, ldy, M, N, K, act, scale};
+        return launch_skinny_generic<float>(a, st);
+    }
+    SkArgs<bf16> a{(const bf16*)x, (const bf16*)W, (const bf16*)bias, (const bf16*)residual, (bf16*)y, ldx, ldw, ldy, M, N, K, act, scale};
+    // the MFMA kernel addresses W rows of a workgroup and the whole x through 32-bit buffer offsets
+    const bool mfma = K % 64 == 0 && N % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && aligned16(x) && aligned16(W) &&
+                      ((size_t)(M - 1) * ldx + K) * 2 < (1ull << 31) && (size_t)16 * ldw * 2 < (1ull << 31);
+    if (!mfma) return launch_skinny_generic<bf16>(a, st);
+    // 16 weight rows per workgroup where that still gives every CU one, else 8
+    if (N % 16 == 0 && N / 16 >= mmgl_num_cu()) return launch_skinny_mt<false>(a, st);
+    return launch_skinny_mt<true>(a, st);
+}
+
+extern "C" int mmgl_attn_decode_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,
+                                    const uint8_t* key_valid, int ld_valid, void* out, int B, int H, int S, int D, int dtype, void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && H >= 1 && S >= 1, "mmgl_attn_decode_fwd: bad sizes B=%d H=%d S=%d", B, H, S);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_attn_decode_fwd: bad dtype %d", dtype);
+    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_fwd: head_dim %d (16, 32, 64, 128)", D);
+    const int vec = dtype == MMGL_BF16 ? 8 : 4;
+    if (ldq % vec || ldkv % vec || batch_stride_kv % vec)
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_fwd: strides (%d, %d, %zu) must be multiples of 16 bytes", ldq, ldkv, batch_stride_kv);
+    MMGL_CHECK_ARG(q && k && v && key_valid && out, "mmgl_attn_decode_fwd: null pointer");
+    MMGL_CHECK_ARG(ldq >= H * D && ldkv >= H * D && ld_valid >= S, "mmgl_attn_decode_fwd: strides (%d, %d, %d) smaller than the rows", ldq, ldkv, ld_valid);
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_fwd: q, k and v must be 16-byte aligned");
+    if (((size_t)(S - 1) * ldkv + D) * (dtype == MMGL_BF16 ? 2 : 4) >= (1ull << 31))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_fwd: a sample's key rows span 2 GiB or more (S=%d, ldkv=%d)", S, ldkv);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_BF16) return attn_decode_d<bf16>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, S, D, st);
+    return attn_decode_d<float>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, S, D, st);
+}

@@ -69,4 +69,5 @@ int mmgl_num_cu() {
 // 102: round 4 (tile counters bound to one stream; entry points added / removed with the kernel families).
 // 103: mmgl_comm_* / mmgl_allreduce_sum / mmgl_allgather / mmgl_broadcast.
 // 105: the stand-alone dgrad, weight-gradient and transpose entry points removed (mmgl_linear_bwd covers them).
-extern "C" int mmgl_version(void) { return 105; }
+// 106: mmgl_gemm_skinny / mmgl_attn_decode_fwd (the decode step of generate()).
+extern "C" int mmgl_version(void) { return 106; }

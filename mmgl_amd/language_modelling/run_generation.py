@@ -318,6 +318,9 @@ def _pass_sizes(n_micro, samples, tokens_per_sample, budget_tokens):
 
 
 _META_KEYS = ("attention_mask", "neighbor_pos_ids", "neighbor_attention_mask", "neighbor_images_pos_ids")
+# the neighbor arguments CrossAttentionModel.generate shares with forward; any other key a collate adds stays out of the call
+_GENERATE_FIELDS = ("neighbor_input_ids", "neighbor_attention_mask", "neighbor_pos_ids", "text_locations", "neighbor_images",
+                    "neighbor_images_pos_ids", "image_locations")
 
 
 class _GroupFeeder:
@@ -561,6 +564,13 @@ def _eval_groups(loader, args, limit):
 def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="val"):
     """Teacher-forced evaluation (reference :527-703): argmax tokens on the summary span, all-gathered, decoded,
     truncated at the first '.', scored with BLEU-1..4 and CIDEr.  Returns BLEU-4 (the model-selection metric, :703).
+    prefix == "test" with a model whose can_generate() is true (CrossAttentionModel over the OPT fork): the captions are generated
+    instead -- greedy, 32 new tokens, from the prompt alone (the first max_input_length columns) with the batch's neighbor fields
+    and host_meta, and only the new tokens are decoded.  A deviation from the reference's :600, which feeds the whole input (the
+    gold summary included) to a generate() its wrappers do not have and has no neighbors to pass.  The loss meter is still the
+    teacher-forced one.  Like the forward pass, one generate() call serves the whole fused group of validation batches: its cache
+    holds fused_pass_tokens / max_input_length samples (9.6 GB of bf16 K|V at config 3's default).  Every other model keeps the argmax
+    path under "test".
     Several validation batches share one forward pass (_eval_groups); meters, gathers and caption order are per batch, as in the
     reference.  `evaluate_loop.last` also carries `samples_per_sec` (this rank's samples / wall time of the loop)."""
     from . import utils
@@ -602,8 +612,13 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                 chunk = [outputs.loss.item()]
             for v in chunk:
                 losses.update(v, mb)
-            if prefix == "test" and hasattr(model, "generate"):
-                generated_ids = model.generate(input_ids=batch["input_ids"], attention_mask=batch["attention_mask"], max_new_tokens=32)
+            if prefix == "test" and hasattr(model, "generate") and getattr(model, "can_generate", lambda: False)():
+                L_in = args.max_input_length
+                fields = {key: batch[key] for key in _GENERATE_FIELDS if key in batch}       # generate()'s named neighbor arguments only
+                generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),
+                                               attention_mask=batch["attention_mask"][:, :L_in].contiguous(), **fields,
+                                               host_meta=extra.get("host_meta"), max_new_tokens=32,
+                                               eos_token_id=getattr(tokenizer, "eos_token_id", None), pad_token_id=pad_id)[:, L_in:]
             else:
                 generated_ids = torch.argmax(logits, dim=-1)            # the reference's wrappers have no generate() (:600)
             labels = labels.contiguous()

@@ -148,7 +148,7 @@ class MPTAttention(nn.Module):
         self.v_proj = nn.Linear(self.embed_dim, self.embed_dim, bias=bias)
 
     # -- fused HIP path: projections with bias/scale epilogue + single-pass masked core
-    def _forward_cross(self, hidden_states, neighbor_embeds, neighbor_attention_mask, layer_head_mask, output_attentions):
+    def _forward_cross(self, hidden_states, neighbor_embeds, neighbor_attention_mask, layer_head_mask, output_attentions, kv_out=None):
         if neighbor_embeds is None:
             raise ValueError("cross-attention layer called without neighbor_embeds")
         # layer_head_mask / output_attentions / attention-probability dropout (reference :237-256): the general HIP core
@@ -166,6 +166,8 @@ class MPTAttention(nn.Module):
         q = ops.linear(hidden_states, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
         k = ops.linear(neighbor_embeds, self.k_proj.weight, self.k_proj.bias)
         v = ops.linear(neighbor_embeds, self.v_proj.weight, self.v_proj.bias)
+        if kv_out is not None:               # prefill of generate(): the projected neighbor tokens are constant over the decode steps
+            kv_out.append((k, v))
         attn_w = None
         if general:
             o, attn_w = ops.attn_general(q, k, v, key_valid, self.num_heads, causal=False, head_mask=layer_head_mask, p_drop=self.dropout,
@@ -215,7 +217,8 @@ class MPTAttention(nn.Module):
         return cache[1]
 
     # -- causal self-attention of the (frozen) OPT layers: HIP flash kernels, no [B,1,T,T] mask, no [B,H,T,T] scores
-    def _forward_self(self, hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value=None):
+    def _forward_self(self, hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value=None, kv_out=None):
+        """kv_out: the layer's [B, capacity, 2d] K|V buffer of a DecodeCache -- the prefill copies its keys and values there."""
         H = self.num_heads
         if attention_mask is None or attention_mask.dim() != 2:
             raise ValueError("self-attention takes the [bsz, seq_len] key mask (causality is implied); additive 4-D masks are "
@@ -254,11 +257,16 @@ class MPTAttention(nn.Module):
             v = torch.cat([vp.to(v.dtype).expand(B, P, d), v], dim=1)
             o = ops.selfattn_core_prefix(q, k, v, attention_mask, H, P)
         elif fused is not None:              # frozen layer: one QKV GEMM forward, one dgrad GEMM backward, no gradient adds
-            o = ops.selfattn_core_fused(ops.frozen_linear(hidden_states, *fused), attention_mask, H)
+            qkv = ops.frozen_linear(hidden_states, *fused)
+            if kv_out is not None:
+                kv_out[:, :qkv.shape[1]].copy_(qkv[..., qkv.shape[-1] // 3:])
+            o = ops.selfattn_core_fused(qkv, attention_mask, H)
         elif (lq := self._lora_qkv()) is not None and ops.lora_qkv_supported(hidden_states, lq[0], self.q_proj.r):
             # LoRA on q_proj / v_proj: one node for the three projections (fused base GEMM, one dgrad GEMM, no gradient adds)
             qkv = ops.lora_qkv(hidden_states, lq[0], lq[1], self.q_proj.lora_A, self.q_proj.lora_B, self.v_proj.lora_A, self.v_proj.lora_B,
                                self.q_proj.scaling, self.scaling)
+            if kv_out is not None:
+                kv_out[:, :qkv.shape[1]].copy_(qkv[..., qkv.shape[-1] // 3:])
             o = ops.selfattn_core_fused(qkv, attention_mask, H)
         else:
             if type(self.q_proj) is nn.Linear and self.q_proj.weight.requires_grad:
@@ -267,15 +275,45 @@ class MPTAttention(nn.Module):
                 q = self.q_proj(hidden_states, out_scale=self.scaling)           # LoRA: the scaling rides in the GEMM epilogues
             else:
                 q = _lin(self.q_proj, hidden_states) * self.scaling
-            o = ops.selfattn_core(q, _lin(self.k_proj, hidden_states), _lin(self.v_proj, hidden_states), attention_mask, H)
+            k, v = _lin(self.k_proj, hidden_states), _lin(self.v_proj, hidden_states)
+            if kv_out is not None:
+                kv_out[:, :k.shape[1], :k.shape[2]].copy_(k)
+                kv_out[:, :k.shape[1], k.shape[2]:].copy_(v)
+            o = ops.selfattn_core(q, k, v, attention_mask, H)
         return _lin(self.out_proj, o), None, None
 
     def forward(self, hidden_states, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None,
-                past_key_value=None, layer_head_mask=None, output_attentions=False):
+                past_key_value=None, layer_head_mask=None, output_attentions=False, kv_out=None):
         """Input shape: Batch x Time x Channel.  Returns (attn_output, attn_weights-or-None, None)."""
         if self.cross_attention:
-            return self._forward_cross(hidden_states, neighbor_embeds, neighbor_attention_mask, layer_head_mask, output_attentions)
-        return self._forward_self(hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value)
+            return self._forward_cross(hidden_states, neighbor_embeds, neighbor_attention_mask, layer_head_mask, output_attentions, kv_out)
+        return self._forward_self(hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value, kv_out)
+
+    # -- one decode step of generate(): M = batch rows, weight-streaming GEMMs and single-query attention (csrc/decode.hip)
+    def _plain(self, *mods):
+        if any(type(m) is not nn.Linear for m in mods):
+            raise ValueError("the decode step runs plain nn.Linear projections only (adapted projections, e.g. LoRA, have no decode path)")
+
+    def decode_self(self, x, kv, key_mask, col):
+        """x [B, d]: the new token's layer input.  Projects q and writes k|v into column `col` of the layer's cache rows kv
+        [B, capacity, 2d], then attends over columns 0..col (all at or before the query: no causal test)."""
+        d = self.embed_dim
+        self._plain(self.q_proj, self.k_proj, self.v_proj, self.out_proj)
+        fused = self._frozen_qkv()
+        if fused is not None:
+            w, b = fused
+            q = ops.decode_linear(x, w[:d], b[:d])
+            ops.decode_linear(x, w[d:], b[d:], out=kv[:, col])
+        else:
+            q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
+            ops.decode_linear(x, self.k_proj.weight, self.k_proj.bias, out=kv[:, col, :d])
+            ops.decode_linear(x, self.v_proj.weight, self.v_proj.bias, out=kv[:, col, d:])
+        return ops.attn_decode(q, kv[:, :col + 1, :d], kv[:, :col + 1, d:], key_mask[:, :col + 1], self.num_heads)
+
+    def decode_cross(self, x, k, v, key_valid):
+        self._plain(self.q_proj, self.out_proj)
+        q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
+        return ops.attn_decode(q, k, v, key_valid, self.num_heads)
 
 
 
@@ -328,12 +366,12 @@ class MPTDecoderLayer(nn.Module):
             return ops.layer_norm_fanout(x, ln.weight, ln.bias, ln.eps)
         return x, ops.layer_norm(x, ln.weight, ln.bias, ln.eps)
 
-    def _forward_cross(self, h, neighbor_embeds, neighbor_attention_mask, layer_head_mask, output_attentions):
+    def _forward_cross(self, h, neighbor_embeds, neighbor_attention_mask, layer_head_mask, output_attentions, kv_out=None):
         gated = self.peft_type == "flamingo"
         # pre-LN: the block input feeds the LayerNorm AND the residual add -- both gradients meet inside the LayerNorm backward kernel
         residual, x = self._ln_fanout(self.self_attn_layer_norm, h) if self.do_layer_norm_before else (h, h)
         a, attn_w, _ = self.self_attn(x, neighbor_embeds=neighbor_embeds, neighbor_attention_mask=neighbor_attention_mask,
-                                      layer_head_mask=layer_head_mask, output_attentions=output_attentions)
+                                      layer_head_mask=layer_head_mask, output_attentions=output_attentions, kv_out=kv_out)
         h = ops.gated_residual(residual, a, self.gating1 if gated else None, self.dropout, self.training)
         if not self.do_layer_norm_before:
             h = self._ln(self.self_attn_layer_norm, h)
@@ -350,7 +388,7 @@ class MPTDecoderLayer(nn.Module):
             h = self._ln(self.final_layer_norm, h)
         return h, attn_w
 
-    def _forward_self(self, h, attention_mask, layer_head_mask, output_attentions, defer_residual=False, past_key_value=None):
+    def _forward_self(self, h, attention_mask, layer_head_mask, output_attentions, defer_residual=False, past_key_value=None, kv_out=None):
         """OPT layer (frozen in every peft mode of the reference, :731-737): GEMMs, attention (ops.selfattn_core*), LayerNorm and
         dropout + residual all run on this repo's HIP kernels.  Every `residual + dropout(branch)` is folded into the LayerNorm that
         follows it (ops.add_layer_norm_pair: one forward and one backward kernel per pair); the layer's last add can be
@@ -369,7 +407,7 @@ class MPTDecoderLayer(nn.Module):
             x = h
         residual = h
         a, attn_w, _ = self.self_attn(x, attention_mask=attention_mask, layer_head_mask=layer_head_mask,
-                                      output_attentions=output_attentions, past_key_value=past_key_value)
+                                      output_attentions=output_attentions, past_key_value=past_key_value, kv_out=kv_out)
         if pre:
             h, x = pair(a, residual, ln2)
         else:
@@ -391,18 +429,74 @@ class MPTDecoderLayer(nn.Module):
         return ops.gated_residual(residual, x, None, self.dropout, self.training), attn_w
 
     def forward(self, hidden_states, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None,
-                layer_head_mask=None, past_key_value=None, output_attentions=False, use_cache=False, defer_residual=False):
+                layer_head_mask=None, past_key_value=None, output_attentions=False, use_cache=False, defer_residual=False, kv_out=None):
         if self.cross_attention:
             h, attn_w = self._forward_cross(_materialize(hidden_states), neighbor_embeds, neighbor_attention_mask, layer_head_mask,
-                                            output_attentions)
+                                            output_attentions, kv_out)
         else:
-            h, attn_w = self._forward_self(hidden_states, attention_mask, layer_head_mask, output_attentions, defer_residual, past_key_value)
+            h, attn_w = self._forward_self(hidden_states, attention_mask, layer_head_mask, output_attentions, defer_residual, past_key_value,
+                                           kv_out)
         outputs = (h,)
         if output_attentions:
             outputs += (attn_w,)
         if use_cache:
             outputs += (None,)
         return outputs
+
+
+    def _decode_ffn(self, x):
+        if self.activation_name == "relu":
+            return ops.decode_linear(x, self.fc1.weight, self.fc1.bias, act="relu")
+        return ops.activation_(ops.decode_linear(x, self.fc1.weight, self.fc1.bias), self.activation_name)
+
+    def decode_step(self, h, cache, idx):
+        """The layer on the one new token of a decode step, h [B, d]: the existing LayerNorm / gated-residual kernels at M = B,
+        ops.decode_linear for every projection (residual adds in the GEMM epilogue of the frozen layers) and ops.attn_decode over
+        the cache -- layer idx's K|V rows (frozen layer) or neighbor layer idx's projected neighbor tokens (gated layer)."""
+        pre = self.do_layer_norm_before
+        attn = self.self_attn
+        ln1, ln2 = self.self_attn_layer_norm, self.final_layer_norm
+        if type(self.fc1) is not nn.Linear or type(self.fc2) is not nn.Linear or type(attn.out_proj) is not nn.Linear:
+            raise ValueError("the decode step runs plain nn.Linear projections only (adapted projections, e.g. LoRA, have no decode path)")
+        x = self._ln(ln1, h) if pre else h
+        if self.cross_attention:
+            gated = self.peft_type == "flamingo"
+            k, v = cache.cross[idx]
+            a = attn.decode_cross(x, k, v, cache.cross_valid)
+            a = ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias)
+            h = ops.gated_residual(h, a, self.gating1 if gated else None, 0.0, False)
+            if not pre:
+                h = self._ln(ln1, h)
+            x = self._ln(ln2, h) if pre else h
+            x = ops.decode_linear(self._decode_ffn(x), self.fc2.weight, self.fc2.bias)
+            h = ops.gated_residual(h, x, self.gating2 if gated else None, 0.0, False)
+            return h if pre else self._ln(ln2, h)
+        a = attn.decode_self(x, cache.kv[idx], cache.mask, cache.col)
+        h = ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias, residual=h)
+        if not pre:
+            h = self._ln(ln1, h)
+        x = self._ln(ln2, h) if pre else h
+        h = ops.decode_linear(self._decode_ffn(x), self.fc2.weight, self.fc2.bias, residual=h)
+        return h if pre else self._ln(ln2, h)
+
+
+class DecodeCache:
+    """State of greedy generation with a key/value cache (MPTDecoder.forward(use_cache=True) builds it, each decode step advances it):
+      kv          per frozen layer one preallocated [B, capacity, 2d] buffer: columns [0, d) of a row are that position's key, [d, 2d) its value
+                  (the project's [B, S, H*D] layout, never head-transposed; the kernels address the two slabs in place)
+      cross       per gated layer the neighbor tokens' (k_proj, v_proj) outputs [B, S, d], projected once at prefill; cross_valid their [B, S] mask
+      mask        the running [B, capacity] uint8 key mask: the prompt's attention mask (pad keys stay masked), then 1 per new token
+      col         the column the next token is written to -- the same for every sample (prompts are right-padded to a common width)
+      next_pos    [B] position id of the next token, counted from the mask as HF does (valid tokens so far + OPT's offset 2)"""
+
+    def __init__(self, num_layers, batch_size, capacity, hidden_size, dtype, device):
+        self.capacity = int(capacity)
+        self.kv = [torch.empty(batch_size, self.capacity, 2 * hidden_size, dtype=dtype, device=device) for _ in range(num_layers)]
+        self.mask = torch.zeros(batch_size, self.capacity, dtype=torch.uint8, device=device)
+        self.cross = []
+        self.cross_valid = None
+        self.col = 0
+        self.next_pos = None
 
 
 class MPTPreTrainedModel(nn.Module):
@@ -477,12 +571,27 @@ class MPTDecoder(MPTPreTrainedModel):
 
     def forward(self, input_ids=None, attention_mask=None, head_mask=None, past_key_values=None, inputs_embeds=None,
                 neighbor_embeds=None, neighbor_attention_mask=None, use_cache=None, output_attentions=None,
-                output_hidden_states=None, return_dict=None, first_key_valid=False):
+                output_hidden_states=None, return_dict=None, first_key_valid=False, cache_capacity=None):
+        """use_cache=True: the prefill of greedy generation -- the same kernels as any forward, plus a copy of every layer's keys and
+        values into a DecodeCache (capacity `cache_capacity` columns, default max_position_embeddings) returned as past_key_values.
+        past_key_values=DecodeCache with input_ids [B, 1]: one decode step (see _decode_step).  Any other past_key_values keeps its
+        meaning: a fixed key/value prefix (prefix tuning)."""
         output_attentions = bool(output_attentions)
         output_hidden_states = bool(output_hidden_states)
         return_dict = True if return_dict is None else return_dict
-        if use_cache:
-            raise ValueError("KV-cache decoding is not implemented (the reference's cross-attention ignores the cache, :275)")
+        decoding = isinstance(past_key_values, DecodeCache)
+        cache = None
+        if decoding or use_cache:
+            if past_key_values is not None and not decoding:
+                raise ValueError("prefix tuning (a key/value prefix in past_key_values) together with a decode cache is not implemented")
+            if head_mask is not None:
+                raise ValueError("layer_head_mask together with a decode cache is not implemented")
+            if output_attentions:
+                raise ValueError("output_attentions together with a decode cache is not implemented")
+            if self.training and (self.dropout > 0 or self.config.attention_dropout > 0 or self.layerdrop > 0):
+                raise ValueError("a decode cache in training mode with dropout: generation is deterministic, call eval() first")
+            if decoding:
+                return self._decode_step(input_ids, inputs_embeds, past_key_values, output_hidden_states, return_dict)
         # past_key_values: a FIXED per-layer key/value prefix (peft prefix tuning, reference model/modelling_self_attention.py:88-93),
         # either peft's prefix-encoder table [P, 2 * n_layers * d] (layer i: keys = columns [2i d, (2i+1) d), values the next d)
         # or a sequence of (key [P or B x P, d], value) pairs, one per layer
@@ -511,6 +620,12 @@ class MPTDecoder(MPTPreTrainedModel):
         if inputs_embeds is None:
             inputs_embeds = self.embed_tokens(input_ids)
         batch_size, seq_length = input_shape
+        if use_cache:
+            capacity = self.max_target_positions if cache_capacity is None else int(cache_capacity)
+            if seq_length > capacity or capacity > self.max_target_positions:
+                raise ValueError(f"decode cache: a prompt of {seq_length} columns, capacity {capacity}, max_position_embeddings "
+                                 f"{self.max_target_positions}")
+            cache = DecodeCache(len(self.layers), batch_size, capacity, self.config.hidden_size, inputs_embeds.dtype, inputs_embeds.device)
         if attention_mask is None:
             attention_mask = torch.ones(batch_size, seq_length + prefix_len, device=inputs_embeds.device)
         elif attention_mask.shape[1] == seq_length and prefix_len:
@@ -555,13 +670,15 @@ class MPTDecoder(MPTPreTrainedModel):
             lhm = head_mask[idx] if head_mask is not None else None
             layer_outputs = decoder_layer(hidden_states, attention_mask=causal_attention_mask, layer_head_mask=lhm,
                                           output_attentions=output_attentions, defer_residual=defer,
-                                          past_key_value=None if past_key_values is None else past_key_values[idx])
+                                          past_key_value=None if past_key_values is None else past_key_values[idx],
+                                          kv_out=None if cache is None else cache.kv[idx])
             if self.cross_attention and neighbor_embeds is not None and (idx + 1) % self.neighbor_layer_wise == 0:
                 hidden_states = _materialize(layer_outputs[0])
                 neighbor_idx = (idx + 1) // self.neighbor_layer_wise - 1
                 layer_outputs = self.neighbor_layers[neighbor_idx](
                     hidden_states, attention_mask=causal_attention_mask, neighbor_embeds=neighbor_embeds,
-                    neighbor_attention_mask=key_valid, layer_head_mask=lhm, output_attentions=output_attentions)     # (:613-623)
+                    neighbor_attention_mask=key_valid, layer_head_mask=lhm, output_attentions=output_attentions,
+                    kv_out=None if cache is None else cache.cross)     # (:613-623)
             hidden_states = layer_outputs[0]
             if output_attentions:
                 all_self_attns += (layer_outputs[1],)
@@ -578,10 +695,59 @@ class MPTDecoder(MPTPreTrainedModel):
             hidden_states = _lin(self.project_out, hidden_states)
         if output_hidden_states:
             all_hidden_states += (hidden_states,)
+        if cache is not None:
+            cache.mask[:, :seq_length] = causal_attention_mask
+            cache.col = seq_length
+            cache.next_pos = causal_attention_mask.sum(dim=1, dtype=torch.int64) + self.embed_positions.offset
+            if cache.cross:
+                cache.cross_valid = key_valid if key_valid is not None else torch.ones(cache.cross[0][0].shape[:2], dtype=torch.uint8,
+                                                                                       device=hidden_states.device)
         if not return_dict:
-            return tuple(v for v in [hidden_states, None, all_hidden_states, all_self_attns] if v is not None)
-        return BaseModelOutputWithPast(last_hidden_state=hidden_states, past_key_values=None,
+            return tuple(v for v in [hidden_states, cache, all_hidden_states, all_self_attns] if v is not None)
+        return BaseModelOutputWithPast(last_hidden_state=hidden_states, past_key_values=cache,
                                        hidden_states=all_hidden_states, attentions=all_self_attns)
+
+    def _decode_step(self, input_ids, inputs_embeds, cache, output_hidden_states, return_dict):
+        """One new token per sample against the cache: input_ids [B, 1] (or inputs_embeds [B, 1, d_embed]).  The token is appended
+        at column cache.col of every sample; its position id is the count of valid tokens so far, as HF derives it from the mask."""
+        if (input_ids is None) == (inputs_embeds is None):
+            raise ValueError("You have to specify either decoder_input_ids or decoder_inputs_embeds")
+        shape = input_ids.shape if input_ids is not None else inputs_embeds.shape[:2]
+        if len(shape) != 2 or shape[1] != 1 or shape[0] != cache.mask.shape[0]:
+            raise ValueError(f"a decode step takes one new token per cached sample ([{cache.mask.shape[0]}, 1]), got {tuple(shape)}")
+        if cache.next_pos is None:
+            raise ValueError("the DecodeCache has not been filled: run the prompt with use_cache=True first")
+        if cache.col >= cache.capacity or cache.col >= self.max_target_positions:
+            raise ValueError(f"decode cache is full: column {cache.col} of capacity {cache.capacity} "
+                             f"(max_position_embeddings {self.max_target_positions})")
+        ops.require_cuda(cache.mask, input_ids, inputs_embeds)
+        with torch.no_grad():
+            emb = self.embed_tokens(input_ids[:, 0]) if inputs_embeds is None else inputs_embeds[:, 0]
+            if self.project_in is not None:
+                emb = ops.decode_linear(emb.contiguous(), self.project_in.weight, self.project_in.bias)
+            h = emb + F.embedding(cache.next_pos, self.embed_positions.weight)
+            cache.mask[:, cache.col] = 1
+            all_hidden_states = () if output_hidden_states else None
+            for idx, layer in enumerate(self.layers):
+                if output_hidden_states:
+                    all_hidden_states += (h[:, None],)
+                h = layer.decode_step(h, cache, idx)
+                if cache.cross and (idx + 1) % self.neighbor_layer_wise == 0:
+                    nb = (idx + 1) // self.neighbor_layer_wise - 1
+                    h = self.neighbor_layers[nb].decode_step(h, cache, nb)
+            if self.final_layer_norm is not None:
+                fln = self.final_layer_norm
+                h = ops.layer_norm(h, fln.weight, fln.bias, fln.eps)
+            if self.project_out is not None:
+                h = ops.decode_linear(h, self.project_out.weight, self.project_out.bias)
+            cache.col += 1
+            cache.next_pos = cache.next_pos + 1
+        h = h[:, None]
+        if output_hidden_states:
+            all_hidden_states += (h,)
+        if not return_dict:
+            return tuple(v for v in [h, cache, all_hidden_states] if v is not None)
+        return BaseModelOutputWithPast(last_hidden_state=h, past_key_values=cache, hidden_states=all_hidden_states, attentions=None)
 
 
 class MPTModel(MPTPreTrainedModel):
@@ -684,15 +850,26 @@ class MPTForCausalLM(MPTPreTrainedModel):
 
     def forward(self, input_ids=None, attention_mask=None, head_mask=None, past_key_values=None, inputs_embeds=None,
                 labels=None, neighbor_embeds=None, neighbor_attention_mask=None, use_cache=None, output_attentions=None,
-                output_hidden_states=None, return_dict=None, first_key_valid=False, return_logits=None, logits_slice=None):
-        """return_logits / logits_slice: see lm_head_loss_and_logits (training steps never build the [B, T, V] logits unless asked)."""
+                output_hidden_states=None, return_dict=None, first_key_valid=False, return_logits=None, logits_slice=None,
+                cache_capacity=None):
+        """return_logits / logits_slice: see lm_head_loss_and_logits (training steps never build the [B, T, V] logits unless asked).
+        use_cache / past_key_values=DecodeCache / cache_capacity: see MPTDecoder.forward; a decode step returns [B, 1, V] logits."""
         return_dict = True if return_dict is None else return_dict
         outputs = self.model.decoder(input_ids=input_ids, attention_mask=attention_mask, head_mask=head_mask,
                                      past_key_values=past_key_values, inputs_embeds=inputs_embeds,
                                      neighbor_embeds=neighbor_embeds, neighbor_attention_mask=neighbor_attention_mask,
                                      use_cache=use_cache, output_attentions=output_attentions,
-                                     output_hidden_states=output_hidden_states, return_dict=True, first_key_valid=first_key_valid)
+                                     output_hidden_states=output_hidden_states, return_dict=True, first_key_valid=first_key_valid,
+                                     cache_capacity=cache_capacity)
         hidden = outputs.last_hidden_state
+        if isinstance(past_key_values, DecodeCache):
+            if labels is not None:
+                raise ValueError("a decode step takes no labels")
+            logits = self._last_logits(hidden[:, 0])[:, None]
+            if not return_dict:
+                return (logits, outputs.past_key_values)
+            return CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=outputs.past_key_values,
+                                          hidden_states=outputs.hidden_states, attentions=None)
         nxt = None
         if labels is not None:
             # tokens < n predict n (:831-836).  Instead of copying the [B,T-1,V] slice, every row is scored against the
@@ -702,10 +879,69 @@ class MPTForCausalLM(MPTPreTrainedModel):
             nxt[:, :-1] = labels[:, 1:]
         loss, logits = lm_head_loss_and_logits(self, self.lm_head, hidden, nxt, return_logits, logits_slice)
         if not return_dict:
-            output = (logits,) + tuple(v for v in (outputs.hidden_states, outputs.attentions) if v is not None)
+            output = (logits,) + tuple(v for v in (outputs.past_key_values, outputs.hidden_states, outputs.attentions) if v is not None)
             return (loss,) + output if loss is not None else output
-        return CausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=None, hidden_states=outputs.hidden_states,
+        return CausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=outputs.past_key_values, hidden_states=outputs.hidden_states,
                                       attentions=outputs.attentions)
+
+    def _last_logits(self, hidden):
+        """lm_head on one row per sample, hidden [B, d] (any row stride): the [V, d] head is read once for the B rows."""
+        if type(self.lm_head) is not nn.Linear:
+            raise ValueError("generate(): lm_head must be a plain nn.Linear")
+        return ops.decode_linear(hidden.contiguous(), self.lm_head.weight, self.lm_head.bias)      # dense rows: decode_linear picks the route
+
+    def can_generate(self):
+        return True
+
+    @torch.no_grad()
+    def generate(self, input_ids, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
+                 eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False):
+        """Greedy decoding (do_sample=False, one beam) with a key/value cache: what the reference's test protocol asks of its
+        wrappers (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of
+        every layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
+        ops.attn_decode); lm_head runs on the last row only.
+        Prompts are right-padded to the common width T (the layout the model is trained on: the summary starts at column
+        max_input_length); every new token is appended at the same column for all samples and the pad keys stay masked.
+        eos_token_id: a row that has emitted it gets pad_token_id (default config.pad_token_id) from then on, as in HF's greedy loop;
+        None: no end-of-sequence handling.  All max_new_tokens steps run (no host synchronisation to stop early).
+        Returns the [B, T + max_new_tokens] ids; with return_step_logits=True also the [B, max_new_tokens, V] logits the tokens
+        were picked from."""
+        if not input_ids.is_cuda:
+            raise RuntimeError(f"generate() runs on the GPU only (input_ids is on {input_ids.device}); there is no CPU path")
+        B, T = input_ids.shape
+        n_new = int(max_new_tokens)
+        if n_new < 1:
+            raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
+        dec = self.model.decoder
+        if T + n_new - 1 > dec.max_target_positions:
+            raise ValueError(f"generate(): {T} prompt columns + {n_new} new tokens exceed max_position_embeddings {dec.max_target_positions}")
+        if eos_token_id is not None and pad_token_id is None:
+            pad_token_id = self.config.pad_token_id
+            if pad_token_id is None:
+                raise ValueError("generate(): eos_token_id needs a pad_token_id")
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        out = dec(input_ids=input_ids, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
+                  neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
+                  cache_capacity=min(T + n_new - 1, dec.max_target_positions))
+        cache = out.past_key_values
+        hidden = out.last_hidden_state[:, -1]
+        ids = torch.empty(B, T + n_new, dtype=input_ids.dtype, device=input_ids.device)
+        ids[:, :T] = input_ids
+        finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
+        steps = []
+        for s in range(n_new):
+            logits = self._last_logits(hidden)
+            if return_step_logits:
+                steps.append(logits)
+            tok = torch.argmax(logits, dim=-1)
+            if eos_token_id is not None:
+                tok = torch.where(finished, torch.full_like(tok, pad_token_id), tok)
+                finished = finished | (tok == eos_token_id)
+            ids[:, T + s] = tok
+            if s + 1 < n_new:
+                hidden = dec(input_ids=tok[:, None], past_key_values=cache).last_hidden_state[:, 0]
+        return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
 
 
 def copy_opt_weights(opt_model, mpt_model):
@@ -977,20 +1213,48 @@ class CrossAttentionModel(nn.Module):
         """`host_meta` (optional, not in the reference's signature): the dict of `host_metadata(batch)` computed by the collate /
         trainer while the batch was still in host memory; with it the step has no device->host synchronisation.
         `return_logits` / `logits_slice`: see lm_head_loss_and_logits -- a training step does not build the [B, T, V] logits."""
-        if self.neighbor_mode == "raw" or self.context == "section_only":
-            neighbor_embeds, key_valid = None, None          # sanity path: the plain OPT (:1068-1071)
-        elif self.cross_path and self.context == "text_only":
-            text = self.get_text_embs(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, host_meta)
-            neighbor_embeds, key_valid = ops.neighbor_interleave(
-                text, None, torch.arange(text.shape[1], device=text.device).expand(text.shape[0], -1).contiguous(), None,
-                neighbor_pos_ids, None)
-        elif self.cross_path and self.context in ("section_all", "all"):
-            text = self.get_text_embs(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, host_meta)
-            visual = self.get_visual_embs(neighbor_images, neighbor_images_pos_ids, host_meta)
-            neighbor_embeds, key_valid = ops.neighbor_interleave(text, visual, text_locations, image_locations,
-                                                                 neighbor_pos_ids, neighbor_images_pos_ids)
-        else:
-            raise ValueError(f"Neighbor mode: {self.neighbor_mode} and context: {self.context} are not supported.")
+        neighbor_embeds, key_valid = self._neighbor_tokens(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, text_locations,
+                                                           neighbor_images, neighbor_images_pos_ids, image_locations, host_meta)
         return self.lm(input_ids=input_ids, attention_mask=attention_mask, labels=labels, neighbor_embeds=neighbor_embeds,
                        neighbor_attention_mask=key_valid, first_key_valid=bool(host_meta and host_meta.get("first_key_valid")),
                        return_logits=return_logits, logits_slice=logits_slice)
+
+    def _neighbor_tokens(self, neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, text_locations, neighbor_images,
+                         neighbor_images_pos_ids, image_locations, host_meta):
+        """(neighbor_embeds [B, S, d], key_valid [B, S]) of a batch: the neighbors encoded, pooled, projected and interleaved
+        (reference :1068-1104); (None, None) on the plain-LM paths."""
+        if self.neighbor_mode == "raw" or self.context == "section_only":
+            return None, None                                # sanity path: the plain OPT (:1068-1071)
+        if self.cross_path and self.context == "text_only":
+            text = self.get_text_embs(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, host_meta)
+            return ops.neighbor_interleave(
+                text, None, torch.arange(text.shape[1], device=text.device).expand(text.shape[0], -1).contiguous(), None,
+                neighbor_pos_ids, None)
+        if self.cross_path and self.context in ("section_all", "all"):
+            text = self.get_text_embs(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, host_meta)
+            visual = self.get_visual_embs(neighbor_images, neighbor_images_pos_ids, host_meta)
+            return ops.neighbor_interleave(text, visual, text_locations, image_locations, neighbor_pos_ids, neighbor_images_pos_ids)
+        raise ValueError(f"Neighbor mode: {self.neighbor_mode} and context: {self.context} are not supported.")
+
+    def can_generate(self):
+        """Whether generate() exists for this wrapper's LM: the OPT fork in any context / neighbor mode; not the Llama-family LM."""
+        return isinstance(self.lm, MPTForCausalLM)
+
+    @torch.no_grad()
+    def generate(self, input_ids, attention_mask, images=None, image_positions=None, neighbor_input_ids=None,
+                 neighbor_attention_mask=None, neighbor_pos_ids=None, text_locations=None, neighbor_images=None,
+                 neighbor_images_pos_ids=None, image_locations=None, host_meta=None, max_new_tokens=32, eos_token_id=None,
+                 pad_token_id=None, return_step_logits=False):
+        """Greedy generation from the prompt `input_ids` [B, T] (right-padded): the neighbors are encoded and interleaved once, exactly
+        as forward does, then MPTForCausalLM.generate runs the prefill and the cached decode steps.  Returns [B, T + max_new_tokens]
+        ids (and the step logits with return_step_logits=True)."""
+        if not self.can_generate():
+            raise ValueError(f"generate() is implemented for the OPT fork only, not for {type(self.lm).__name__}")
+        if not input_ids.is_cuda:
+            raise RuntimeError(f"generate() runs on the GPU only (input_ids is on {input_ids.device}); there is no CPU path")
+        neighbor_embeds, key_valid = self._neighbor_tokens(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, text_locations,
+                                                           neighbor_images, neighbor_images_pos_ids, image_locations, host_meta)
+        return self.lm.generate(input_ids, attention_mask, neighbor_embeds=neighbor_embeds, neighbor_attention_mask=key_valid,
+                                max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                                return_step_logits=return_step_logits,
+                                first_key_valid=bool(host_meta and host_meta.get("first_key_valid")))

@@ -1383,3 +1383,95 @@ def activation_(x, name):
         raise ValueError("activation_: tensor must be contiguous")
     _lib.call("mmgl_activation_fwd", dict(bytes=2.0 * x.numel() * x.element_size()), ptr(x), ptr(x), x.numel(), ACT_CODES[name], dtype_code(x), stream_ptr())
     return x
+
+
+# ------------------------------------------------------------------------------------------ decode step (generate())
+def _no_grad_inputs(op, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise ValueError(f"{op} is forward only (the decode step of generate()): run it under torch.no_grad() or detach its inputs")
+
+
+_SKINNY_MAX_N = 32768
+
+
+def _skinny_route(M, N, K, dtype):
+    """Whether mmgl_gemm_skinny takes a dense [M <= 64, K] x [N, K]^T linear of a decode step rather than mmgl_gemm_nt: the table of
+    profiles/decode_gemm_skinny.txt (tools/bench_gemm_skinny.py, the two entry points alternating in one process, cold weights).  The
+    skinny kernel is 1.4-7x faster on every layer shape (N <= 8192, K = 768 / 2048 / 8192) at M = 2, 16 and 64; on the lm_head shape
+    (N = 50272, K = 2048: 3142 workgroups that each re-stage x) mmgl_gemm_nt ties at M = 2 and wins at M = 16 (1.13x) and 64 (1.6x).
+    The boundary sits between the two measured widths; fp32 has one route (the plain skinny kernel takes any stride)."""
+    return dtype != torch.bfloat16 or N < _SKINNY_MAX_N
+
+
+def gemm_skinny(x, weight, bias=None, residual=None, act=0, out_scale=1.0, out=None):
+    """Raw mmgl_gemm_skinny call: x [M <= 64, K], weight [N, K], out [M, N]; row strides are free, column strides 1.  No autograd."""
+    require_cuda(x, weight)
+    M, K = x.shape
+    N = weight.shape[0]
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+    _lib.call("mmgl_gemm_skinny", dict(flops=2.0 * M * N * K, bytes=float(M * K + N * K + M * N) * x.element_size(), tag=f"{M}x{N}x{K}"),
+              ptr(x), x.stride(0), ptr(weight), weight.stride(0), ptr(bias), ptr(residual), ptr(y), y.stride(0), M, N, K, act,
+              float(out_scale), dtype_code(x), stream_ptr())
+    return y
+
+
+def decode_linear(x, weight, bias=None, act="none", out_scale=1.0, residual=None, out=None):
+    """act((x @ weight^T + bias) * out_scale) + residual for the few rows of a decode step: x [M, K] (M = batch rows), weight [N, K].
+    `out` [M, N] may be a strided view with unit column stride -- a column of the key/value cache -- and `residual` shares its row
+    stride.  Rows go to mmgl_gemm_skinny in chunks of 64; a dense bf16 call of a shape where mmgl_gemm_nt measured faster (_skinny_route:
+    the lm_head width) goes there.
+    Forward only; GPU only."""
+    require_cuda(x, weight)
+    _no_grad_inputs("decode_linear", x, weight, bias, residual)
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1]:
+        raise ValueError(f"decode_linear: shapes x{tuple(x.shape)} weight{tuple(weight.shape)}")
+    M, K = x.shape
+    N = weight.shape[0]
+    code = _act_code("decode_linear", act)
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    weight = weight if weight.stride(1) == 1 else weight.contiguous()
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+    if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.dtype != x.dtype or weight.dtype != x.dtype:
+        raise ValueError(f"decode_linear: out{tuple(y.shape)} {y.dtype} for x{tuple(x.shape)} {x.dtype} weight{tuple(weight.shape)} {weight.dtype}")
+    if residual is not None and (tuple(residual.shape) != (M, N) or residual.stride(1) != 1 or residual.stride(0) != y.stride(0)):
+        raise ValueError("decode_linear: residual must have the output's shape and row stride")
+    if bias is not None and bias.dtype != x.dtype:
+        bias = bias.to(x.dtype)
+    if M == 0:
+        return y
+    dense = y.stride(0) == N and x.stride(0) == K and weight.stride(0) == K
+    if dense and x.dtype == torch.bfloat16 and K % 8 == 0 and N % 8 == 0 and not _skinny_route(M, N, K, x.dtype):
+        return gemm_nt(x, weight, bias, residual, None, code, out_scale, K, y)
+    for m0 in range(0, M, 64):
+        m1 = min(M, m0 + 64)
+        gemm_skinny(x[m0:m1], weight, bias, None if residual is None else residual[m0:m1], code, out_scale, y[m0:m1])
+    return y
+
+
+def attn_decode(q, k, v, key_valid, num_heads):
+    """One query row per (sample, head) against S keys: q [B, d] already scaled; k, v [B, S, d] views with unit column stride and
+    common strides (column slabs of the cache rows [B, capacity, 2d]); key_valid [B, S] bool/uint8 view (True = attend).  Returns [B, d].
+    A sample with no valid key attends uniformly over its S keys.  Forward only; GPU only."""
+    require_cuda(q, k, v, key_valid)
+    _no_grad_inputs("attn_decode", q, k, v)
+    if (q.dim() != 2 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[1] != k.shape[2] or k.stride() != v.stride()
+            or k.stride(2) != 1 or q.stride(1) != 1 or k.dtype != q.dtype or v.dtype != q.dtype):
+        raise ValueError(f"attn_decode: incompatible q{tuple(q.shape)} k{tuple(k.shape)}/{k.stride()} v{tuple(v.shape)}/{v.stride()}")
+    B, d = q.shape
+    S = k.shape[1]
+    if d % num_heads:
+        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {d} and `num_heads`: {num_heads}).")
+    _check_mask(key_valid, (B, S))
+    if S == 0:
+        raise ValueError("attn_decode: no keys")
+    if key_valid.dtype == torch.bool:
+        key_valid = key_valid.view(torch.uint8)
+    elif key_valid.dtype != torch.uint8:
+        key_valid = key_valid.to(torch.uint8)
+    if key_valid.stride(1) != 1:
+        key_valid = key_valid.contiguous()
+    out = torch.empty(B, d, dtype=q.dtype, device=q.device)
+    _lib.call("mmgl_attn_decode_fwd", dict(bytes=2.0 * B * S * d * q.element_size()), ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(1), k.stride(0),
+              ptr(key_valid), key_valid.stride(0), ptr(out), B, num_heads, S, d // num_heads, dtype_code(q), stream_ptr())
+    return out
