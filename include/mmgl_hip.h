@@ -382,7 +382,7 @@ int mmgl_broadcast(void* comm, void* buf, size_t count, int dtype, int root, voi
 int mmgl_comm_destroy(void* comm);
 
 /* ---------------------------------------------------------------------------------------------
- * Greedy generation with a key/value cache: the two kernels of a decode step (csrc/decode.hip).
+ * Greedy generation with a key/value cache: the kernels of a decode step (csrc/decode.hip).
  * replaces: the sequential generation of the test protocol, language_modelling/run_generation.py:597-603
  *   (model.module.generate(..., max_new_tokens=32)), which the reference's wrappers cannot serve: its self-attention
  *   returns no cache (model/modelling_cross_attention.py:372), the decoder collects none (:629) and the causal LM hands
@@ -402,7 +402,19 @@ int mmgl_comm_destroy(void* comm);
  *   key_valid [B, S] uint8 with row stride ld_valid, 1 = attend.  Causality is the caller's: a cache holds only keys at or before
  *             the query.  A sample with no valid key gets the uniform distribution over its S keys (as mmgl_xattn_fwd).
  *   out       [B, H*D] dense
- *   D in {16,32,64,128} (those of mmgl_xattn_fwd); any S >= 1; strides multiples of 16 bytes.  fp32 softmax. */
+ *   D in {16,32,64,128} (those of mmgl_xattn_fwd); any S >= 1; strides multiples of 16 bytes.  fp32 softmax.
+ *
+ * mmgl_gemm_skinny_lora: y[M,N] = act((x . W^T + bias + lora_scale * (x . A^T) . B^T) * scale) + residual -- mmgl_gemm_skinny for a
+ *   projection that carries a LoRA adapter (q_proj / v_proj of model/modelling_self_attention.py's LoRALinear; the training forward
+ *   is mmgl_lora_linear_fwd).  lora_A [r, K] row stride lda, lora_B [N, r] row stride ldb, 1 <= r <= 256 (> 256: MMGL_ERR_UNSUPPORTED);
+ *   x, W, bias, residual, y, act, scale, the dtypes and the M <= 64 limit as mmgl_gemm_skinny (ldy free: v goes into its cache
+ *   column in place).  workspace: M * r floats owned by the caller, 4-byte aligned; on return it holds t = x . A^T in fp32.
+ *   Two launches: t (fp32, never rounded to the storage type), then the kernels of mmgl_gemm_skinny with sum_j t[m,j] B[n,j] added in
+ *   fp32 to the folded K sum, in front of bias, scale, activation and residual.  W is not modified and no merged copy of it is
+ *   built.  Any r works on either kernel; deterministic (no atomics). */
+int mmgl_gemm_skinny_lora(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* residual, void* y, int ldy,
+                          const void* lora_A, int lda, const void* lora_B, int ldb, int r, float lora_scale, void* workspace,
+                          int M, int N, int K, int act, float scale, int dtype, void* stream);
 int mmgl_gemm_skinny(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* residual, void* y, int ldy,
                      int M, int N, int K, int act, float scale, int dtype, void* stream);
 int mmgl_attn_decode_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,

@@ -18,6 +18,14 @@
 // Any dtype / alignment the MFMA kernel does not take (fp32: a correctness path; K % 64, N % 8, unaligned rows) runs on
 // skinny_generic_kernel: one wave per output column, 8 rows of x per wave, fp32 accumulation, same epilogue.
 //
+// mmgl_gemm_skinny_lora.  The same two kernels with a rank-r term in fp32 in front of the epilogue (a trailing parameter pack E...: empty for
+// mmgl_gemm_skinny -- one kernel argument and the same instructions as before -- or one SkLora):
+//   * stage 1, lora_t_kernel: t[M, r] = x . A^T in fp32 into the caller's workspace, one wave per (adapter row, 8 rows of x), 16/32-byte
+//     lane loads over K where the rows are aligned, a fixed butterfly per sum.  A is r K elements (64 KB at r = 16, K = 2048).
+//   * stage 2: the thread that folds output (m, n) adds lora_scale * sum_j t[m, j] B[n, j] to the folded sum -- r FMAs from the
+//     L2-resident t and one row of B -- then bias, scale, activation and residual as before.  The adapter never touches W, and the
+//     term is never rounded to the storage type on its own (ops.lora_linear keeps it in the fp32 accumulators likewise).
+//
 // mmgl_attn_decode_fwd (attn_decode_kernel).  One query row per (batch, head) against S keys addressed in place in the [B, S, H*D] cache
 // rows.  D / VEC lanes share a key (16-byte K and V loads straight to registers, VEC = 8 bf16 / 4 fp32), so a wave covers 64 VEC / D
 // keys per instruction and the 4 waves of the workgroup interleave key blocks; U blocks are loaded before the first is used.  Every lane
@@ -49,8 +57,37 @@ __device__ __forceinline__ void sk_store(const SkArgs<T>& a, int m, int n, float
     a.Y[o] = Elem<T>::from_f(v);
 }
 
-template <int MT, bool HALF>
-__global__ __launch_bounds__(SK_THREADS) void skinny_mfma_kernel(const SkArgs<bf16> a) {
+// the extra term of the epilogue, lora_scale * t[m, :] . B[n, :]: the trailing kernel argument of mmgl_gemm_skinny_lora.  The kernels take
+// it as a parameter pack E...: empty for mmgl_gemm_skinny, whose instantiations keep their one argument and their code.
+template <typename T> struct SkLora {
+    const T* B; const float* t;
+    int ldb, r, vec;                               // vec: r % 8 == 0 and the rows of B and t are aligned for 8-element loads
+    float ls;
+};
+
+template <typename T> __device__ __forceinline__ float sk_extra(int, int) { return 0.f; }
+template <typename T> __device__ __forceinline__ float sk_extra(int m, int n, const SkLora<T>& e) {
+    typedef typename Elem<T>::v8 V8;
+    const float* tr = e.t + (size_t)m * e.r;
+    const T* br = e.B + (size_t)n * e.ldb;
+    float s = 0.f;
+    if (e.vec) {
+        for (int j = 0; j < e.r; j += 8) {
+            const V8 bv = *(const V8*)(br + j);
+            const f32x4 t0 = *(const f32x4*)(tr + j), t1 = *(const f32x4*)(tr + j + 4);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) s += t0[c] * Elem<T>::to_f(bv[c]);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) s += t1[c] * Elem<T>::to_f(bv[4 + c]);
+        }
+    } else {
+        for (int j = 0; j < e.r; ++j) s += tr[j] * Elem<T>::to_f(br[j]);
+    }
+    return e.ls * s;
+}
+
+template <int MT, bool HALF, class... E>
+__global__ __launch_bounds__(SK_THREADS) void skinny_mfma_kernel(const SkArgs<bf16> a, const E... e) {
     constexpr int SL = HALF ? 2 : 1;               // K slots per wave
     constexpr int ROWS = HALF ? 8 : 16;            // weight rows per workgroup
     constexpr int NS = SK_WAVES * SL;              // K slots per workgroup
@@ -153,12 +190,13 @@ __global__ __launch_bounds__(SK_THREADS) void skinny_mfma_kernel(const SkArgs<bf
         float s = 0.f;
 #pragma unroll
         for (int sl = 0; sl < NS; ++sl) s += part[((size_t)sl * MR + m) * ROWS + n];
+        if (sizeof...(E)) s += sk_extra<bf16>(m, n0 + n, e...);
         sk_store(a, m, n0 + n, s);
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void skinny_generic_kernel(const SkArgs<T> a) {
+template <typename T, class... E>
+__global__ __launch_bounds__(256) void skinny_generic_kernel(const SkArgs<T> a, const E... e) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int n = blockIdx.x * 4 + w, m0 = blockIdx.y * 8;
     if (n >= a.N) return;                           // whole waves leave; the kernel has no barrier
@@ -180,26 +218,93 @@ __global__ __launch_bounds__(256) void skinny_generic_kernel(const SkArgs<T> a) 
         const float s = wave_sum(acc[r]);
         if (lane == r) mine = s;
     }
-    if (lane < 8 && m0 + lane < a.M) sk_store(a, m0 + lane, n, mine);
+    if (lane < 8 && m0 + lane < a.M) {
+        if (sizeof...(E)) mine += sk_extra<T>(m0 + lane, n, e...);
+        sk_store(a, m0 + lane, n, mine);
+    }
 }
 
-template <int MT, bool HALF> int launch_skinny_mfma(const SkArgs<bf16>& a, hipStream_t st) {
-    hipLaunchKernelGGL((skinny_mfma_kernel<MT, HALF>), dim3(a.N / (HALF ? 8 : 16)), dim3(SK_THREADS), 0, st, a);
-    MMGL_CHECK_LAUNCH("mmgl_gemm_skinny");
+// stage 1 of mmgl_gemm_skinny_lora: t[M, r] = X[M, K] . A[r, K]^T, fp32.  One wave per adapter row j and 8 rows of x.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void lora_t_kernel(const T* __restrict__ X, int ldx, const T* __restrict__ A, int lda,
+                                                     float* __restrict__ t, int M, int r, int K) {
+    typedef typename Elem<T>::v8 V8;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int j = blockIdx.x * 4 + w, m0 = blockIdx.y * 8;
+    if (j >= r) return;                             // whole waves leave; the kernel has no barrier
+    float acc[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q] = 0.f;
+    const T* arow = A + (size_t)j * lda;
+    if (VEC) {
+        for (int k = lane * 8; k < K; k += WAVE * 8) {
+            const V8 av = *(const V8*)(arow + k);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int m = min(m0 + q, M - 1);
+                const V8 xv = *(const V8*)(X + (size_t)m * ldx + k);
+#pragma unroll
+                for (int c = 0; c < 8; ++c) acc[q] += Elem<T>::to_f(av[c]) * Elem<T>::to_f(xv[c]);
+            }
+        }
+    } else {
+        for (int k = lane; k < K; k += WAVE) {
+            const float av = Elem<T>::to_f(arow[k]);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int m = min(m0 + q, M - 1);
+                acc[q] += av * Elem<T>::to_f(X[(size_t)m * ldx + k]);
+            }
+        }
+    }
+    float mine = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const float s = wave_sum(acc[q]);
+        if (lane == q) mine = s;
+    }
+    if (lane < 8 && m0 + lane < M) t[(size_t)(m0 + lane) * r + j] = mine;
+}
+
+template <int MT, bool HALF, class... E> int launch_skinny_mfma(const SkArgs<bf16>& a, hipStream_t st, const E&... e) {
+    hipLaunchKernelGGL((skinny_mfma_kernel<MT, HALF, E...>), dim3(a.N / (HALF ? 8 : 16)), dim3(SK_THREADS), 0, st, a, e...);
+    MMGL_CHECK_LAUNCH(sizeof...(E) ? "mmgl_gemm_skinny_lora" : "mmgl_gemm_skinny");
     return MMGL_OK;
 }
 
-template <bool HALF> int launch_skinny_mt(const SkArgs<bf16>& a, hipStream_t st) {
-    if (a.M <= 16) return launch_skinny_mfma<1, HALF>(a, st);
-    if (a.M <= 32) return launch_skinny_mfma<2, HALF>(a, st);
-    return launch_skinny_mfma<4, HALF>(a, st);
+template <bool HALF, class... E> int launch_skinny_mt(const SkArgs<bf16>& a, hipStream_t st, const E&... e) {
+    if (a.M <= 16) return launch_skinny_mfma<1, HALF>(a, st, e...);
+    if (a.M <= 32) return launch_skinny_mfma<2, HALF>(a, st, e...);
+    return launch_skinny_mfma<4, HALF>(a, st, e...);
 }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-template <typename T> int launch_skinny_generic(const SkArgs<T>& a, hipStream_t st) {
-    hipLaunchKernelGGL((skinny_generic_kernel<T>), dim3(cdiv(a.N, 4), cdiv(a.M, 8)), dim3(256), 0, st, a);
-    MMGL_CHECK_LAUNCH("mmgl_gemm_skinny");
+template <typename T, class... E> int launch_skinny_generic(const SkArgs<T>& a, hipStream_t st, const E&... e) {
+    hipLaunchKernelGGL((skinny_generic_kernel<T, E...>), dim3(cdiv(a.N, 4), cdiv(a.M, 8)), dim3(256), 0, st, a, e...);
+    MMGL_CHECK_LAUNCH(sizeof...(E) ? "mmgl_gemm_skinny_lora" : "mmgl_gemm_skinny");
+    return MMGL_OK;
+}
+
+// the route of a bf16 call, with or without the extra term: the MFMA kernel where it takes the shape, else the generic one
+template <class... E> int skinny_bf16(const SkArgs<bf16>& a, hipStream_t st, const E&... e) {
+    // the MFMA kernel addresses W rows of a workgroup and the whole x through 32-bit buffer offsets
+    const bool mfma = a.K % 64 == 0 && a.N % 8 == 0 && a.ldx % 8 == 0 && a.ldw % 8 == 0 && aligned16(a.X) && aligned16(a.W) &&
+                      ((size_t)(a.M - 1) * a.ldx + a.K) * 2 < (1ull << 31) && (size_t)16 * a.ldw * 2 < (1ull << 31);
+    if (!mfma) return launch_skinny_generic<bf16>(a, st, e...);
+    // 16 weight rows per workgroup where that still gives every CU one, else 8
+    if (a.N % 16 == 0 && a.N / 16 >= mmgl_num_cu()) return launch_skinny_mt<false>(a, st, e...);
+    return launch_skinny_mt<true>(a, st, e...);
+}
+
+template <typename T>
+int launch_lora_t(const T* x, int ldx, const T* A, int lda, float* t, int M, int r, int K, hipStream_t st) {
+    const size_t al = 8 * sizeof(T);
+    const bool vec = K % 8 == 0 && ldx % 8 == 0 && lda % 8 == 0 && (uintptr_t)x % al == 0 && (uintptr_t)A % al == 0;
+    const dim3 grid(cdiv(r, 4), cdiv(M, 8));
+    if (vec) hipLaunchKernelGGL((lora_t_kernel<T, true>), grid, dim3(256), 0, st, x, ldx, A, lda, t, M, r, K);
+    else hipLaunchKernelGGL((lora_t_kernel<T, false>), grid, dim3(256), 0, st, x, ldx, A, lda, t, M, r, K);
+    MMGL_CHECK_LAUNCH("mmgl_gemm_skinny_lora (x A^T)");
     return MMGL_OK;
 }
 
@@ -342,13 +447,36 @@ extern "C" int mmgl_gemm_skinny(const void* x, int ldx, const void* W, int ldw, 
         return launch_skinny_generic<float>(a, st);
     }
     SkArgs<bf16> a{(const bf16*)x, (const bf16*)W, (const bf16*)bias, (const bf16*)residual, (bf16*)y, ldx, ldw, ldy, M, N, K, act, scale};
-    // the MFMA kernel addresses W rows of a workgroup and the whole x through 32-bit buffer offsets
-    const bool mfma = K % 64 == 0 && N % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && aligned16(x) && aligned16(W) &&
-                      ((size_t)(M - 1) * ldx + K) * 2 < (1ull << 31) && (size_t)16 * ldw * 2 < (1ull << 31);
-    if (!mfma) return launch_skinny_generic<bf16>(a, st);
-    // 16 weight rows per workgroup where that still gives every CU one, else 8
-    if (N % 16 == 0 && N / 16 >= mmgl_num_cu()) return launch_skinny_mt<false>(a, st);
-    return launch_skinny_mt<true>(a, st);
+    return skinny_bf16(a, st);
+}
+
+extern "C" int mmgl_gemm_skinny_lora(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* residual, void* y, int ldy,
+                                     const void* lora_A, int lda, const void* lora_B, int ldb, int r, float lora_scale, void* workspace,
+                                     int M, int N, int K, int act, float scale, int dtype, void* stream) {
+    MMGL_CHECK_ARG(M >= 1 && N >= 1 && K >= 1 && r >= 1, "mmgl_gemm_skinny_lora: bad sizes M=%d N=%d K=%d r=%d", M, N, K, r);
+    if (M > 64) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_gemm_skinny_lora: M=%d > 64 rows (chunk the rows)", M);
+    if (r > 256) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_gemm_skinny_lora: rank %d > 256", r);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_gemm_skinny_lora: bad dtype %d", dtype);
+    MMGL_CHECK_ARG(x && W && y && lora_A && lora_B && workspace, "mmgl_gemm_skinny_lora: null pointer");
+    MMGL_CHECK_ARG(act == MMGL_ACT_NONE || act == MMGL_ACT_RELU, "mmgl_gemm_skinny_lora: unknown activation %d", act);
+    MMGL_CHECK_ARG(ldx >= K && ldw >= K && ldy >= N && lda >= K && ldb >= r,
+                   "mmgl_gemm_skinny_lora: leading dimensions (%d, %d, %d, %d, %d) smaller than the rows (K=%d, N=%d, r=%d)", ldx, ldw, ldy, lda,
+                   ldb, K, N, r);
+    MMGL_CHECK_ARG(((uintptr_t)workspace & 3) == 0, "mmgl_gemm_skinny_lora: the fp32 workspace is not 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    float* t = (float*)workspace;
+    if (dtype == MMGL_F32) {
+        const int rc = launch_lora_t<float>((const float*)x, ldx, (const float*)lora_A, lda, t, M, r, K, st);
+        if (rc != MMGL_OK) return rc;
+        SkArgs<float> a{(const float*)x, (const float*)W, (const float*)bias, (const float*)residual, (float*)y, ldx, ldw, ldy, M, N, K, act, scale};
+        const int vec = r % 8 == 0 && ldb % 8 == 0 && ((uintptr_t)lora_B & 31) == 0 && aligned16(t);
+        return launch_skinny_generic<float>(a, st, SkLora<float>{(const float*)lora_B, t, ldb, r, vec, lora_scale});
+    }
+    const int rc = launch_lora_t<bf16>((const bf16*)x, ldx, (const bf16*)lora_A, lda, t, M, r, K, st);
+    if (rc != MMGL_OK) return rc;
+    SkArgs<bf16> a{(const bf16*)x, (const bf16*)W, (const bf16*)bias, (const bf16*)residual, (bf16*)y, ldx, ldw, ldy, M, N, K, act, scale};
+    const int vec = r % 8 == 0 && ldb % 8 == 0 && aligned16(lora_B) && aligned16(t);
+    return skinny_bf16(a, st, SkLora<bf16>{(const bf16*)lora_B, t, ldb, r, vec, lora_scale});
 }
 
 extern "C" int mmgl_attn_decode_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,

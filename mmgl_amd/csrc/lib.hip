@@ -70,4 +70,5 @@ int mmgl_num_cu() {
 // 103: mmgl_comm_* / mmgl_allreduce_sum / mmgl_allgather / mmgl_broadcast.
 // 105: the stand-alone dgrad, weight-gradient and transpose entry points removed (mmgl_linear_bwd covers them).
 // 106: mmgl_gemm_skinny / mmgl_attn_decode_fwd (the decode step of generate()).
-extern "C" int mmgl_version(void) { return 106; }
+// 107: mmgl_gemm_skinny_lora (the decode step of a LoRA-adapted projection).
+extern "C" int mmgl_version(void) { return 107; }

@@ -19,6 +19,7 @@
 wandb / torchmetrics / warmup_scheduler are absent here: logging goes to stdout, BLEU is a local corpus-BLEU,
 ROUGE is not computed, the warm-up is restated as linear 0 -> lr over lr_warmup_steps then StepLR (parity unpinned).
 """
+import inspect
 import os
 import random
 import sys
@@ -318,9 +319,10 @@ def _pass_sizes(n_micro, samples, tokens_per_sample, budget_tokens):
 
 
 _META_KEYS = ("attention_mask", "neighbor_pos_ids", "neighbor_attention_mask", "neighbor_images_pos_ids")
-# the neighbor arguments CrossAttentionModel.generate shares with forward; any other key a collate adds stays out of the call
+# the batch fields a wrapper's generate() may share with its forward; those it names in its signature are passed (SelfAttentionModel
+# adds images / image_positions / lpe / graph to CrossAttentionModel's neighbor arguments), any other key a collate adds stays out
 _GENERATE_FIELDS = ("neighbor_input_ids", "neighbor_attention_mask", "neighbor_pos_ids", "text_locations", "neighbor_images",
-                    "neighbor_images_pos_ids", "image_locations")
+                    "neighbor_images_pos_ids", "image_locations", "images", "image_positions", "lpe", "graph")
 
 
 class _GroupFeeder:
@@ -614,7 +616,8 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                 losses.update(v, mb)
             if prefix == "test" and hasattr(model, "generate") and getattr(model, "can_generate", lambda: False)():
                 L_in = args.max_input_length
-                fields = {key: batch[key] for key in _GENERATE_FIELDS if key in batch}       # generate()'s named neighbor arguments only
+                named = inspect.signature(getattr(type(model), "generate", model.generate)).parameters     # the class's own signature
+                fields = {key: batch[key] for key in _GENERATE_FIELDS if key in batch and key in named}    # generate()'s named arguments only
                 generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),
                                                attention_mask=batch["attention_mask"][:, :L_in].contiguous(), **fields,
                                                host_meta=extra.get("host_meta"), max_new_tokens=32,

@@ -294,20 +294,31 @@ class MPTAttention(nn.Module):
         if any(type(m) is not nn.Linear for m in mods):
             raise ValueError("the decode step runs plain nn.Linear projections only (adapted projections, e.g. LoRA, have no decode path)")
 
+    @staticmethod
+    def _decode_proj(mod, x, out_scale=1.0, out=None):
+        """One of q / k / v on the rows of a decode step: a plain nn.Linear, or a LoRA-adapted one through its own decode()
+        (model/modelling_self_attention.LoRALinear: the rank-r term rides in the skinny GEMM's epilogue)."""
+        if type(mod) is nn.Linear:
+            return ops.decode_linear(x, mod.weight, mod.bias, out_scale=out_scale, out=out)
+        if hasattr(mod, "lora_A") and hasattr(mod, "decode"):
+            return mod.decode(x, out_scale=out_scale, out=out)
+        raise ValueError("the decode step runs plain nn.Linear projections only (adapted projections, e.g. LoRA, have no decode path)")
+
     def decode_self(self, x, kv, key_mask, col):
         """x [B, d]: the new token's layer input.  Projects q and writes k|v into column `col` of the layer's cache rows kv
-        [B, capacity, 2d], then attends over columns 0..col (all at or before the query: no causal test)."""
+        [B, capacity, 2d], then attends over columns 0..col (all at or before the query: no causal test).  q_proj and v_proj may be
+        LoRA-adapted (any other adapter type, and an adapted k_proj / out_proj, is refused)."""
         d = self.embed_dim
-        self._plain(self.q_proj, self.k_proj, self.v_proj, self.out_proj)
+        self._plain(self.k_proj, self.out_proj)
         fused = self._frozen_qkv()
         if fused is not None:
             w, b = fused
             q = ops.decode_linear(x, w[:d], b[:d])
             ops.decode_linear(x, w[d:], b[d:], out=kv[:, col])
         else:
-            q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
+            q = self._decode_proj(self.q_proj, x, out_scale=self.scaling)
             ops.decode_linear(x, self.k_proj.weight, self.k_proj.bias, out=kv[:, col, :d])
-            ops.decode_linear(x, self.v_proj.weight, self.v_proj.bias, out=kv[:, col, d:])
+            self._decode_proj(self.v_proj, x, out=kv[:, col, d:])
         return ops.attn_decode(q, kv[:, :col + 1, :d], kv[:, :col + 1, d:], key_mask[:, :col + 1], self.num_heads)
 
     def decode_cross(self, x, k, v, key_valid):
@@ -894,8 +905,8 @@ class MPTForCausalLM(MPTPreTrainedModel):
         return True
 
     @torch.no_grad()
-    def generate(self, input_ids, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
-                 eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False):
+    def generate(self, input_ids=None, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
+                 eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, inputs_embeds=None):
         """Greedy decoding (do_sample=False, one beam) with a key/value cache: what the reference's test protocol asks of its
         wrappers (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of
         every layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
@@ -905,10 +916,18 @@ class MPTForCausalLM(MPTPreTrainedModel):
         eos_token_id: a row that has emitted it gets pad_token_id (default config.pad_token_id) from then on, as in HF's greedy loop;
         None: no end-of-sequence handling.  All max_new_tokens steps run (no host synchronisation to stop early).
         Returns the [B, T + max_new_tokens] ids; with return_step_logits=True also the [B, max_new_tokens, V] logits the tokens
-        were picked from."""
-        if not input_ids.is_cuda:
-            raise RuntimeError(f"generate() runs on the GPU only (input_ids is on {input_ids.device}); there is no CPU path")
-        B, T = input_ids.shape
+        were picked from.
+        inputs_embeds [B, T, d_embed] instead of input_ids (exactly one of the two): the prefill runs on the embeddings (virtual
+        tokens, image or neighbor tokens already in the sequence); there are no prompt ids to repeat, so only the new tokens
+        [B, max_new_tokens] come back (HF's convention for inputs_embeds)."""
+        if (input_ids is None) == (inputs_embeds is None):
+            raise ValueError("generate() takes exactly one of input_ids and inputs_embeds")
+        prompt = input_ids if input_ids is not None else inputs_embeds
+        if not prompt.is_cuda:
+            raise RuntimeError(f"generate() runs on the GPU only (the prompt is on {prompt.device}); there is no CPU path")
+        if prompt.dim() != (2 if input_ids is not None else 3):
+            raise ValueError(f"generate(): input_ids [B, T] or inputs_embeds [B, T, d_embed], got {tuple(prompt.shape)}")
+        B, T = prompt.shape[:2]
         n_new = int(max_new_tokens)
         if n_new < 1:
             raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
@@ -920,15 +939,17 @@ class MPTForCausalLM(MPTPreTrainedModel):
             if pad_token_id is None:
                 raise ValueError("generate(): eos_token_id needs a pad_token_id")
         if attention_mask is None:
-            attention_mask = torch.ones_like(input_ids)
-        out = dec(input_ids=input_ids, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
+            attention_mask = torch.ones(B, T, dtype=torch.int64, device=prompt.device)
+        out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
                   cache_capacity=min(T + n_new - 1, dec.max_target_positions))
         cache = out.past_key_values
         hidden = out.last_hidden_state[:, -1]
-        ids = torch.empty(B, T + n_new, dtype=input_ids.dtype, device=input_ids.device)
-        ids[:, :T] = input_ids
-        finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
+        T = T if input_ids is not None else 0                  # columns of the result in front of the new tokens
+        ids = torch.empty(B, T + n_new, dtype=torch.int64 if input_ids is None else input_ids.dtype, device=prompt.device)
+        if input_ids is not None:
+            ids[:, :T] = input_ids
+        finished = torch.zeros(B, dtype=torch.bool, device=prompt.device)
         steps = []
         for s in range(n_new):
             logits = self._last_logits(hidden)

@@ -70,6 +70,11 @@ class LoRALinear(nn.Module):
             return y if out_scale == 1.0 else y * out_scale
         return ops.lora_linear(x, self.base_layer.weight, self.base_layer.bias, self.lora_A, self.lora_B, self.scaling, out_scale)
 
+    def decode(self, x, out_scale=1.0, out=None):
+        """The layer on the rows of a decode step, x [B, in_features]: ops.decode_lora_linear -- the same function as forward (the
+        rank-r term kept apart from the bf16 weight, in fp32), never a merged weight.  `out`: a strided [B, out_features] view."""
+        return ops.decode_lora_linear(x, self.base_layer.weight, self.base_layer.bias, self.lora_A, self.lora_B, self.scaling, out_scale, out)
+
 
 def inject_lora(model: nn.Module, r: int, alpha: float, dropout: float, targets=("q_proj", "v_proj", "q", "v")):
     """Freeze `model`, swap every attention q/v nn.Linear for LoRALinear, keep lm_head trainable.  Returns #swapped."""
@@ -245,7 +250,59 @@ class SelfAttentionModel(nn.Module):
         return self
 
     # ------------------------------------------------------------------------------------------ LM call
-    def _run_lm(self, input_embs=None, input_ids=None, attention_mask=None, labels=None):
+    def _lm_inputs(self, input_ids, attention_mask, images=None, image_positions=None, neighbor_input_ids=None,
+                   neighbor_attention_mask=None, neighbor_pos_ids=None, text_locations=None, neighbor_images=None,
+                   neighbor_images_pos_ids=None, image_locations=None, lpe=None, graph=None):
+        """What the LM is fed for a batch, shared by forward and generate: (lm_input, attention_mask).  lm_input is the [B, T] ids
+        when the sequence is text alone, else the [B, T', d] input embeddings
+            [virtual tokens (prompt tuning) | token embeddings, image tokens scattered in (raw + images) | neighbor tokens (embedding mode)]
+        and attention_mask [B, T'] covers the same columns (virtual tokens always valid, padded neighbor slots masked)."""
+        input_embs = None
+        if self.neighbor_mode == "raw" and self.context in ("section_only", "text_only"):
+            pass
+        elif self.neighbor_mode == "raw" and self.context in ("section_all", "all"):
+            input_embs = self.input_embeddings(input_ids.clamp_min(0)).clone()
+            visual_embs = self.get_visual_embs(images)
+            B, _, hidden_dim = input_embs.shape
+            batch_idx = torch.arange(B, device=input_embs.device)[:, None]
+            input_embs[batch_idx, image_positions] = visual_embs.reshape(B, -1, hidden_dim).to(input_embs.dtype)
+        else:
+            if self.neighbor_mode == "embedding" and self.context in ("section_only", "text_only"):
+                text = self.get_text_embs(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids)
+                B, Nt = text.shape[:2]
+                loc = torch.arange(Nt, device=text.device).expand(B, -1).contiguous()
+                neighbor_embeds, key_valid = ops.neighbor_interleave(text, None, loc, None, neighbor_pos_ids, None)
+            elif self.neighbor_mode == "embedding" and self.context in ("section_all", "all"):
+                text = self.get_text_embs(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids)
+                visual = self.get_visual_embs(neighbor_images, neighbor_images_pos_ids)
+                B, Nt, n_tokens, hidden_dim = text.shape
+                total = Nt + visual.shape[1]
+                neighbor_embeds, key_valid = ops.neighbor_interleave(text, visual, text_locations, image_locations,
+                                                                     neighbor_pos_ids, neighbor_images_pos_ids)
+                if self.context == "all":
+                    if self.position_type == "laplacian":
+                        lpe_emb = ops.linear(lpe.to(neighbor_embeds.dtype), self.lpe_embeddings.weight, self.lpe_embeddings.bias)
+                        lpe_emb = lpe_emb.reshape(B, total + 1, n_tokens, hidden_dim)
+                        neighbor_embeds = neighbor_embeds + lpe_emb[:, 1:].reshape(B, -1, hidden_dim)
+                    elif self.position_type == "gnn":
+                        flat = neighbor_embeds.reshape(B, total, n_tokens * hidden_dim)
+                        neighbor_embeds = (flat + self.gnn(flat, graph)).reshape(B, -1, hidden_dim)
+            else:
+                raise ValueError(f"Neighbor mode: {self.neighbor_mode} and context: {self.context} are not supported.")
+            # neighbors go AFTER the token embeddings (reference :323-325)
+            input_embs = torch.cat((self.input_embeddings(input_ids), neighbor_embeds.to(self.input_embeddings.weight.dtype)), dim=1)
+            attention_mask = torch.cat((attention_mask, key_valid.to(attention_mask.dtype)), dim=1)
+        if self.prompt_embeddings is not None:
+            if input_embs is None:
+                input_embs = self.input_embeddings(input_ids)
+            B = input_embs.shape[0]
+            prompt = self.prompt_embeddings.weight.to(input_embs.dtype)[None].expand(B, -1, -1)
+            input_embs = torch.cat([prompt, input_embs], dim=1)
+            attention_mask = torch.cat([attention_mask.new_ones(B, NUM_VIRTUAL_TOKENS), attention_mask], dim=1)
+        return (input_ids if input_embs is None else input_embs), attention_mask
+
+    def _run_lm(self, lm_input, attention_mask, labels=None):
+        """lm_input: the ids or the embeddings of _lm_inputs."""
         kw = {}
         opts = getattr(self, "_logit_opts", None)
         if opts and hasattr(self.lm, "model") and "t5" not in self.args.model_name_or_path:
@@ -255,21 +312,12 @@ class SelfAttentionModel(nn.Module):
                 shift = lambda v: v + NUM_VIRTUAL_TOKENS if (v is not None and v >= 0) else v
                 sl = slice(shift(sl.start if sl.start is not None else 0), shift(sl.stop), sl.step)
             kw.update(return_logits=rl, logits_slice=sl)
-        if self.prompt_embeddings is not None:
-            if input_embs is None:
-                input_embs = self.input_embeddings(input_ids)
-            B = input_embs.shape[0]
-            prompt = self.prompt_embeddings.weight.to(input_embs.dtype)[None].expand(B, -1, -1)
-            input_embs = torch.cat([prompt, input_embs], dim=1)
-            attention_mask = torch.cat([attention_mask.new_ones(B, NUM_VIRTUAL_TOKENS), attention_mask], dim=1)
-            if self.decoder_only and labels is not None:
-                labels = torch.cat([labels.new_full((B, NUM_VIRTUAL_TOKENS), -100), labels], dim=1)
         if self.prefix_encoder is not None:
             # labels and logits keep the sequence length: the prefix lives in the attention of every layer, not in the sequence
             kw["past_key_values"] = self.prefix_encoder.weight.to(self.input_embeddings.weight.dtype)
-        if input_embs is not None:
-            return self.lm(inputs_embeds=input_embs, attention_mask=attention_mask, labels=labels, **kw)
-        return self.lm(input_ids=input_ids, attention_mask=attention_mask, labels=labels, **kw)
+        if lm_input.dim() == 3:
+            return self.lm(inputs_embeds=lm_input, attention_mask=attention_mask, labels=labels, **kw)
+        return self.lm(input_ids=lm_input, attention_mask=attention_mask, labels=labels, **kw)
 
     def forward(self, input_ids, attention_mask, labels, images=None, image_positions=None, neighbor_input_ids=None,
                 neighbor_attention_mask=None, neighbor_pos_ids=None, text_locations=None, neighbor_images=None,
@@ -279,46 +327,60 @@ class SelfAttentionModel(nn.Module):
         self._logit_opts = (return_logits, logits_slice) if (return_logits is not None or logits_slice is not None) else None
         # host_meta (optional, see modelling_cross_attention.host_metadata): accepted for a uniform trainer call; this wrapper
         # encodes every neighbor slot (the concatenated sequence keeps padded slots as masked keys), so it has no use for it
-        if self.neighbor_mode == "raw" and self.context in ("section_only", "text_only"):
-            return self._run_lm(input_ids=input_ids, attention_mask=attention_mask, labels=labels)
-
-        if self.neighbor_mode == "raw" and self.context in ("section_all", "all"):
-            input_embs = self.input_embeddings(input_ids.clamp_min(0)).clone()
-            visual_embs = self.get_visual_embs(images)
-            B, _, hidden_dim = input_embs.shape
-            batch_idx = torch.arange(B, device=input_embs.device)[:, None]
-            input_embs[batch_idx, image_positions] = visual_embs.reshape(B, -1, hidden_dim).to(input_embs.dtype)
-            if self.decoder_only:
+        lm_input, lm_mask = self._lm_inputs(input_ids, attention_mask, images, image_positions, neighbor_input_ids, neighbor_attention_mask,
+                                            neighbor_pos_ids, text_locations, neighbor_images, neighbor_images_pos_ids, image_locations,
+                                            lpe, graph)
+        if self.decoder_only and labels is not None:
+            # labels follow the layout of _lm_inputs: -100 on image tokens, on the neighbor tokens behind the text (reference :327-330)
+            # and on the virtual tokens in front of it
+            if self.neighbor_mode == "raw" and self.context in ("section_all", "all"):
                 labels = labels.clone()
-                labels[batch_idx, image_positions] = -100
-            return self._run_lm(input_embs=input_embs, attention_mask=attention_mask, labels=labels)
+                labels[torch.arange(labels.shape[0], device=labels.device)[:, None], image_positions] = -100
+            front = NUM_VIRTUAL_TOKENS if self.prompt_embeddings is not None else 0
+            back = lm_mask.shape[1] - front - labels.shape[1]
+            if back:
+                labels = torch.cat((labels, labels.new_full((labels.shape[0], back), -100)), dim=1)
+            if front:
+                labels = torch.cat([labels.new_full((labels.shape[0], front), -100), labels], dim=1)
+        return self._run_lm(lm_input, lm_mask, labels)
 
-        if self.neighbor_mode == "embedding" and self.context in ("section_only", "text_only"):
-            text = self.get_text_embs(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids)
-            B, Nt = text.shape[:2]
-            loc = torch.arange(Nt, device=text.device).expand(B, -1).contiguous()
-            neighbor_embeds, key_valid = ops.neighbor_interleave(text, None, loc, None, neighbor_pos_ids, None)
-        elif self.neighbor_mode == "embedding" and self.context in ("section_all", "all"):
-            text = self.get_text_embs(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids)
-            visual = self.get_visual_embs(neighbor_images, neighbor_images_pos_ids)
-            B, Nt, n_tokens, hidden_dim = text.shape
-            total = Nt + visual.shape[1]
-            neighbor_embeds, key_valid = ops.neighbor_interleave(text, visual, text_locations, image_locations,
-                                                                 neighbor_pos_ids, neighbor_images_pos_ids)
-            if self.context == "all":
-                if self.position_type == "laplacian":
-                    lpe_emb = ops.linear(lpe.to(neighbor_embeds.dtype), self.lpe_embeddings.weight, self.lpe_embeddings.bias)
-                    lpe_emb = lpe_emb.reshape(B, total + 1, n_tokens, hidden_dim)
-                    neighbor_embeds = neighbor_embeds + lpe_emb[:, 1:].reshape(B, -1, hidden_dim)
-                elif self.position_type == "gnn":
-                    flat = neighbor_embeds.reshape(B, total, n_tokens * hidden_dim)
-                    neighbor_embeds = (flat + self.gnn(flat, graph)).reshape(B, -1, hidden_dim)
-        else:
-            raise ValueError(f"Neighbor mode: {self.neighbor_mode} and context: {self.context} are not supported.")
+    def can_generate(self):
+        """Whether generate() exists for this wrapper: the decoder-only OPT fork without adapters, with LoRA or with prompt tuning.
+        Not T5 (the stock HuggingFace model) and not OPT prefix tuning (a key/value prefix has no decode cache)."""
+        from .modelling_cross_attention import MPTForCausalLM
+        return isinstance(self.lm, MPTForCausalLM) and self.args.peft_type in ("none", "lora", "prompt")
 
-        # neighbors go AFTER the token embeddings (reference :323-325); labels padded with -100 (:327-330)
-        input_embs = torch.cat((self.input_embeddings(input_ids), neighbor_embeds.to(self.input_embeddings.weight.dtype)), dim=1)
-        attention_mask = torch.cat((attention_mask, key_valid.to(attention_mask.dtype)), dim=1)
-        if self.decoder_only:
-            labels = torch.cat((labels, labels.new_full(key_valid.shape, -100)), dim=1)
-        return self._run_lm(input_embs=input_embs, attention_mask=attention_mask, labels=labels)
+    @torch.no_grad()
+    def generate(self, input_ids, attention_mask, images=None, image_positions=None, neighbor_input_ids=None,
+                 neighbor_attention_mask=None, neighbor_pos_ids=None, text_locations=None, neighbor_images=None,
+                 neighbor_images_pos_ids=None, image_locations=None, lpe=None, graph=None, host_meta=None, max_new_tokens=32,
+                 eos_token_id=None, pad_token_id=None, return_step_logits=False):
+        """Greedy generation from the prompt `input_ids` [B, T] (right-padded).  The LM input is built exactly as forward builds it
+        (_lm_inputs), then MPTForCausalLM.generate runs the prefill and the cached decode steps (LoRA-adapted q / v projections on
+        ops.decode_lora_linear).  New tokens are appended behind the whole LM input:
+            [virtual tokens | prompt, image tokens scattered in | neighbor tokens | new tokens ...]
+        so in embedding mode they follow the neighbor tokens and see them; padded neighbor slots stay masked keys, and position ids
+        count the valid keys, as the cache does.  Returns [B, T + max_new_tokens] ids -- input_ids followed by the new tokens -- and the
+        [B, max_new_tokens, V] step logits with return_step_logits=True."""
+        if not self.can_generate():
+            raise ValueError(f"generate() is implemented for the decoder-only OPT fork with peft_type none / lora / prompt, not for "
+                             f"{type(self.lm).__name__} with peft_type {self.args.peft_type!r}")
+        if not input_ids.is_cuda:
+            raise RuntimeError(f"generate() runs on the GPU only (input_ids is on {input_ids.device}); there is no CPU path")
+        T = input_ids.shape[1]
+        if image_positions is not None and self.neighbor_mode == "raw" and self.context in ("section_all", "all"):
+            if bool((image_positions >= T).any()):          # one host read per call: the scatter below would write out of bounds
+                raise ValueError(f"generate(): image_positions must lie inside the {T} prompt columns")
+        lm_input, lm_mask = self._lm_inputs(input_ids, attention_mask, images, image_positions, neighbor_input_ids, neighbor_attention_mask,
+                                            neighbor_pos_ids, text_locations, neighbor_images, neighbor_images_pos_ids, image_locations,
+                                            lpe, graph)
+        # key 0 is a virtual token under prompt tuning (always valid); otherwise the collate may vouch for the prompt's first column
+        first = self.prompt_embeddings is not None or bool(host_meta and host_meta.get("first_key_valid"))
+        kw = dict(max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, return_step_logits=return_step_logits,
+                  first_key_valid=first)
+        if lm_input.dim() == 2:
+            return self.lm.generate(lm_input, lm_mask, **kw)
+        out = self.lm.generate(inputs_embeds=lm_input, attention_mask=lm_mask, **kw)
+        new, logits = out if return_step_logits else (out, None)
+        ids = torch.cat([input_ids, new.to(input_ids.dtype)], dim=1)
+        return (ids, logits) if return_step_logits else ids

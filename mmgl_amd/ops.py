@@ -1449,6 +1449,61 @@ def decode_linear(x, weight, bias=None, act="none", out_scale=1.0, residual=None
     return y
 
 
+def gemm_skinny_lora(x, weight, lora_A, lora_B, scaling, bias=None, residual=None, act=0, out_scale=1.0, out=None, workspace=None):
+    """Raw mmgl_gemm_skinny_lora call: x [M <= 64, K], weight [N, K], lora_A [r, K], lora_B [N, r], out [M, N]; row strides are free,
+    column strides 1; workspace: at least M * r fp32 (allocated when None).  No autograd."""
+    require_cuda(x, weight, lora_A, lora_B)
+    M, K = x.shape
+    N, r = lora_B.shape
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+    ws = torch.empty(M * r, dtype=torch.float32, device=x.device) if workspace is None else workspace
+    if ws.dtype != torch.float32 or ws.numel() < M * r or not ws.is_contiguous():
+        raise ValueError(f"gemm_skinny_lora: the workspace must hold {M * r} contiguous fp32 values")
+    _lib.call("mmgl_gemm_skinny_lora", dict(flops=2.0 * M * (N * K + r * K + N * r), bytes=float(M * (K + N) + N * K + r * K + N * r) * x.element_size(),
+                                            tag=f"{M}x{N}x{K}r{r}"),
+              ptr(x), x.stride(0), ptr(weight), weight.stride(0), ptr(bias), ptr(residual), ptr(y), y.stride(0), ptr(lora_A), lora_A.stride(0),
+              ptr(lora_B), lora_B.stride(0), r, float(scaling), ptr(ws), M, N, K, act, float(out_scale), dtype_code(x), stream_ptr())
+    return y
+
+
+def decode_lora_linear(x, weight, bias, lora_A, lora_B, scaling, out_scale=1.0, out=None):
+    """(x @ weight^T + bias + scaling * (x @ lora_A^T) @ lora_B^T) * out_scale for the few rows of a decode step: the forward of a
+    LoRA-adapted projection (lora_linear is its training forward) on mmgl_gemm_skinny_lora -- the weight-streaming GEMM with the rank-r
+    term added in fp32 in its epilogue; no merged copy of the weight.  x [M, K], weight [N, K], lora_A [r, K], lora_B [N, r], r <= 256.
+    `out` [M, N] may be a strided view with unit column stride (the v columns of a key/value cache row).  Rows go in chunks of 64.
+    Forward only; GPU only."""
+    require_cuda(x, weight, lora_A, lora_B)
+    _no_grad_inputs("decode_lora_linear", x, weight, bias, lora_A, lora_B)
+    if (x.dim() != 2 or weight.dim() != 2 or lora_A.dim() != 2 or lora_B.dim() != 2 or x.shape[1] != weight.shape[1]
+            or lora_A.shape[1] != x.shape[1] or lora_B.shape != (weight.shape[0], lora_A.shape[0])):
+        raise ValueError(f"decode_lora_linear: shapes x{tuple(x.shape)} weight{tuple(weight.shape)} lora_A{tuple(lora_A.shape)} "
+                         f"lora_B{tuple(lora_B.shape)}")
+    M, K = x.shape
+    N, r = lora_B.shape
+    if not 1 <= r <= 256:
+        raise ValueError(f"decode_lora_linear: rank {r} (1..256)")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    weight = weight if weight.stride(1) == 1 else weight.contiguous()
+    A = lora_A.detach().to(x.dtype)
+    B = lora_B.detach().to(x.dtype)
+    A = A if A.stride(1) == 1 else A.contiguous()
+    B = B if B.stride(1) == 1 else B.contiguous()
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+    if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.dtype != x.dtype or weight.dtype != x.dtype:
+        raise ValueError(f"decode_lora_linear: out{tuple(y.shape)} {y.dtype} for x{tuple(x.shape)} {x.dtype} weight{tuple(weight.shape)} "
+                         f"{weight.dtype}")
+    if bias is not None and bias.dtype != x.dtype:
+        bias = bias.to(x.dtype)
+    if M == 0:
+        return y
+    ws = torch.empty(min(M, 64) * r, dtype=torch.float32, device=x.device)       # t = x A^T of one chunk
+    for m0 in range(0, M, 64):
+        m1 = min(M, m0 + 64)
+        gemm_skinny_lora(x[m0:m1], weight, A, B, scaling, bias, None, 0, out_scale, y[m0:m1], ws)
+    return y
+
+
 def attn_decode(q, k, v, key_valid, num_heads):
     """One query row per (sample, head) against S keys: q [B, d] already scaled; k, v [B, S, d] views with unit column stride and
     common strides (column slabs of the cache rows [B, capacity, 2d]); key_valid [B, S] bool/uint8 view (True = attend).  Returns [B, d].
