@@ -1504,9 +1504,10 @@ def decode_lora_linear(x, weight, bias, lora_A, lora_B, scaling, out_scale=1.0, 
     return y
 
 
-def attn_decode(q, k, v, key_valid, num_heads):
+def attn_decode(q, k, v, key_valid, num_heads, out=None):
     """One query row per (sample, head) against S keys: q [B, d] already scaled; k, v [B, S, d] views with unit column stride and
-    common strides (column slabs of the cache rows [B, capacity, 2d]); key_valid [B, S] bool/uint8 view (True = attend).  Returns [B, d].
+    common strides (column slabs of the cache rows [B, capacity, 2d]); key_valid [B, S] bool/uint8 view (True = attend).  Returns [B, d]
+    (`out`, a dense [B, d] tensor of q's dtype, when given: a refused call leaves it as it was).
     A sample with no valid key attends uniformly over its S keys.  Forward only; GPU only."""
     require_cuda(q, k, v, key_valid)
     _no_grad_inputs("attn_decode", q, k, v)
@@ -1526,7 +1527,10 @@ def attn_decode(q, k, v, key_valid, num_heads):
         key_valid = key_valid.to(torch.uint8)
     if key_valid.stride(1) != 1:
         key_valid = key_valid.contiguous()
-    out = torch.empty(B, d, dtype=q.dtype, device=q.device)
+    if out is None:
+        out = torch.empty(B, d, dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (B, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError(f"attn_decode: out{tuple(out.shape)} {out.dtype} must be a dense [{B}, {d}] {q.dtype} tensor on {q.device}")
     _lib.call("mmgl_attn_decode_fwd", dict(bytes=2.0 * B * S * d * q.element_size()), ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(1), k.stride(0),
               ptr(key_valid), key_valid.stride(0), ptr(out), B, num_heads, S, d // num_heads, dtype_code(q), stream_ptr())
     return out

@@ -111,6 +111,94 @@ def assert_close(a, b, tol, what="", floor=1e-6):
     return e
 
 
+# ------------------------------------------------------------------------------------------ decode kernels (csrc/decode.hip)
+class SkinnyRef:
+    """fp64 reference of mmgl_gemm_skinny / mmgl_gemm_skinny_lora on the device the (storage-rounded) operands live on:
+        want = act((x W^T + bias + s (x A^T) B^T) * scale) + residual
+        mag  = (|x| |W|^T + |bias| + |s| (|x| |A|^T) |B|^T) * |scale| + |residual|
+    and two deliberately wrong references of the same call, for the assertion that a comparison can fail: `drop_k` (the last 64 K
+    columns of x left out of both products) and, with an adapter, `no_lora` (the rank-r term left out).
+
+    Per-element bound (every element is checked):  |got - want| <= u |want| + 2^-16 mag,  u = 2^-8 (bf16) or 2^-23 (fp32).
+      * u |want| is the half ulp of the one round-to-nearest store of the fp32 result; rounding alone reaches it, so it has no margin.
+      * 2^-16 mag is 256 fp32 roundings of 2^-24 on the magnitude sum: the longest summation chain of either kernel at K = 8192 is
+        below 100 on the MFMA kernel (64 MFMA steps, the in-MFMA tree, the 8-slot fold) and 128 + 6 on the plain one; it also covers
+        a rounding decision, or a ReLU whose pre-activation lies within 2^-16 mag of zero, that the summation order flips.
+    The bound is a function of the reference alone, never of the kernel's output."""
+
+    def __init__(self, x, w, bias=None, relu=False, scale=1.0, residual=None, A=None, B=None, s=1.0):
+        d = lambda t: t.detach().double()
+        X, W = d(x), d(w)
+        K = X.shape[1]
+        tail = slice(max(K - 64, 0), K)
+        pre = X @ W.t()
+        mag = X.abs() @ W.abs().t()
+        gone = X[:, tail] @ W[:, tail].t()
+        lora = None
+        if A is not None:
+            Ad, Bd = d(A), d(B)
+            lora = s * ((X @ Ad.t()) @ Bd.t())
+            pre = pre + lora
+            mag = mag + abs(s) * ((X.abs() @ Ad.abs().t()) @ Bd.abs().t())
+            gone = gone + s * ((X[:, tail] @ Ad[:, tail].t()) @ Bd.t())
+        if bias is not None:
+            mag = mag + d(bias).abs()
+        mag = mag * abs(scale)
+        if residual is not None:
+            mag = mag + d(residual).abs()
+
+        def epilogue(y):
+            if bias is not None:
+                y = y + d(bias)
+            y = y * scale
+            if relu:
+                y = torch.relu(y)
+            return y if residual is None else y + d(residual)
+
+        self.want, self.mag = epilogue(pre), mag
+        self.drop_k = epilogue(pre - gone)
+        self.no_lora = None if lora is None else epilogue(pre - lora)
+
+    def bound(self, dtype):
+        return 2.0 ** (-8 if dtype == torch.bfloat16 else -23) * self.want.abs() + 2.0 ** -16 * self.mag
+
+    @staticmethod
+    def assert_can_fail(refs, dtype, what):
+        """From the references alone: a kernel that drops one 64-wide K unit (or the rank-r term) leaves the bound on >= 25 % of the
+        elements (of the pooled `refs`: the calls of one test, where a single call has too few elements to count on)."""
+        for name, pick in (("the last 64 K columns", lambda r: r.drop_k), ("the rank-r term", lambda r: r.no_lora)):
+            if pick(refs[0]) is not None:
+                out = sum(((pick(r) - r.want).abs() > r.bound(dtype)).sum().item() for r in refs)
+                frac = out / sum(r.want.numel() for r in refs)
+                assert frac >= 0.25, f"{what}: dropping {name} moves only {frac:.0%} of the elements out of the bound"
+
+    def check(self, got, what, group="", can_fail=True):
+        """Asserts the bound on every element of `got` (first, unless can_fail is off, that the comparison can fail); prints and
+        returns the largest err / bound."""
+        if can_fail:
+            SkinnyRef.assert_can_fail([self], got.dtype, what)
+        assert torch.isfinite(got.float()).all(), f"{what}: non-finite output"
+        err, bound = (got.detach().double() - self.want).abs(), self.bound(got.dtype)
+        ratio = (err / bound.clamp_min(1e-300)).max().item()
+        print(f"[bound {group}] {what}: max err/bound {ratio:.3f}")
+        bad = (err > bound).nonzero()
+        assert bad.numel() == 0, (f"{what}: {bad.shape[0]} of {err.numel()} elements outside the bound (max err/bound {ratio:.2f}); "
+                                  f"rows {bad[:, 0].unique().tolist()[:16]}, columns {bad[:, 1].unique().tolist()[:16]}")
+        return ratio
+
+
+def attn_decode_ref(q, k, v, valid, num_heads):
+    """fp64 reference of mmgl_attn_decode_fwd from the storage-rounded operands: q [B, d] (already scaled), k, v [B, S, d],
+    valid [B, S]; softmax over the valid keys of each (sample, head), uniform over all S keys where none is valid.  Returns [B, d]."""
+    B, S, d = k.shape
+    D = d // num_heads
+    sc = torch.einsum("bhd,bshd->bhs", q.double().reshape(B, num_heads, D), k.double().reshape(B, S, num_heads, D))
+    ok = valid.bool()
+    sc = sc.masked_fill(~ok[:, None, :], float("-inf"))
+    sc[~ok.any(1)] = 0.0
+    return torch.einsum("bhs,bshd->bhd", torch.softmax(sc, -1), v.double().reshape(B, S, num_heads, D)).reshape(B, d)
+
+
 # ------------------------------------------------------------------------------------------ tiny model builders
 def tiny_opt_config(pre_ln=True, proj=None, dropout=0.1):
     from transformers import OPTConfig

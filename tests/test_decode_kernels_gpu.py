@@ -1,19 +1,21 @@
 """-m gpu: the two kernels of the decode step (csrc/decode.hip) at the C-ABI level of mmgl_amd.ops.
   * mmgl_gemm_skinny against an fp32 torch GEMM of the same (bf16-rounded) operands, bound as in tests/test_gemm_nt_gpu.py
     (2e-2 * max|want| + 1e-2 on the largest absolute error); every epilogue option; a strided output inside a larger buffer whose
-    other bytes must stay untouched; two runs bitwise equal (the K partials are folded in a fixed order).
+    other bytes must stay untouched; two runs bitwise equal (the K partials are folded in a fixed order).  Every comparison also
+    holds element by element against the fp64 reference, within helpers.SkinnyRef's bound (half an ulp of the store plus 256 fp32
+    roundings on the magnitude sum), which a dropped 64-wide K unit leaves on a quarter of the elements or more.
   * mmgl_attn_decode_fwd against oracle.lm_ref.attention_core with one query row: random key masks, a sample without any valid key
     (uniform over its keys), K and V addressed in place as column slabs of wider cache rows.  Tolerances of tests/test_xattn_gpu.py:
     1e-3 fp32, 2e-2 bf16 (relative to the largest reference magnitude)."""
 import pytest
 import torch
 
-from helpers import rel_err
+from helpers import SkinnyRef, rel_err
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(2048, 2048), (4096, 2048), (8192, 2048), (2048, 8192), (50272, 2048), (768, 768), (3072, 768)]
-ROWS = [1, 2, 7, 16, 64]
+ROWS = [1, 2, 7, 16, 17, 32, 33, 64]            # 16 | 17 and 32 | 33: the kernel's 1, 2 and 4 x-tile variants
 
 
 def _operands(M, N, K, dtype, seed):
@@ -37,12 +39,19 @@ def _want(x, w, bias=None, relu=False, scale=1.0, residual=None):
     return y
 
 
-def _check(got, want, what):
+def _ref(x, w, bias=None, relu=False, scale=1.0, residual=None):
+    """The fp32 reference of the max-norm bound and the fp64 one of the per-element bound, both on the GPU."""
+    return _want(x, w, bias, relu, scale, residual), SkinnyRef(x, w, bias, relu, scale, residual)
+
+
+def _check(got, ref, what, can_fail=True):
+    want, ref64 = ref
     err = (got.float() - want).abs().max().item()
     bound = 2e-2 * want.abs().max().item() + 1e-2
     print(f"{what}: max abs err {err:.3e} (bound {bound:.3e})")
     assert torch.isfinite(got.float()).all(), what
     assert err <= bound, f"{what}: {err:.3e} > {bound:.3e}"
+    ref64.check(got, what, "F", can_fail)
 
 
 @pytest.mark.parametrize("N,K", SHAPES)
@@ -51,10 +60,10 @@ def test_skinny_gemm_bf16_shapes(N, K):
     for M in ROWS:
         x, w, b, r = _operands(M, N, K, torch.bfloat16, 1000 + M)
         y = ops.gemm_skinny(x, w)
-        _check(y, _want(x, w), f"skinny {M}x{N}x{K}")
+        _check(y, _ref(x, w), f"skinny {M}x{N}x{K}")
         assert torch.equal(y, ops.gemm_skinny(x, w)), f"{M}x{N}x{K}: two runs differ"
         y = ops.gemm_skinny(x, w, b, r, act=1, out_scale=0.5)
-        _check(y, _want(x, w, b, True, 0.5, r), f"skinny {M}x{N}x{K} +bias*0.5+relu+residual")
+        _check(y, _ref(x, w, b, True, 0.5, r), f"skinny {M}x{N}x{K} +bias*0.5+relu+residual")
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -62,10 +71,10 @@ def test_skinny_gemm_epilogue_options_one_by_one(dtype):
     from mmgl_amd import ops
     M, N, K = 7, 768, 768
     x, w, b, r = _operands(M, N, K, dtype, 7)
-    _check(ops.gemm_skinny(x, w, bias=b), _want(x, w, bias=b), "bias")
-    _check(ops.gemm_skinny(x, w, act=1), _want(x, w, relu=True), "relu")
-    _check(ops.gemm_skinny(x, w, residual=r), _want(x, w, residual=r), "residual")
-    _check(ops.gemm_skinny(x, w, out_scale=0.125), _want(x, w, scale=0.125), "scale")
+    _check(ops.gemm_skinny(x, w, bias=b), _ref(x, w, bias=b), "bias")
+    _check(ops.gemm_skinny(x, w, act=1), _ref(x, w, relu=True), "relu")
+    _check(ops.gemm_skinny(x, w, residual=r), _ref(x, w, residual=r), "residual")
+    _check(ops.gemm_skinny(x, w, out_scale=0.125), _ref(x, w, scale=0.125), "scale")
     assert (ops.gemm_skinny(x, w, act=1) >= 0).all()
 
 
@@ -82,14 +91,14 @@ def test_skinny_gemm_writes_a_cache_column_in_place(dtype, M):
     out = cache[:, col, 8:8 + 2 * d]
     assert out.stride(0) == cap * (2 * d + 16)
     ops.decode_linear(x, w, b, out=out)
-    _check(cache[:, col, 8:8 + 2 * d], _want(x, w, b), f"strided ldy M={M}")
+    _check(cache[:, col, 8:8 + 2 * d], _ref(x, w, b), f"strided ldy M={M}")
     keep = torch.ones_like(cache, dtype=torch.bool)
     keep[:, col, 8:8 + 2 * d] = False
     assert torch.equal(cache[keep], before[keep]), "bytes outside the written slab changed"
     # the residual shares the output's row stride
     res = torch.randn(M, cap, 2 * d + 16, device="cuda").to(dtype)
     ops.decode_linear(x, w, None, residual=res[:, col, 8:8 + 2 * d], out=out)
-    _check(cache[:, col, 8:8 + 2 * d], _want(x, w, residual=res[:, col, 8:8 + 2 * d]), "strided residual")
+    _check(cache[:, col, 8:8 + 2 * d], _ref(x, w, residual=res[:, col, 8:8 + 2 * d]), "strided residual")
 
 
 def test_skinny_gemm_fp32_and_odd_shapes():
@@ -99,18 +108,19 @@ def test_skinny_gemm_fp32_and_odd_shapes():
                              (torch.bfloat16, (9, 128, 100)), (torch.float32, (1, 7, 13))]:
         x, w, b, r = _operands(M, N, K, dtype, 3)
         y = ops.gemm_skinny(x, w, b, r, act=1)
-        want = _want(x, w, b, True, 1.0, r)
+        want, ref64 = _ref(x, w, b, True, 1.0, r)
         if dtype == torch.float32:
             assert rel_err(y, want) <= 1e-3, (M, N, K, rel_err(y, want))
+            ref64.check(y, f"generic fp32 {M}x{N}x{K}", "F", can_fail=M * N >= 64)      # 1 x 7 under a ReLU: too few elements to count on
         else:
-            _check(y, want, f"generic {M}x{N}x{K}")
+            _check(y, (want, ref64), f"generic {M}x{N}x{K}")
         assert torch.equal(y, ops.gemm_skinny(x, w, b, r, act=1))
 
 
 def test_decode_linear_chunks_rows_and_refuses_gradients():
     from mmgl_amd import ops
     x, w, b, _ = _operands(150, 768, 768, torch.bfloat16, 5)
-    _check(ops.decode_linear(x, w, b, act="relu"), _want(x, w, b, True), "150 rows in chunks of 64")
+    _check(ops.decode_linear(x, w, b, act="relu"), _ref(x, w, b, True), "150 rows in chunks of 64")
     with pytest.raises(ValueError):
         ops.gemm_skinny(x[:65], w)                       # the kernel itself stops at 64 rows
     wg = w.clone().requires_grad_()

@@ -2,13 +2,15 @@
     y = act((x W^T + bias + s (x A^T) B^T) * out_scale) + residual
 against an fp32 torch reference on the same (bf16-rounded) operands, with the bound of tests/test_decode_kernels_gpu.py::_check
 (2e-2 * max|want| + 1e-2 on the largest absolute error).  B is scaled so that the rank-r term is of the size of the base product: every
-comparison first asserts, from the reference alone, that dropping the term would miss the bound tenfold.  Also: the epilogue options
+comparison first asserts, from the reference alone, that dropping the term would miss the bound tenfold, and then holds element by
+element against the fp64 reference within helpers.SkinnyRef's bound (which the reference without the term, or without its last 64 K
+columns, leaves on a quarter of the elements or more).  Also: the epilogue options
 one by one and together; a strided output inside a larger buffer whose other bytes stay untouched; two runs bitwise equal; agreement
 with the training forward ops.lora_linear on the same operands (2e-2 bf16, 1e-3 fp32, max-norm relative: DESIGN.md 2)."""
 import pytest
 import torch
 
-from helpers import rel_err
+from helpers import SkinnyRef, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +47,13 @@ def _want(x, w, A, Bm, bias=None, relu=False, scale=1.0, residual=None, lora=Tru
     return y
 
 
-def _check(got, want, want_plain, what):
+def _ref(x, w, A, Bm, bias=None, relu=False, scale=1.0, residual=None):
+    """(fp32 reference, the same without the rank-r term, the fp64 reference of the per-element bound), on the GPU."""
+    return (_want(x, w, A, Bm, bias, relu, scale, residual), _want(x, w, A, Bm, bias, relu, scale, residual, lora=False),
+            SkinnyRef(x, w, bias, relu, scale, residual, A, Bm, SCALING))
+
+
+def _check(got, want, want_plain, ref64, what):
     bound = 2e-2 * want.abs().max().item() + 1e-2
     live = (want - want_plain).abs().max().item()
     assert live > 10 * bound, f"{what}: the rank-r term ({live:.3e}) is not visible at the bound {bound:.3e}"
@@ -53,6 +61,7 @@ def _check(got, want, want_plain, what):
     print(f"{what}: max abs err {err:.3e} (bound {bound:.3e}, rank-r term {live:.3e})")
     assert torch.isfinite(got.float()).all(), what
     assert err <= bound, f"{what}: {err:.3e} > {bound:.3e}"
+    ref64.check(got, what, "F")
 
 
 @pytest.mark.parametrize("N,K", SHAPES)
@@ -63,7 +72,7 @@ def test_decode_lora_linear_bf16_shapes(N, K):
             x, w, b, _, A, Bm = _operands(M, N, K, r, torch.bfloat16, 1000 * r + M)
             y = ops.decode_lora_linear(x, w, b, A, Bm, SCALING)
             assert y.shape == (M, N) and y.dtype == torch.bfloat16
-            _check(y, _want(x, w, A, Bm, b), _want(x, w, A, Bm, b, lora=False), f"lora {M}x{N}x{K} r={r}")
+            _check(y, *_ref(x, w, A, Bm, b), f"lora {M}x{N}x{K} r={r}")
             assert torch.equal(y, ops.decode_lora_linear(x, w, b, A, Bm, SCALING)), f"{M}x{N}x{K} r={r}: two runs differ"
 
 
@@ -74,8 +83,8 @@ def test_decode_lora_linear_fp32():
         for M in ROWS:
             x, w, b, _, A, Bm = _operands(M, N, K, r, torch.float32, 2000 * r + M)
             y = ops.decode_lora_linear(x, w, b, A, Bm, SCALING)
-            want, plain = _want(x, w, A, Bm, b), _want(x, w, A, Bm, b, lora=False)
-            _check(y, want, plain, f"lora fp32 {M}x{N}x{K} r={r}")
+            want, plain, ref64 = _ref(x, w, A, Bm, b)
+            _check(y, want, plain, ref64, f"lora fp32 {M}x{N}x{K} r={r}")
             e = rel_err(y, want)
             assert e <= 1e-3, (M, r, e)
             assert torch.equal(y, ops.decode_lora_linear(x, w, b, A, Bm, SCALING))
@@ -88,7 +97,7 @@ def test_every_rank_from_one(r):
     for (N, K) in [(768, 768), (72, 40)]:
         x, w, b, _, A, Bm = _operands(9, N, K, r, torch.bfloat16, 77 + r)
         y = ops.decode_lora_linear(x, w, b, A, Bm, SCALING)
-        _check(y, _want(x, w, A, Bm, b), _want(x, w, A, Bm, b, lora=False), f"lora 9x{N}x{K} r={r}")
+        _check(y, *_ref(x, w, A, Bm, b), f"lora 9x{N}x{K} r={r}")
     with pytest.raises(ValueError):
         ops.decode_lora_linear(x, w, b, torch.zeros(257, K, device="cuda", dtype=torch.bfloat16),
                                torch.zeros(N, 257, device="cuda", dtype=torch.bfloat16), SCALING)
@@ -102,14 +111,15 @@ def test_epilogue_order_one_by_one_and_together(dtype, N, K):
     M, r = 7, 8
     x, w, b, res, A, Bm = _operands(M, N, K, r, dtype, 7)
     run = lambda **kw: ops.gemm_skinny_lora(x, w, A, Bm, SCALING, **kw)
-    ref = lambda **kw: (_want(x, w, A, Bm, **kw), _want(x, w, A, Bm, lora=False, **kw))
+    ref = lambda **kw: _ref(x, w, A, Bm, **kw)
     _check(run(), *ref(), "plain")
     _check(run(bias=b), *ref(bias=b), "bias")
     _check(run(act=1), *ref(relu=True), "relu")
     assert (run(act=1) >= 0).all()
     _check(run(residual=res), *ref(residual=res), "residual")
     # the scale multiplies the rank-r term too: at 0.125 the reference's term is an eighth, and so must the kernel's be
-    got, (want, plain) = run(out_scale=0.125), ref(scale=0.125)
+    got, (want, plain, ref64) = run(out_scale=0.125), ref(scale=0.125)
+    ref64.check(got, "scale", "F")
     bound = 2e-2 * want.abs().max().item() + 1e-2
     assert (got.float() - want).abs().max().item() <= bound
     assert (want - plain).abs().max().item() > 3 * bound             # an eighth of the term: still visible, less than tenfold
@@ -118,6 +128,7 @@ def test_epilogue_order_one_by_one_and_together(dtype, N, K):
     got = run(bias=b, residual=res, act=1, out_scale=0.125)
     want = _want(x, w, A, Bm, b, True, 0.125, res)
     assert (got.float() - want).abs().max().item() <= 2e-2 * want.abs().max().item() + 1e-2
+    SkinnyRef(x, w, b, True, 0.125, res, A, Bm, SCALING).check(got, "bias, scale, relu, residual", "F")
     wrong_order = torch.relu(_want(x, w, A, Bm, b, False, 0.125, res))                   # residual in front of the ReLU
     assert (want - wrong_order).abs().max().item() > 10 * (2e-2 * want.abs().max().item() + 1e-2)
     if dtype == torch.float32:
@@ -136,7 +147,7 @@ def test_writes_the_value_columns_of_a_cache_row_in_place(dtype, M):
     out = cache[:, col, 8 + d:8 + 2 * d]
     assert out.stride(0) == cap * (2 * d + 16)
     ops.decode_lora_linear(x, w, b, A, Bm, SCALING, out=out)
-    _check(cache[:, col, 8 + d:8 + 2 * d], _want(x, w, A, Bm, b), _want(x, w, A, Bm, b, lora=False), f"strided out M={M}")
+    _check(cache[:, col, 8 + d:8 + 2 * d], *_ref(x, w, A, Bm, b), f"strided out M={M}")
     keep = torch.ones_like(cache, dtype=torch.bool)
     keep[:, col, 8 + d:8 + 2 * d] = False
     assert torch.equal(cache[keep], before[keep]), "bytes outside the written slab changed"
