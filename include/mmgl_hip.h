@@ -104,6 +104,21 @@ int mmgl_selfattn_prefix_fwd(const void* q, const void* k, const void* v, const 
 int mmgl_selfattn_prefix_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
                              const uint8_t* key_valid, void* dq, void* dk, void* dv, void* workspace, size_t workspace_bytes,
                              int B, int H, int T, int P, int D, int ld_q, int ld_kv, int ld_dq, int ld_dkv, int dtype, void* stream);
+/* The same attention (no prefix) with GROUPED-QUERY heads: k, v, dk, dv hold Hkv heads, H = G * Hkv, and query head h reads key /
+ * value head h / G -- transformers' repeat_kv, the self-attention of Llama-2-70B, Llama-3.x, TinyLlama (Hkv = 1: multi-query).
+ *   q, dq [B,T,·] (row strides ld_q / ld_dq >= H*D), k, v, dk, dv [B,T,·] (ld_kv / ld_dkv >= Hkv*D), 0 = packed; three column
+ *   slices of one [B,T,(H + 2 Hkv)*D] buffer are the intended use.  out, dout [B,T,H*D] packed, lse [B,H,T], key_valid [B,T].
+ * H % Hkv != 0 or Hkv < 1: MMGL_ERR_INVALID before any launch.  head_dim / dtype rules and the kernel family chosen are those of
+ * mmgl_selfattn_*; Hkv == H IS mmgl_selfattn_fwd / _bwd (same kernels, same numbers, workspace = mmgl_selfattn_bwd_workspace).
+ * Backward, Hkv < H: out, lse, dq are computed per query head exactly as in the multi-head kernels; the dK / dV kernel writes one
+ * gradient per QUERY head into the workspace ([B,T,2,H*D] behind delta) and a fold kernel sums each group in fp32, g = 0 .. G-1,
+ * into dk / dv with one rounding (no atomics, deterministic).  dk, dv and workspace must be 16-byte aligned. */
+int mmgl_selfattn_gqa_fwd(const void* q, const void* k, const void* v, const uint8_t* key_valid, void* out, float* lse,
+                          int B, int H, int Hkv, int T, int D, int ld_q, int ld_kv, int dtype, void* stream);
+size_t mmgl_selfattn_gqa_bwd_workspace(int B, int H, int Hkv, int T, int D, int dtype);
+int mmgl_selfattn_gqa_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
+                          const uint8_t* key_valid, void* dq, void* dk, void* dv, void* workspace, size_t workspace_bytes,
+                          int B, int H, int Hkv, int T, int D, int ld_q, int ld_kv, int ld_dq, int ld_dkv, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * General attention core: the options of MPTAttention.forward the fused kernels above leave out -- attention-probability dropout,

@@ -71,4 +71,5 @@ int mmgl_num_cu() {
 // 105: the stand-alone dgrad, weight-gradient and transpose entry points removed (mmgl_linear_bwd covers them).
 // 106: mmgl_gemm_skinny / mmgl_attn_decode_fwd (the decode step of generate()).
 // 107: mmgl_gemm_skinny_lora (the decode step of a LoRA-adapted projection).
-extern "C" int mmgl_version(void) { return 107; }
+// 108: mmgl_selfattn_gqa_fwd / _bwd_workspace / _bwd (grouped-query self-attention of the Llama family).
+extern "C" int mmgl_version(void) { return 108; }

@@ -125,11 +125,14 @@ template <typename T, typename C, bool K_ROWMAJOR, bool V_ROWMAJOR> struct TileS
 };
 
 // ============================================================================================ forward
-template <typename T, int D>
+// GQA = true (every kernel of this file that takes it): grouped-query attention, k / v hold H / G heads and query head h reads key /
+// value head h / G (HF's repeat_kv).  Only those two base addresses differ; the GQA = false instantiations ignore G and are the
+// multi-head kernels as they were.
+template <typename T, int D, bool GQA = false>
 __global__ __launch_bounds__(256) void selfattn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                            const T* __restrict__ v, const uint8_t* __restrict__ valid,
                                                            T* __restrict__ out, float* __restrict__ lse, int B, int H,
-                                                           int T_, int nqb, int ldq, int P, int ldk) {
+                                                           int T_, int nqb, int ldq, int P, int ldk, int G) {
     // P > 0: keys / values carry P always-visible prefix rows in front of the T causal ones (peft prefix tuning: a learned
     // per-layer key/value prefix); k, v: [B, P + T, ldk], valid: [B, P + T]; key s is visible to query t iff s <= t + P
     typedef SC<T, D> C;
@@ -144,7 +147,7 @@ __global__ __launch_bounds__(256) void selfattn_fwd_kernel(const T* __restrict__
 
     const int vid = xcd_remap(blockIdx.x, B * H * nqb);
     const int bh = vid / nqb, qblk = nqb - 1 - vid % nqb;        // longest (most key tiles) first
-    const int b = bh / H, h = bh % H;
+    const int b = bh / H, h = bh % H, hk = GQA ? h / G : h;
     const size_t HD = (size_t)H * D;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = lane & 15, g = lane >> 4;
@@ -159,8 +162,8 @@ __global__ __launch_bounds__(256) void selfattn_fwd_kernel(const T* __restrict__
     const __amdgpu_buffer_rsrc_t ro = make_rsrc(out + (size_t)b * T_ * HD + h * D, slab);
     const __amdgpu_buffer_rsrc_t rl = make_rsrc(lse + (size_t)bh * T_, (uint32_t)(T_ * sizeof(float)));
     const uint32_t slabk = (uint32_t)(((size_t)(Tk - 1) * ldk + D) * sizeof(T));
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(k + (size_t)b * Tk * ldk + h * D, slabk);
-    const __amdgpu_buffer_rsrc_t rv = make_rsrc(v + (size_t)b * Tk * ldk + h * D, slabk);
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(k + (size_t)b * Tk * ldk + hk * D, slabk);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(v + (size_t)b * Tk * ldk + hk * D, slabk);
 
     v8 qf[C::QT][C::NDC];
 #pragma unroll
@@ -383,12 +386,12 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const T* __restrict__ dout,
 }
 
 // ============================================================================================ backward: dQ
-template <typename T, int D>
+template <typename T, int D, bool GQA = false>
 __global__ __launch_bounds__(256) void selfattn_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ q,
                                                               const T* __restrict__ k, const T* __restrict__ v,
                                                               const float* __restrict__ lse, const float* __restrict__ delta,
                                                               const uint8_t* __restrict__ valid, T* __restrict__ dq, int B, int H,
-                                                              int T_, int nqb, int ldq, int ldg, int P, int ldk) {
+                                                              int T_, int nqb, int ldq, int ldg, int P, int ldk, int G) {
     typedef XC<T, D, 4, 2> C;
     typedef typename Elem<T>::v8 v8;
     constexpr int TILE = 16 * C::QT, QB = 4 * TILE;
@@ -401,7 +404,7 @@ __global__ __launch_bounds__(256) void selfattn_bwd_dq_kernel(const T* __restric
 
     const int vid = xcd_remap(blockIdx.x, B * H * nqb);
     const int bh = vid / nqb, qblk = nqb - 1 - vid % nqb;
-    const int b = bh / H, h = bh % H;
+    const int b = bh / H, h = bh % H, hk = GQA ? h / G : h;
     const size_t HD = (size_t)H * D;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = lane & 15, g = lane >> 4;
@@ -415,8 +418,8 @@ __global__ __launch_bounds__(256) void selfattn_bwd_dq_kernel(const T* __restric
     const __amdgpu_buffer_rsrc_t rg = make_rsrc(dout + (size_t)b * T_ * HD + h * D, slab);
     const __amdgpu_buffer_rsrc_t rd = make_rsrc(dq + (size_t)b * T_ * ldg + h * D, (uint32_t)(((size_t)(T_ - 1) * ldg + D) * sizeof(T)));
     const uint32_t slabk = (uint32_t)(((size_t)(Tk - 1) * ldk + D) * sizeof(T));
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(k + (size_t)b * Tk * ldk + h * D, slabk);
-    const __amdgpu_buffer_rsrc_t rv = make_rsrc(v + (size_t)b * Tk * ldk + h * D, slabk);
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(k + (size_t)b * Tk * ldk + hk * D, slabk);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(v + (size_t)b * Tk * ldk + hk * D, slabk);
 
     v8 qf[C::QT][C::NDC], gf[C::QT][C::NDC];
     float lse2[C::QT], dlt[C::QT];
@@ -535,13 +538,14 @@ __global__ __launch_bounds__(256) void selfattn_bwd_dq_kernel(const T* __restric
 // lane = key column, P / dS leave the accumulators in B-operand layout for the contraction over t; Q^T / dO^T come
 // from a wave-private row-major LDS tile via tr16 (bf16) or scalar gathers (f32).  The two parity waves of a key half
 // are folded through LDS at the end: every dK / dV element is written exactly once (deterministic, no partials).
-template <typename T, int D, int PAR>
+// (GQA: K / V of head h / G, dK / dV still of QUERY head h -- the host points dk / dv at the expanded scratch and folds each group)
+template <typename T, int D, int PAR, bool GQA = false>
 __global__ __launch_bounds__(128 * PAR) void selfattn_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ q,
                                                                const T* __restrict__ k, const T* __restrict__ v,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                const uint8_t* __restrict__ valid, T* __restrict__ dk,
                                                                T* __restrict__ dv, int B, int H, int T_, int nkb, int ldq, int ldg,
-                                                               int P, int ldk) {
+                                                               int P, int ldk, int G) {
     typedef XC<T, D, 2> C;                         // one wave's key group: 32 keys = 2 blocks
     const int Tk = T_ + P;                         // keys: P always-visible prefix rows, then the T causal ones
     typedef typename Elem<T>::v8 v8;
@@ -558,11 +562,11 @@ __global__ __launch_bounds__(128 * PAR) void selfattn_bwd_dkv_kernel(const T* __
 
     const int vid = xcd_remap(blockIdx.x, B * H * nkb);
     const int bh = vid / nkb, kblk = vid % nkb;                 // low key tiles (most query tiles) first
-    const int b = bh / H, h = bh % H;
+    const int b = bh / H, h = bh % H, hk = GQA ? h / G : h;
     const size_t HD = (size_t)H * D;
     const int s0 = kblk * KT + half * 32;
-    const T* kb = k + ((size_t)b * Tk + kblk * KT) * ldk + h * D;
-    const T* vb = v + ((size_t)b * Tk + kblk * KT) * ldk + h * D;
+    const T* kb = k + ((size_t)b * Tk + kblk * KT) * ldk + hk * D;
+    const T* vb = v + ((size_t)b * Tk + kblk * KT) * ldk + hk * D;
 
     // stage both halves' K / V row fragments (64 keys): image `half` holds keys [32 half, 32 half + 32)
     for (int hh = 0; hh < 2; ++hh) {
@@ -724,25 +728,78 @@ __global__ __launch_bounds__(128 * PAR) void selfattn_bwd_dkv_kernel(const T* __
     }
 }
 
+// ============================================================================================ GQA: fold the group's dK / dV
+// The dK / dV kernels above write one gradient per QUERY head into a scratch [rows, 2, H*D] (dK slab, dV slab).  This sums the G query
+// heads of each key / value head into dk / dv [rows, Hkv*D] (row stride ld): one thread = one 16-byte output vector, G 16-byte loads D
+// elements apart, fp32 adds in the fixed order g = 0 .. G-1, one rounding, one store.  No atomics; every output element written once.
+template <typename T>
+__global__ __launch_bounds__(256) void gqa_fold_kernel(const T* __restrict__ scratch, T* __restrict__ dk, T* __restrict__ dv, size_t rows,
+                                                       int Hkv, int G, int D, int ld) {
+    constexpr int VN = 16 / sizeof(T);
+    typedef T V __attribute__((ext_vector_type(16 / sizeof(T))));
+    const int cpv = D / VN;                                   // vectors per head
+    const size_t per_slab = (size_t)Hkv * cpv, per_row = 2 * per_slab, total = rows * per_row;
+    const size_t HD = (size_t)Hkv * G * D;
+    for (size_t id = (size_t)blockIdx.x * 256 + threadIdx.x; id < total; id += (size_t)gridDim.x * 256) {
+        const size_t row = id / per_row;
+        const int rem = (int)(id - row * per_row);
+        const int which = rem >= (int)per_slab, r2 = rem - which * (int)per_slab;
+        const int hk = r2 / cpv, c = r2 - hk * cpv;
+        const T* src = scratch + (row * 2 + which) * HD + (size_t)hk * G * D + c * VN;
+        float acc[VN];
+#pragma unroll
+        for (int e = 0; e < VN; ++e) acc[e] = 0.f;
+#pragma unroll 4
+        for (int g = 0; g < G; ++g) {
+            const V x = *(const V*)(src + (size_t)g * D);
+#pragma unroll
+            for (int e = 0; e < VN; ++e) acc[e] += (float)x[e];
+        }
+        V o;
+#pragma unroll
+        for (int e = 0; e < VN; ++e) o[e] = (T)acc[e];
+        *(V*)((which ? dv : dk) + row * (size_t)ld + (size_t)hk * D + c * VN) = o;
+    }
+}
+
+template <typename T>
+int gqa_fold(const void* scratch, void* dk, void* dv, size_t rows, int Hkv, int G, int D, int ld, hipStream_t st) {
+    const size_t total = rows * 2 * Hkv * (D / (16 / sizeof(T)));
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(gqa_fold_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)scratch, (T*)dk, (T*)dv, rows, Hkv, G, D, ld);
+    MMGL_CHECK_LAUNCH("selfattn_gqa_fold");
+    return MMGL_OK;
+}
+
 // ============================================================================================ host
-template <typename T, int D>
-int sa_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, void* out, float* lse, int B, int H, int T_,
-           int ldq, int P, int ldk, hipStream_t st) {
+// (G > 1 launches the GQA instantiations, G = 1 the multi-head ones)
+template <typename T, int D, bool GQA>
+int sa_fwd_g(const void* q, const void* k, const void* v, const uint8_t* valid, void* out, float* lse, int B, int H, int T_,
+           int ldq, int P, int ldk, hipStream_t st, int G) {
     typedef SC<T, D> C;
     const int QB = 4 * 16 * C::QT, nqb = cdiv(T_, QB);
     const size_t lds = 2 * (C::KV_BYTES + KT);
-    auto kern = selfattn_fwd_kernel<T, D>;
+    auto kern = selfattn_fwd_kernel<T, D, GQA>;
     int rc = mmgl_set_lds(kern, lds, "selfattn");
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(B * H * nqb), dim3(256), lds, st, (const T*)q, (const T*)k, (const T*)v, valid, (T*)out, lse, B, H,
-                       T_, nqb, ldq, P, ldk);
+                       T_, nqb, ldq, P, ldk, G);
     MMGL_CHECK_LAUNCH("selfattn_fwd");
     return MMGL_OK;
 }
 
 template <typename T, int D>
-int sa_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse, const uint8_t* valid,
-           void* dq, void* dk, void* dv, float* delta, int B, int H, int T_, int ldq, int ldg, int P, int ldk, int ldgk, hipStream_t st) {
+int sa_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, void* out, float* lse, int B, int H, int T_,
+           int ldq, int P, int ldk, hipStream_t st, int G) {
+    return G > 1 ? sa_fwd_g<T, D, true>(q, k, v, valid, out, lse, B, H, T_, ldq, P, ldk, st, G)
+                 : sa_fwd_g<T, D, false>(q, k, v, valid, out, lse, B, H, T_, ldq, P, ldk, st, 1);
+}
+
+template <typename T, int D, bool GQA>
+int sa_bwd_g(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse, const uint8_t* valid,
+             void* dq, void* dk, void* dv, float* delta, int B, int H, int T_, int ldq, int ldg, int P, int ldk, int ldgk, hipStream_t st,
+             int G) {
     // ldq / ldg: row strides of q / dq; ldk / ldgk: of k, v / dk, dv ([B, P + T] rows); P prefix keys (0 = plain causal attention)
     {
         const size_t total = (size_t)B * T_ * H * (D / 8);
@@ -755,11 +812,11 @@ int sa_bwd(const void* dout, const void* q, const void* k, const void* v, const 
         typedef XC<T, D, 4, 2> C;
         const int QB = 4 * 16 * C::QT, nqb = cdiv(T_, QB);
         const size_t lds = 2 * (C::KV_BYTES + KT);
-        auto kern = selfattn_bwd_dq_kernel<T, D>;
+        auto kern = selfattn_bwd_dq_kernel<T, D, GQA>;
         int rc = mmgl_set_lds(kern, lds, "selfattn");
         if (rc) return rc;
         hipLaunchKernelGGL(kern, dim3(B * H * nqb), dim3(256), lds, st, (const T*)dout, (const T*)q, (const T*)k, (const T*)v, lse,
-                           delta, valid, (T*)dq, B, H, T_, nqb, ldq, ldg, P, ldk);
+                           delta, valid, (T*)dq, B, H, T_, nqb, ldq, ldg, P, ldk, G);
         MMGL_CHECK_LAUNCH("selfattn_bwd_dq");
     }
     {
@@ -773,21 +830,29 @@ int sa_bwd(const void* dout, const void* q, const void* k, const void* v, const 
             return sizeof(T) * 4 * C::ROWIMG + tiles;
         };
         if (lds_for(2) <= 160 * 1024) {
-            auto kern = selfattn_bwd_dkv_kernel<T, D, 2>;
+            auto kern = selfattn_bwd_dkv_kernel<T, D, 2, GQA>;
             int rc = mmgl_set_lds(kern, lds_for(2), "selfattn");
             if (rc) return rc;
             hipLaunchKernelGGL(kern, dim3(B * H * nkb), dim3(256), lds_for(2), st, (const T*)dout, (const T*)q, (const T*)k, (const T*)v,
-                               lse, delta, valid, (T*)dk, (T*)dv, B, H, T_, nkb, ldq, ldgk, P, ldk);
+                               lse, delta, valid, (T*)dk, (T*)dv, B, H, T_, nkb, ldq, ldgk, P, ldk, G);
         } else {
-            auto kern = selfattn_bwd_dkv_kernel<T, D, 1>;
+            auto kern = selfattn_bwd_dkv_kernel<T, D, 1, GQA>;
             int rc = mmgl_set_lds(kern, lds_for(1), "selfattn");
             if (rc) return rc;
             hipLaunchKernelGGL(kern, dim3(B * H * nkb), dim3(128), lds_for(1), st, (const T*)dout, (const T*)q, (const T*)k, (const T*)v,
-                               lse, delta, valid, (T*)dk, (T*)dv, B, H, T_, nkb, ldq, ldgk, P, ldk);
+                               lse, delta, valid, (T*)dk, (T*)dv, B, H, T_, nkb, ldq, ldgk, P, ldk, G);
         }
         MMGL_CHECK_LAUNCH("selfattn_bwd_dkv");
     }
     return MMGL_OK;
+}
+
+template <typename T, int D>
+int sa_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse, const uint8_t* valid,
+           void* dq, void* dk, void* dv, float* delta, int B, int H, int T_, int ldq, int ldg, int P, int ldk, int ldgk, hipStream_t st,
+           int G) {
+    return G > 1 ? sa_bwd_g<T, D, true>(dout, q, k, v, out, lse, valid, dq, dk, dv, delta, B, H, T_, ldq, ldg, P, ldk, ldgk, st, G)
+                 : sa_bwd_g<T, D, false>(dout, q, k, v, out, lse, valid, dq, dk, dv, delta, B, H, T_, ldq, ldg, P, ldk, ldgk, st, 1);
 }
 
 template <typename T, int D>
@@ -837,7 +902,7 @@ extern "C" int mmgl_selfattn_prefix_fwd(const void* q, const void* k, const void
     if ((rc = sa_ld("mmgl_selfattn_prefix_fwd", ld_q, H, D)) || (rc = sa_ld("mmgl_selfattn_prefix_fwd", ld_kv, H, D))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (sa32_supported(dtype, D, T + P)) return sa32_fwd(q, k, v, key_valid, out, lse, B, H, T, P, D, ld_q, ld_kv, st);
-    SA_DISPATCH(sa_fwd, q, k, v, key_valid, out, lse, B, H, T, ld_q, P, ld_kv, st);
+    SA_DISPATCH(sa_fwd, q, k, v, key_valid, out, lse, B, H, T, ld_q, P, ld_kv, st, 1);
 }
 
 extern "C" int mmgl_selfattn_fwd(const void* q, const void* k, const void* v, const uint8_t* key_valid, void* out, float* lse,
@@ -864,7 +929,7 @@ extern "C" int mmgl_selfattn_prefix_bwd(const void* dout, const void* q, const v
     // dQ (+ delta) kernel, then the dK / dV kernel (head_dim 128: one workgroup per CU, 304 registers; Llama shape 1743 -> 1289 us
     // against the 16x16 dK / dV kernel it replaced)
     if (sa32_supported(dtype, D, T + P)) return sa32_bwd(dout, q, k, v, out, lse, key_valid, dq, dk, dv, delta, B, H, T, P, D, ld_q, ld_kv, ld_dq, ld_dkv, st);
-    SA_DISPATCH(sa_bwd, dout, q, k, v, out, lse, key_valid, dq, dk, dv, delta, B, H, T, ld_q, ld_dq, P, ld_kv, ld_dkv, st);
+    SA_DISPATCH(sa_bwd, dout, q, k, v, out, lse, key_valid, dq, dk, dv, delta, B, H, T, ld_q, ld_dq, P, ld_kv, ld_dkv, st, 1);
 }
 
 extern "C" int mmgl_selfattn_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
@@ -872,6 +937,59 @@ extern "C" int mmgl_selfattn_bwd(const void* dout, const void* q, const void* k,
                                  int B, int H, int T, int D, int ld_qkv, int ld_dqkv, int dtype, void* stream) {
     return mmgl_selfattn_prefix_bwd(dout, q, k, v, out, lse, key_valid, dq, dk, dv, workspace, workspace_bytes, B, H, T, 0, D, ld_qkv,
                                     ld_qkv, ld_dqkv, ld_dqkv, dtype, stream);
+}
+
+// ---- grouped-query attention: k, v, dk, dv [B, T, Hkv*D]; query head h reads key / value head h / (H / Hkv)
+static int gqa_check(const char* who, int B, int H, int Hkv, int T, int D, int dtype) {
+    MMGL_CHECK_ARG(Hkv >= 1 && H >= Hkv && H % Hkv == 0, "%s: H = %d must be a positive multiple of Hkv = %d", who, H, Hkv);
+    return sa_check(who, B, H, T, D, dtype);
+}
+
+extern "C" int mmgl_selfattn_gqa_fwd(const void* q, const void* k, const void* v, const uint8_t* key_valid, void* out, float* lse,
+                                     int B, int H, int Hkv, int T, int D, int ld_q, int ld_kv, int dtype, void* stream) {
+    int rc = gqa_check("mmgl_selfattn_gqa_fwd", B, H, Hkv, T, D, dtype);
+    if (rc) return rc;
+    if (Hkv == H) return mmgl_selfattn_prefix_fwd(q, k, v, key_valid, out, lse, B, H, T, 0, D, ld_q, ld_kv, dtype, stream);
+    MMGL_CHECK_ARG(q && k && v && key_valid && out && lse, "mmgl_selfattn_gqa_fwd: null pointer");
+    if ((rc = sa_ld("mmgl_selfattn_gqa_fwd", ld_q, H, D)) || (rc = sa_ld("mmgl_selfattn_gqa_fwd", ld_kv, Hkv, D))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int G = H / Hkv;
+    if (sa32_supported(dtype, D, T)) return sa32_fwd(q, k, v, key_valid, out, lse, B, H, T, 0, D, ld_q, ld_kv, st, G);
+    SA_DISPATCH(sa_fwd, q, k, v, key_valid, out, lse, B, H, T, ld_q, 0, ld_kv, st, G);
+}
+
+// delta [B,H,T] fp32, then (Hkv < H) the expanded gradients [B, T, 2, H*D]: dK slab, dV slab of every query head
+extern "C" size_t mmgl_selfattn_gqa_bwd_workspace(int B, int H, int Hkv, int T, int D, int dtype) {
+    const size_t delta = mmgl_selfattn_bwd_workspace(B, H, T);
+    if (delta == 0 || Hkv < 1 || H % Hkv || D <= 0) return 0;
+    if (Hkv == H) return delta;
+    return delta + align_up((size_t)B * T * 2 * H * D * (dtype == MMGL_BF16 ? 2 : 4), 256);
+}
+
+extern "C" int mmgl_selfattn_gqa_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                     const uint8_t* key_valid, void* dq, void* dk, void* dv, void* workspace, size_t workspace_bytes,
+                                     int B, int H, int Hkv, int T, int D, int ld_q, int ld_kv, int ld_dq, int ld_dkv, int dtype,
+                                     void* stream) {
+    int rc = gqa_check("mmgl_selfattn_gqa_bwd", B, H, Hkv, T, D, dtype);
+    if (rc) return rc;
+    if (Hkv == H)
+        return mmgl_selfattn_prefix_bwd(dout, q, k, v, out, lse, key_valid, dq, dk, dv, workspace, workspace_bytes, B, H, T, 0, D, ld_q,
+                                        ld_kv, ld_dq, ld_dkv, dtype, stream);
+    if ((rc = sa_ld("mmgl_selfattn_gqa_bwd", ld_q, H, D)) || (rc = sa_ld("mmgl_selfattn_gqa_bwd", ld_kv, Hkv, D)) ||
+        (rc = sa_ld("mmgl_selfattn_gqa_bwd", ld_dq, H, D)) || (rc = sa_ld("mmgl_selfattn_gqa_bwd", ld_dkv, Hkv, D))) return rc;
+    MMGL_CHECK_ARG(dout && q && k && v && out && lse && key_valid && dq && dk && dv && workspace, "mmgl_selfattn_gqa_bwd: null pointer");
+    MMGL_CHECK_ARG(workspace_bytes >= mmgl_selfattn_gqa_bwd_workspace(B, H, Hkv, T, D, dtype), "mmgl_selfattn_gqa_bwd: workspace too small");
+    MMGL_CHECK_ARG((((uintptr_t)dk | (uintptr_t)dv | (uintptr_t)workspace) & 15) == 0, "mmgl_selfattn_gqa_bwd: dk, dv and workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int G = H / Hkv, es = dtype == MMGL_BF16 ? 2 : 4, ldx = 2 * H * D;
+    float* delta = (float*)workspace;
+    char* xdk = (char*)workspace + mmgl_selfattn_bwd_workspace(B, H, T);          // expanded dK; the dV slab follows H*D elements on
+    char* xdv = xdk + (size_t)H * D * es;
+    if (sa32_supported(dtype, D, T)) rc = sa32_bwd(dout, q, k, v, out, lse, key_valid, dq, xdk, xdv, delta, B, H, T, 0, D, ld_q, ld_kv, ld_dq, ldx, st, G);
+    else rc = [&]() -> int { SA_DISPATCH(sa_bwd, dout, q, k, v, out, lse, key_valid, dq, xdk, xdv, delta, B, H, T, ld_q, ld_dq, 0, ld_kv, ldx, st, G); }();
+    if (rc) return rc;
+    const size_t rows = (size_t)B * T;
+    return dtype == MMGL_BF16 ? gqa_fold<bf16>(xdk, dk, dv, rows, Hkv, G, D, ld_dkv, st) : gqa_fold<float>(xdk, dk, dv, rows, Hkv, G, D, ld_dkv, st);
 }
 
 extern "C" int mmgl_encattn_fwd(const void* q, const void* k, const void* v, const int32_t* cu_seqlens, void* out, int nseq,

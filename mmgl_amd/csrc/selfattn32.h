@@ -8,14 +8,16 @@
 // THE choice between the 32x32 kernels and the 16x16 ones of selfattn.hip: bf16, head_dim 64 / 128, Tk <= 4096 key rows
 SA32_HIDDEN bool sa32_supported(int dtype, int D, int Tk);
 
-// causal (+ P prefix keys) forward; same argument meaning as mmgl_selfattn_prefix_fwd
+// causal (+ P prefix keys) forward; same argument meaning as mmgl_selfattn_prefix_fwd.  G > 1: grouped-query attention, k / v hold
+// H / G heads and query head h reads head h / G (mmgl_selfattn_gqa_fwd); G = 1 launches the multi-head kernels
 SA32_HIDDEN int sa32_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, void* out, float* lse, int B, int H, int T,
-                         int P, int D, int ldq, int ldk, hipStream_t st);
+                         int P, int D, int ldq, int ldk, hipStream_t st, int G = 1);
 // packed bidirectional forward; same argument meaning as mmgl_encattn_fwd
 SA32_HIDDEN int sa32_enc_fwd(const void* q, const void* k, const void* v, const int* cu, void* out, int nseq, int H, int D, int ld_in,
                              int ld_out, int max_len, int q_rows, hipStream_t st);
 // backward: the dQ kernel (also writes delta [B,H,T] = rowsum(dO * O)), then the dK / dV kernel (reads delta).
-// Argument meaning as mmgl_selfattn_prefix_bwd: ldg / ldgk are the row strides of dq / dk, dv.
+// Argument meaning as mmgl_selfattn_prefix_bwd: ldg / ldgk are the row strides of dq / dk, dv.  G > 1: k / v hold H / G heads; dk / dv
+// are still written per QUERY head ([B, Tk, >= H*D] rows: the caller's scratch, folded over each group afterwards).
 SA32_HIDDEN int sa32_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
                          const uint8_t* valid, void* dq, void* dk, void* dv, float* delta, int B, int H, int T, int P, int D, int ldq,
-                         int ldk, int ldg, int ldgk, hipStream_t st);
+                         int ldk, int ldg, int ldgk, hipStream_t st, int G = 1);

@@ -87,6 +87,7 @@ struct SA32Args {
     const int* cu;             // packed mode: sequence i owns rows cu[i] .. cu[i+1]-1; null = batch mode
     int B, H, T, P, nqb, ldq, ldk, ldo, q_rows;
     long long* trace;          // SA32_TRACE builds (timing experiments): 8 x int64 per workgroup
+    int G;                     // grouped-query attention (GQA instantiations only): query head h reads key / value head h / G
 };
 
 __device__ __forceinline__ f32x16 mma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
@@ -99,7 +100,9 @@ __device__ __forceinline__ void swap32_u32(uint32_t& a, uint32_t& b) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
 }
 
-template <int D, bool CAUSAL>
+// GQA = true: k, v [B, Tk, (H / G) * D], query head h reads key / value head h / a.G (HF's repeat_kv); nothing else differs, and the
+// GQA = false instantiations are the multi-head kernels as they were
+template <int D, bool CAUSAL, bool GQA = false>
 __global__ __launch_bounds__(256, G32<D>::OCC) void sa32_fwd_kernel(SA32Args a) {
     typedef G32<D> G;
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -129,9 +132,10 @@ __global__ __launch_bounds__(256, G32<D>::OCC) void sa32_fwd_kernel(SA32Args a) 
     } else {
         Tq = a.T;
         Tk = a.T + a.P;
+        const int hk = GQA ? h / a.G : h;
         qb = a.q + (size_t)b * a.T * a.ldq + h * D;
-        kb = a.k + (size_t)b * Tk * a.ldk + h * D;
-        vb = a.v + (size_t)b * Tk * a.ldk + h * D;
+        kb = a.k + (size_t)b * Tk * a.ldk + hk * D;
+        vb = a.v + (size_t)b * Tk * a.ldk + hk * D;
         ob = a.out + (size_t)b * a.T * a.ldo + h * D;
         if (a.valid) valid_row = a.valid + (size_t)b * Tk;
     }
@@ -465,12 +469,13 @@ struct SA32BwdArgs {
     bf16 *dq, *dk, *dv;
     float* delta;              // [B, H, T]: written by the dQ kernel, read by the dK / dV kernel
     int B, H, T, P, nqb, nkb, ldq, ldk, ldg, ldgk;
+    int G;                     // GQA instantiations only: query head h reads key / value head h / G (dk, dv stay per QUERY head)
 };
 
 // 16 transposed fragments' worth of reads for ONE 32-channel block: f[blk][jj][half]; rows 32 blk + 16 jj (+ 8) of the tile at `ad`
 #define SA32_TR_READ(dst, ad, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(ad), "i"(off))
 
-template <int D>
+template <int D, bool GQA = false>
 __global__ __launch_bounds__(256, SA32_DQ_OCC) void sa32_bwd_dq_kernel(SA32BwdArgs a) {
     typedef G32<D> G;
     constexpr int NS = SA32_NS_DQ, PD = NS - 1;
@@ -481,15 +486,15 @@ __global__ __launch_bounds__(256, SA32_DQ_OCC) void sa32_bwd_dq_kernel(SA32BwdAr
 
     const int vid = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = vid / a.nqb, qblk = a.nqb - 1 - vid % a.nqb;
-    const int b = bh / a.H, h = bh % a.H;
+    const int b = bh / a.H, h = bh % a.H, hk = GQA ? h / a.G : h;
     const int Tq = a.T, Tk = a.T + a.P, HD = a.H * D;
     const int t0 = qblk * 128 + wave * 32, trow = t0 + key;
     const int nkt = (min(Tq, (qblk + 1) * 128) + a.P + G::KT - 1) / G::KT;
 
     const uint32_t ldqB = (uint32_t)a.ldq * 2u, ldkB = (uint32_t)a.ldk * 2u, ldoB = (uint32_t)HD * 2u, ldgB = (uint32_t)a.ldg * 2u;
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(a.q + (size_t)b * Tq * a.ldq + h * D, (uint32_t)(Tq - 1) * ldqB + D * 2);
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + (size_t)b * Tk * a.ldk + h * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
-    const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + (size_t)b * Tk * a.ldk + h * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + (size_t)b * Tk * a.ldk + hk * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + (size_t)b * Tk * a.ldk + hk * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
     const __amdgpu_buffer_rsrc_t rg = make_rsrc(a.dout + (size_t)b * Tq * HD + h * D, (uint32_t)(Tq - 1) * ldoB + D * 2);
     const __amdgpu_buffer_rsrc_t ro = make_rsrc(a.out + (size_t)b * Tq * HD + h * D, (uint32_t)(Tq - 1) * ldoB + D * 2);
     const __amdgpu_buffer_rsrc_t rd = make_rsrc(a.dq + (size_t)b * Tq * a.ldg + h * D, (uint32_t)(Tq - 1) * ldgB + D * 2);
@@ -715,7 +720,8 @@ template <int D> struct GB32 {
     static constexpr int NPB = 2 * G::PIECES / 4 + 2;                    // LDS-DMA instructions per wave and tile
 };
 
-template <int D>
+// GQA = true: K / V of head h / a.G, dK / dV still of QUERY head h (the host points dk / dv at the expanded scratch and folds the group)
+template <int D, bool GQA = false>
 __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dkv_kernel(SA32BwdArgs a) {
     typedef G32<D> G;
     typedef GB32<D> GB;
@@ -727,7 +733,7 @@ __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dk
 
     const int vid = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = vid / a.nkb, kblk = vid % a.nkb;                      // low key blocks (most query tiles) first
-    const int b = bh / a.H, h = bh % a.H;
+    const int b = bh / a.H, h = bh % a.H, hk = GQA ? h / a.G : h;
     const int Tq = a.T, Tk = a.T + a.P, HD = a.H * D;
     const int k0 = kblk * 128 + wave * 32, krow = k0 + kl;               // this lane's key
     const int nqt = (Tq + 63) / 64;
@@ -735,8 +741,8 @@ __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dk
 
     const uint32_t ldqB = (uint32_t)a.ldq * 2u, ldkB = (uint32_t)a.ldk * 2u, ldoB = (uint32_t)HD * 2u, ldgB = (uint32_t)a.ldgk * 2u;
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(a.q + (size_t)b * Tq * a.ldq + h * D, (uint32_t)(Tq - 1) * ldqB + D * 2);
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + (size_t)b * Tk * a.ldk + h * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
-    const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + (size_t)b * Tk * a.ldk + h * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + (size_t)b * Tk * a.ldk + hk * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + (size_t)b * Tk * a.ldk + hk * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
     const __amdgpu_buffer_rsrc_t rg = make_rsrc(a.dout + (size_t)b * Tq * HD + h * D, (uint32_t)(Tq - 1) * ldoB + D * 2);
     const __amdgpu_buffer_rsrc_t rdk = make_rsrc(a.dk + (size_t)b * Tk * a.ldgk + h * D, (uint32_t)(Tk - 1) * ldgB + D * 2);
     const __amdgpu_buffer_rsrc_t rdv = make_rsrc(a.dv + (size_t)b * Tk * a.ldgk + h * D, (uint32_t)(Tk - 1) * ldgB + D * 2);
@@ -928,28 +934,28 @@ __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dk
             }
 }
 
-template <int D, bool CAUSAL> int launch_fwd(const SA32Args& a, int nblocks, hipStream_t st) {
+template <int D, bool CAUSAL, bool GQA = false> int launch_fwd(const SA32Args& a, int nblocks, hipStream_t st) {
     typedef G32<D> G;
-    auto kern = sa32_fwd_kernel<D, CAUSAL>;
+    auto kern = sa32_fwd_kernel<D, CAUSAL, GQA>;
     if (int rc = mmgl_set_lds(kern, G::LDS, "sa32_fwd")) return rc;
     hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), G::LDS, st, a);
     MMGL_CHECK_LAUNCH("sa32_fwd");
     return MMGL_OK;
 }
 
-template <int D> int launch_bwd_dq(const SA32BwdArgs& a, hipStream_t st) {
+template <int D, bool GQA = false> int launch_bwd_dq(const SA32BwdArgs& a, hipStream_t st) {
     typedef G32<D> G;
     constexpr int LDS = SA32_NS_DQ * G::SLOTB + G::MAXT * 8;
-    auto kern = sa32_bwd_dq_kernel<D>;
+    auto kern = sa32_bwd_dq_kernel<D, GQA>;
     if (int rc = mmgl_set_lds(kern, LDS, "sa32_bwd_dq")) return rc;
     hipLaunchKernelGGL(kern, dim3(a.B * a.H * a.nqb), dim3(256), LDS, st, a);
     MMGL_CHECK_LAUNCH("sa32_bwd_dq");
     return MMGL_OK;
 }
 
-template <int D> int launch_bwd_dkv(const SA32BwdArgs& a, hipStream_t st) {
+template <int D, bool GQA = false> int launch_bwd_dkv(const SA32BwdArgs& a, hipStream_t st) {
     typedef GB32<D> GB;
-    auto kern = sa32_bwd_dkv_kernel<D>;
+    auto kern = sa32_bwd_dkv_kernel<D, GQA>;
     if (int rc = mmgl_set_lds(kern, GB::LDS, "sa32_bwd_dkv")) return rc;
     hipLaunchKernelGGL(kern, dim3(a.B * a.H * a.nkb), dim3(256), GB::LDS, st, a);
     MMGL_CHECK_LAUNCH("sa32_bwd_dkv");
@@ -961,7 +967,7 @@ template <int D> int launch_bwd_dkv(const SA32BwdArgs& a, hipStream_t st) {
 bool sa32_supported(int dtype, int D, int Tk) { return dtype == MMGL_BF16 && (D == 64 || D == 128) && Tk <= 64 * 64; }
 
 int sa32_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, void* out, float* lse, int B, int H, int T, int P,
-             int D, int ldq, int ldk, hipStream_t st) {
+             int D, int ldq, int ldk, hipStream_t st, int G) {
     SA32Args a{};
     a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.valid = valid; a.out = (bf16*)out; a.lse = lse; a.cu = nullptr;
     a.B = B; a.H = H; a.T = T; a.P = P; a.nqb = cdiv(T, 128); a.ldq = ldq; a.ldk = ldk; a.ldo = H * D; a.q_rows = T;
@@ -969,6 +975,8 @@ int sa32_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, 
     if (const char* e = getenv("MMGL_SA32_TRACE")) a.trace = (long long*)strtoull(e, nullptr, 0);
 #endif
     const int nblocks = B * H * a.nqb;
+    a.G = G;
+    if (G > 1) return D == 64 ? launch_fwd<64, true, true>(a, nblocks, st) : launch_fwd<128, true, true>(a, nblocks, st);
     return D == 64 ? launch_fwd<64, true>(a, nblocks, st) : launch_fwd<128, true>(a, nblocks, st);
 }
 
@@ -977,18 +985,23 @@ int sa32_enc_fwd(const void* q, const void* k, const void* v, const int* cu, voi
     SA32Args a{};
     a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.valid = nullptr; a.out = (bf16*)out; a.lse = nullptr; a.cu = cu;
     a.B = nseq; a.H = H; a.T = max_len; a.P = 0; a.nqb = cdiv(max_len < q_rows ? max_len : q_rows, 128); a.ldq = ld_in; a.ldk = ld_in;
-    a.ldo = ld_out; a.q_rows = q_rows;
+    a.ldo = ld_out; a.q_rows = q_rows; a.G = 1;
     const int nblocks = nseq * H * a.nqb;
     return D == 64 ? launch_fwd<64, false>(a, nblocks, st) : launch_fwd<128, false>(a, nblocks, st);
 }
 
 int sa32_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse, const uint8_t* valid,
              void* dq, void* dk, void* dv, float* delta, int B, int H, int T, int P, int D, int ldq, int ldk, int ldg, int ldgk,
-             hipStream_t st) {
+             hipStream_t st, int G) {
     SA32BwdArgs a{};
     a.dout = (const bf16*)dout; a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (const bf16*)out; a.lse = lse;
     a.valid = valid; a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.delta = delta;
     a.B = B; a.H = H; a.T = T; a.P = P; a.nqb = cdiv(T, 128); a.nkb = cdiv(T + P, 128); a.ldq = ldq; a.ldk = ldk; a.ldg = ldg; a.ldgk = ldgk;
+    a.G = G;
+    if (G > 1) {
+        if (int rc = D == 64 ? launch_bwd_dq<64, true>(a, st) : launch_bwd_dq<128, true>(a, st)) return rc;
+        return D == 64 ? launch_bwd_dkv<64, true>(a, st) : launch_bwd_dkv<128, true>(a, st);
+    }
     if (int rc = D == 64 ? launch_bwd_dq<64>(a, st) : launch_bwd_dq<128>(a, st)) return rc;
     return D == 64 ? launch_bwd_dkv<64>(a, st) : launch_bwd_dkv<128>(a, st);
 }

@@ -5,7 +5,8 @@ pre-norm, bias-free projections, SwiGLU FFN, scalar tanh gates initialised at 0 
 `neighbor_layer_wise`-th layer of a frozen LlamaForCausalLM.  The HF object is loaded through the same HF API and owns the
 weights (state-dict keys `llama.*`); its forward is replaced by the HIP path: RMSNorm kernel, ONE fused q|k|v GEMM
 (ping-pong MFMA kernel, D^-1/2 folded into the q rows), rotary embedding in place on that buffer, causal flash attention
-reading Q/K/V in place, ONE fused gate|up GEMM + SwiGLU kernel, down projection; dgrads against cached W^T copies.
+reading Q/K/V in place (multi-head or grouped-query: num_key_value_heads <= num_attention_heads, query head h reads key / value
+head h // G as in transformers' repeat_kv), ONE fused gate|up GEMM + SwiGLU kernel, down projection; dgrads against cached W^T copies.
 No reference counterpart exists: parity is UNPINNED vs MMGL; it is pinned (tests/test_llama_gpu.py) to HF Llama itself
 when the gates are 0 and to the CPU oracle (oracle/llama_ref.py) otherwise.
 """
@@ -59,6 +60,7 @@ class _FrozenLlamaLayer:
     def __init__(self, layer, cfg):
         self.layer, self.cfg = layer, cfg
         self.H = cfg.num_attention_heads
+        self.Hkv = getattr(cfg, "num_key_value_heads", None) or self.H      # < H: grouped-query attention (Hkv = 1: multi-query)
         self.D = getattr(cfg, "head_dim", None) or cfg.hidden_size // self.H
         self._cache = None
 
@@ -82,8 +84,9 @@ class _FrozenLlamaLayer:
             x = ops.rms_norm(h, ly.input_layernorm.weight, eps)
         else:
             h, x = ops.add_rms_norm_pair(pending, h, ly.input_layernorm.weight, eps)
-        qkv = ops.rope_qk_(ops.frozen_linear(x, w_qkv, None), cos_sin, self.H)
-        a = ops.frozen_linear(ops.selfattn_core_fused(qkv, key_valid, self.H), ly.self_attn.o_proj.weight, None)
+        # w_qkv is [(H + 2 Hkv) * D, hidden]: the HF q | k | v weights as loaded, so k and v come out with Hkv heads
+        qkv = ops.rope_qk_(ops.frozen_linear(x, w_qkv, None), cos_sin, self.H, self.Hkv)
+        a = ops.frozen_linear(ops.selfattn_core_fused(qkv, key_valid, self.H, self.Hkv), ly.self_attn.o_proj.weight, None)
         h, x = ops.add_rms_norm_pair(a, h, ly.post_attention_layernorm.weight, eps)
         m = ops.frozen_linear(ops.swiglu(ops.frozen_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None)
         return h, m
@@ -103,9 +106,10 @@ class LlamaNeighborLM(nn.Module):
             self.llama = AutoModelForCausalLM.from_pretrained(args.model_name_or_path, config=cfg)
         cfg = self.llama.config
         self.config = cfg
-        if getattr(cfg, "num_key_value_heads", cfg.num_attention_heads) != cfg.num_attention_heads:
-            raise ValueError("LlamaNeighborLM: grouped-query attention (num_key_value_heads != num_attention_heads) is not implemented "
-                             "(Llama-2-7B, the BASELINE config, is multi-head)")
+        n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
+        if n_kv < 1 or cfg.num_attention_heads % n_kv:
+            raise ValueError(f"LlamaNeighborLM: num_attention_heads = {cfg.num_attention_heads} must be a multiple of "
+                             f"num_key_value_heads = {n_kv}")
         if getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False):
             raise ValueError("LlamaNeighborLM: biased projections are not implemented")
         for p in self.llama.parameters():

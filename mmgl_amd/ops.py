@@ -224,17 +224,112 @@ class _SelfAttnFusedQKV(torch.autograd.Function):
         return dqkv, None, None
 
 
-def selfattn_core_fused(qkv, key_valid, num_heads):
-    """selfattn_core over a fused projection output: qkv [B,T,3d] = [q*scale | k | v] along the last dim."""
+# Grouped-query attention (mmgl_selfattn_gqa_*): k, v [B,T,Hkv*D], query head h reads key / value head h // (H // Hkv).
+def _gqa_fwd(like, qp, kp, vp, key_valid, B, T, H, Hkv, D, ldq, ldkv):
+    out = torch.empty(B, T, H * D, dtype=like.dtype, device=like.device)
+    lse = torch.empty(B, H, T, dtype=torch.float32, device=like.device)
+    work = dict(flops=2.0 * B * T * T * H * D, bytes=2.0 * B * T * (H + Hkv) * D * like.element_size())
+    _lib.call("mmgl_selfattn_gqa_fwd", work, qp, kp, vp, ptr(key_valid), ptr(out), ptr(lse), B, H, Hkv, T, D, ldq, ldkv, dtype_code(like),
+              stream_ptr())
+    return out, lse
+
+
+def _gqa_bwd(like, dout, qp, kp, vp, out, lse, key_valid, dqp, dkp, dvp, B, T, H, Hkv, D, ldq, ldkv, ldgq, ldgkv):
+    dout = dout.contiguous()
+    nbytes = lib().mmgl_selfattn_gqa_bwd_workspace(B, H, Hkv, T, D, dtype_code(like))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=like.device)
+    work = dict(flops=5.0 * B * T * T * H * D, bytes=(4.0 * (H + Hkv) + 4.0 * H) * B * T * D * like.element_size())
+    _lib.call("mmgl_selfattn_gqa_bwd", work, ptr(dout), qp, kp, vp, ptr(out), ptr(lse), ptr(key_valid), dqp, dkp, dvp, ptr(ws), nbytes,
+              B, H, Hkv, T, D, ldq, ldkv, ldgq, ldgkv, dtype_code(like), stream_ptr())
+
+
+class _SelfAttnGQA(torch.autograd.Function):
+    """Causal grouped-query self-attention over separate q [B,T,H*D], k, v [B,T,Hkv*D]."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, key_valid, H, Hkv):
+        require_cuda(q, k, v, key_valid)
+        B, T, d = q.shape
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out, lse = _gqa_fwd(q, ptr(q), ptr(k), ptr(v), key_valid, B, T, H, Hkv, d // H, 0, 0)
+        ctx.save_for_backward(q, k, v, key_valid, out, lse)
+        ctx.heads = (H, Hkv)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, key_valid, out, lse = ctx.saved_tensors
+        H, Hkv = ctx.heads
+        B, T, d = q.shape
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        _gqa_bwd(q, dout, ptr(q), ptr(k), ptr(v), out, lse, key_valid, ptr(dq), ptr(dk), ptr(dv), B, T, H, Hkv, d // H, 0, 0, 0, 0)
+        return dq, dk, dv, None, None, None
+
+
+class _SelfAttnFusedGQA(torch.autograd.Function):
+    """Same kernels, Q/K/V read in place from one fused projection output [B,T,(H+2Hkv)*D] and dQ/dK/dV written into one buffer of
+    the same layout, so the projection's dgrad stays ONE GEMM."""
+
+    @staticmethod
+    def forward(ctx, qkv, key_valid, H, Hkv):
+        require_cuda(qkv, key_valid)
+        B, T, ld = qkv.shape
+        D = ld // (H + 2 * Hkv)
+        qkv = qkv.contiguous()
+        es = qkv.element_size()
+        out, lse = _gqa_fwd(qkv, ptr(qkv), ptr_off(qkv, H * D * es), ptr_off(qkv, (H + Hkv) * D * es), key_valid, B, T, H, Hkv, D, ld, ld)
+        ctx.save_for_backward(qkv, key_valid, out, lse)
+        ctx.heads = (H, Hkv)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, key_valid, out, lse = ctx.saved_tensors
+        H, Hkv = ctx.heads
+        B, T, ld = qkv.shape
+        D = ld // (H + 2 * Hkv)
+        es = qkv.element_size()
+        dqkv = torch.empty_like(qkv)
+        _gqa_bwd(qkv, dout, ptr(qkv), ptr_off(qkv, H * D * es), ptr_off(qkv, (H + Hkv) * D * es), out, lse, key_valid,
+                 ptr(dqkv), ptr_off(dqkv, H * D * es), ptr_off(dqkv, (H + Hkv) * D * es), B, T, H, Hkv, D, ld, ld, ld, ld)
+        return dqkv, None, None, None
+
+
+def _kv_heads(op, num_heads, num_kv_heads):
+    """None for the multi-head path (num_kv_heads is None or == num_heads), else the validated number of key / value heads."""
+    if num_kv_heads is None or num_kv_heads == num_heads:
+        return None
+    if num_kv_heads < 1 or num_heads % num_kv_heads:
+        raise ValueError(f"{op}: num_heads = {num_heads} must be a multiple of num_kv_heads = {num_kv_heads}")
+    return int(num_kv_heads)
+
+
+def selfattn_core_fused(qkv, key_valid, num_heads, num_kv_heads=None):
+    """selfattn_core over a fused projection output: qkv [B,T,3d] = [q*scale | k | v] along the last dim.  Grouped-query attention
+    (num_kv_heads = Hkv < H = num_heads): qkv [B,T,(H+2Hkv)*D], and the gradient comes back in the same layout."""
+    Hkv = _kv_heads("selfattn_core_fused", num_heads, num_kv_heads)
+    if Hkv is not None:
+        if qkv.dim() != 3 or qkv.shape[2] % (num_heads + 2 * Hkv):
+            raise ValueError(f"selfattn_core_fused: qkv{tuple(qkv.shape)} is not [B, T, (H+2*Hkv)*D] for H={num_heads}, Hkv={Hkv}")
+        _check_mask(key_valid, qkv.shape[:2])
+        return _SelfAttnFusedGQA.apply(qkv, _key_valid(key_valid), num_heads, Hkv)
     if qkv.dim() != 3 or qkv.shape[2] % (3 * num_heads):
         raise ValueError(f"selfattn_core_fused: qkv{tuple(qkv.shape)} is not [B, T, 3*H*D] for H={num_heads}")
     _check_mask(key_valid, qkv.shape[:2])
     return _SelfAttnFusedQKV.apply(qkv, _key_valid(key_valid), num_heads)
 
 
-def selfattn_core(q, k, v, key_valid, num_heads):
+def selfattn_core(q, k, v, key_valid, num_heads, num_kv_heads=None):
     """Causal self-attention softmax(mask(q k^T)) v with mask = (s <= t) & key_valid[b, s]; q is already scaled.
-    The caller guarantees key_valid[:, 0] is all ones (see include/mmgl_hip.h).  (reference :203-271 self branch)"""
+    The caller guarantees key_valid[:, 0] is all ones (see include/mmgl_hip.h).  (reference :203-271 self branch)
+    num_kv_heads = Hkv < num_heads: grouped-query attention, k, v [B,T,Hkv*D], query head h reads key / value head h // (H // Hkv)."""
+    Hkv = _kv_heads("selfattn_core", num_heads, num_kv_heads)
+    if Hkv is not None:
+        if (q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[:2] != k.shape[:2] or q.shape[2] % num_heads
+                or k.shape[2] != q.shape[2] // num_heads * Hkv):
+            raise ValueError(f"selfattn_core: incompatible shapes q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} for H={num_heads}, Hkv={Hkv}")
+        _check_mask(key_valid, k.shape[:2])
+        return _SelfAttnGQA.apply(q, k, v, _key_valid(key_valid), num_heads, Hkv)
     _attn_args("selfattn_core", q, k, v, key_valid, num_heads, 0)
     return _SelfAttn.apply(q, k, v, _key_valid(key_valid), num_heads, None)
 
@@ -1266,43 +1361,54 @@ def frozen_linear(x, weight, bias, act="none", mask_dx=False, bwd_premasked=Fals
 
 # ------------------------------------------------------------------------------------------ Llama-family elementwise ops
 class _RopeQK(torch.autograd.Function):
-    """Rotary embedding of the q and k blocks of a fused-QKV buffer [B, T, 3*H*D], in place (the buffer is a fresh GEMM output)."""
+    """Rotary embedding of the q and k blocks of a fused-QKV buffer [B, T, 3*H*D], in place (the buffer is a fresh GEMM output).
+    The kernel sees the row as `nall` column blocks of `unit` heads each and rotates the first `nblk`: (H, 2, 3) for multi-head,
+    (Hkv, G + 1, G + 2) for a grouped-query row [q: G blocks | k | v]."""
 
     @staticmethod
-    def forward(ctx, qkv, cos_sin, num_heads):
+    def forward(ctx, qkv, cos_sin, unit, nblk, nall):
         require_cuda(qkv, cos_sin)
-        B, T, d3 = qkv.shape
-        D = d3 // 3 // num_heads
+        B, T, ld = qkv.shape
+        D = ld // nall // unit
         if not qkv.is_contiguous():
             raise ValueError("rope_qk_: qkv must be contiguous")
-        _lib.call("mmgl_rope_inplace", dict(bytes=2.0 * B * T * (2 * d3 // 3) * qkv.element_size()), ptr(qkv), ptr(cos_sin), B * T, T, num_heads, D, d3, 2, 0,
+        _lib.call("mmgl_rope_inplace", dict(bytes=2.0 * B * T * (nblk * ld // nall) * qkv.element_size()), ptr(qkv), ptr(cos_sin), B * T, T, unit, D, ld, nblk, 0,
                   dtype_code(qkv), stream_ptr())
         ctx.mark_dirty(qkv)
         ctx.save_for_backward(cos_sin)
-        ctx.meta = (T, num_heads, D)
+        ctx.meta = (T, unit, D, nblk, nall)
         return qkv
 
     @staticmethod
     def backward(ctx, dqkv):
         (cos_sin,) = ctx.saved_tensors
-        T, H, D = ctx.meta
+        T, H, D, nblk, nall = ctx.meta
         dqkv = dqkv.contiguous()                                         # autograd owns the incoming buffer: rotate INTO a new one, never in place
         out = torch.empty_like(dqkv)
         rows = dqkv.numel() // dqkv.shape[-1]
         _lib.call("mmgl_rope", dict(bytes=2.0 * rows * dqkv.shape[-1] * dqkv.element_size()), ptr(dqkv), ptr(out), ptr(cos_sin), rows, T, H, D,
-                  dqkv.shape[-1], 2, 3, 1, dtype_code(dqkv), stream_ptr())
-        return out, None, None
+                  dqkv.shape[-1], nblk, nall, 1, dtype_code(dqkv), stream_ptr())
+        return out, None, None, None, None
 
 
-def rope_qk_(qkv, cos_sin, num_heads):
+def rope_qk_(qkv, cos_sin, num_heads, num_kv_heads=None):
     """In-place rotary position embedding of the q and k thirds of qkv [B, T, 3*H*D] (transformers' rotate_half convention,
-    position = index along T).  cos_sin: fp32 [T, D/2, 2]."""
-    if qkv.dim() != 3 or qkv.shape[2] % (3 * num_heads):
-        raise ValueError(f"rope_qk_: qkv{tuple(qkv.shape)} is not [B, T, 3*H*D] for H={num_heads}")
-    D = qkv.shape[2] // 3 // num_heads
+    position = index along T).  cos_sin: fp32 [T, D/2, 2].  Grouped-query attention (num_kv_heads = Hkv < H): qkv
+    [B, T, (H+2*Hkv)*D]; the H q heads and the Hkv k heads are rotated, the v block is left alone."""
+    Hkv = _kv_heads("rope_qk_", num_heads, num_kv_heads)
+    if Hkv is not None:
+        if qkv.dim() != 3 or qkv.shape[2] % (num_heads + 2 * Hkv):
+            raise ValueError(f"rope_qk_: qkv{tuple(qkv.shape)} is not [B, T, (H+2*Hkv)*D] for H={num_heads}, Hkv={Hkv}")
+        D, G = qkv.shape[2] // (num_heads + 2 * Hkv), num_heads // Hkv
+        unit, nblk, nall = Hkv, G + 1, G + 2
+    else:
+        if qkv.dim() != 3 or qkv.shape[2] % (3 * num_heads):
+            raise ValueError(f"rope_qk_: qkv{tuple(qkv.shape)} is not [B, T, 3*H*D] for H={num_heads}")
+        D = qkv.shape[2] // 3 // num_heads
+        unit, nblk, nall = num_heads, 2, 3
     if cos_sin.dtype != torch.float32 or tuple(cos_sin.shape) != (qkv.shape[1], D // 2, 2):
         raise ValueError(f"rope_qk_: cos_sin must be fp32 [T={qkv.shape[1]}, D/2={D // 2}, 2], got {cos_sin.dtype} {tuple(cos_sin.shape)}")
-    return _RopeQK.apply(qkv, cos_sin.contiguous(), num_heads)
+    return _RopeQK.apply(qkv, cos_sin.contiguous(), unit, nblk, nall)
 
 
 class _SwiGLU(torch.autograd.Function):
