@@ -435,6 +435,34 @@ int mmgl_gemm_skinny(const void* x, int ldx, const void* W, int ldw, const void*
 int mmgl_attn_decode_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,
                          const uint8_t* key_valid, int ld_valid, void* out, int B, int H, int S, int D, int dtype, void* stream);
 
+/* The decode step of the Llama-family LM (model/modelling_llama_cross_attention.py: LlamaNeighborLM.generate): a key/value cache of
+ * Hkv <= H heads and a rotary embedding at one position.  No reference counterpart (its fork is OPT-only).  Forward only.
+ *
+ * mmgl_attn_decode_gqa_fwd: mmgl_attn_decode_fwd over Hkv key/value heads: query head h reads key / value head h / (H / Hkv)
+ *   (transformers' repeat_kv, the mapping of mmgl_selfattn_gqa_*).
+ *   q, out    [B, H*D] (q: row stride ldq, already scaled by D^-0.5; out dense)
+ *   k, v      S rows of Hkv*D per sample, row stride ldkv, sample stride batch_stride_kv (elements): column slabs of the cache rows
+ *             [B, capacity, 2 Hkv D].  Nothing is expanded to H heads in memory.
+ *   key_valid [B, S] uint8, row stride ld_valid; a sample with no valid key attends uniformly over its S keys.
+ *   One workgroup per (sample, key/value head, block of at most 8 query heads of its group): each 16-byte K / V load is issued once
+ *   and used for every query head of the block; a group of more than 8 heads takes further blocks (12 = 6 + 6).  Softmax and
+ *   accumulation in fp32, partial states merged in a fixed order (no atomics: deterministic).  The S keys of a sample are not split
+ *   over workgroups.  D in {16,32,64,128} (else MMGL_ERR_UNSUPPORTED); Hkv any divisor of H (else MMGL_ERR_INVALID); any S >= 1;
+ *   strides multiples of 16 bytes, q / k / v 16-byte aligned.
+ *
+ * mmgl_rope_kv_append: the new token's row of the fused q | k | v projection, rotated and filed in one launch.
+ *   qkv         [B, (H + 2 Hkv) * D], row stride ldqkv: the H query heads are rotated IN PLACE; the k and v blocks are only read
+ *   cos_sin_row fp32 [D/2, 2] (cos, sin): the row of the position's angles of the table mmgl_rope_inplace takes; rotate_half
+ *               convention and the arithmetic of mmgl_rope_inplace
+ *   kv_col      the cache column of the new token: sample b's rotated Hkv key heads and unrotated Hkv value heads go to
+ *               kv_col[b * batch_stride_kv + 0 .. 2 Hkv D)
+ *   D in {16,32,64,128}; strides multiples of 16 bytes; qkv and kv_col 16-byte aligned. */
+int mmgl_attn_decode_gqa_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,
+                             const uint8_t* key_valid, int ld_valid, void* out, int B, int H, int Hkv, int S, int D, int dtype,
+                             void* stream);
+int mmgl_rope_kv_append(void* qkv, int ldqkv, const float* cos_sin_row, void* kv_col, size_t batch_stride_kv, int B, int H, int Hkv,
+                        int D, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 // Decode-step kernels: the weight-streaming GEMM for M = batch rows and single-query attention over a key/value cache.
-// Reached only from the generation path (ops.decode_linear / ops.attn_decode); no training or prefill caller routes here.
+// Reached only from the generation path (ops.decode_linear / ops.attn_decode / ops.rope_kv_append); no training or prefill caller routes here.
 //
 // mmgl_gemm_skinny, bf16 (skinny_mfma_kernel).  Y[M,N] = epi(X[M,K] . W[N,K]^T), 1 <= M <= 64.  The step is bound by the weight bytes:
 //   * W is the MFMA A operand (as everywhere in this library) and goes HBM -> VGPR as 16-byte lane loads in A-fragment shape, two per lane
@@ -32,6 +32,14 @@
 // group keeps its own online-softmax state (max, sum, partial O) in fp32; the states are merged by a fixed butterfly inside the wave and
 // in wave order through LDS.  A masked key scores -FLT_MAX: with a valid key in the row it weighs exp(-FLT_MAX - max) = 0, and a row of
 // masked keys only has every weight exp(0) = 1 -- the uniform distribution of the reference's finfo.min clamp.
+//
+// mmgl_attn_decode_gqa_fwd (attn_decode_gqa_kernel).  The same kernel over a cache of Hkv <= H key/value heads: one workgroup per (sample,
+// key/value head, block of at most 8 of the G = H / Hkv query heads that read it).  The decode step is a memory-bound read of the cache,
+// so each 16-byte K / V load is issued once and scored against every query head of the block from registers; G > 8 takes further blocks.
+// The keys of a sample are not split over workgroups (no flash-decoding: DESIGN.md 4.11).
+//
+// mmgl_rope_kv_append (rope_kv_append_kernel).  The new token's q | k | v row: q rotated in place, k rotated into the token's cache column,
+// v copied there -- one launch where separate projections and rotations would take four (the step is launch-bound).
 #include "common.h"
 #include "attn_common.h"      // make_rsrc / OOB: hardware-bounds-checked buffer loads
 #include <float.h>
@@ -430,6 +438,210 @@ int attn_decode_d(const void* q, int ldq, const void* k, const void* v, int ldkv
     }
 }
 
+// ------------------------------------------------------------------------------------------------ grouped-query single-query attention
+// sum over the N = 2^n lanes of a lane group (aligned to N), returned in every lane of the group.  Up to 16 lanes the exchange is DPP --
+// quad permutes, then the mirror of a half row and of a row, which pair the two halves once each half holds its sum -- so a dot
+// product costs VALU adds instead of LDS-routed permutes; wider groups finish with the wave shuffle.  A fixed order: deterministic.
+template <int CTRL> __device__ __forceinline__ float dpp_read(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+template <int N> __device__ __forceinline__ float group_sum(float v) {
+    if constexpr (N >= 2) v += dpp_read<0xB1>(v);          // quad_perm [1, 0, 3, 2]
+    if constexpr (N >= 4) v += dpp_read<0x4E>(v);          // quad_perm [2, 3, 0, 1]
+    if constexpr (N >= 8) v += dpp_read<0x141>(v);         // row_half_mirror
+    if constexpr (N >= 16) v += dpp_read<0x140>(v);        // row_mirror
+#pragma unroll
+    for (int o = 16; o < N; o <<= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// One workgroup per (sample, key/value head, block of NQ <= 8 query heads of that head's group): the key and value registers of
+// attn_decode_kernel (same lane layout, same trip constants) feed NQ online-softmax states per lane group, so every 16-byte K / V load
+// is issued once for the whole block and nothing is expanded in memory.  A block with fewer than NQ heads (nq < NQ) computes its last
+// head NQ - nq times more and stores nq rows: no divergent branch in the loop.
+template <typename T, int D, int NQ>
+__global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_gqa_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k,
+                                                                          const T* __restrict__ v, int ldkv, size_t bs_kv,
+                                                                          const uint8_t* __restrict__ valid, int ld_valid,
+                                                                          T* __restrict__ out, int H, int Hkv, int S, int qpb, int nblk) {
+    typedef typename Vec16<T>::type V;
+    constexpr int VEC = 16 / sizeof(T);
+    constexpr int LPK = D / VEC;                    // lanes per key
+    constexpr int KPI = WAVE / LPK;                 // keys per wave and load instruction
+    constexpr float NEG = -FLT_MAX;
+    __shared__ float sm_m[AD_WAVES][NQ], sm_l[AD_WAVES][NQ], sm_o[AD_WAVES][NQ][D];
+
+    const int G = H / Hkv;
+    const int qb = blockIdx.x % nblk, kvh = (blockIdx.x / nblk) % Hkv, b = blockIdx.x / (nblk * Hkv);
+    const int h0 = kvh * G + qb * qpb, nq = min(qpb, G - qb * qpb);        // query heads h0 .. h0 + nq - 1
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane % LPK, kk = lane / LPK;
+
+    float qf[NQ][VEC];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const V qv = *(const V*)(q + (size_t)b * ldq + (h0 + min(j, nq - 1)) * D + c * VEC);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) qf[j][e] = Elem<T>::to_f(qv[e]);
+    }
+    // branch-free loads: keys past S fall outside the descriptors
+    const uint32_t slab = (uint32_t)(((size_t)(S - 1) * ldkv + D) * sizeof(T)), row_bytes = (uint32_t)(ldkv * sizeof(T));
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(k + b * bs_kv + kvh * D, slab);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(v + b * bs_kv + kvh * D, slab);
+    const uint8_t* mb = valid + (size_t)b * ld_valid;
+
+    float m[NQ], l[NQ], acc[NQ][VEC];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        m[j] = NEG;
+        l[j] = 0.f;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[j][e] = 0.f;
+    }
+
+    for (int base = w * KPI; base < S; base += AD_WAVES * KPI * AD_UNROLL) {          // wave-uniform trip count
+        V kr[AD_UNROLL], vr[AD_UNROLL];
+        uint8_t ok[AD_UNROLL];
+        bool in[AD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            const int s = base + u * AD_WAVES * KPI + kk;
+            in[u] = s < S;
+            const uint32_t off = in[u] ? (uint32_t)s * row_bytes + (uint32_t)(c * 16) : OOB;
+            kr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+            vr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+            ok[u] = mb[min(s, S - 1)];
+        }
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            // the trip's AD_UNROLL keys enter the online softmax together: one rescale of the state per trip instead of one per key
+            float sc[AD_UNROLL], mn = m[j];
+#pragma unroll
+            for (int u = 0; u < AD_UNROLL; ++u) {
+                float dot = 0.f;
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) dot += qf[j][e] * Elem<T>::to_f(kr[u][e]);
+                dot = group_sum<LPK>(dot);
+                sc[u] = ok[u] ? dot : NEG;
+                if (in[u]) mn = fmaxf(mn, sc[u]);
+            }
+            const float corr = __expf(m[j] - mn);
+            float pu[AD_UNROLL], ps = 0.f;
+#pragma unroll
+            for (int u = 0; u < AD_UNROLL; ++u) {
+                pu[u] = in[u] ? __expf(sc[u] - mn) : 0.f;             // a key past S weighs nothing, also in a row of masked keys
+                ps += pu[u];
+            }
+            l[j] = l[j] * corr + ps;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                float a = acc[j][e] * corr;
+#pragma unroll
+                for (int u = 0; u < AD_UNROLL; ++u) a += pu[u] * Elem<T>::to_f(vr[u][e]);
+                acc[j][e] = a;
+            }
+            m[j] = mn;
+        }
+    }
+    // per query head: merge the lane groups of the wave (fixed butterfly), then the waves in order
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+#pragma unroll
+        for (int o = LPK; o < WAVE; o <<= 1) {
+            const float m2 = __shfl_xor(m[j], o), l2 = __shfl_xor(l[j], o);
+            const float mn = fmaxf(m[j], m2);
+            const float c1 = __expf(m[j] - mn), c2 = __expf(m2 - mn);
+            l[j] = l[j] * c1 + l2 * c2;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[j][e] = acc[j][e] * c1 + __shfl_xor(acc[j][e], o) * c2;
+            m[j] = mn;
+        }
+        if (lane < LPK) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) sm_o[w][j][c * VEC + e] = acc[j][e];
+            if (lane == 0) { sm_m[w][j] = m[j]; sm_l[w][j] = l[j]; }
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < nq * D; idx += AD_WAVES * WAVE) {
+        const int j = idx / D, x = idx % D;
+        float mm = sm_m[0][j];
+#pragma unroll
+        for (int i = 1; i < AD_WAVES; ++i) mm = fmaxf(mm, sm_m[i][j]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int i = 0; i < AD_WAVES; ++i) {
+            const float ci = __expf(sm_m[i][j] - mm);
+            ll += sm_l[i][j] * ci;
+            o += sm_o[i][j][x] * ci;
+        }
+        out[((size_t)b * H + h0 + j) * D + x] = Elem<T>::from_f(o / ll);
+    }
+}
+
+template <typename T, int D>
+int attn_decode_gqa_nq(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t bs_kv, const uint8_t* valid, int ld_valid,
+                       void* out, int B, int H, int Hkv, int S, hipStream_t st) {
+    const int G = H / Hkv, nblk = cdiv(G, 8), qpb = cdiv(G, nblk);        // G > 8: further blocks, of equal size up to one head
+    const dim3 grid(B * Hkv * nblk), block(AD_WAVES * WAVE);
+#define MMGL_GQA_DECODE(NQ)                                                                                                          \
+    hipLaunchKernelGGL((attn_decode_gqa_kernel<T, D, NQ>), grid, block, 0, st, (const T*)q, ldq, (const T*)k, (const T*)v, ldkv, bs_kv, \
+                       valid, ld_valid, (T*)out, H, Hkv, S, qpb, nblk)
+    if (qpb == 1) MMGL_GQA_DECODE(1);
+    else if (qpb == 2) MMGL_GQA_DECODE(2);
+    else if (qpb <= 4) MMGL_GQA_DECODE(4);
+    else MMGL_GQA_DECODE(8);
+#undef MMGL_GQA_DECODE
+    MMGL_CHECK_LAUNCH("mmgl_attn_decode_gqa_fwd");
+    return MMGL_OK;
+}
+
+template <typename T>
+int attn_decode_gqa_d(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t bs_kv, const uint8_t* valid, int ld_valid,
+                      void* out, int B, int H, int Hkv, int S, int D, hipStream_t st) {
+    switch (D) {
+        case 16: return attn_decode_gqa_nq<T, 16>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, Hkv, S, st);
+        case 32: return attn_decode_gqa_nq<T, 32>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, Hkv, S, st);
+        case 64: return attn_decode_gqa_nq<T, 64>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, Hkv, S, st);
+        default: return attn_decode_gqa_nq<T, 128>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, Hkv, S, st);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ rotary embedding of one new token
+// qkv [B, ldqkv] = [q: H heads | k: Hkv | v: Hkv] x D of the new token; cs [D/2] float2 (cos, sin) of its position.  One thread = VN
+// consecutive i of one (sample, head): the pair (i, i + D/2) of a q head is rotated in place, that of a k head is rotated into the
+// cache column, that of a v head is copied there; the k and v blocks of qkv are only read.  The arithmetic of rope_kernel (llama_ops.hip).
+template <typename T>
+__global__ __launch_bounds__(256) void rope_kv_append_kernel(T* __restrict__ qkv, int ldqkv, const f32x2* __restrict__ cs, T* __restrict__ kv_col,
+                                                             size_t bs_kv, int B, int H, int Hkv, int D) {
+    constexpr int VN = 16 / sizeof(T);
+    typedef typename Vec16<T>::type V;
+    const int half = D / 2, per_head = half / VN, heads = H + 2 * Hkv;
+    const int total = B * heads * per_head;
+    for (int id = blockIdx.x * 256 + threadIdx.x; id < total; id += gridDim.x * 256) {
+        const int b = id / (heads * per_head), rem = id - b * heads * per_head;
+        const int hd = rem / per_head, c = rem - hd * per_head;
+        T* src = qkv + (size_t)b * ldqkv + (size_t)hd * D + c * VN;
+        V lo = *(const V*)src, hi = *(const V*)(src + half);
+        if (hd < H + Hkv) {
+            const f32x2* a = cs + c * VN;
+            V olo, ohi;
+#pragma unroll
+            for (int e = 0; e < VN; ++e) {
+                const float co = a[e][0], si = a[e][1];
+                const float x0 = (float)lo[e], x1 = (float)hi[e];
+                olo[e] = (T)(x0 * co - x1 * si);
+                ohi[e] = (T)(x1 * co + x0 * si);
+            }
+            lo = olo;
+            hi = ohi;
+        }
+        T* dst = hd < H ? src : kv_col + (size_t)b * bs_kv + (size_t)(hd - H) * D + c * VN;     // k | v in qkv = k | v in the cache row
+        *(V*)dst = lo;
+        *(V*)(dst + half) = hi;
+    }
+}
+
 }  // namespace
 
 extern "C" int mmgl_gemm_skinny(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* residual, void* y, int ldy,
@@ -496,4 +708,52 @@ extern "C" int mmgl_attn_decode_fwd(const void* q, int ldq, const void* k, const
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MMGL_BF16) return attn_decode_d<bf16>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, S, D, st);
     return attn_decode_d<float>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, S, D, st);
+}
+
+extern "C" int mmgl_attn_decode_gqa_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,
+                                        const uint8_t* key_valid, int ld_valid, void* out, int B, int H, int Hkv, int S, int D, int dtype,
+                                        void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && H >= 1 && Hkv >= 1 && S >= 1, "mmgl_attn_decode_gqa_fwd: bad sizes B=%d H=%d Hkv=%d S=%d", B, H, Hkv, S);
+    MMGL_CHECK_ARG(H % Hkv == 0, "mmgl_attn_decode_gqa_fwd: %d query heads are no multiple of %d key/value heads", H, Hkv);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_attn_decode_gqa_fwd: bad dtype %d", dtype);
+    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_gqa_fwd: head_dim %d (16, 32, 64, 128)", D);
+    const int vec = dtype == MMGL_BF16 ? 8 : 4;
+    if (ldq % vec || ldkv % vec || batch_stride_kv % vec)
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_gqa_fwd: strides (%d, %d, %zu) must be multiples of 16 bytes", ldq, ldkv, batch_stride_kv);
+    MMGL_CHECK_ARG(q && k && v && key_valid && out, "mmgl_attn_decode_gqa_fwd: null pointer");
+    MMGL_CHECK_ARG(ldq >= H * D && ldkv >= Hkv * D && ld_valid >= S, "mmgl_attn_decode_gqa_fwd: strides (%d, %d, %d) smaller than the rows", ldq, ldkv,
+                   ld_valid);
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_gqa_fwd: q, k and v must be 16-byte aligned");
+    if (((size_t)(S - 1) * ldkv + D) * (dtype == MMGL_BF16 ? 2 : 4) >= (1ull << 31))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_gqa_fwd: a sample's key rows span 2 GiB or more (S=%d, ldkv=%d)", S, ldkv);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_BF16) return attn_decode_gqa_d<bf16>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, Hkv, S, D, st);
+    return attn_decode_gqa_d<float>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, Hkv, S, D, st);
+}
+
+extern "C" int mmgl_rope_kv_append(void* qkv, int ldqkv, const float* cos_sin_row, void* kv_col, size_t batch_stride_kv, int B, int H, int Hkv,
+                                   int D, int dtype, void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && H >= 1 && Hkv >= 1, "mmgl_rope_kv_append: bad sizes B=%d H=%d Hkv=%d", B, H, Hkv);
+    MMGL_CHECK_ARG(H % Hkv == 0, "mmgl_rope_kv_append: %d query heads are no multiple of %d key/value heads", H, Hkv);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_rope_kv_append: bad dtype %d", dtype);
+    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_rope_kv_append: head_dim %d (16, 32, 64, 128)", D);
+    const int vec = dtype == MMGL_BF16 ? 8 : 4;
+    if (ldqkv % vec || batch_stride_kv % vec)
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_rope_kv_append: strides (%d, %zu) must be multiples of 16 bytes", ldqkv, batch_stride_kv);
+    MMGL_CHECK_ARG(qkv && cos_sin_row && kv_col, "mmgl_rope_kv_append: null pointer");
+    MMGL_CHECK_ARG((long long)ldqkv >= (long long)(H + 2 * Hkv) * D && (B == 1 || batch_stride_kv >= (size_t)2 * Hkv * D),
+                   "mmgl_rope_kv_append: strides (%d, %zu) smaller than the rows", ldqkv, batch_stride_kv);
+    if (!aligned16(qkv) || !aligned16(kv_col) || ((uintptr_t)cos_sin_row & 7))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_rope_kv_append: qkv and kv_col must be 16-byte aligned, cos_sin_row 8-byte");
+    MMGL_CHECK_ARG((long long)B * (H + 2 * Hkv) * (D / 2 / vec) < (1ll << 31), "mmgl_rope_kv_append: B=%d rows of %d heads are too many", B, H + 2 * Hkv);
+    hipStream_t st = (hipStream_t)stream;
+    const int total = B * (H + 2 * Hkv) * (D / 2 / vec);
+    const dim3 grid(min(cdiv(total, 256), 4096)), block(256);
+    if (dtype == MMGL_BF16)
+        hipLaunchKernelGGL(rope_kv_append_kernel<bf16>, grid, block, 0, st, (bf16*)qkv, ldqkv, (const f32x2*)cos_sin_row, (bf16*)kv_col, batch_stride_kv, B, H, Hkv, D);
+    else
+        hipLaunchKernelGGL(rope_kv_append_kernel<float>, grid, block, 0, st, (float*)qkv, ldqkv, (const f32x2*)cos_sin_row, (float*)kv_col, batch_stride_kv, B, H, Hkv, D);
+    MMGL_CHECK_LAUNCH("mmgl_rope_kv_append");
+    return MMGL_OK;
 }

@@ -9,6 +9,10 @@ reading Q/K/V in place (multi-head or grouped-query: num_key_value_heads <= num_
 head h // G as in transformers' repeat_kv), ONE fused gate|up GEMM + SwiGLU kernel, down projection; dgrads against cached W^T copies.
 No reference counterpart exists: parity is UNPINNED vs MMGL; it is pinned (tests/test_llama_gpu.py) to HF Llama itself
 when the gates are 0 and to the CPU oracle (oracle/llama_ref.py) otherwise.
+Greedy generation (LlamaNeighborLM.generate) keeps a cache of the Hkv key/value heads only -- rows [B, capacity, 2*Hkv*D] -- and runs
+each new token on the decode kernels: one skinny GEMM on the fused q|k|v weight, ops.rope_kv_append (q rotated in place, k rotated and
+v copied into the token's cache column), ops.attn_decode with num_kv_heads (one read of a cached key serves its G query heads),
+residual adds in the GEMM epilogues.  The new token's position is its COLUMN, as in forward() and in HF's default position_ids.
 """
 import torch
 import torch.nn as nn
@@ -16,6 +20,7 @@ import torch.nn.functional as F
 from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from .. import ops
+from .modelling_cross_attention import DecodeCache
 
 
 class LlamaGatedCrossAttentionLayer(nn.Module):
@@ -36,12 +41,14 @@ class LlamaGatedCrossAttentionLayer(nn.Module):
         self.gating1 = nn.Parameter(torch.tensor(0.0))
         self.gating2 = nn.Parameter(torch.tensor(0.0))
 
-    def forward(self, hidden_states, neighbor_embeds, key_valid):
+    def forward(self, hidden_states, neighbor_embeds, key_valid, kv_out=None):
         h = hidden_states
         x = ops.rms_norm(h, self.input_layernorm, self.eps)
         q = ops.linear(x, self.q_proj.weight, None, out_scale=self.head_dim ** -0.5)
         k = ops.linear(neighbor_embeds, self.k_proj.weight, None)
         v = ops.linear(neighbor_embeds, self.v_proj.weight, None)
+        if kv_out is not None:               # prefill of generate(): the projected neighbor tokens are constant over the decode steps
+            kv_out.append((k, v))
         a = ops.linear(ops.xattn_core(q, k, v, key_valid, self.num_heads), self.o_proj.weight, None)
         h = ops.gated_residual(h, a, self.gating1, self.dropout, self.training)
         x = ops.rms_norm(h, self.post_attention_layernorm, self.eps)
@@ -51,6 +58,17 @@ class LlamaGatedCrossAttentionLayer(nn.Module):
         gu = ops.linear(x, torch.cat([self.gate_proj.weight, self.up_proj.weight], dim=0), None)
         m = ops.linear(ops.swiglu(gu), self.down_proj.weight, None)
         return ops.gated_residual(h, m, self.gating2, self.dropout, self.training)
+
+    def decode_step(self, h, k, v, key_valid, w_gu):
+        """The layer on the one new token of a decode step, h [B, hidden], against the neighbor keys and values projected at the
+        prefill (k, v [B, S, hidden]); w_gu: the [gate | up] weight, concatenated once per generation."""
+        x = ops.rms_norm(h, self.input_layernorm, self.eps)
+        q = ops.decode_linear(x, self.q_proj.weight, None, out_scale=self.head_dim ** -0.5)
+        a = ops.decode_linear(ops.attn_decode(q, k, v, key_valid, self.num_heads), self.o_proj.weight, None)
+        h = ops.gated_residual(h, a, self.gating1, 0.0, False)
+        x = ops.rms_norm(h, self.post_attention_layernorm, self.eps)
+        m = ops.decode_linear(ops.swiglu(ops.decode_linear(x, w_gu, None)), self.down_proj.weight, None)
+        return ops.gated_residual(h, m, self.gating2, 0.0, False)
 
 
 class _FrozenLlamaLayer:
@@ -75,9 +93,10 @@ class _FrozenLlamaLayer:
             self._cache = (key, qkv, gu)
         return self._cache[1], self._cache[2]
 
-    def __call__(self, h, pending, key_valid, cos_sin):
+    def __call__(self, h, pending, key_valid, cos_sin, kv_out=None):
         """(h, pending) -> (h', pending'): the residual stream and the MLP output NOT yet added to it -- the add runs inside the
-        RMSNorm kernel of whoever consumes the sum next (this layer's successor, the final norm), forward and backward."""
+        RMSNorm kernel of whoever consumes the sum next (this layer's successor, the final norm), forward and backward.
+        kv_out: the layer's [B, capacity, 2*Hkv*D] rows of a DecodeCache -- the prefill copies its rotated keys and its values there."""
         ly, eps = self.layer, self.cfg.rms_norm_eps
         w_qkv, w_gu = self._fused()
         if pending is None:
@@ -86,10 +105,26 @@ class _FrozenLlamaLayer:
             h, x = ops.add_rms_norm_pair(pending, h, ly.input_layernorm.weight, eps)
         # w_qkv is [(H + 2 Hkv) * D, hidden]: the HF q | k | v weights as loaded, so k and v come out with Hkv heads
         qkv = ops.rope_qk_(ops.frozen_linear(x, w_qkv, None), cos_sin, self.H, self.Hkv)
+        if kv_out is not None:
+            kv_out[:, :qkv.shape[1]].copy_(qkv[:, :, self.H * self.D:])
         a = ops.frozen_linear(ops.selfattn_core_fused(qkv, key_valid, self.H, self.Hkv), ly.self_attn.o_proj.weight, None)
         h, x = ops.add_rms_norm_pair(a, h, ly.post_attention_layernorm.weight, eps)
         m = ops.frozen_linear(ops.swiglu(ops.frozen_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None)
         return h, m
+
+    def decode_step(self, h, kv, key_mask, col, cos_sin_row):
+        """The layer on the one new token of a decode step, h [B, hidden] -> [B, hidden]: the token's q|k|v row from one skinny GEMM,
+        rotated and filed into column `col` of kv [B, capacity, 2*Hkv*D] by one kernel, single-query attention over columns 0..col
+        (all at or before the query: no causal test), both residual adds in GEMM epilogues."""
+        ly, eps = self.layer, self.cfg.rms_norm_eps
+        w_qkv, w_gu = self._fused()
+        nq, nkv = self.H * self.D, self.Hkv * self.D
+        x = ops.rms_norm(h, ly.input_layernorm.weight, eps)
+        qkv = ops.rope_kv_append(ops.decode_linear(x, w_qkv, None), cos_sin_row, kv[:, col], self.H, self.Hkv)
+        a = ops.attn_decode(qkv[:, :nq], kv[:, :col + 1, :nkv], kv[:, :col + 1, nkv:], key_mask[:, :col + 1], self.H, num_kv_heads=self.Hkv)
+        h = ops.decode_linear(a, ly.self_attn.o_proj.weight, None, residual=h)
+        x = ops.rms_norm(h, ly.post_attention_layernorm.weight, eps)
+        return ops.decode_linear(ops.swiglu(ops.decode_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None, residual=h)
 
 
 class LlamaNeighborLM(nn.Module):
@@ -147,10 +182,48 @@ class LlamaNeighborLM(nn.Module):
         return self._rope[1]
 
     def forward(self, input_ids=None, attention_mask=None, labels=None, neighbor_embeds=None, neighbor_attention_mask=None,
-                first_key_valid=False, return_logits=None, logits_slice=None, **kw):
+                first_key_valid=False, return_logits=None, logits_slice=None, use_cache=False, cache_capacity=None, past_key_values=None,
+                **kw):
+        """use_cache=True: the prefill of greedy generation -- the same kernels as any forward, plus a copy of every frozen layer's
+        rotated keys and its values into a DecodeCache with rows [B, capacity, 2*Hkv*D] (capacity `cache_capacity` columns, default
+        max_position_embeddings) and of every gated layer's projected neighbor tokens; returned as past_key_values.
+        past_key_values=DecodeCache with input_ids [B, 1]: one decode step (see _decode_step), logits [B, 1, V]."""
+        if past_key_values is not None:
+            if not isinstance(past_key_values, DecodeCache):
+                raise ValueError("LlamaNeighborLM: past_key_values must be the DecodeCache of a forward(use_cache=True)")
+            if labels is not None:
+                raise ValueError("a decode step takes no labels")
+            logits = self._last_logits(self._decode_step(input_ids, past_key_values))[:, None]
+            return CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=past_key_values)
+        hidden, cache = self._hidden(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid, use_cache,
+                                     cache_capacity)
+        nxt = None
+        if labels is not None:
+            nxt = torch.full_like(labels, -100)
+            nxt[:, :-1] = labels[:, 1:]
+        from .modelling_cross_attention import lm_head_loss_and_logits
+        loss, logits = lm_head_loss_and_logits(self, self.llama.lm_head, hidden, nxt, return_logits, logits_slice)
+        return CausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=cache)
+
+    def _hidden(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid=False, use_cache=False,
+                cache_capacity=None):
+        """(final-norm hidden states [B, T, hidden], the filled DecodeCache or None)."""
         emb = self.llama.get_input_embeddings()
-        h = emb(input_ids)
         B, T = input_ids.shape
+        cache = None
+        table = T                                 # rows of the rotary table
+        if use_cache:
+            if self.training:
+                raise ValueError("a decode cache in training mode: generation is deterministic, call eval() first")
+            limit = self.config.max_position_embeddings
+            capacity = limit if cache_capacity is None else int(cache_capacity)
+            if T > capacity or capacity > limit:
+                raise ValueError(f"decode cache: a prompt of {T} columns, capacity {capacity}, max_position_embeddings {limit}")
+            ops.require_cuda(input_ids)
+            fr = self._frozen[0]
+            cache = DecodeCache(len(self._frozen), B, capacity, fr.Hkv * fr.D, emb.weight.dtype, input_ids.device)
+            table = capacity
+        h = emb(input_ids)
         if attention_mask is None:
             attention_mask = torch.ones(B, T, dtype=torch.long, device=h.device)
         if not first_key_valid:                   # same precondition (and device-side check) as MPTDecoder.forward
@@ -162,24 +235,110 @@ class LlamaNeighborLM(nn.Module):
             if valid is None:
                 valid = torch.ones(neighbor_embeds.shape[:2], dtype=torch.uint8, device=neighbor_embeds.device)
             ne, valid = neighbor_embeds.to(emb.weight.dtype), valid.to(torch.uint8).contiguous()
-        cos_sin = self._cos_sin(T, h.device)
+        # with a cache the table is built once at the cache's capacity: its first T rows are bitwise the table of T positions
+        cos_sin = self._cos_sin(table, h.device)[:T]
         k = 0
         pending = None                            # a frozen layer's MLP output, added inside the next RMSNorm kernel
         for l, layer in enumerate(self._frozen):
-            h, pending = layer(h, pending, key_mask, cos_sin)
+            h, pending = layer(h, pending, key_mask, cos_sin, None if cache is None else cache.kv[l])
             if (l + 1) % self.neighbor_layer_wise == 0:
                 if ne is not None:
                     h, pending = ops.gated_residual(h, pending), None
-                    h = self.neighbor_layers[k](h, ne, valid)
+                    h = self.neighbor_layers[k](h, ne, valid, None if cache is None else cache.cross)
                 k += 1
         if pending is None:
             hidden = ops.rms_norm(h, self.llama.model.norm.weight, self.config.rms_norm_eps)
         else:
             hidden = ops.add_rms_norm_pair(pending, h, self.llama.model.norm.weight, self.config.rms_norm_eps)[1]
-        nxt = None
-        if labels is not None:
-            nxt = torch.full_like(labels, -100)
-            nxt[:, :-1] = labels[:, 1:]
-        from .modelling_cross_attention import lm_head_loss_and_logits
-        loss, logits = lm_head_loss_and_logits(self, self.llama.lm_head, hidden, nxt, return_logits, logits_slice)
-        return CausalLMOutputWithPast(loss=loss, logits=logits)
+        if cache is not None:
+            cache.mask[:, :T] = key_mask
+            cache.col = T
+            cache.cross_valid = valid if cache.cross else None
+            cache.cos_sin = self._cos_sin(table, h.device)
+            # the gated layers' [gate | up] weights, concatenated once per generation instead of once per step
+            cache.cross_gu = [torch.cat([ly.gate_proj.weight, ly.up_proj.weight], dim=0) for ly in self.neighbor_layers] if cache.cross else []
+        return hidden, cache
+
+    def _decode_step(self, input_ids, cache):
+        """One new token per sample against the cache, input_ids [B, 1] -> final-norm hidden [B, hidden].  The token is appended at
+        column cache.col of every sample and that column is its rotary position: forward() (mmgl_rope_inplace: row r % T) and HF's
+        default position_ids count columns, not valid tokens, so cached generation equals the uncached forward on the same ids."""
+        if input_ids is None or input_ids.dim() != 2 or input_ids.shape[1] != 1 or input_ids.shape[0] != cache.mask.shape[0]:
+            raise ValueError(f"a decode step takes one new token per cached sample ([{cache.mask.shape[0]}, 1]), "
+                             f"got {None if input_ids is None else tuple(input_ids.shape)}")
+        if getattr(cache, "cos_sin", None) is None:
+            raise ValueError("the DecodeCache has not been filled: run the prompt with use_cache=True first")
+        if cache.col >= cache.capacity:
+            raise ValueError(f"decode cache is full: column {cache.col} of capacity {cache.capacity}")
+        ops.require_cuda(cache.mask, input_ids)
+        col, eps = cache.col, self.config.rms_norm_eps
+        with torch.no_grad():
+            h = self.llama.get_input_embeddings()(input_ids[:, 0])
+            cache.mask[:, col] = 1
+            row = cache.cos_sin[col]
+            k = 0
+            for l, layer in enumerate(self._frozen):
+                h = layer.decode_step(h, cache.kv[l], cache.mask, col, row)
+                if (l + 1) % self.neighbor_layer_wise == 0:
+                    if cache.cross:
+                        h = self.neighbor_layers[k].decode_step(h, *cache.cross[k], cache.cross_valid, cache.cross_gu[k])
+                    k += 1
+            h = ops.rms_norm(h, self.llama.model.norm.weight, eps)
+            cache.col += 1
+        return h
+
+    def _last_logits(self, hidden):
+        """lm_head on one row per sample, hidden [B, hidden] (any row stride): the [V, hidden] head is read once for the B rows."""
+        head = self.llama.lm_head
+        if type(head) is not nn.Linear:
+            raise ValueError("generate(): lm_head must be a plain nn.Linear")
+        return ops.decode_linear(hidden.contiguous(), head.weight, head.bias)
+
+    def can_generate(self):
+        return True
+
+    @torch.no_grad()
+    def generate(self, input_ids, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
+                 eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False):
+        """Greedy decoding with a key/value cache: the contract of MPTForCausalLM.generate (without inputs_embeds).  One prefill over
+        the right-padded prompts [B, T] -- the kernels of forward(), plus the copy of every layer's Hkv key/value heads into a
+        DecodeCache -- then max_new_tokens - 1 decode steps; lm_head runs on the last row only.  Every new token is appended at the
+        same column for all samples (its rotary position), the pad keys stay masked.
+        eos_token_id: a row that has emitted it gets pad_token_id (default config.pad_token_id) from then on; None: no end-of-sequence
+        handling.  All max_new_tokens steps run (no host synchronisation to stop early).
+        Returns the [B, T + max_new_tokens] ids; with return_step_logits=True also the [B, max_new_tokens, V] logits the tokens
+        were picked from."""
+        n_new = int(max_new_tokens)
+        if n_new < 1:
+            raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
+        if not input_ids.is_cuda:
+            raise RuntimeError(f"generate() runs on the GPU only (the prompt is on {input_ids.device}); there is no CPU path")
+        if input_ids.dim() != 2:
+            raise ValueError(f"generate(): input_ids [B, T], got {tuple(input_ids.shape)}")
+        B, T = input_ids.shape
+        limit = self.config.max_position_embeddings
+        if T + n_new - 1 > limit:
+            raise ValueError(f"generate(): {T} prompt columns + {n_new} new tokens exceed max_position_embeddings {limit}")
+        if eos_token_id is not None and pad_token_id is None:
+            pad_token_id = self.config.pad_token_id
+            if pad_token_id is None:
+                raise ValueError("generate(): eos_token_id needs a pad_token_id")
+        hidden, cache = self._hidden(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid, True,
+                                     T + n_new - 1)
+        hidden = hidden[:, -1]
+        ids = torch.empty(B, T + n_new, dtype=input_ids.dtype, device=input_ids.device)
+        ids[:, :T] = input_ids
+        finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
+        steps = []
+        for s in range(n_new):
+            logits = self._last_logits(hidden)
+            if return_step_logits:
+                steps.append(logits)
+            tok = torch.argmax(logits, dim=-1)
+            if eos_token_id is not None:
+                tok = torch.where(finished, torch.full_like(tok, pad_token_id), tok)
+                finished = finished | (tok == eos_token_id)
+            ids[:, T + s] = tok
+            if s + 1 < n_new:
+                hidden = self._decode_step(tok[:, None], cache)
+        return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids

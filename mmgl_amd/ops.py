@@ -1610,16 +1610,22 @@ def decode_lora_linear(x, weight, bias, lora_A, lora_B, scaling, out_scale=1.0, 
     return y
 
 
-def attn_decode(q, k, v, key_valid, num_heads, out=None):
+def attn_decode(q, k, v, key_valid, num_heads, out=None, num_kv_heads=None):
     """One query row per (sample, head) against S keys: q [B, d] already scaled; k, v [B, S, d] views with unit column stride and
     common strides (column slabs of the cache rows [B, capacity, 2d]); key_valid [B, S] bool/uint8 view (True = attend).  Returns [B, d]
     (`out`, a dense [B, d] tensor of q's dtype, when given: a refused call leaves it as it was).
-    A sample with no valid key attends uniformly over its S keys.  Forward only; GPU only."""
+    A sample with no valid key attends uniformly over its S keys.  Forward only; GPU only.
+    Grouped-query attention (num_kv_heads = Hkv < num_heads = H, Hkv a divisor of H): k, v [B, S, Hkv*D] with D = d / H -- column
+    slabs of cache rows [B, capacity, 2*Hkv*D] -- and query head h reads key / value head h // (H / Hkv) (mmgl_attn_decode_gqa_fwd:
+    one read of a cached key serves the H / Hkv query heads of its group; nothing is expanded)."""
     require_cuda(q, k, v, key_valid)
     _no_grad_inputs("attn_decode", q, k, v)
-    if (q.dim() != 2 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[1] != k.shape[2] or k.stride() != v.stride()
+    Hkv = _kv_heads("attn_decode", num_heads, num_kv_heads)
+    kd = q.shape[-1] if Hkv is None or q.shape[-1] % num_heads else q.shape[-1] // num_heads * Hkv     # columns of a key row
+    if (q.dim() != 2 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or kd != k.shape[2] or k.stride() != v.stride()
             or k.stride(2) != 1 or q.stride(1) != 1 or k.dtype != q.dtype or v.dtype != q.dtype):
-        raise ValueError(f"attn_decode: incompatible q{tuple(q.shape)} k{tuple(k.shape)}/{k.stride()} v{tuple(v.shape)}/{v.stride()}")
+        raise ValueError(f"attn_decode: incompatible q{tuple(q.shape)} k{tuple(k.shape)}/{k.stride()} v{tuple(v.shape)}/{v.stride()}"
+                         + ("" if Hkv is None else f" for H={num_heads}, Hkv={Hkv}"))
     B, d = q.shape
     S = k.shape[1]
     if d % num_heads:
@@ -1637,6 +1643,36 @@ def attn_decode(q, k, v, key_valid, num_heads, out=None):
         out = torch.empty(B, d, dtype=q.dtype, device=q.device)
     elif tuple(out.shape) != (B, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
         raise ValueError(f"attn_decode: out{tuple(out.shape)} {out.dtype} must be a dense [{B}, {d}] {q.dtype} tensor on {q.device}")
-    _lib.call("mmgl_attn_decode_fwd", dict(bytes=2.0 * B * S * d * q.element_size()), ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(1), k.stride(0),
-              ptr(key_valid), key_valid.stride(0), ptr(out), B, num_heads, S, d // num_heads, dtype_code(q), stream_ptr())
+    if Hkv is None:
+        _lib.call("mmgl_attn_decode_fwd", dict(bytes=2.0 * B * S * d * q.element_size()), ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(1), k.stride(0),
+                  ptr(key_valid), key_valid.stride(0), ptr(out), B, num_heads, S, d // num_heads, dtype_code(q), stream_ptr())
+    else:
+        _lib.call("mmgl_attn_decode_gqa_fwd", dict(bytes=2.0 * B * S * kd * q.element_size()), ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(1),
+                  k.stride(0), ptr(key_valid), key_valid.stride(0), ptr(out), B, num_heads, Hkv, S, d // num_heads, dtype_code(q), stream_ptr())
     return out
+
+
+def rope_kv_append(qkv, cos_sin_row, kv_col, num_heads, num_kv_heads):
+    """The new token's row of the fused q | k | v projection, qkv [B, (H + 2*Hkv)*D] (unit column stride), at one position:
+    rotates the H query heads in place and writes the rotated Hkv key heads and the unrotated Hkv value heads to kv_col
+    [B, 2*Hkv*D] -- the token's column of the cache rows, a strided view with unit column stride; the k and v blocks of qkv stay as
+    they were.  cos_sin_row: fp32 [D/2, 2], the position's row of the table rope_qk_ takes (rotate_half convention).  One launch.
+    Returns qkv.  A refused call leaves qkv and kv_col untouched.  Forward only; GPU only."""
+    require_cuda(qkv, cos_sin_row, kv_col)
+    _no_grad_inputs("rope_kv_append", qkv, kv_col)
+    H, Hkv = int(num_heads), int(num_kv_heads)
+    if H < 1 or Hkv < 1 or H % Hkv:
+        raise ValueError(f"rope_kv_append: num_heads = {H} must be a multiple of num_kv_heads = {Hkv}")
+    if qkv.dim() != 2 or qkv.shape[1] % (H + 2 * Hkv) or qkv.stride(1) != 1:
+        raise ValueError(f"rope_kv_append: qkv{tuple(qkv.shape)}/{qkv.stride()} is not [B, (H+2*Hkv)*D] for H={H}, Hkv={Hkv}")
+    B, D = qkv.shape[0], qkv.shape[1] // (H + 2 * Hkv)
+    if (tuple(kv_col.shape) != (B, 2 * Hkv * D) or kv_col.stride(1) != 1 or kv_col.dtype != qkv.dtype or kv_col.device != qkv.device):
+        raise ValueError(f"rope_kv_append: kv_col{tuple(kv_col.shape)}/{kv_col.stride()} {kv_col.dtype} must be a [{B}, {2 * Hkv * D}] "
+                         f"{qkv.dtype} view with unit column stride")
+    if cos_sin_row.dtype != torch.float32 or tuple(cos_sin_row.shape) != (D // 2, 2) or not cos_sin_row.is_contiguous():
+        raise ValueError(f"rope_kv_append: cos_sin_row must be contiguous fp32 [D/2={D // 2}, 2], got {cos_sin_row.dtype} {tuple(cos_sin_row.shape)}")
+    if B == 0:
+        return qkv
+    _lib.call("mmgl_rope_kv_append", dict(bytes=float(2 * H + 4 * Hkv) * B * D * qkv.element_size()), ptr(qkv), qkv.stride(0), ptr(cos_sin_row),
+              ptr(kv_col), kv_col.stride(0), B, H, Hkv, D, dtype_code(qkv), stream_ptr())
+    return qkv
