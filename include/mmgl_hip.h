@@ -463,6 +463,64 @@ int mmgl_attn_decode_gqa_fwd(const void* q, int ldq, const void* k, const void* 
 int mmgl_rope_kv_append(void* qkv, int ldqkv, const float* cos_sin_row, void* kv_col, size_t batch_stride_kv, int B, int H, int Hkv,
                         int D, int dtype, void* stream);
 
+/* Beam search on a beam-shared key/value cache (generate(num_beams = W), 1 <= W <= 8; csrc/decode.hip, csrc/beam.hip).
+ * replaces: HuggingFace generate(num_beams=W) behind the reference's test protocol (language_modelling/run_generation.py:597-603),
+ *   which repeats the prompt W times and reorders whole cache rows at every step.  Forward only; deterministic (no atomics).
+ *
+ * mmgl_attn_decode_beam_fwd: single-query attention for the R = B*W rows of a beam step; row b*W + w is beam slot w of sample b.
+ *   q, out      [B*W, H*D] (q: row stride ldq, already scaled by D^-0.5; out dense)
+ *   k_pre,v_pre S_pre >= 1 rows of H*D per SAMPLE, row stride ld_pre, sample stride batch_stride_pre (elements), and
+ *   key_valid   [B, S_pre] uint8, row stride ld_valid: exactly the k / v / key_valid of mmgl_attn_decode_fwd -- the prompt's cache
+ *               rows [B, T, 2 H D] or the projected neighbor tokens.  Read once per (sample, head) and scored against the W queries.
+ *   k_tail,v_tail column slabs of the tail buffer [B*W, n_cap, 2 H D]: column stride ld_tail, row stride row_stride_tail (elements);
+ *               n_tail >= 0 columns are in use.  The keys the hypotheses generated themselves; always valid.
+ *   src         int32 [B*W, n_cap], row stride ld_src: tail key j of row (b, w) is row b*W + src[b*W + w][j], column j, of the
+ *               tail buffer.  Values lie in [0, W).  A table in host-visible memory is checked here (MMGL_ERR_INVALID); a device table
+ *               is the caller's contract: the kernel clamps a value into [0, W) (a wrong beam's key, never an access outside the
+ *               sample's W rows) and asserts nothing.
+ *   n_tail = 0 is the cross-attention call: k_tail, v_tail and src may be NULL.
+ *   A masked prefix key scores -FLT_MAX.  A sample whose prefix has NO valid key is uniform over all its S_pre + n_tail keys
+ *   (the tail keys then weigh as the masked ones do), so n_tail = 0 gives mmgl_attn_decode_fwd's uniform distribution.
+ *   One workgroup per (sample, head); W in {1, 2, 4, 8} instantiations, W = 3, 5, 6, 7 run the next size up with the surplus rows
+ *   computed and not stored; W > 8: MMGL_ERR_UNSUPPORTED.  D in {16,32,64,128}; strides multiples of 16 bytes; q, k_*, v_* 16-byte
+ *   aligned; a sample's prefix rows and its W tail rows each span less than 2 GiB.  fp32 softmax, partial states merged in a fixed order.
+ *
+ * mmgl_beam_topk: per sample the 2W best of its rows_in * V candidates score = beam_score[row] + (logit[row][v] - logsumexp(row)),
+ *   fp32, sorted descending; an exact tie goes to the lower flat index r*V + v (r: the row's slot in its sample).
+ *   logits      [B*rows_in, V] bf16 / fp32, row stride ld_logits (elements); rows_in = 1 (the prefill's row per sample) or W
+ *   beam_score  fp32 [B*rows_in];  cand_score fp32 [B, 2W];  cand_index int32 [B, 2W] (flat indices)
+ *   workspace   mmgl_beam_topk_workspace(B*rows_in, V, W) bytes, 4-byte aligned: per (row, chunk of 4096 logits) the chunk's
+ *               (max, sum exp) and its 2W best logits -- no [rows, V] intermediate.  Two launches.
+ *   Any V >= 2W with rows_in * ceil(V / 4096) * 2W <= 4096 candidates after the first launch (V <= 131072 at W = 8, rows_in = 8;
+ *   else MMGL_ERR_UNSUPPORTED).  Within a row candidates are ordered by logit (two logits that round to one score keep that order).
+ *
+ * mmgl_beam_advance: one launch, one wave per sample: the sorted candidates of step s become the state of step s + 1.
+ *   tokens int64 / parents int32 / beam_score fp32 [B*W]: the next running beams = the first W candidates whose token is not
+ *               eos_token_id (< 0: none), in candidate order; score copied.
+ *   src_old -> src_new (int32 [B*W, ld_src], different buffers): new[w][0..n_cols-1) = old[parent][0..n_cols-1),
+ *               new[w][n_cols-1] = parent; columns >= n_cols are not written.  n_cols = s: the tail columns the parents own.
+ *   pool_*_old -> pool_*_new ([B*W] score fp32 / len int32 / tok int64, anc int32 [B*W, ld_src]; different buffers): the finished
+ *               hypotheses of a sample, the W best sorted descending (ties: older entry first, then candidate order); len = 0 and
+ *               score = -inf mark an empty slot.  A candidate among the first W that is EOS, or any of the first W when last_step
+ *               is set, enters with score = cand_score / length_divisor (the caller passes (s + 1)^length_penalty as fp32: one IEEE
+ *               division), len = n_cols + 1, its ancestry row (old[parent][0..n_cols-1), parent) and its token -- unless the sample
+ *               is frozen: done[b] is set, or early_stopping and its pool was full before this step.
+ *   done        int32 [B]: set once the pool is full and NOT best_running_score / length_divisor > worst pooled score (the
+ *               early-stop heuristic of transformers' beam search, early_stopping in {False, True}); never cleared.
+ *   Plain vector stores only. */
+size_t mmgl_beam_topk_workspace(int rows, int V, int W);
+int mmgl_attn_decode_beam_fwd(const void* q, int ldq, const void* k_pre, const void* v_pre, int ld_pre, size_t batch_stride_pre,
+                              const uint8_t* key_valid, int ld_valid, const void* k_tail, const void* v_tail, int ld_tail,
+                              size_t row_stride_tail, const int* src, int ld_src, void* out, int B, int W, int H, int S_pre, int n_tail,
+                              int D, int dtype, void* stream);
+int mmgl_beam_topk(const void* logits, size_t ld_logits, const float* beam_score, float* cand_score, int* cand_index, void* workspace,
+                   size_t workspace_bytes, int B, int rows_in, int W, int V, int dtype, void* stream);
+int mmgl_beam_advance(const float* cand_score, const int* cand_index, int64_t* tokens, int* parents, float* beam_score,
+                      const int* src_old, int* src_new, int ld_src, const float* pool_score_old, float* pool_score_new,
+                      const int* pool_len_old, int* pool_len_new, const int* pool_anc_old, int* pool_anc_new,
+                      const int64_t* pool_tok_old, int64_t* pool_tok_new, int* done, int B, int W, int V, int n_cols, int eos_token_id,
+                      int last_step, int early_stopping, float length_divisor, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

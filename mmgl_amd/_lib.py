@@ -11,7 +11,7 @@ import torch  # imported first on purpose: the .so must bind to the HIP runtime 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMGL_LIB_PATH") or os.path.join(_HERE, "libmmgl_hip.so")     # override: timing experiments with ablated builds
 
-ABI_VERSION = 109        # = mmgl_version() of the library this binding was written against (csrc/lib.hip)
+ABI_VERSION = 110        # = mmgl_version() of the library this binding was written against (csrc/lib.hip)
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 _ERR_INVALID, _ERR_UNSUPPORTED, _ERR_HIP = 1, 2, 3
@@ -90,6 +90,10 @@ SIGNATURES = {
     "mmgl_gemm_skinny_lora": (I, [P, I, P, I, P, P, P, I, P, I, P, I, I, F, P, I, I, I, I, F, I, P]),
     "mmgl_attn_decode_gqa_fwd": (I, [P, I, P, P, I, Z, P, I, P, I, I, I, I, I, I, P]),
     "mmgl_rope_kv_append": (I, [P, I, P, P, Z, I, I, I, I, I, P]),
+    "mmgl_attn_decode_beam_fwd": (I, [P, I, P, P, I, Z, P, I, P, P, I, Z, P, I, P, I, I, I, I, I, I, I, P]),
+    "mmgl_beam_topk_workspace": (Z, [I, I, I]),
+    "mmgl_beam_topk": (I, [P, Z, P, P, P, P, Z, I, I, I, I, I, P]),
+    "mmgl_beam_advance": (I, [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P]),
 }
 
 _lib = None

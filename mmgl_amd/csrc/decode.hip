@@ -38,6 +38,10 @@
 // so each 16-byte K / V load is issued once and scored against every query head of the block from registers; G > 8 takes further blocks.
 // The keys of a sample are not split over workgroups (no flash-decoding: DESIGN.md 4.11).
 //
+// mmgl_attn_decode_beam_fwd (attn_decode_beam_kernel).  Beam search: the W <= 8 hypotheses of a sample share its prefix keys (one read,
+// W queries from registers, as the grouped-query kernel does for its group) and differ only in the few keys generated so far, which a
+// per-row int32 parent table addresses in a [B*W, n_cap, 2d] tail buffer.  No cache row is copied when the beams are reordered.
+//
 // mmgl_rope_kv_append (rope_kv_append_kernel).  The new token's q | k | v row: q rotated in place, k rotated into the token's cache column,
 // v copied there -- one launch where separate projections and rotations would take four (the step is launch-bound).
 #include "common.h"
@@ -607,6 +611,209 @@ int attn_decode_gqa_d(const void* q, int ldq, const void* k, const void* v, int 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ beam-shared single-query attention
+// One workgroup per (sample, head) serves the W <= NQ beam rows b*W + w of the sample.  Phase 1 is the loop of attn_decode_gqa_kernel
+// over the sample's S_pre shared prefix keys (the prompt's cache rows or the projected neighbor tokens): every 16-byte K / V load is
+// issued once and scored against the NQ queries from registers.  Phase 2 walks the n_tail keys the hypotheses generated themselves:
+// tail key t of row (b, w) is row b*W + src[b*W + w][t], column t, of the [B*W, n_cap, 2d] tail buffer, so reordering the beams rewrites
+// the small int32 table and never a cache row.  The same lane layout and online-softmax state run through both phases (one rescale per
+// trip: AD_UNROLL prefix keys, TAIL_UNROLL tail keys of a row), then the merge of attn_decode_kernel.  Surplus rows (w >= W) repeat row W - 1 and are not stored.  A src
+// value is clamped into [0, W): a table the caller filled wrongly reads a wrong beam's key, never memory outside the sample's rows.
+// A sample whose prefix has no valid key weighs ALL its S_pre + n_tail keys equally (the tail scores take -FLT_MAX too).
+template <typename T, int D, int NQ>
+__global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_beam_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ kp,
+                                                                           const T* __restrict__ vp, int ld_pre, size_t bs_pre,
+                                                                           const uint8_t* __restrict__ valid, int ld_valid,
+                                                                           const T* __restrict__ kt, const T* __restrict__ vt, int ld_tail,
+                                                                           size_t rs_tail, const int* __restrict__ src, int ld_src,
+                                                                           T* __restrict__ out, int W, int H, int S, int n_tail) {
+    typedef typename Vec16<T>::type V;
+    constexpr int VEC = 16 / sizeof(T);
+    constexpr int LPK = D / VEC;                    // lanes per key
+    constexpr int KPI = WAVE / LPK;                 // keys per wave and load instruction
+    constexpr float NEG = -FLT_MAX;
+    constexpr int TAIL_UNROLL = 2;                  // keys per trip of the tail: W rows of loads are in flight at once, and a tail is short
+    __shared__ float sm_m[AD_WAVES][NQ], sm_l[AD_WAVES][NQ], sm_o[AD_WAVES][NQ][D];
+
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane % LPK, kk = lane / LPK;
+    const size_t row0 = (size_t)b * W;
+
+    float qf[NQ][VEC];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const V qv = *(const V*)(q + (row0 + min(j, W - 1)) * ldq + h * D + c * VEC);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) qf[j][e] = Elem<T>::to_f(qv[e]);
+    }
+    float m[NQ], l[NQ], acc[NQ][VEC];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        m[j] = NEG;
+        l[j] = 0.f;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[j][e] = 0.f;
+    }
+    // the AD_UNROLL keys of a trip enter row j's online softmax together: one rescale of the state per trip
+    auto fold = [&](int j, const auto& kr, const auto& vr, const auto& ok, const auto& in) {
+        constexpr int U = sizeof(ok) / sizeof(bool);
+        float sc[U], mn = m[j];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) dot += qf[j][e] * Elem<T>::to_f(kr[u][e]);
+            dot = group_sum<LPK>(dot);
+            sc[u] = ok[u] ? dot : NEG;
+            if (in[u]) mn = fmaxf(mn, sc[u]);
+        }
+        const float corr = __expf(m[j] - mn);
+        float pu[U], ps = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            pu[u] = in[u] ? __expf(sc[u] - mn) : 0.f;                 // a key past the end weighs nothing, also in a row of masked keys
+            ps += pu[u];
+        }
+        l[j] = l[j] * corr + ps;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            float a = acc[j][e] * corr;
+#pragma unroll
+            for (int u = 0; u < U; ++u) a += pu[u] * Elem<T>::to_f(vr[u][e]);
+            acc[j][e] = a;
+        }
+        m[j] = mn;
+    };
+
+    // ---- phase 1: the shared prefix (branch-free loads: keys past S fall outside the descriptors)
+    bool any_ok = false;
+    {
+        const uint32_t slab = (uint32_t)(((size_t)(S - 1) * ld_pre + D) * sizeof(T)), row_bytes = (uint32_t)(ld_pre * sizeof(T));
+        const __amdgpu_buffer_rsrc_t rk = make_rsrc(kp + b * bs_pre + h * D, slab);
+        const __amdgpu_buffer_rsrc_t rv = make_rsrc(vp + b * bs_pre + h * D, slab);
+        const uint8_t* mb = valid + (size_t)b * ld_valid;
+        for (int base = w * KPI; base < S; base += AD_WAVES * KPI * AD_UNROLL) {          // wave-uniform trip count
+            V kr[AD_UNROLL], vr[AD_UNROLL];
+            bool ok[AD_UNROLL], in[AD_UNROLL];
+#pragma unroll
+            for (int u = 0; u < AD_UNROLL; ++u) {
+                const int s = base + u * AD_WAVES * KPI + kk;
+                in[u] = s < S;
+                const uint32_t off = in[u] ? (uint32_t)s * row_bytes + (uint32_t)(c * 16) : OOB;
+                kr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+                vr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+                ok[u] = mb[min(s, S - 1)] != 0;
+                any_ok |= in[u] && ok[u];
+            }
+#pragma unroll
+            for (int j = 0; j < NQ; ++j) fold(j, kr, vr, ok, in);
+        }
+    }
+    // ---- phase 2: the per-beam tail, addressed through src
+    if (n_tail > 0) {
+        const bool live = __syncthreads_or(any_ok) != 0;           // some prefix key of the sample is valid (uniform over the workgroup)
+        const uint32_t span = (uint32_t)(((size_t)(W - 1) * rs_tail + (size_t)(n_tail - 1) * ld_tail + D) * sizeof(T));
+        const uint32_t col_bytes = (uint32_t)(ld_tail * sizeof(T)), beam_bytes = (uint32_t)(rs_tail * sizeof(T));
+        const __amdgpu_buffer_rsrc_t rk = make_rsrc(kt + row0 * rs_tail + h * D, span);
+        const __amdgpu_buffer_rsrc_t rv = make_rsrc(vt + row0 * rs_tail + h * D, span);
+        for (int base = w * KPI; base < n_tail; base += AD_WAVES * KPI * TAIL_UNROLL) {     // wave-uniform trip count
+            int from[NQ][TAIL_UNROLL];
+#pragma unroll
+            for (int j = 0; j < NQ; ++j) {
+                const int* sr = src + (row0 + min(j, W - 1)) * ld_src;
+#pragma unroll
+                for (int u = 0; u < TAIL_UNROLL; ++u) from[j][u] = sr[min(base + u * AD_WAVES * KPI + kk, n_tail - 1)];
+            }
+#pragma unroll
+            for (int j = 0; j < NQ; ++j) {
+                V kr[TAIL_UNROLL], vr[TAIL_UNROLL];
+                bool ok[TAIL_UNROLL], in[TAIL_UNROLL];
+#pragma unroll
+                for (int u = 0; u < TAIL_UNROLL; ++u) {
+                    const int t = base + u * AD_WAVES * KPI + kk;
+                    in[u] = t < n_tail;
+                    ok[u] = live;
+                    const uint32_t beam = (uint32_t)min(max(from[j][u], 0), W - 1);
+                    const uint32_t off = in[u] ? beam * beam_bytes + (uint32_t)t * col_bytes + (uint32_t)(c * 16) : OOB;
+                    kr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+                    vr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+                }
+                fold(j, kr, vr, ok, in);
+            }
+        }
+    }
+    // per beam row: merge the lane groups of the wave (fixed butterfly), then the waves in order
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+#pragma unroll
+        for (int o = LPK; o < WAVE; o <<= 1) {
+            const float m2 = __shfl_xor(m[j], o), l2 = __shfl_xor(l[j], o);
+            const float mn = fmaxf(m[j], m2);
+            const float c1 = __expf(m[j] - mn), c2 = __expf(m2 - mn);
+            l[j] = l[j] * c1 + l2 * c2;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[j][e] = acc[j][e] * c1 + __shfl_xor(acc[j][e], o) * c2;
+            m[j] = mn;
+        }
+        if (lane < LPK) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) sm_o[w][j][c * VEC + e] = acc[j][e];
+            if (lane == 0) { sm_m[w][j] = m[j]; sm_l[w][j] = l[j]; }
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < W * D; idx += AD_WAVES * WAVE) {
+        const int j = idx / D, x = idx % D;
+        float mm = sm_m[0][j];
+#pragma unroll
+        for (int i = 1; i < AD_WAVES; ++i) mm = fmaxf(mm, sm_m[i][j]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int i = 0; i < AD_WAVES; ++i) {
+            const float ci = __expf(sm_m[i][j] - mm);
+            ll += sm_l[i][j] * ci;
+            o += sm_o[i][j][x] * ci;
+        }
+        out[((row0 + j) * H + h) * D + x] = Elem<T>::from_f(o / ll);
+    }
+}
+
+struct BeamAttnArgs {
+    const void *q, *kp, *vp, *kt, *vt;
+    const uint8_t* valid;
+    const int* src;
+    void* out;
+    int ldq, ld_pre, ld_valid, ld_tail, ld_src, B, W, H, S, n_tail;
+    size_t bs_pre, rs_tail;
+};
+
+template <typename T, int D>
+int attn_decode_beam_nq(const BeamAttnArgs& a, hipStream_t st) {
+    const dim3 grid(a.B * a.H), block(AD_WAVES * WAVE);
+#define MMGL_BEAM_DECODE(NQ)                                                                                                            \
+    hipLaunchKernelGGL((attn_decode_beam_kernel<T, D, NQ>), grid, block, 0, st, (const T*)a.q, a.ldq, (const T*)a.kp, (const T*)a.vp,  \
+                       a.ld_pre, a.bs_pre, a.valid, a.ld_valid, (const T*)a.kt, (const T*)a.vt, a.ld_tail, a.rs_tail, a.src, a.ld_src, \
+                       (T*)a.out, a.W, a.H, a.S, a.n_tail)
+    if (a.W == 1) MMGL_BEAM_DECODE(1);
+    else if (a.W == 2) MMGL_BEAM_DECODE(2);
+    else if (a.W <= 4) MMGL_BEAM_DECODE(4);
+    else MMGL_BEAM_DECODE(8);
+#undef MMGL_BEAM_DECODE
+    MMGL_CHECK_LAUNCH("mmgl_attn_decode_beam_fwd");
+    return MMGL_OK;
+}
+
+template <typename T>
+int attn_decode_beam_d(const BeamAttnArgs& a, int D, hipStream_t st) {
+    switch (D) {
+        case 16: return attn_decode_beam_nq<T, 16>(a, st);
+        case 32: return attn_decode_beam_nq<T, 32>(a, st);
+        case 64: return attn_decode_beam_nq<T, 64>(a, st);
+        default: return attn_decode_beam_nq<T, 128>(a, st);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ rotary embedding of one new token
 // qkv [B, ldqkv] = [q: H heads | k: Hkv | v: Hkv] x D of the new token; cs [D/2] float2 (cos, sin) of its position.  One thread = VN
 // consecutive i of one (sample, head): the pair (i, i + D/2) of a q head is rotated in place, that of a k head is rotated into the
@@ -730,6 +937,53 @@ extern "C" int mmgl_attn_decode_gqa_fwd(const void* q, int ldq, const void* k, c
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MMGL_BF16) return attn_decode_gqa_d<bf16>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, Hkv, S, D, st);
     return attn_decode_gqa_d<float>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, Hkv, S, D, st);
+}
+
+extern "C" int mmgl_attn_decode_beam_fwd(const void* q, int ldq, const void* k_pre, const void* v_pre, int ld_pre, size_t batch_stride_pre,
+                                         const uint8_t* key_valid, int ld_valid, const void* k_tail, const void* v_tail, int ld_tail,
+                                         size_t row_stride_tail, const int* src, int ld_src, void* out, int B, int W, int H, int S_pre,
+                                         int n_tail, int D, int dtype, void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && W >= 1 && H >= 1 && S_pre >= 1 && n_tail >= 0, "mmgl_attn_decode_beam_fwd: bad sizes B=%d W=%d H=%d S_pre=%d n_tail=%d",
+                   B, W, H, S_pre, n_tail);
+    if (W > 8) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: %d beams per sample (1..8)", W);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_attn_decode_beam_fwd: bad dtype %d", dtype);
+    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: head_dim %d (16, 32, 64, 128)", D);
+    const int vec = dtype == MMGL_BF16 ? 8 : 4, esz = dtype == MMGL_BF16 ? 2 : 4;
+    if (ldq % vec || ld_pre % vec || batch_stride_pre % vec)
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: strides (%d, %d, %zu) must be multiples of 16 bytes", ldq, ld_pre, batch_stride_pre);
+    MMGL_CHECK_ARG(q && k_pre && v_pre && key_valid && out, "mmgl_attn_decode_beam_fwd: null pointer");
+    MMGL_CHECK_ARG(ldq >= H * D && ld_pre >= H * D && ld_valid >= S_pre, "mmgl_attn_decode_beam_fwd: strides (%d, %d, %d) smaller than the rows", ldq,
+                   ld_pre, ld_valid);
+    if (!aligned16(q) || !aligned16(k_pre) || !aligned16(v_pre))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: q, k_pre and v_pre must be 16-byte aligned");
+    if (((size_t)(S_pre - 1) * ld_pre + D) * esz >= (1ull << 31))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: a sample's prefix rows span 2 GiB or more (S_pre=%d, ld_pre=%d)", S_pre, ld_pre);
+    if (n_tail > 0) {
+        MMGL_CHECK_ARG(k_tail && v_tail && src, "mmgl_attn_decode_beam_fwd: null tail pointer with n_tail=%d", n_tail);
+        if (ld_tail % vec || row_stride_tail % vec || !aligned16(k_tail) || !aligned16(v_tail) || ((uintptr_t)src & 3))
+            MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: tail strides (%d, %zu) must be multiples of 16 bytes, k_tail and v_tail 16-byte "
+                                            "aligned, src 4-byte", ld_tail, row_stride_tail);
+        MMGL_CHECK_ARG(ld_tail >= H * D && ld_src >= n_tail && (B * W == 1 || row_stride_tail >= (size_t)(n_tail - 1) * ld_tail + (size_t)H * D),
+                       "mmgl_attn_decode_beam_fwd: tail strides (%d, %zu, %d) smaller than the rows", ld_tail, row_stride_tail, ld_src);
+        if (((size_t)(W - 1) * row_stride_tail + (size_t)(n_tail - 1) * ld_tail + D) * esz >= (1ull << 31))
+            MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: a sample's tail rows span 2 GiB or more (W=%d, row stride %zu)", W, row_stride_tail);
+        // a table the host can read is checked here; a device table is the caller's contract (the kernel clamps, it never asserts)
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, src) != hipSuccess) (void)hipGetLastError();
+        else if (attr.type == hipMemoryTypeHost && attr.hostPointer) {
+            const int* hs = (const int*)attr.hostPointer;
+            for (int r = 0; r < B * W; ++r)
+                for (int t = 0; t < n_tail; ++t) {
+                    const int sv = hs[(size_t)r * ld_src + t];
+                    MMGL_CHECK_ARG(sv >= 0 && sv < W, "mmgl_attn_decode_beam_fwd: src[%d][%d] = %d outside [0, %d)", r, t, sv, W);
+                }
+        }
+    }
+    const BeamAttnArgs a{q, k_pre, v_pre, k_tail, v_tail, key_valid, src, out, ldq, ld_pre, ld_valid, ld_tail, ld_src, B, W, H, S_pre, n_tail,
+                         batch_stride_pre, row_stride_tail};
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_BF16) return attn_decode_beam_d<bf16>(a, D, st);
+    return attn_decode_beam_d<float>(a, D, st);
 }
 
 extern "C" int mmgl_rope_kv_append(void* qkv, int ldqkv, const float* cos_sin_row, void* kv_col, size_t batch_stride_kv, int B, int H, int Hkv,

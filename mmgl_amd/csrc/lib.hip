@@ -73,4 +73,5 @@ int mmgl_num_cu() {
 // 107: mmgl_gemm_skinny_lora (the decode step of a LoRA-adapted projection).
 // 108: mmgl_selfattn_gqa_fwd / _bwd_workspace / _bwd (grouped-query self-attention of the Llama family).
 // 109: mmgl_attn_decode_gqa_fwd / mmgl_rope_kv_append (the decode step of the Llama-family LM: grouped-query cache, rotary at one position).
-extern "C" int mmgl_version(void) { return 109; }
+// 110: mmgl_attn_decode_beam_fwd / mmgl_beam_topk(_workspace) / mmgl_beam_advance (beam search on a beam-shared cache).
+extern "C" int mmgl_version(void) { return 110; }

@@ -39,7 +39,7 @@ def _f(default, help_):
 
 @dataclass
 class Arguments:
-    """Same field names and defaults as the reference's Arguments (:66-229) + `neighbor_layer_wise`."""
+    """Same field names and defaults as the reference's Arguments (:66-229) + `neighbor_layer_wise` + `num_beams`."""
     overwrite_cache: Optional[bool] = _f(False, "Overwrite the cached preprocessed datasets or not.")
     dataset: Optional[str] = _f("wikiweb2m", "The name of the dataset to use.")
     task: Optional[str] = _f("section", "One of three generation tasks in WikiWeb2M")
@@ -95,6 +95,8 @@ class Arguments:
     num_neighbor_layers: int = _f(4, "number of cross-attention layers to encode neighbor information")
     neighbor_layer_wise: Optional[int] = _f(None, "insert a cross-attention layer after every this-many LM layers "
                                                   "(default: num_hidden_layers // num_neighbor_layers)")
+    num_beams: int = _f(1, "beams of the test protocol's generate(): 1 = greedy (the default), 2..8 = beam search (OPT fork, "
+                           "cross-attention wrapper)")
     peft_type: str = _f("none", "peft type: none, prefix, prompt, lora, flamingo")
     lora_r: int = _f(64, "lora row rank")
     lora_alpha: float = _f(1, "lora scaling factor")
@@ -618,6 +620,8 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                 L_in = args.max_input_length
                 named = inspect.signature(getattr(type(model), "generate", model.generate)).parameters     # the class's own signature
                 fields = {key: batch[key] for key in _GENERATE_FIELDS if key in batch and key in named}    # generate()'s named arguments only
+                if getattr(args, "num_beams", 1) > 1:                   # beam search (CrossAttentionModel); the default stays greedy
+                    fields["num_beams"] = int(args.num_beams)
                 generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),
                                                attention_mask=batch["attention_mask"][:, :L_in].contiguous(), **fields,
                                                host_meta=extra.get("host_meta"), max_new_tokens=32,

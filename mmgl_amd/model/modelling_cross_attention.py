@@ -304,12 +304,29 @@ class MPTAttention(nn.Module):
             return mod.decode(x, out_scale=out_scale, out=out)
         raise ValueError("the decode step runs plain nn.Linear projections only (adapted projections, e.g. LoRA, have no decode path)")
 
-    def decode_self(self, x, kv, key_mask, col):
+    def decode_self(self, x, kv, key_mask, col, beam=None, tail=None):
         """x [B, d]: the new token's layer input.  Projects q and writes k|v into column `col` of the layer's cache rows kv
         [B, capacity, 2d], then attends over columns 0..col (all at or before the query: no causal test).  q_proj and v_proj may be
-        LoRA-adapted (any other adapter type, and an adapted k_proj / out_proj, is refused)."""
+        LoRA-adapted (any other adapter type, and an adapted k_proj / out_proj, is refused).
+        beam (a BeamState) with the layer's tail buffer [B*W, n_cap, 2d]: x [B*W, d]; k|v go into column beam.n_tail of `tail`, and
+        the rows attend over the sample's `col` prompt columns of kv (shared, never copied) plus their own n_tail + 1 tail keys,
+        addressed through beam.book.src (ops.attn_decode_beam).  Plain nn.Linear projections only."""
         d = self.embed_dim
         self._plain(self.k_proj, self.out_proj)
+        if beam is not None:
+            self._plain(self.q_proj, self.v_proj)
+            j = beam.n_tail
+            fused = self._frozen_qkv()
+            if fused is not None:
+                w, b = fused
+                q = ops.decode_linear(x, w[:d], b[:d])
+                ops.decode_linear(x, w[d:], b[d:], out=tail[:, j])
+            else:
+                q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
+                ops.decode_linear(x, self.k_proj.weight, self.k_proj.bias, out=tail[:, j, :d])
+                ops.decode_linear(x, self.v_proj.weight, self.v_proj.bias, out=tail[:, j, d:])
+            return ops.attn_decode_beam(q, kv[:, :col, :d], kv[:, :col, d:], key_mask[:, :col], self.num_heads, beam.W,
+                                        tail[:, :j + 1, :d], tail[:, :j + 1, d:], beam.book.src)
         fused = self._frozen_qkv()
         if fused is not None:
             w, b = fused
@@ -321,9 +338,11 @@ class MPTAttention(nn.Module):
             self._decode_proj(self.v_proj, x, out=kv[:, col, d:])
         return ops.attn_decode(q, kv[:, :col + 1, :d], kv[:, :col + 1, d:], key_mask[:, :col + 1], self.num_heads)
 
-    def decode_cross(self, x, k, v, key_valid):
+    def decode_cross(self, x, k, v, key_valid, beam=None):
         self._plain(self.q_proj, self.out_proj)
         q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
+        if beam is not None:                  # the W beams of a sample read its neighbor tokens once: k, v stay at B rows
+            return ops.attn_decode_beam(q, k, v, key_valid, self.num_heads, beam.W)
         return ops.attn_decode(q, k, v, key_valid, self.num_heads)
 
 
@@ -463,7 +482,8 @@ class MPTDecoderLayer(nn.Module):
     def decode_step(self, h, cache, idx):
         """The layer on the one new token of a decode step, h [B, d]: the existing LayerNorm / gated-residual kernels at M = B,
         ops.decode_linear for every projection (residual adds in the GEMM epilogue of the frozen layers) and ops.attn_decode over
-        the cache -- layer idx's K|V rows (frozen layer) or neighbor layer idx's projected neighbor tokens (gated layer)."""
+        the cache -- layer idx's K|V rows (frozen layer) or neighbor layer idx's projected neighbor tokens (gated layer).
+        With cache.beam set h is [B*W, d]: the same kernels at M = B*W rows, the attention through ops.attn_decode_beam."""
         pre = self.do_layer_norm_before
         attn = self.self_attn
         ln1, ln2 = self.self_attn_layer_norm, self.final_layer_norm
@@ -473,7 +493,7 @@ class MPTDecoderLayer(nn.Module):
         if self.cross_attention:
             gated = self.peft_type == "flamingo"
             k, v = cache.cross[idx]
-            a = attn.decode_cross(x, k, v, cache.cross_valid)
+            a = attn.decode_cross(x, k, v, cache.cross_valid, cache.beam)
             a = ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias)
             h = ops.gated_residual(h, a, self.gating1 if gated else None, 0.0, False)
             if not pre:
@@ -482,7 +502,8 @@ class MPTDecoderLayer(nn.Module):
             x = ops.decode_linear(self._decode_ffn(x), self.fc2.weight, self.fc2.bias)
             h = ops.gated_residual(h, x, self.gating2 if gated else None, 0.0, False)
             return h if pre else self._ln(ln2, h)
-        a = attn.decode_self(x, cache.kv[idx], cache.mask, cache.col)
+        beam = cache.beam
+        a = attn.decode_self(x, cache.kv[idx], cache.mask, cache.col, beam, None if beam is None else beam.tail[idx])
         h = ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias, residual=h)
         if not pre:
             h = self._ln(ln1, h)
@@ -498,7 +519,9 @@ class DecodeCache:
       cross       per gated layer the neighbor tokens' (k_proj, v_proj) outputs [B, S, d], projected once at prefill; cross_valid their [B, S] mask
       mask        the running [B, capacity] uint8 key mask: the prompt's attention mask (pad keys stay masked), then 1 per new token
       col         the column the next token is written to -- the same for every sample (prompts are right-padded to a common width)
-      next_pos    [B] position id of the next token, counted from the mask as HF does (valid tokens so far + OPT's offset 2)"""
+      next_pos    [B] position id of the next token, counted from the mask as HF does (valid tokens so far + OPT's offset 2)
+      beam        None (greedy), or the BeamState of a beam search: then kv / mask / cross / cross_valid / next_pos stay at B rows --
+                  the prompt is prefilled once per sample and col stays at the prompt width -- and the decode steps run B*W rows"""
 
     def __init__(self, num_layers, batch_size, capacity, hidden_size, dtype, device):
         self.capacity = int(capacity)
@@ -508,6 +531,24 @@ class DecodeCache:
         self.cross_valid = None
         self.col = 0
         self.next_pos = None
+        self.beam = None
+
+
+class BeamState:
+    """What a beam search adds to a prefilled DecodeCache (cache.beam): W hypotheses per sample that share the sample's cache rows.
+      tail    per frozen layer one [B*W, n_cap, 2d] buffer of the keys | values the hypotheses generated themselves: decode step j
+              writes column j of row b*W + w in place (the k|v projection's ldy), as a greedy step writes its cache column
+      book    ops.BeamBook: the running beams, the two parent tables that say which tail row holds a hypothesis' key of step j
+              (reordering the beams rewrites these few int32, never a cache row) and the pool of finished hypotheses
+      n_tail  tail columns filled so far = decode steps done"""
+
+    def __init__(self, cache, num_beams, n_cap):
+        B, _, two_d = cache.kv[0].shape
+        self.W = int(num_beams)
+        self.n_cap = max(int(n_cap), 1)
+        self.tail = [torch.empty(B * self.W, self.n_cap, two_d, dtype=kv.dtype, device=kv.device) for kv in cache.kv]
+        self.book = ops.BeamBook(B, self.W, self.n_cap, cache.mask.device)
+        self.n_tail = 0
 
 
 class MPTPreTrainedModel(nn.Module):
@@ -724,11 +765,18 @@ class MPTDecoder(MPTPreTrainedModel):
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You have to specify either decoder_input_ids or decoder_inputs_embeds")
         shape = input_ids.shape if input_ids is not None else inputs_embeds.shape[:2]
-        if len(shape) != 2 or shape[1] != 1 or shape[0] != cache.mask.shape[0]:
-            raise ValueError(f"a decode step takes one new token per cached sample ([{cache.mask.shape[0]}, 1]), got {tuple(shape)}")
+        beam = cache.beam
+        rows = cache.mask.shape[0] * (1 if beam is None else beam.W)
+        if len(shape) != 2 or shape[1] != 1 or shape[0] != rows:
+            raise ValueError(f"a decode step takes one new token per cached " + ("sample" if beam is None else "beam")
+                             + f" ([{rows}, 1]), got {tuple(shape)}")
         if cache.next_pos is None:
             raise ValueError("the DecodeCache has not been filled: run the prompt with use_cache=True first")
-        if cache.col >= cache.capacity or cache.col >= self.max_target_positions:
+        if beam is not None:
+            if beam.n_tail >= beam.n_cap or cache.col + beam.n_tail >= self.max_target_positions:
+                raise ValueError(f"beam tail is full: column {beam.n_tail} of capacity {beam.n_cap} behind {cache.col} prompt columns "
+                                 f"(max_position_embeddings {self.max_target_positions})")
+        elif cache.col >= cache.capacity or cache.col >= self.max_target_positions:
             raise ValueError(f"decode cache is full: column {cache.col} of capacity {cache.capacity} "
                              f"(max_position_embeddings {self.max_target_positions})")
         ops.require_cuda(cache.mask, input_ids, inputs_embeds)
@@ -736,8 +784,10 @@ class MPTDecoder(MPTPreTrainedModel):
             emb = self.embed_tokens(input_ids[:, 0]) if inputs_embeds is None else inputs_embeds[:, 0]
             if self.project_in is not None:
                 emb = ops.decode_linear(emb.contiguous(), self.project_in.weight, self.project_in.bias)
-            h = emb + F.embedding(cache.next_pos, self.embed_positions.weight)
-            cache.mask[:, cache.col] = 1
+            pos = cache.next_pos if beam is None else cache.next_pos.repeat_interleave(beam.W)      # the beams of a sample share it
+            h = emb + F.embedding(pos, self.embed_positions.weight)
+            if beam is None:
+                cache.mask[:, cache.col] = 1
             all_hidden_states = () if output_hidden_states else None
             for idx, layer in enumerate(self.layers):
                 if output_hidden_states:
@@ -751,7 +801,10 @@ class MPTDecoder(MPTPreTrainedModel):
                 h = ops.layer_norm(h, fln.weight, fln.bias, fln.eps)
             if self.project_out is not None:
                 h = ops.decode_linear(h, self.project_out.weight, self.project_out.bias)
-            cache.col += 1
+            if beam is None:
+                cache.col += 1
+            else:
+                beam.n_tail += 1
             cache.next_pos = cache.next_pos + 1
         h = h[:, None]
         if output_hidden_states:
@@ -906,7 +959,9 @@ class MPTForCausalLM(MPTPreTrainedModel):
 
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
-                 eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, inputs_embeds=None):
+                 eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, inputs_embeds=None,
+                 num_beams=1, length_penalty=1.0, early_stopping=False, return_sequences_scores=False, return_beam_trace=False,
+                 num_return_sequences=1):
         """Greedy decoding (do_sample=False, one beam) with a key/value cache: what the reference's test protocol asks of its
         wrappers (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of
         every layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
@@ -919,7 +974,27 @@ class MPTForCausalLM(MPTPreTrainedModel):
         were picked from.
         inputs_embeds [B, T, d_embed] instead of input_ids (exactly one of the two): the prefill runs on the embeddings (virtual
         tokens, image or neighbor tokens already in the sequence); there are no prompt ids to repeat, so only the new tokens
-        [B, max_new_tokens] come back (HF's convention for inputs_embeds)."""
+        [B, max_new_tokens] come back (HF's convention for inputs_embeds).
+        num_beams = W > 1 (at most 8): beam search with the semantics of transformers' generate(num_beams=W, do_sample=False,
+        length_penalty, early_stopping in {False, True}) -- see _generate_beam; num_beams = 1 is the greedy path above, untouched."""
+        W = int(num_beams)
+        if W < 1:
+            raise ValueError(f"generate(): num_beams = {num_beams} must be positive")
+        if num_return_sequences != 1:
+            raise ValueError(f"generate(): num_return_sequences = {num_return_sequences} is not implemented (the best hypothesis per sample "
+                             "is returned)")
+        if early_stopping not in (True, False):
+            raise ValueError(f"generate(): early_stopping = {early_stopping!r} is not implemented (True or False)")
+        if W > 1:
+            if inputs_embeds is not None:
+                raise ValueError("generate(): beam search (num_beams > 1) takes input_ids prompts, not inputs_embeds")
+            if return_step_logits:
+                raise ValueError("generate(): return_step_logits belongs to the greedy path; beam search has return_beam_trace")
+            return self._generate_beam(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
+                                       pad_token_id, first_key_valid, W, float(length_penalty), bool(early_stopping),
+                                       return_sequences_scores, return_beam_trace)
+        if return_sequences_scores or return_beam_trace:
+            raise ValueError("generate(): return_sequences_scores / return_beam_trace belong to beam search (num_beams > 1)")
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("generate() takes exactly one of input_ids and inputs_embeds")
         prompt = input_ids if input_ids is not None else inputs_embeds
@@ -963,6 +1038,79 @@ class MPTForCausalLM(MPTPreTrainedModel):
             if s + 1 < n_new:
                 hidden = dec(input_ids=tok[:, None], past_key_values=cache).last_hidden_state[:, 0]
         return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
+
+    def _generate_beam(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
+                       pad_token_id, first_key_valid, W, length_penalty, early_stopping, return_scores, return_trace):
+        """Beam search, W hypotheses per sample on ONE copy of the sample's cache.  The unchanged prefill runs once
+        with B rows; its last-row logits seed the W beams (rows_in = 1 of ops.beam_topk, in place of HF's -1e9 start scores).  Every
+        later step runs the decode kernels at M = B*W rows: the prompt keys and the neighbor tokens are read once per sample and
+        scored against its W queries, the keys generated so far live in a [B*W, max_new_tokens - 1, 2d] tail per layer that a parent
+        table addresses (ops.attn_decode_beam) -- reordering hypotheses rewrites that table, no cache row moves.  Per step
+        ops.beam_topk (two launches) picks each sample's 2W best continuations and ops.beam_advance (one launch) turns them into the
+        next tokens, parents, running scores, table and pool of finished hypotheses; nothing synchronises with the host.
+        Semantics of transformers' beam search: the first W non-EOS candidates run on; an EOS candidate among the first W (every one
+        of them at the last step) enters the pool with score = log-prob sum / generated_length ** length_penalty; a sample is frozen
+        once its pool is full under early_stopping=True or the early-stop heuristic is met.  All max_new_tokens steps run.
+        Returns ids [B, T + max_new_tokens] -- the best pooled hypothesis, pad_token_id behind its last token -- then, as asked,
+        sequences_scores fp32 [B] and the trace: per step a dict of the running beams' parents / tokens / scores [B, W] and the 2W
+        candidates cand_index / cand_score [B, 2W]."""
+        if input_ids is None or input_ids.dim() != 2:
+            raise ValueError("generate(): beam search takes input_ids [B, T]")
+        if not input_ids.is_cuda:
+            raise RuntimeError(f"generate() runs on the GPU only (the prompt is on {input_ids.device}); there is no CPU path")
+        if W > ops.MAX_BEAMS:
+            raise ValueError(f"generate(): num_beams = {W} (1..{ops.MAX_BEAMS})")
+        B, T = input_ids.shape
+        n_new = int(max_new_tokens)
+        if n_new < 1:
+            raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
+        dec = self.model.decoder
+        if T + n_new - 1 > dec.max_target_positions:
+            raise ValueError(f"generate(): {T} prompt columns + {n_new} new tokens exceed max_position_embeddings {dec.max_target_positions}")
+        if pad_token_id is None:
+            pad_token_id = self.config.pad_token_id
+            if pad_token_id is None:
+                if eos_token_id is not None:
+                    raise ValueError("generate(): eos_token_id needs a pad_token_id")
+                pad_token_id = 0                                   # without EOS every hypothesis has all max_new_tokens tokens
+        dev = input_ids.device
+        if attention_mask is None:
+            attention_mask = torch.ones(B, T, dtype=torch.int64, device=dev)
+        out = dec(input_ids=input_ids, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
+                  neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid, cache_capacity=T)
+        cache = out.past_key_values
+        cache.beam = beam = BeamState(cache, W, n_new - 1)
+        book = beam.book
+        hidden = out.last_hidden_state[:, -1]
+        V = self.lm_head.weight.shape[0]
+        start = torch.zeros(B, dtype=torch.float32, device=dev)
+        history = torch.empty(n_new, B, W, dtype=torch.int64, device=dev)       # history[s, b, w]: the token slot w took at step s
+        trace = []
+        for s in range(n_new):
+            logits = self._last_logits(hidden)
+            cs, ci = ops.beam_topk(logits, start if s == 0 else book.beam_score, W, rows_in=1 if s == 0 else W)
+            ops.beam_advance(cs, ci, book, s, V, eos_token_id, s == n_new - 1, early_stopping, float(s + 1) ** length_penalty)
+            history[s] = book.tokens.view(B, W)
+            if return_trace:
+                trace.append(dict(parents=book.parents.view(B, W).clone(), tokens=book.tokens.view(B, W).clone(),
+                                  scores=book.beam_score.view(B, W).clone(), cand_index=ci, cand_score=cs))
+            if s + 1 < n_new:
+                hidden = dec(input_ids=history[s].reshape(B * W, 1), past_key_values=cache).last_hidden_state[:, 0]
+        # the best pooled hypothesis of each sample: tokens 0 .. len-2 through its ancestry row, its own last token, then padding
+        score, length, anc, last = (t.view(B, W, *t.shape[1:])[:, 0] for t in book.pool)
+        cols = torch.arange(n_new, device=dev)[None, :]
+        slot = torch.zeros(B, n_new, dtype=torch.int64, device=dev)
+        slot[:, :n_new - 1] = anc[:, :n_new - 1]
+        new = history.permute(1, 0, 2).gather(2, slot[:, :, None])[:, :, 0]                       # [B, n_new]
+        length = length.long()[:, None]
+        new = torch.where(cols < length - 1, new, torch.where(cols == length - 1, last[:, None], torch.full_like(new, pad_token_id)))
+        ids = torch.cat([input_ids, new.to(input_ids.dtype)], dim=1)
+        res = (ids,)
+        if return_scores:
+            res += (score.clone(),)
+        if return_trace:
+            res += (trace,)
+        return res[0] if len(res) == 1 else res
 
 
 def copy_opt_weights(opt_model, mpt_model):
@@ -1265,10 +1413,13 @@ class CrossAttentionModel(nn.Module):
     def generate(self, input_ids, attention_mask, images=None, image_positions=None, neighbor_input_ids=None,
                  neighbor_attention_mask=None, neighbor_pos_ids=None, text_locations=None, neighbor_images=None,
                  neighbor_images_pos_ids=None, image_locations=None, host_meta=None, max_new_tokens=32, eos_token_id=None,
-                 pad_token_id=None, return_step_logits=False):
+                 pad_token_id=None, return_step_logits=False, num_beams=1, length_penalty=1.0, early_stopping=False,
+                 return_sequences_scores=False, return_beam_trace=False):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded): the neighbors are encoded and interleaved once, exactly
         as forward does, then MPTForCausalLM.generate runs the prefill and the cached decode steps.  Returns [B, T + max_new_tokens]
-        ids (and the step logits with return_step_logits=True)."""
+        ids (and the step logits with return_step_logits=True).  num_beams, length_penalty, early_stopping, return_sequences_scores and
+        return_beam_trace are MPTForCausalLM.generate's beam-search keywords, passed through: the neighbors are still encoded once per
+        sample and their tokens stay at B rows."""
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the OPT fork only, not for {type(self.lm).__name__}")
         if not input_ids.is_cuda:
@@ -1278,4 +1429,6 @@ class CrossAttentionModel(nn.Module):
         return self.lm.generate(input_ids, attention_mask, neighbor_embeds=neighbor_embeds, neighbor_attention_mask=key_valid,
                                 max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                 return_step_logits=return_step_logits,
-                                first_key_valid=bool(host_meta and host_meta.get("first_key_valid")))
+                                first_key_valid=bool(host_meta and host_meta.get("first_key_valid")), num_beams=num_beams,
+                                length_penalty=length_penalty, early_stopping=early_stopping,
+                                return_sequences_scores=return_sequences_scores, return_beam_trace=return_beam_trace)

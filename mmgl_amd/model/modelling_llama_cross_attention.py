@@ -299,7 +299,7 @@ class LlamaNeighborLM(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
-                 eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False):
+                 eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, num_beams=1):
         """Greedy decoding with a key/value cache: the contract of MPTForCausalLM.generate (without inputs_embeds).  One prefill over
         the right-padded prompts [B, T] -- the kernels of forward(), plus the copy of every layer's Hkv key/value heads into a
         DecodeCache -- then max_new_tokens - 1 decode steps; lm_head runs on the last row only.  Every new token is appended at the
@@ -307,7 +307,10 @@ class LlamaNeighborLM(nn.Module):
         eos_token_id: a row that has emitted it gets pad_token_id (default config.pad_token_id) from then on; None: no end-of-sequence
         handling.  All max_new_tokens steps run (no host synchronisation to stop early).
         Returns the [B, T + max_new_tokens] ids; with return_step_logits=True also the [B, max_new_tokens, V] logits the tokens
-        were picked from."""
+        were picked from.  num_beams > 1 is refused (beam search is implemented for the OPT fork only)."""
+        if int(num_beams) != 1:
+            raise ValueError(f"LlamaNeighborLM.generate(): num_beams = {num_beams} is not implemented (beam search runs on the OPT fork "
+                             "only); this path is greedy")
         n_new = int(max_new_tokens)
         if n_new < 1:
             raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")

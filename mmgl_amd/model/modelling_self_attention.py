@@ -354,14 +354,18 @@ class SelfAttentionModel(nn.Module):
     def generate(self, input_ids, attention_mask, images=None, image_positions=None, neighbor_input_ids=None,
                  neighbor_attention_mask=None, neighbor_pos_ids=None, text_locations=None, neighbor_images=None,
                  neighbor_images_pos_ids=None, image_locations=None, lpe=None, graph=None, host_meta=None, max_new_tokens=32,
-                 eos_token_id=None, pad_token_id=None, return_step_logits=False):
+                 eos_token_id=None, pad_token_id=None, return_step_logits=False, num_beams=1):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded).  The LM input is built exactly as forward builds it
         (_lm_inputs), then MPTForCausalLM.generate runs the prefill and the cached decode steps (LoRA-adapted q / v projections on
         ops.decode_lora_linear).  New tokens are appended behind the whole LM input:
             [virtual tokens | prompt, image tokens scattered in | neighbor tokens | new tokens ...]
         so in embedding mode they follow the neighbor tokens and see them; padded neighbor slots stay masked keys, and position ids
         count the valid keys, as the cache does.  Returns [B, T + max_new_tokens] ids -- input_ids followed by the new tokens -- and the
-        [B, max_new_tokens, V] step logits with return_step_logits=True."""
+        [B, max_new_tokens, V] step logits with return_step_logits=True.  num_beams > 1 is refused: beam search takes input_ids
+        prompts and plain projections (CrossAttentionModel / MPTForCausalLM), this wrapper generates from embeddings."""
+        if int(num_beams) != 1:
+            raise ValueError(f"SelfAttentionModel.generate(): num_beams = {num_beams} is not implemented (beam search runs on "
+                             "CrossAttentionModel / MPTForCausalLM with input_ids prompts); this path is greedy")
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the decoder-only OPT fork with peft_type none / lora / prompt, not for "
                              f"{type(self.lm).__name__} with peft_type {self.args.peft_type!r}")

@@ -1676,3 +1676,167 @@ def rope_kv_append(qkv, cos_sin_row, kv_col, num_heads, num_kv_heads):
     _lib.call("mmgl_rope_kv_append", dict(bytes=float(2 * H + 4 * Hkv) * B * D * qkv.element_size()), ptr(qkv), qkv.stride(0), ptr(cos_sin_row),
               ptr(kv_col), kv_col.stride(0), B, H, Hkv, D, dtype_code(qkv), stream_ptr())
     return qkv
+
+
+# ------------------------------------------------------------------------------------------ beam search (csrc/decode.hip, csrc/beam.hip)
+MAX_BEAMS = 8
+
+
+def _beams(op, num_beams):
+    W = int(num_beams)
+    if W < 1:
+        raise ValueError(f"{op}: num_beams = {num_beams} must be positive")
+    if W > MAX_BEAMS:
+        raise ValueError(f"{op}: {W} beams per sample (1..{MAX_BEAMS})")
+    return W
+
+
+def attn_decode_beam(q, k_pre, v_pre, key_valid, num_heads, num_beams, k_tail=None, v_tail=None, src=None, out=None):
+    """Single-query attention for the B*W rows of a beam-search step; row b*W + w is beam slot w of sample b (W = num_beams <= 8).
+      q [B*W, d] already scaled; k_pre, v_pre [B, S_pre, d] and key_valid [B, S_pre]: the views ops.attn_decode takes, one row set
+      per SAMPLE (the prompt's cache rows or the projected neighbor tokens), read once for the W queries;
+      k_tail, v_tail [B*W, n_tail, d]: column slabs of the tail buffer [B*W, n_cap, 2d] (unit column stride, common strides), the keys
+      the hypotheses generated themselves; src int32 [B*W, >= n_tail] (unit column stride): tail key j of row (b, w) is row
+      b*W + src[b*W + w, j] of the tail.  src values lie in [0, W): the caller's contract (the kernel clamps, nothing is checked on
+      the device).  No tail (None, or n_tail = 0) is the cross-attention call.
+    A sample whose prefix has no valid key attends uniformly over all its S_pre + n_tail keys.  Returns [B*W, d] (`out`, a dense tensor
+    of q's dtype, when given: a refused call leaves it as it was).  Forward only; GPU only."""
+    require_cuda(q, k_pre, v_pre, key_valid, k_tail, v_tail, src)
+    _no_grad_inputs("attn_decode_beam", q, k_pre, v_pre, k_tail, v_tail)
+    W = _beams("attn_decode_beam", num_beams)
+    if (q.dim() != 2 or k_pre.dim() != 3 or k_pre.shape != v_pre.shape or q.shape[0] != k_pre.shape[0] * W or q.shape[1] != k_pre.shape[2]
+            or k_pre.stride() != v_pre.stride() or k_pre.stride(2) != 1 or q.stride(1) != 1 or k_pre.dtype != q.dtype or v_pre.dtype != q.dtype):
+        raise ValueError(f"attn_decode_beam: incompatible q{tuple(q.shape)} k_pre{tuple(k_pre.shape)}/{k_pre.stride()} "
+                         f"v_pre{tuple(v_pre.shape)}/{v_pre.stride()} for {W} beams")
+    R, d = q.shape
+    B, S = k_pre.shape[:2]
+    if d % num_heads:
+        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {d} and `num_heads`: {num_heads}).")
+    _check_mask(key_valid, (B, S))
+    if S == 0:
+        raise ValueError("attn_decode_beam: no prefix keys")
+    n_tail = 0 if k_tail is None else k_tail.shape[1] if k_tail.dim() == 3 else -1
+    if (k_tail is None) != (v_tail is None) or n_tail < 0:
+        raise ValueError("attn_decode_beam: k_tail and v_tail come together, as [B*W, n_tail, d] views")
+    if n_tail:
+        if (tuple(k_tail.shape) != (R, n_tail, d) or k_tail.shape != v_tail.shape or k_tail.stride() != v_tail.stride() or k_tail.stride(2) != 1
+                or k_tail.dtype != q.dtype or v_tail.dtype != q.dtype):
+            raise ValueError(f"attn_decode_beam: incompatible k_tail{tuple(k_tail.shape)}/{k_tail.stride()} v_tail{tuple(v_tail.shape)}/"
+                             f"{v_tail.stride()} for q{tuple(q.shape)}")
+        if src is None or src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != R or src.shape[1] < n_tail or src.stride(1) != 1:
+            raise ValueError(f"attn_decode_beam: src must be an int32 [{R}, >= {n_tail}] view with unit column stride")
+    if key_valid.dtype == torch.bool:
+        key_valid = key_valid.view(torch.uint8)
+    elif key_valid.dtype != torch.uint8:
+        key_valid = key_valid.to(torch.uint8)
+    if key_valid.stride(1) != 1:
+        key_valid = key_valid.contiguous()
+    if out is None:
+        out = torch.empty(R, d, dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (R, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError(f"attn_decode_beam: out{tuple(out.shape)} {out.dtype} must be a dense [{R}, {d}] {q.dtype} tensor on {q.device}")
+    tail = (ptr(k_tail), ptr(v_tail), k_tail.stride(1), k_tail.stride(0), ptr(src), src.stride(0)) if n_tail else (None, None, 0, 0, None, 0)
+    _lib.call("mmgl_attn_decode_beam_fwd", dict(bytes=2.0 * (B * S + R * n_tail) * d * q.element_size()), ptr(q), q.stride(0), ptr(k_pre),
+              ptr(v_pre), k_pre.stride(1), k_pre.stride(0), ptr(key_valid), key_valid.stride(0), *tail, ptr(out), B, W, num_heads, S, n_tail,
+              d // num_heads, dtype_code(q), stream_ptr())
+    return out
+
+
+def beam_topk(logits, beam_score, num_beams, rows_in=None, out=None):
+    """Per sample the 2W best continuations of its rows: logits [B*rows_in, V] (bf16 / fp32, unit column stride, any row stride) with
+    rows_in = W = num_beams (the default) or 1 (the first step: the prefill's one row per sample); beam_score fp32 [B*rows_in].
+    Returns (cand_score fp32 [B, 2W], cand_index int32 [B, 2W]) -- score = beam_score + log_softmax(logits) in fp32, sorted descending,
+    index = r*V + v with r the row's slot in its sample; an exact tie goes to the lower index.  `out`: that pair, preallocated.  Two
+    launches, no [rows, V] intermediate, no host synchronisation.  Forward only; GPU only."""
+    require_cuda(logits, beam_score)
+    W = _beams("beam_topk", num_beams)
+    if logits.dim() != 2 or logits.stride(1) != 1 or beam_score.dtype != torch.float32 or beam_score.dim() != 1 or not beam_score.is_contiguous():
+        raise ValueError(f"beam_topk: logits{tuple(logits.shape)}/{logits.stride()} [rows, V] with unit column stride, beam_score "
+                         f"{beam_score.dtype}{tuple(beam_score.shape)} dense fp32 [rows]")
+    rows, V = logits.shape
+    if beam_score.shape[0] != rows or rows == 0:
+        raise ValueError(f"beam_topk: {beam_score.shape[0]} scores for {rows} rows")
+    rows_in = W if rows_in is None else int(rows_in)
+    if rows_in not in (1, W) or rows % rows_in:
+        raise ValueError(f"beam_topk: rows_in = {rows_in} must be 1 or num_beams = {W} and divide the {rows} rows")
+    B = rows // rows_in
+    if V < 2 * W:
+        raise ValueError(f"beam_topk: V = {V} holds fewer than 2W = {2 * W} candidates")
+    code = dtype_code(logits)
+    if out is None:
+        out = (torch.empty(B, 2 * W, dtype=torch.float32, device=logits.device), torch.empty(B, 2 * W, dtype=torch.int32, device=logits.device))
+    cs, ci = out
+    if (tuple(cs.shape) != (B, 2 * W) or tuple(ci.shape) != (B, 2 * W) or cs.dtype != torch.float32 or ci.dtype != torch.int32
+            or not cs.is_contiguous() or not ci.is_contiguous() or cs.device != logits.device or ci.device != logits.device):
+        raise ValueError(f"beam_topk: out must be dense (fp32, int32) [{B}, {2 * W}] tensors on {logits.device}")
+    nbytes = _lib.lib().mmgl_beam_topk_workspace(rows, V, W)
+    ws = _ws(nbytes, logits.device)
+    _lib.call("mmgl_beam_topk", dict(bytes=float(rows) * V * logits.element_size()), ptr(logits), logits.stride(0), ptr(beam_score), ptr(cs), ptr(ci),
+              ptr(ws), nbytes, B, rows_in, W, V, code, stream_ptr())
+    return cs, ci
+
+
+class BeamBook:
+    """The bookkeeping state of a beam search over B samples x W beams, all on the device (ops.beam_advance moves it one step):
+      tokens int64 / parents int32 / beam_score fp32 [B*W]   the running beams of the last step (slot order = candidate order)
+      src        two int32 [B*W, n_cap] parent tables (ops.attn_decode_beam reads `src`, the current one): src[b*W + w, j] is the slot
+                 that held the ancestor of running beam (b, w) at decode step j -- the row of the tail buffer whose column j is its key.
+                 Every column starts as the identity (a row reads its own column until a later step has reordered it).
+      pool       two sets (score fp32, length int32, ancestry int32 [B*W, n_cap], last token int64) of the W best finished
+                 hypotheses per sample, sorted descending; length 0 / score -inf mark an empty slot
+      done       int32 [B]: the sample's pool is closed (the early-stop heuristic was met)
+      cur        which of the two buffers is current"""
+
+    def __init__(self, batch_size, num_beams, n_cap, device):
+        B, W, C = int(batch_size), _beams("BeamBook", num_beams), max(int(n_cap), 1)
+        self.B, self.W, self.n_cap, self.cur = B, W, C, 0
+        i32 = dict(dtype=torch.int32, device=device)
+        self.tokens = torch.zeros(B * W, dtype=torch.int64, device=device)
+        self.parents = torch.zeros(B * W, **i32)
+        self.beam_score = torch.zeros(B * W, dtype=torch.float32, device=device)
+        ident = (torch.arange(B * W, **i32) % W)[:, None].expand(B * W, C)
+        self._src = [ident.clone(), ident.clone()]
+        self._pool = [(torch.full((B * W,), float("-inf"), dtype=torch.float32, device=device), torch.zeros(B * W, **i32),
+                       torch.zeros(B * W, C, **i32), torch.zeros(B * W, dtype=torch.int64, device=device)) for _ in range(2)]
+        self.done = torch.zeros(B, **i32)
+
+    @property
+    def src(self):
+        return self._src[self.cur]
+
+    @property
+    def pool(self):
+        return self._pool[self.cur]
+
+
+def beam_advance(cand_score, cand_index, book, n_cols, vocab_size, eos_token_id=None, last_step=False, early_stopping=False,
+                 length_divisor=1.0):
+    """One step of beam-search bookkeeping in one launch (mmgl_beam_advance): the sorted candidates of ops.beam_topk (fp32 / int32
+    [B, 2W]) become book's next state -- the running beams (the first W candidates whose token is not eos_token_id), the parent table
+    (new[w, :n_cols-1] = old[parent, :n_cols-1], new[w, n_cols-1] = parent; n_cols = the step index = the tail columns the parents
+    own) and the pool: a candidate among the first W that is EOS, or any of them at last_step, enters with score / length_divisor
+    (pass float32((step + 1) ** length_penalty)), length n_cols + 1, its ancestry row and its token, unless the sample is frozen
+    (book.done, or early_stopping with a pool that was already full).  Flips book.cur; no host synchronisation.  Returns book."""
+    require_cuda(cand_score, cand_index, book.tokens)
+    B, W = book.B, book.W
+    if (tuple(cand_score.shape) != (B, 2 * W) or tuple(cand_index.shape) != (B, 2 * W) or cand_score.dtype != torch.float32
+            or cand_index.dtype != torch.int32 or not cand_score.is_contiguous() or not cand_index.is_contiguous()):
+        raise ValueError(f"beam_advance: candidates must be dense (fp32, int32) [{B}, {2 * W}] tensors, got {cand_score.dtype}"
+                         f"{tuple(cand_score.shape)} / {cand_index.dtype}{tuple(cand_index.shape)}")
+    n_cols = int(n_cols)
+    if not 0 <= n_cols <= book.n_cap:
+        raise ValueError(f"beam_advance: n_cols = {n_cols} outside [0, {book.n_cap}]")
+    if int(vocab_size) < 2 * W:
+        raise ValueError(f"beam_advance: V = {vocab_size} holds fewer than 2W = {2 * W} candidates")
+    if early_stopping not in (True, False):
+        raise ValueError(f"beam_advance: early_stopping = {early_stopping!r} (True or False)")
+    if not float(length_divisor) > 0.0:
+        raise ValueError(f"beam_advance: length_divisor = {length_divisor} must be positive")
+    old, new = book.cur, 1 - book.cur
+    po, pn = book._pool[old], book._pool[new]
+    _lib.call("mmgl_beam_advance", None, ptr(cand_score), ptr(cand_index), ptr(book.tokens), ptr(book.parents), ptr(book.beam_score),
+              ptr(book._src[old]), ptr(book._src[new]), book.n_cap, ptr(po[0]), ptr(pn[0]), ptr(po[1]), ptr(pn[1]), ptr(po[2]), ptr(pn[2]),
+              ptr(po[3]), ptr(pn[3]), ptr(book.done), B, W, int(vocab_size), n_cols, -1 if eos_token_id is None else int(eos_token_id),
+              int(bool(last_step)), int(bool(early_stopping)), float(length_divisor), stream_ptr())
+    book.cur = new
+    return book
