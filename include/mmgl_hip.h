@@ -521,6 +521,28 @@ int mmgl_beam_advance(const float* cand_score, const int* cand_index, int64_t* t
                       const int64_t* pool_tok_old, int64_t* pool_tok_new, int* done, int B, int W, int V, int n_cols, int eos_token_id,
                       int last_step, int early_stopping, float length_divisor, void* stream);
 
+/* ---- sampling (generate(do_sample=True)): temperature, top-k, top-p and the draw, one launch --------------------------------------
+ * replaces: transformers' TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper (min_tokens_to_keep = 1) -> softmax ->
+ *           multinomial, and the where / full_like / == / | / setitem tail of the greedy loops
+ *
+ * mmgl_sample_tokens: per row of logits [rows, V] (bf16 / fp32, row stride ld_logits elements) n_draws tokens.
+ *   x = logit / temperature in fp32 (a NaN logit counts as -inf).
+ *   top-k  (top_k = 0 or >= V: off): v survives iff fewer than top_k tokens have x > x_v -- every token tied with the k-th is kept.
+ *   top-p  (top_p = 1: off): with p = softmax(x) over the survivors, v is kept iff the mass of the survivors with x > x_v is < top_p;
+ *          every token tied with the boundary is kept; the largest logit is always kept.
+ *   draw   u fp32 [rows, n_draws] in [0, 1): the smallest kept v, in vocabulary index order, whose running mass over the kept set
+ *          exceeds u * Z_K.  Always in [0, V).
+ *   Masses are the integers trunc(2^40 * expf(x - max x)), summed as integers: no sum depends on an order, two runs are bitwise equal.
+ *   tokens   int64, draw i = row * n_draws + j is written to tokens[i * token_stride] (a column of an ids tensor)
+ *   finished optional uint8 [rows * n_draws], read and written: a finished draw gets pad_token_id; a draw that returns eos_token_id
+ *            (< 0: none) becomes finished
+ *   kept     optional int32 [rows]: the size of the kept set
+ *   V <= 131072 and n_draws <= 8, else MMGL_ERR_UNSUPPORTED; temperature > 0, top_k >= 0, 0 < top_p <= 1.  A refused call writes nothing.
+ *   One workgroup per row, no workspace, no host synchronisation.  Plain vector stores only. */
+int mmgl_sample_tokens(const void* logits, size_t ld_logits, const float* u, int64_t* tokens, int64_t token_stride, uint8_t* finished,
+                       int* kept, int rows, int n_draws, int V, float temperature, int top_k, float top_p, int eos_token_id,
+                       int64_t pad_token_id, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

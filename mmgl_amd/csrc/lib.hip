@@ -74,4 +74,6 @@ int mmgl_num_cu() {
 // 108: mmgl_selfattn_gqa_fwd / _bwd_workspace / _bwd (grouped-query self-attention of the Llama family).
 // 109: mmgl_attn_decode_gqa_fwd / mmgl_rope_kv_append (the decode step of the Llama-family LM: grouped-query cache, rotary at one position).
 // 110: mmgl_attn_decode_beam_fwd / mmgl_beam_topk(_workspace) / mmgl_beam_advance (beam search on a beam-shared cache).
+// mmgl_sample_tokens (sampling for generate()) was added at 110 without a bump: no existing signature changed, and the binding
+// resolves every declared symbol at load, so a library built without it is refused all the same.
 extern "C" int mmgl_version(void) { return 110; }

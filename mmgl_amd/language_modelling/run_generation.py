@@ -39,7 +39,8 @@ def _f(default, help_):
 
 @dataclass
 class Arguments:
-    """Same field names and defaults as the reference's Arguments (:66-229) + `neighbor_layer_wise` + `num_beams`."""
+    """Same field names and defaults as the reference's Arguments (:66-229) + `neighbor_layer_wise` + `num_beams` + the sampling knobs
+    `do_sample` / `temperature` / `top_k` / `top_p`."""
     overwrite_cache: Optional[bool] = _f(False, "Overwrite the cached preprocessed datasets or not.")
     dataset: Optional[str] = _f("wikiweb2m", "The name of the dataset to use.")
     task: Optional[str] = _f("section", "One of three generation tasks in WikiWeb2M")
@@ -97,6 +98,10 @@ class Arguments:
                                                   "(default: num_hidden_layers // num_neighbor_layers)")
     num_beams: int = _f(1, "beams of the test protocol's generate(): 1 = greedy (the default), 2..8 = beam search (OPT fork, "
                            "cross-attention wrapper)")
+    do_sample: bool = _f(False, "sample in the test protocol's generate() instead of greedy decoding (seeded with `seed`)")
+    temperature: float = _f(1.0, "sampling temperature (do_sample)")
+    top_k: int = _f(0, "keep the k most likely tokens (do_sample); 0 = off")
+    top_p: float = _f(1.0, "nucleus sampling: the smallest set of tokens with this probability mass (do_sample); 1 = off")
     peft_type: str = _f("none", "peft type: none, prefix, prompt, lora, flamingo")
     lora_r: int = _f(64, "lora row rank")
     lora_alpha: float = _f(1, "lora scaling factor")
@@ -622,6 +627,9 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                 fields = {key: batch[key] for key in _GENERATE_FIELDS if key in batch and key in named}    # generate()'s named arguments only
                 if getattr(args, "num_beams", 1) > 1:                   # beam search (CrossAttentionModel); the default stays greedy
                     fields["num_beams"] = int(args.num_beams)
+                if getattr(args, "do_sample", False):                   # sampling; the default protocol stays greedy
+                    fields.update(do_sample=True, temperature=float(args.temperature), top_k=int(args.top_k), top_p=float(args.top_p),
+                                  seed=getattr(args, "seed", None))
                 generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),
                                                attention_mask=batch["attention_mask"][:, :L_in].contiguous(), **fields,
                                                host_meta=extra.get("host_meta"), max_new_tokens=32,

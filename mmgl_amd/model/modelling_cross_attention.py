@@ -38,6 +38,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from .. import ops
 from .encoders import ClipTextEncoder, PackedTextEncoder, PackedVisionEncoder
+from .sampling import check_sampling, sampling_u
 
 CROSS_MODES = ("cross_attention", "embedding")
 
@@ -961,7 +962,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
     def generate(self, input_ids=None, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
                  eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, inputs_embeds=None,
                  num_beams=1, length_penalty=1.0, early_stopping=False, return_sequences_scores=False, return_beam_trace=False,
-                 num_return_sequences=1):
+                 num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None):
         """Greedy decoding (do_sample=False, one beam) with a key/value cache: what the reference's test protocol asks of its
         wrappers (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of
         every layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
@@ -976,13 +977,17 @@ class MPTForCausalLM(MPTPreTrainedModel):
         tokens, image or neighbor tokens already in the sequence); there are no prompt ids to repeat, so only the new tokens
         [B, max_new_tokens] come back (HF's convention for inputs_embeds).
         num_beams = W > 1 (at most 8): beam search with the semantics of transformers' generate(num_beams=W, do_sample=False,
-        length_penalty, early_stopping in {False, True}) -- see _generate_beam; num_beams = 1 is the greedy path above, untouched."""
+        length_penalty, early_stopping in {False, True}) -- see _generate_beam; num_beams = 1 is the greedy path above, untouched.
+        do_sample=True (one beam): every step draws its token with ops.sample_tokens -- transformers' temperature -> top_k -> top_p
+        pipeline and the draw in one launch, see _generate_sample; seed / sample_u fix the uniform numbers; num_return_sequences = R
+        (2..8, input_ids prompts) draws R continuations per prompt on one prefill and returns [B*R, T + max_new_tokens]."""
         W = int(num_beams)
         if W < 1:
             raise ValueError(f"generate(): num_beams = {num_beams} must be positive")
-        if num_return_sequences != 1:
+        if num_return_sequences != 1 and not (do_sample and W == 1):
             raise ValueError(f"generate(): num_return_sequences = {num_return_sequences} is not implemented (the best hypothesis per sample "
-                             "is returned)")
+                             "is returned; several sequences per prompt need do_sample=True)")
+        R = check_sampling("generate()", do_sample, temperature, top_k, top_p, seed, sample_u, W, num_return_sequences, multi=True)
         if early_stopping not in (True, False):
             raise ValueError(f"generate(): early_stopping = {early_stopping!r} is not implemented (True or False)")
         if W > 1:
@@ -995,6 +1000,10 @@ class MPTForCausalLM(MPTPreTrainedModel):
                                        return_sequences_scores, return_beam_trace)
         if return_sequences_scores or return_beam_trace:
             raise ValueError("generate(): return_sequences_scores / return_beam_trace belong to beam search (num_beams > 1)")
+        if do_sample:
+            return self._generate_sample(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
+                                         pad_token_id, return_step_logits, first_key_valid, inputs_embeds, R, temperature, top_k, top_p,
+                                         seed, sample_u)
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("generate() takes exactly one of input_ids and inputs_embeds")
         prompt = input_ids if input_ids is not None else inputs_embeds
@@ -1037,6 +1046,64 @@ class MPTForCausalLM(MPTPreTrainedModel):
             ids[:, T + s] = tok
             if s + 1 < n_new:
                 hidden = dec(input_ids=tok[:, None], past_key_values=cache).last_hidden_state[:, 0]
+        return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
+
+    def _generate_sample(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
+                         pad_token_id, return_step_logits, first_key_valid, inputs_embeds, R, temperature, top_k, top_p, seed, sample_u):
+        """generate(do_sample=True): the greedy loop with its argmax / EOS / ids-column tail replaced by one ops.sample_tokens launch
+        that writes the ids column and updates the finished flags in place.  The uniform numbers [max_new_tokens,
+        rows] are drawn once before the loop (sampling_u).
+        R > 1 continuations per prompt: the prompt is prefilled once with B rows into a cache of capacity T, and the cache gets a
+        BeamState of R rows per sample whose parent table stays the identity (nobody calls ops.beam_advance) -- R independent rows
+        that share the prompt's keys.  The first step draws R tokens from each prefill row, every later step runs the decode kernels
+        at M = B*R rows.  Rows b*R .. b*R + R - 1 of the result belong to prompt b; sample_u is then [max_new_tokens, B*R]."""
+        if (input_ids is None) == (inputs_embeds is None):
+            raise ValueError("generate() takes exactly one of input_ids and inputs_embeds")
+        if R > 1 and input_ids is None:
+            raise ValueError(f"generate(): num_return_sequences = {R} takes input_ids prompts, not inputs_embeds")
+        prompt = input_ids if input_ids is not None else inputs_embeds
+        if not prompt.is_cuda:
+            raise RuntimeError(f"generate() runs on the GPU only (the prompt is on {prompt.device}); there is no CPU path")
+        if prompt.dim() != (2 if input_ids is not None else 3):
+            raise ValueError(f"generate(): input_ids [B, T] or inputs_embeds [B, T, d_embed], got {tuple(prompt.shape)}")
+        B, T = prompt.shape[:2]
+        n_new = int(max_new_tokens)
+        if n_new < 1:
+            raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
+        dec = self.model.decoder
+        if T + n_new - 1 > dec.max_target_positions:
+            raise ValueError(f"generate(): {T} prompt columns + {n_new} new tokens exceed max_position_embeddings {dec.max_target_positions}")
+        if eos_token_id is not None and pad_token_id is None:
+            pad_token_id = self.config.pad_token_id
+            if pad_token_id is None:
+                raise ValueError("generate(): eos_token_id needs a pad_token_id")
+        dev, rows = prompt.device, B * R
+        u = sampling_u("generate()", n_new, rows, dev, seed, sample_u)
+        if attention_mask is None:
+            attention_mask = torch.ones(B, T, dtype=torch.int64, device=dev)
+        out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
+                  neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
+                  cache_capacity=T if R > 1 else min(T + n_new - 1, dec.max_target_positions))
+        cache = out.past_key_values
+        if R > 1:
+            cache.beam = BeamState(cache, R, n_new - 1)
+        hidden = out.last_hidden_state[:, -1]
+        T = T if input_ids is not None else 0                  # columns of the result in front of the new tokens
+        ids = torch.empty(rows, T + n_new, dtype=torch.int64, device=dev)
+        if input_ids is not None:
+            ids[:, :T] = input_ids if R == 1 else input_ids.repeat_interleave(R, dim=0)
+        finished = torch.zeros(rows, dtype=torch.uint8, device=dev) if eos_token_id is not None else None
+        steps = []
+        for s in range(n_new):
+            logits = self._last_logits(hidden)                 # step 0 of R > 1: the prefill's B rows, R draws each
+            if return_step_logits:
+                steps.append(logits if logits.shape[0] == rows else logits.repeat_interleave(R, dim=0))
+            col = ids[:, T + s]
+            ops.sample_tokens(logits, u[s].view(logits.shape[0], -1), temperature, top_k, top_p, finished, eos_token_id, pad_token_id, out=col)
+            if s + 1 < n_new:
+                hidden = dec(input_ids=col[:, None], past_key_values=cache).last_hidden_state[:, 0]
+        if input_ids is not None:
+            ids = ids.to(input_ids.dtype)
         return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
 
     def _generate_beam(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
@@ -1414,14 +1481,17 @@ class CrossAttentionModel(nn.Module):
                  neighbor_attention_mask=None, neighbor_pos_ids=None, text_locations=None, neighbor_images=None,
                  neighbor_images_pos_ids=None, image_locations=None, host_meta=None, max_new_tokens=32, eos_token_id=None,
                  pad_token_id=None, return_step_logits=False, num_beams=1, length_penalty=1.0, early_stopping=False,
-                 return_sequences_scores=False, return_beam_trace=False):
+                 return_sequences_scores=False, return_beam_trace=False, num_return_sequences=1, do_sample=False, temperature=1.0,
+                 top_k=0, top_p=1.0, seed=None, sample_u=None):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded): the neighbors are encoded and interleaved once, exactly
         as forward does, then MPTForCausalLM.generate runs the prefill and the cached decode steps.  Returns [B, T + max_new_tokens]
         ids (and the step logits with return_step_logits=True).  num_beams, length_penalty, early_stopping, return_sequences_scores and
         return_beam_trace are MPTForCausalLM.generate's beam-search keywords, passed through: the neighbors are still encoded once per
-        sample and their tokens stay at B rows."""
+        sample and their tokens stay at B rows.  So are its sampling keywords do_sample, temperature, top_k, top_p, seed, sample_u and
+        num_return_sequences (R continuations per prompt also read the prompt's neighbor tokens once)."""
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the OPT fork only, not for {type(self.lm).__name__}")
+        check_sampling("generate()", do_sample, temperature, top_k, top_p, seed, sample_u, num_beams, num_return_sequences, multi=True)
         if not input_ids.is_cuda:
             raise RuntimeError(f"generate() runs on the GPU only (input_ids is on {input_ids.device}); there is no CPU path")
         neighbor_embeds, key_valid = self._neighbor_tokens(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, text_locations,
@@ -1431,4 +1501,6 @@ class CrossAttentionModel(nn.Module):
                                 return_step_logits=return_step_logits,
                                 first_key_valid=bool(host_meta and host_meta.get("first_key_valid")), num_beams=num_beams,
                                 length_penalty=length_penalty, early_stopping=early_stopping,
-                                return_sequences_scores=return_sequences_scores, return_beam_trace=return_beam_trace)
+                                return_sequences_scores=return_sequences_scores, return_beam_trace=return_beam_trace,
+                                num_return_sequences=num_return_sequences, do_sample=do_sample, temperature=temperature, top_k=top_k,
+                                top_p=top_p, seed=seed, sample_u=sample_u)

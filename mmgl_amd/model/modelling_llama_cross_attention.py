@@ -21,6 +21,7 @@ from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from .. import ops
 from .modelling_cross_attention import DecodeCache
+from .sampling import check_sampling, sampling_u
 
 
 class LlamaGatedCrossAttentionLayer(nn.Module):
@@ -299,7 +300,8 @@ class LlamaNeighborLM(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
-                 eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, num_beams=1):
+                 eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, num_beams=1,
+                 num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None):
         """Greedy decoding with a key/value cache: the contract of MPTForCausalLM.generate (without inputs_embeds).  One prefill over
         the right-padded prompts [B, T] -- the kernels of forward(), plus the copy of every layer's Hkv key/value heads into a
         DecodeCache -- then max_new_tokens - 1 decode steps; lm_head runs on the last row only.  Every new token is appended at the
@@ -307,10 +309,15 @@ class LlamaNeighborLM(nn.Module):
         eos_token_id: a row that has emitted it gets pad_token_id (default config.pad_token_id) from then on; None: no end-of-sequence
         handling.  All max_new_tokens steps run (no host synchronisation to stop early).
         Returns the [B, T + max_new_tokens] ids; with return_step_logits=True also the [B, max_new_tokens, V] logits the tokens
-        were picked from.  num_beams > 1 is refused (beam search is implemented for the OPT fork only)."""
+        were picked from.  num_beams > 1 is refused (beam search is implemented for the OPT fork only).
+        do_sample=True: every step draws its token with ops.sample_tokens (temperature -> top_k -> top_p and the draw, one launch that
+        writes the ids column and the finished flags) from uniform numbers [max_new_tokens, B] drawn once before the loop -- sample_u
+        itself, or torch.rand on a generator seeded with `seed` (None: torch's global device generator).  num_return_sequences > 1 is
+        refused (it needs the beam-shared cache of the OPT fork)."""
         if int(num_beams) != 1:
             raise ValueError(f"LlamaNeighborLM.generate(): num_beams = {num_beams} is not implemented (beam search runs on the OPT fork "
                              "only); this path is greedy")
+        check_sampling("LlamaNeighborLM.generate()", do_sample, temperature, top_k, top_p, seed, sample_u, 1, num_return_sequences)
         n_new = int(max_new_tokens)
         if n_new < 1:
             raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
@@ -331,6 +338,21 @@ class LlamaNeighborLM(nn.Module):
         hidden = hidden[:, -1]
         ids = torch.empty(B, T + n_new, dtype=input_ids.dtype, device=input_ids.device)
         ids[:, :T] = input_ids
+        if do_sample:
+            if ids.dtype != torch.int64:
+                raise ValueError(f"generate(do_sample=True): input_ids must be int64, got {ids.dtype}")
+            u = sampling_u("LlamaNeighborLM.generate()", n_new, B, input_ids.device, seed, sample_u)
+            done = torch.zeros(B, dtype=torch.uint8, device=input_ids.device) if eos_token_id is not None else None
+            steps = []
+            for s in range(n_new):
+                logits = self._last_logits(hidden)
+                if return_step_logits:
+                    steps.append(logits)
+                col = ids[:, T + s]
+                ops.sample_tokens(logits, u[s], temperature, top_k, top_p, done, eos_token_id, pad_token_id, out=col)
+                if s + 1 < n_new:
+                    hidden = self._decode_step(col[:, None], cache)
+            return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
         finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
         steps = []
         for s in range(n_new):

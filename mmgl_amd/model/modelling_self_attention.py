@@ -27,6 +27,7 @@ from .. import ops
 from .encoders import PackedTextEncoder, PackedVisionEncoder
 from .graph import GCN
 from .modelling_cross_attention import TextPooler
+from .sampling import check_sampling
 
 NUM_VIRTUAL_TOKENS = 20
 
@@ -354,7 +355,8 @@ class SelfAttentionModel(nn.Module):
     def generate(self, input_ids, attention_mask, images=None, image_positions=None, neighbor_input_ids=None,
                  neighbor_attention_mask=None, neighbor_pos_ids=None, text_locations=None, neighbor_images=None,
                  neighbor_images_pos_ids=None, image_locations=None, lpe=None, graph=None, host_meta=None, max_new_tokens=32,
-                 eos_token_id=None, pad_token_id=None, return_step_logits=False, num_beams=1):
+                 eos_token_id=None, pad_token_id=None, return_step_logits=False, num_beams=1, num_return_sequences=1, do_sample=False,
+                 temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded).  The LM input is built exactly as forward builds it
         (_lm_inputs), then MPTForCausalLM.generate runs the prefill and the cached decode steps (LoRA-adapted q / v projections on
         ops.decode_lora_linear).  New tokens are appended behind the whole LM input:
@@ -362,10 +364,13 @@ class SelfAttentionModel(nn.Module):
         so in embedding mode they follow the neighbor tokens and see them; padded neighbor slots stay masked keys, and position ids
         count the valid keys, as the cache does.  Returns [B, T + max_new_tokens] ids -- input_ids followed by the new tokens -- and the
         [B, max_new_tokens, V] step logits with return_step_logits=True.  num_beams > 1 is refused: beam search takes input_ids
-        prompts and plain projections (CrossAttentionModel / MPTForCausalLM), this wrapper generates from embeddings."""
+        prompts and plain projections (CrossAttentionModel / MPTForCausalLM), this wrapper generates from embeddings.
+        do_sample, temperature, top_k, top_p, seed and sample_u are MPTForCausalLM.generate's sampling keywords, passed through;
+        num_return_sequences > 1 is refused for the same reason as beams."""
         if int(num_beams) != 1:
             raise ValueError(f"SelfAttentionModel.generate(): num_beams = {num_beams} is not implemented (beam search runs on "
                              "CrossAttentionModel / MPTForCausalLM with input_ids prompts); this path is greedy")
+        check_sampling("SelfAttentionModel.generate()", do_sample, temperature, top_k, top_p, seed, sample_u, 1, num_return_sequences)
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the decoder-only OPT fork with peft_type none / lora / prompt, not for "
                              f"{type(self.lm).__name__} with peft_type {self.args.peft_type!r}")
@@ -382,6 +387,8 @@ class SelfAttentionModel(nn.Module):
         first = self.prompt_embeddings is not None or bool(host_meta and host_meta.get("first_key_valid"))
         kw = dict(max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, return_step_logits=return_step_logits,
                   first_key_valid=first)
+        if do_sample:
+            kw.update(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, sample_u=sample_u)
         if lm_input.dim() == 2:
             return self.lm.generate(lm_input, lm_mask, **kw)
         out = self.lm.generate(inputs_embeds=lm_input, attention_mask=lm_mask, **kw)

@@ -1776,6 +1776,59 @@ def beam_topk(logits, beam_score, num_beams, rows_in=None, out=None):
     return cs, ci
 
 
+def sample_tokens(logits, u, temperature=1.0, top_k=0, top_p=1.0, finished=None, eos_token_id=None, pad_token_id=None, out=None,
+                  return_kept=False):
+    """The selection step of generate(do_sample=True) in one launch (mmgl_sample_tokens): transformers' temperature -> top-k -> top-p
+    warpers (min_tokens_to_keep = 1) and the draw, per row of logits [rows, V] (bf16 / fp32, unit column stride, any row stride;
+    V <= 131072).  u: fp32 [rows, n_draws] (or [rows]: one draw) in [0, 1), n_draws <= 8 draws per row on one kept set.
+    With x = logit / temperature in fp32: top_k (0 or >= V: off) keeps v iff fewer than top_k tokens have x > x_v; top_p (1: off)
+    keeps a survivor v iff the softmax mass of the survivors with x > x_v is < top_p.  Ties at either boundary are all kept, the
+    largest logit always is.  The token is the smallest kept v, in vocabulary index order, whose running mass exceeds u * Z_K.
+    finished (uint8 / bool [rows * n_draws], updated in place) with eos_token_id / pad_token_id: a finished draw gets pad_token_id, a
+    draw that returns eos_token_id becomes finished.  `out`: an int64 view of rows * n_draws elements with any positive stride (a
+    column of the ids tensor).  Returns the tokens (int64 [rows * n_draws], or `out`), with return_kept=True also the size of each
+    row's kept set (int32 [rows]).  No [rows, V] intermediate, no host synchronisation, bitwise reproducible.  Forward only; GPU only."""
+    require_cuda(logits, u, finished, out)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] == 0 or logits.shape[1] == 0:
+        raise ValueError(f"sample_tokens: logits{tuple(logits.shape)}/{logits.stride()} must be [rows, V] with unit column stride")
+    rows, V = logits.shape
+    code = dtype_code(logits)
+    if V > 131072:
+        raise ValueError(f"sample_tokens: V = {V} (at most 131072)")
+    if u.dtype != torch.float32 or u.dim() not in (1, 2) or u.shape[0] != rows or not u.is_contiguous() or u.device != logits.device:
+        raise ValueError(f"sample_tokens: u {u.dtype}{tuple(u.shape)} must be a dense fp32 [{rows}, n_draws] tensor on {logits.device}")
+    n_draws = 1 if u.dim() == 1 else u.shape[1]
+    if not 1 <= n_draws <= MAX_BEAMS:
+        raise ValueError(f"sample_tokens: {n_draws} draws per row (1..{MAX_BEAMS})")
+    temperature, top_k, top_p = float(temperature), int(top_k), float(top_p)
+    if not (0.0 < temperature < float("inf")):
+        raise ValueError(f"sample_tokens: temperature = {temperature} must be positive and finite")
+    if top_k < 0:
+        raise ValueError(f"sample_tokens: top_k = {top_k} must not be negative (0: off)")
+    if not (0.0 < top_p <= 1.0):
+        raise ValueError(f"sample_tokens: top_p = {top_p} outside (0, 1]")
+    n = rows * n_draws
+    if finished is not None:
+        if finished.dtype == torch.bool:
+            finished = finished.view(torch.uint8)
+        if finished.dtype != torch.uint8 or tuple(finished.shape) != (n,) or not finished.is_contiguous() or finished.device != logits.device:
+            raise ValueError(f"sample_tokens: finished must be a dense uint8 / bool [{n}] tensor on {logits.device}")
+        if eos_token_id is not None and pad_token_id is None:
+            raise ValueError("sample_tokens: eos_token_id needs a pad_token_id")
+    elif eos_token_id is not None:
+        raise ValueError("sample_tokens: eos_token_id needs the finished buffer")
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=logits.device)
+    elif out.dtype != torch.int64 or out.dim() != 1 or out.shape[0] != n or (n > 1 and out.stride(0) < 1) or out.device != logits.device:
+        raise ValueError(f"sample_tokens: out {out.dtype}{tuple(out.shape)}/{out.stride()} must be an int64 [{n}] view with a positive "
+                         f"stride on {logits.device}")
+    kept = torch.empty(rows, dtype=torch.int32, device=logits.device) if return_kept else None
+    _lib.call("mmgl_sample_tokens", dict(bytes=float(rows) * V * logits.element_size()), ptr(logits), logits.stride(0), ptr(u), ptr(out),
+              max(out.stride(0), 1), ptr(finished), ptr(kept), rows, n_draws, V, temperature, top_k, top_p,
+              -1 if eos_token_id is None else int(eos_token_id), 0 if pad_token_id is None else int(pad_token_id), code, stream_ptr())
+    return (out, kept) if return_kept else out
+
+
 class BeamBook:
     """The bookkeeping state of a beam search over B samples x W beams, all on the device (ops.beam_advance moves it one step):
       tokens int64 / parents int32 / beam_score fp32 [B*W]   the running beams of the last step (slot order = candidate order)
