@@ -543,6 +543,31 @@ int mmgl_sample_tokens(const void* logits, size_t ld_logits, const float* u, int
                        int* kept, int rows, int n_draws, int V, float temperature, int top_k, float top_p, int eos_token_id,
                        int64_t pad_token_id, int dtype, void* stream);
 
+/* ---- logits processors (generate(repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens)), one launch ----------
+ * replaces: transformers' RepetitionPenaltyLogitsProcessor -> NoRepeatNGramLogitsProcessor -> MinNewTokensLengthLogitsProcessor ->
+ *           SuppressTokensLogitsProcessor (three to five aten launches each, on [rows, V] or [rows, L] intermediates)
+ *
+ * mmgl_logits_process: rewrites, in place, at most hist_len + n_ban elements per row of logits [rows, V] (bf16 / fp32, row stride
+ * ld_logits >= V elements).  The row's history h[0..L) is the row of `history` (int64 [rows, hist_len], ANY row stride ld_history
+ * in elements, 0 and strided views included) with the columns c < n_masked whose hist_valid[row * ld_valid + c] is 0 removed;
+ * columns from n_masked on are always valid.  hist_valid may be NULL with n_masked = 0, history may be NULL with hist_len = 0.
+ * On x = the row, in this order:
+ *   1. repetition_penalty p (1: off): for every DISTINCT token t of the history, x[t] = x[t] * p if x[t] < 0 else x[t] / p, in fp32
+ *      (one IEEE division), rounded once to the logits' dtype.  A token that occurs several times is penalised once.
+ *   2. no_repeat_ngram_size n (0: off): with pre = h[L-n+1 .. L) (empty for n = 1), x[h[i+n-1]] = -inf for every i in [0, L-n]
+ *      with h[i .. i+n-1) == pre.  Nothing while L < n.
+ *   3. x[t] = -inf for the n_ban tokens of `ban` (int32, device memory; NULL with n_ban = 0).  -inf wins over a penalised value.
+ * A history or ban token outside [0, V) is never an address; such a history token keeps its place in the sequence and equals
+ * nothing, so an n-gram that contains it neither matches nor bans.  Every other logit, and the columns between V and ld_logits, keep
+ * their bits.  Two runs are bitwise equal.
+ *   hist_len <= 8192, n_ban <= 64, V <= 131072, else MMGL_ERR_UNSUPPORTED.  MMGL_ERR_INVALID: a null pointer, rows <= 0, ld_logits < V,
+ *   a non-positive or non-finite penalty, negative n / n_ban / n_masked / hist_len, n_masked > hist_len, a bad dtype.  A refused call
+ *   writes nothing; a call with everything off (p = 1 and n = 0, or hist_len = 0, and n_ban = 0) launches nothing.
+ *   One workgroup per row, no workspace, no atomics on global memory, no host synchronisation.  Plain vector stores only. */
+int mmgl_logits_process(void* logits, size_t ld_logits, const int64_t* history, size_t ld_history, const uint8_t* hist_valid,
+                        size_t ld_valid, int n_masked, int hist_len, const int* ban, int n_ban, int rows, int V,
+                        float repetition_penalty, int no_repeat_ngram_size, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,7 @@ SIGNATURES = {
     "mmgl_beam_topk": (I, [P, Z, P, P, P, P, Z, I, I, I, I, I, P]),
     "mmgl_beam_advance": (I, [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P]),
     "mmgl_sample_tokens": (I, [P, Z, P, P, L, P, P, I, I, I, F, I, F, I, L, I, P]),
+    "mmgl_logits_process": (I, [P, Z, P, Z, P, Z, I, I, P, I, I, I, F, I, I, P]),
 }
 
 _lib = None

@@ -76,4 +76,5 @@ int mmgl_num_cu() {
 // 110: mmgl_attn_decode_beam_fwd / mmgl_beam_topk(_workspace) / mmgl_beam_advance (beam search on a beam-shared cache).
 // mmgl_sample_tokens (sampling for generate()) was added at 110 without a bump: no existing signature changed, and the binding
 // resolves every declared symbol at load, so a library built without it is refused all the same.
+// mmgl_logits_process (repetition penalty, n-gram and token bans for generate()) was added at 110 the same way.
 extern "C" int mmgl_version(void) { return 110; }

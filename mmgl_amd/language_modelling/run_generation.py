@@ -40,7 +40,8 @@ def _f(default, help_):
 @dataclass
 class Arguments:
     """Same field names and defaults as the reference's Arguments (:66-229) + `neighbor_layer_wise` + `num_beams` + the sampling knobs
-    `do_sample` / `temperature` / `top_k` / `top_p`."""
+    `do_sample` / `temperature` / `top_k` / `top_p` + the logits processors `repetition_penalty` / `no_repeat_ngram_size` /
+    `min_new_tokens`."""
     overwrite_cache: Optional[bool] = _f(False, "Overwrite the cached preprocessed datasets or not.")
     dataset: Optional[str] = _f("wikiweb2m", "The name of the dataset to use.")
     task: Optional[str] = _f("section", "One of three generation tasks in WikiWeb2M")
@@ -102,6 +103,9 @@ class Arguments:
     temperature: float = _f(1.0, "sampling temperature (do_sample)")
     top_k: int = _f(0, "keep the k most likely tokens (do_sample); 0 = off")
     top_p: float = _f(1.0, "nucleus sampling: the smallest set of tokens with this probability mass (do_sample); 1 = off")
+    repetition_penalty: float = _f(1.0, "repetition penalty of the test protocol's generate(); 1 = off")
+    no_repeat_ngram_size: int = _f(0, "no n-gram of this size occurs twice in the test protocol's generations; 0 = off")
+    min_new_tokens: int = _f(0, "the end-of-sequence token is banned for this many new tokens in the test protocol's generate()")
     peft_type: str = _f("none", "peft type: none, prefix, prompt, lora, flamingo")
     lora_r: int = _f(64, "lora row rank")
     lora_alpha: float = _f(1, "lora scaling factor")
@@ -630,6 +634,12 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                 if getattr(args, "do_sample", False):                   # sampling; the default protocol stays greedy
                     fields.update(do_sample=True, temperature=float(args.temperature), top_k=int(args.top_k), top_p=float(args.top_p),
                                   seed=getattr(args, "seed", None))
+                if float(getattr(args, "repetition_penalty", 1.0)) != 1.0:      # logits processors; the default protocol has none
+                    fields["repetition_penalty"] = float(args.repetition_penalty)
+                if int(getattr(args, "no_repeat_ngram_size", 0)) != 0:
+                    fields["no_repeat_ngram_size"] = int(args.no_repeat_ngram_size)
+                if int(getattr(args, "min_new_tokens", 0)) != 0:
+                    fields["min_new_tokens"] = int(args.min_new_tokens)
                 generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),
                                                attention_mask=batch["attention_mask"][:, :L_in].contiguous(), **fields,
                                                host_meta=extra.get("host_meta"), max_new_tokens=32,

@@ -38,7 +38,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from .. import ops
 from .encoders import ClipTextEncoder, PackedTextEncoder, PackedVisionEncoder
-from .sampling import check_sampling, sampling_u
+from .sampling import check_processors, check_sampling, sampling_u
 
 CROSS_MODES = ("cross_attention", "embedding")
 
@@ -881,6 +881,28 @@ def lm_head_loss_and_logits(module, lm_head, hidden, next_labels, return_logits=
     return loss, logits
 
 
+def _bind_processors(proc, ids, prompt_mask, history_ids, history_mask, repeat=1):
+    """Per-generation setup of the logits processors (sampling.LogitsProcessors) for a result buffer ids [rows, T + n_new].  Returns
+    (hist, ids): hist is the buffer whose leading columns are each step's history -- ids itself, or, for an embeddings prompt with
+    history_ids [B, Th], a new [B, Th + n_new] buffer that starts with them and whose last n_new columns become `ids`."""
+    if history_ids is None:
+        if history_mask is not None:
+            raise ValueError("generate(): history_mask without history_ids")
+        proc.bind(ids.device, prompt_mask, repeat)
+        return ids, ids
+    B, n_new = ids.shape
+    if (not torch.is_tensor(history_ids) or history_ids.dtype != torch.int64 or history_ids.dim() != 2 or history_ids.shape[0] != B
+            or history_ids.device != ids.device):
+        raise ValueError(f"generate(): history_ids must be an int64 [{B}, Th] tensor on {ids.device}")
+    Th = history_ids.shape[1]
+    if history_mask is not None and (tuple(history_mask.shape) != (B, Th) or history_mask.device != ids.device):
+        raise ValueError(f"generate(): history_mask must be a [{B}, {Th}] tensor on {ids.device}")
+    hist = torch.empty(B, Th + n_new, dtype=torch.int64, device=ids.device)
+    hist[:, :Th] = history_ids
+    proc.bind(ids.device, history_mask, repeat)
+    return hist, hist[:, Th:]
+
+
 class MPTForCausalLM(MPTPreTrainedModel):
     _tied_weights_keys = ["lm_head.weight"]
 
@@ -962,7 +984,9 @@ class MPTForCausalLM(MPTPreTrainedModel):
     def generate(self, input_ids=None, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
                  eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, inputs_embeds=None,
                  num_beams=1, length_penalty=1.0, early_stopping=False, return_sequences_scores=False, return_beam_trace=False,
-                 num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None):
+                 num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None,
+                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, history_ids=None,
+                 history_mask=None):
         """Greedy decoding (do_sample=False, one beam) with a key/value cache: what the reference's test protocol asks of its
         wrappers (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of
         every layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
@@ -980,7 +1004,15 @@ class MPTForCausalLM(MPTPreTrainedModel):
         length_penalty, early_stopping in {False, True}) -- see _generate_beam; num_beams = 1 is the greedy path above, untouched.
         do_sample=True (one beam): every step draws its token with ops.sample_tokens -- transformers' temperature -> top_k -> top_p
         pipeline and the draw in one launch, see _generate_sample; seed / sample_u fix the uniform numbers; num_return_sequences = R
-        (2..8, input_ids prompts) draws R continuations per prompt on one prefill and returns [B*R, T + max_new_tokens]."""
+        (2..8, input_ids prompts) draws R continuations per prompt on one prefill and returns [B*R, T + max_new_tokens].
+        repetition_penalty, no_repeat_ngram_size, min_new_tokens (needs eos_token_id) and suppress_tokens are transformers' logits
+        processors of those names: with any of them on, every greedy or sampled step makes one ops.process_logits
+        call on its logits in front of the selection, with the returned row so far -- the prompt without its masked columns, then
+        the new tokens -- as history, and return_step_logits returns the processed logits.  At their defaults nothing is added.
+        history_ids / history_mask [B, Th] (with inputs_embeds only): the prompt ids the embeddings stand for, used as history and
+        nothing else; without them the history of an embeddings prompt is the new tokens.  history_mask may have any integer or bool
+        dtype (non-zero: valid).  With every processor at its default there is no history and the two are not read.  num_beams > 1
+        with a processor raises."""
         W = int(num_beams)
         if W < 1:
             raise ValueError(f"generate(): num_beams = {num_beams} must be positive")
@@ -990,6 +1022,10 @@ class MPTForCausalLM(MPTPreTrainedModel):
         R = check_sampling("generate()", do_sample, temperature, top_k, top_p, seed, sample_u, W, num_return_sequences, multi=True)
         if early_stopping not in (True, False):
             raise ValueError(f"generate(): early_stopping = {early_stopping!r} is not implemented (True or False)")
+        proc = check_processors("generate()", repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id,
+                                max_new_tokens, self.config.vocab_size, W, None if input_ids is None else input_ids.dtype)
+        if history_ids is not None and input_ids is not None:
+            raise ValueError("generate(): history_ids / history_mask belong to inputs_embeds prompts; input_ids are their own history")
         if W > 1:
             if inputs_embeds is not None:
                 raise ValueError("generate(): beam search (num_beams > 1) takes input_ids prompts, not inputs_embeds")
@@ -1003,7 +1039,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
         if do_sample:
             return self._generate_sample(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
                                          pad_token_id, return_step_logits, first_key_valid, inputs_embeds, R, temperature, top_k, top_p,
-                                         seed, sample_u)
+                                         seed, sample_u, proc, history_ids, history_mask)
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("generate() takes exactly one of input_ids and inputs_embeds")
         prompt = input_ids if input_ids is not None else inputs_embeds
@@ -1024,6 +1060,8 @@ class MPTForCausalLM(MPTPreTrainedModel):
                 raise ValueError("generate(): eos_token_id needs a pad_token_id")
         if attention_mask is None:
             attention_mask = torch.ones(B, T, dtype=torch.int64, device=prompt.device)
+        if proc is not None:
+            proc.upload(prompt.device)                         # in front of the prefill: see LogitsProcessors
         out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
                   cache_capacity=min(T + n_new - 1, dec.max_target_positions))
@@ -1033,10 +1071,14 @@ class MPTForCausalLM(MPTPreTrainedModel):
         ids = torch.empty(B, T + n_new, dtype=torch.int64 if input_ids is None else input_ids.dtype, device=prompt.device)
         if input_ids is not None:
             ids[:, :T] = input_ids
+        if proc is not None:
+            hist, ids = _bind_processors(proc, ids, attention_mask if input_ids is not None else None, history_ids, history_mask)
         finished = torch.zeros(B, dtype=torch.bool, device=prompt.device)
         steps = []
         for s in range(n_new):
             logits = self._last_logits(hidden)
+            if proc is not None:
+                proc(logits, hist[:, :hist.shape[1] - n_new + s], s)
             if return_step_logits:
                 steps.append(logits)
             tok = torch.argmax(logits, dim=-1)
@@ -1046,17 +1088,22 @@ class MPTForCausalLM(MPTPreTrainedModel):
             ids[:, T + s] = tok
             if s + 1 < n_new:
                 hidden = dec(input_ids=tok[:, None], past_key_values=cache).last_hidden_state[:, 0]
+        if not ids.is_contiguous():
+            ids = ids.contiguous()                             # the new-token columns of the history buffer (history_ids)
         return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
 
     def _generate_sample(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
-                         pad_token_id, return_step_logits, first_key_valid, inputs_embeds, R, temperature, top_k, top_p, seed, sample_u):
+                         pad_token_id, return_step_logits, first_key_valid, inputs_embeds, R, temperature, top_k, top_p, seed, sample_u,
+                         proc=None, history_ids=None, history_mask=None):
         """generate(do_sample=True): the greedy loop with its argmax / EOS / ids-column tail replaced by one ops.sample_tokens launch
         that writes the ids column and updates the finished flags in place.  The uniform numbers [max_new_tokens,
         rows] are drawn once before the loop (sampling_u).
         R > 1 continuations per prompt: the prompt is prefilled once with B rows into a cache of capacity T, and the cache gets a
         BeamState of R rows per sample whose parent table stays the identity (nobody calls ops.beam_advance) -- R independent rows
         that share the prompt's keys.  The first step draws R tokens from each prefill row, every later step runs the decode kernels
-        at M = B*R rows.  Rows b*R .. b*R + R - 1 of the result belong to prompt b; sample_u is then [max_new_tokens, B*R]."""
+        at M = B*R rows.  Rows b*R .. b*R + R - 1 of the result belong to prompt b; sample_u is then [max_new_tokens, B*R].
+        proc (the logits processors, None: off) rewrites each step's logits in front of the draw; on the first step of R > 1 the R
+        draws of a prompt share its row of logits and the prompt (ids[::R]) as history, afterwards every row has its own."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("generate() takes exactly one of input_ids and inputs_embeds")
         if R > 1 and input_ids is None:
@@ -1079,6 +1126,8 @@ class MPTForCausalLM(MPTPreTrainedModel):
                 raise ValueError("generate(): eos_token_id needs a pad_token_id")
         dev, rows = prompt.device, B * R
         u = sampling_u("generate()", n_new, rows, dev, seed, sample_u)
+        if proc is not None:
+            proc.upload(dev)                                   # in front of the prefill: see LogitsProcessors
         if attention_mask is None:
             attention_mask = torch.ones(B, T, dtype=torch.int64, device=dev)
         out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
@@ -1092,10 +1141,15 @@ class MPTForCausalLM(MPTPreTrainedModel):
         ids = torch.empty(rows, T + n_new, dtype=torch.int64, device=dev)
         if input_ids is not None:
             ids[:, :T] = input_ids if R == 1 else input_ids.repeat_interleave(R, dim=0)
+        if proc is not None:
+            hist, ids = _bind_processors(proc, ids, attention_mask if input_ids is not None else None, history_ids, history_mask, R)
         finished = torch.zeros(rows, dtype=torch.uint8, device=dev) if eos_token_id is not None else None
         steps = []
         for s in range(n_new):
             logits = self._last_logits(hidden)                 # step 0 of R > 1: the prefill's B rows, R draws each
+            if proc is not None:
+                shared = R if logits.shape[0] != rows else 1
+                proc(logits, hist[::shared, :hist.shape[1] - n_new + s], s, shared)
             if return_step_logits:
                 steps.append(logits if logits.shape[0] == rows else logits.repeat_interleave(R, dim=0))
             col = ids[:, T + s]
@@ -1104,6 +1158,8 @@ class MPTForCausalLM(MPTPreTrainedModel):
                 hidden = dec(input_ids=col[:, None], past_key_values=cache).last_hidden_state[:, 0]
         if input_ids is not None:
             ids = ids.to(input_ids.dtype)
+        elif not ids.is_contiguous():
+            ids = ids.contiguous()                             # the new-token columns of the history buffer (history_ids)
         return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
 
     def _generate_beam(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
@@ -1482,16 +1538,21 @@ class CrossAttentionModel(nn.Module):
                  neighbor_images_pos_ids=None, image_locations=None, host_meta=None, max_new_tokens=32, eos_token_id=None,
                  pad_token_id=None, return_step_logits=False, num_beams=1, length_penalty=1.0, early_stopping=False,
                  return_sequences_scores=False, return_beam_trace=False, num_return_sequences=1, do_sample=False, temperature=1.0,
-                 top_k=0, top_p=1.0, seed=None, sample_u=None):
+                 top_k=0, top_p=1.0, seed=None, sample_u=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
+                 suppress_tokens=None):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded): the neighbors are encoded and interleaved once, exactly
         as forward does, then MPTForCausalLM.generate runs the prefill and the cached decode steps.  Returns [B, T + max_new_tokens]
         ids (and the step logits with return_step_logits=True).  num_beams, length_penalty, early_stopping, return_sequences_scores and
         return_beam_trace are MPTForCausalLM.generate's beam-search keywords, passed through: the neighbors are still encoded once per
         sample and their tokens stay at B rows.  So are its sampling keywords do_sample, temperature, top_k, top_p, seed, sample_u and
-        num_return_sequences (R continuations per prompt also read the prompt's neighbor tokens once)."""
+        num_return_sequences (R continuations per prompt also read the prompt's neighbor tokens once), and its logits processors
+        repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens (history: input_ids without the masked columns,
+        then the new tokens)."""
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the OPT fork only, not for {type(self.lm).__name__}")
         check_sampling("generate()", do_sample, temperature, top_k, top_p, seed, sample_u, num_beams, num_return_sequences, multi=True)
+        check_processors("generate()", repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id,
+                         max_new_tokens, self.lm.config.vocab_size, num_beams, input_ids.dtype)
         if not input_ids.is_cuda:
             raise RuntimeError(f"generate() runs on the GPU only (input_ids is on {input_ids.device}); there is no CPU path")
         neighbor_embeds, key_valid = self._neighbor_tokens(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, text_locations,
@@ -1503,4 +1564,5 @@ class CrossAttentionModel(nn.Module):
                                 length_penalty=length_penalty, early_stopping=early_stopping,
                                 return_sequences_scores=return_sequences_scores, return_beam_trace=return_beam_trace,
                                 num_return_sequences=num_return_sequences, do_sample=do_sample, temperature=temperature, top_k=top_k,
-                                top_p=top_p, seed=seed, sample_u=sample_u)
+                                top_p=top_p, seed=seed, sample_u=sample_u, repetition_penalty=repetition_penalty,
+                                no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens)

@@ -21,7 +21,7 @@ from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from .. import ops
 from .modelling_cross_attention import DecodeCache
-from .sampling import check_sampling, sampling_u
+from .sampling import check_processors, check_sampling, sampling_u
 
 
 class LlamaGatedCrossAttentionLayer(nn.Module):
@@ -301,7 +301,8 @@ class LlamaNeighborLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
                  eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, num_beams=1,
-                 num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None):
+                 num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None,
+                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None):
         """Greedy decoding with a key/value cache: the contract of MPTForCausalLM.generate (without inputs_embeds).  One prefill over
         the right-padded prompts [B, T] -- the kernels of forward(), plus the copy of every layer's Hkv key/value heads into a
         DecodeCache -- then max_new_tokens - 1 decode steps; lm_head runs on the last row only.  Every new token is appended at the
@@ -313,11 +314,16 @@ class LlamaNeighborLM(nn.Module):
         do_sample=True: every step draws its token with ops.sample_tokens (temperature -> top_k -> top_p and the draw, one launch that
         writes the ids column and the finished flags) from uniform numbers [max_new_tokens, B] drawn once before the loop -- sample_u
         itself, or torch.rand on a generator seeded with `seed` (None: torch's global device generator).  num_return_sequences > 1 is
-        refused (it needs the beam-shared cache of the OPT fork)."""
+        refused (it needs the beam-shared cache of the OPT fork).
+        repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens: with any of them on, one ops.process_logits call
+        per step rewrites the logits in front of the selection, greedy or sampled, with the returned row so far (the prompt without
+        its masked columns, then the new tokens) as history; return_step_logits returns the processed logits."""
         if int(num_beams) != 1:
             raise ValueError(f"LlamaNeighborLM.generate(): num_beams = {num_beams} is not implemented (beam search runs on the OPT fork "
                              "only); this path is greedy")
         check_sampling("LlamaNeighborLM.generate()", do_sample, temperature, top_k, top_p, seed, sample_u, 1, num_return_sequences)
+        proc = check_processors("LlamaNeighborLM.generate()", repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens,
+                                eos_token_id, max_new_tokens, self.config.vocab_size, 1, input_ids.dtype)
         n_new = int(max_new_tokens)
         if n_new < 1:
             raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
@@ -333,11 +339,15 @@ class LlamaNeighborLM(nn.Module):
             pad_token_id = self.config.pad_token_id
             if pad_token_id is None:
                 raise ValueError("generate(): eos_token_id needs a pad_token_id")
+        if proc is not None:
+            proc.upload(input_ids.device)                      # in front of the prefill: see LogitsProcessors
         hidden, cache = self._hidden(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid, True,
                                      T + n_new - 1)
         hidden = hidden[:, -1]
         ids = torch.empty(B, T + n_new, dtype=input_ids.dtype, device=input_ids.device)
         ids[:, :T] = input_ids
+        if proc is not None:
+            proc.bind(input_ids.device, attention_mask)
         if do_sample:
             if ids.dtype != torch.int64:
                 raise ValueError(f"generate(do_sample=True): input_ids must be int64, got {ids.dtype}")
@@ -346,6 +356,8 @@ class LlamaNeighborLM(nn.Module):
             steps = []
             for s in range(n_new):
                 logits = self._last_logits(hidden)
+                if proc is not None:
+                    proc(logits, ids[:, :T + s], s)
                 if return_step_logits:
                     steps.append(logits)
                 col = ids[:, T + s]
@@ -357,6 +369,8 @@ class LlamaNeighborLM(nn.Module):
         steps = []
         for s in range(n_new):
             logits = self._last_logits(hidden)
+            if proc is not None:
+                proc(logits, ids[:, :T + s], s)
             if return_step_logits:
                 steps.append(logits)
             tok = torch.argmax(logits, dim=-1)

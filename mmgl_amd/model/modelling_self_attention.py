@@ -27,7 +27,7 @@ from .. import ops
 from .encoders import PackedTextEncoder, PackedVisionEncoder
 from .graph import GCN
 from .modelling_cross_attention import TextPooler
-from .sampling import check_sampling
+from .sampling import check_processors, check_sampling
 
 NUM_VIRTUAL_TOKENS = 20
 
@@ -356,7 +356,8 @@ class SelfAttentionModel(nn.Module):
                  neighbor_attention_mask=None, neighbor_pos_ids=None, text_locations=None, neighbor_images=None,
                  neighbor_images_pos_ids=None, image_locations=None, lpe=None, graph=None, host_meta=None, max_new_tokens=32,
                  eos_token_id=None, pad_token_id=None, return_step_logits=False, num_beams=1, num_return_sequences=1, do_sample=False,
-                 temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None):
+                 temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                 min_new_tokens=0, suppress_tokens=None):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded).  The LM input is built exactly as forward builds it
         (_lm_inputs), then MPTForCausalLM.generate runs the prefill and the cached decode steps (LoRA-adapted q / v projections on
         ops.decode_lora_linear).  New tokens are appended behind the whole LM input:
@@ -366,7 +367,10 @@ class SelfAttentionModel(nn.Module):
         [B, max_new_tokens, V] step logits with return_step_logits=True.  num_beams > 1 is refused: beam search takes input_ids
         prompts and plain projections (CrossAttentionModel / MPTForCausalLM), this wrapper generates from embeddings.
         do_sample, temperature, top_k, top_p, seed and sample_u are MPTForCausalLM.generate's sampling keywords, passed through;
-        num_return_sequences > 1 is refused for the same reason as beams."""
+        num_return_sequences > 1 is refused for the same reason as beams.  So are its logits processors repetition_penalty,
+        no_repeat_ngram_size, min_new_tokens and suppress_tokens; in either mode their history is the returned row so far, input_ids
+        without the masked columns and then the new tokens (embedding mode hands input_ids / attention_mask over as history_ids /
+        history_mask: virtual, image and neighbor tokens are no part of it)."""
         if int(num_beams) != 1:
             raise ValueError(f"SelfAttentionModel.generate(): num_beams = {num_beams} is not implemented (beam search runs on "
                              "CrossAttentionModel / MPTForCausalLM with input_ids prompts); this path is greedy")
@@ -374,6 +378,8 @@ class SelfAttentionModel(nn.Module):
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the decoder-only OPT fork with peft_type none / lora / prompt, not for "
                              f"{type(self.lm).__name__} with peft_type {self.args.peft_type!r}")
+        proc = check_processors("SelfAttentionModel.generate()", repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens,
+                                eos_token_id, max_new_tokens, self.lm.config.vocab_size, 1, input_ids.dtype)
         if not input_ids.is_cuda:
             raise RuntimeError(f"generate() runs on the GPU only (input_ids is on {input_ids.device}); there is no CPU path")
         T = input_ids.shape[1]
@@ -389,8 +395,13 @@ class SelfAttentionModel(nn.Module):
                   first_key_valid=first)
         if do_sample:
             kw.update(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, sample_u=sample_u)
+        if proc is not None:
+            kw.update(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens,
+                      suppress_tokens=suppress_tokens)
         if lm_input.dim() == 2:
             return self.lm.generate(lm_input, lm_mask, **kw)
+        if proc is not None:
+            kw.update(history_ids=input_ids, history_mask=attention_mask)
         out = self.lm.generate(inputs_embeds=lm_input, attention_mask=lm_mask, **kw)
         new, logits = out if return_step_logits else (out, None)
         ids = torch.cat([input_ids, new.to(input_ids.dtype)], dim=1)

@@ -1829,6 +1829,76 @@ def sample_tokens(logits, u, temperature=1.0, top_k=0, top_p=1.0, finished=None,
     return (out, kept) if return_kept else out
 
 
+MAX_HISTORY, MAX_BAN = 8192, 64
+
+
+def process_logits(logits, history, history_valid=None, n_masked=None, repetition_penalty=1.0, no_repeat_ngram_size=0, ban=None):
+    """The logits processors of generate() in one launch (mmgl_logits_process), in place on logits [rows, V] (bf16 / fp32, unit column
+    stride, any row stride; V <= 131072): transformers' RepetitionPenalty -> NoRepeatNGram -> (MinNewTokensLength, SuppressTokens as
+    `ban`) chain.  history: int64 [rows, L] (unit column stride, ANY row stride -- ids[::R] serves R draws that share a prompt;
+    L <= 8192; None: no history), the tokens in front of the column being chosen.  history_valid: bool / uint8 [rows, >= n_masked]
+    over the first n_masked columns (default: all of its columns); a column it marks 0 is not part of the history, columns from
+    n_masked on always are.  Per row, on its history h[0..L'):
+      repetition_penalty p (1: off)     x[t] = x[t] * p if x[t] < 0 else x[t] / p, once per distinct token t, fp32, rounded once
+      no_repeat_ngram_size n (0: off)   x[h[i+n-1]] = -inf wherever h[i .. i+n-1) equals the last n-1 tokens
+      ban (int32 device tensor [n_ban <= 64], None: none)   x[t] = -inf
+    in this order (-inf wins).  A token outside [0, V) is never an address.  Every other element keeps its bits.  Returns `logits`.
+    Nothing is launched when everything is off.  No host synchronisation, bitwise reproducible.  Forward only; GPU only."""
+    require_cuda(logits, history, history_valid, ban)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] == 0 or logits.shape[1] == 0:
+        raise ValueError(f"process_logits: logits{tuple(logits.shape)}/{logits.stride()} must be [rows, V] with unit column stride")
+    rows, V = logits.shape
+    code = dtype_code(logits)
+    if V > 131072:
+        raise ValueError(f"process_logits: V = {V} (at most 131072)")
+    p, n = float(repetition_penalty), int(no_repeat_ngram_size)
+    if not (0.0 < p < float("inf")):
+        raise ValueError(f"process_logits: repetition_penalty = {repetition_penalty} must be positive and finite")
+    if n < 0:
+        raise ValueError(f"process_logits: no_repeat_ngram_size = {no_repeat_ngram_size} must not be negative (0: off)")
+    L = 0
+    if history is not None:
+        if (history.dtype != torch.int64 or history.dim() != 2 or history.shape[0] != rows or (history.shape[1] > 1 and history.stride(1) != 1)
+                or history.stride(0) < 0 or history.device != logits.device):
+            raise ValueError(f"process_logits: history {history.dtype}{tuple(history.shape)}/{history.stride()} must be an int64 "
+                             f"[{rows}, L] view with unit column stride on {logits.device}")
+        L = history.shape[1]
+        if L > MAX_HISTORY:
+            raise ValueError(f"process_logits: history of {L} columns (at most {MAX_HISTORY})")
+    if history_valid is None:
+        if n_masked not in (None, 0):
+            raise ValueError(f"process_logits: n_masked = {n_masked} without history_valid")
+        n_masked = 0
+    else:
+        if history_valid.dtype == torch.bool:
+            history_valid = history_valid.view(torch.uint8)
+        if (history_valid.dtype != torch.uint8 or history_valid.dim() != 2 or history_valid.shape[0] != rows
+                or (history_valid.shape[1] > 1 and history_valid.stride(1) != 1) or history_valid.stride(0) < 0
+                or history_valid.device != logits.device):
+            raise ValueError(f"process_logits: history_valid {history_valid.dtype}{tuple(history_valid.shape)}/{history_valid.stride()} must "
+                             f"be a bool / uint8 [{rows}, n_masked] view with unit column stride on {logits.device}")
+        n_masked = history_valid.shape[1] if n_masked is None else int(n_masked)
+        if not 0 <= n_masked <= min(L, history_valid.shape[1]):
+            raise ValueError(f"process_logits: n_masked = {n_masked} outside [0, min(history columns {L}, mask columns "
+                             f"{history_valid.shape[1]})]")
+        if n_masked == 0:
+            history_valid = None
+    n_ban = 0
+    if ban is not None:
+        if ban.dtype != torch.int32 or ban.dim() != 1 or not ban.is_contiguous() or ban.device != logits.device:
+            raise ValueError(f"process_logits: ban {ban.dtype}{tuple(ban.shape)} must be a dense int32 [n_ban] tensor on {logits.device}")
+        n_ban = ban.shape[0]
+        if n_ban > MAX_BAN:
+            raise ValueError(f"process_logits: {n_ban} banned tokens (at most {MAX_BAN})")
+    if n_ban == 0 and (L == 0 or (p == 1.0 and n == 0)):
+        return logits
+    _lib.call("mmgl_logits_process", dict(bytes=float(rows) * (L * 8 + (L + n_ban) * logits.element_size())), ptr(logits), logits.stride(0),
+              ptr(history) if L else None, history.stride(0) if L else 0, ptr(history_valid),
+              history_valid.stride(0) if history_valid is not None else 0, n_masked, L, ptr(ban) if n_ban else None, n_ban, rows, V, p, n,
+              code, stream_ptr())
+    return logits
+
+
 class BeamBook:
     """The bookkeeping state of a beam search over B samples x W beams, all on the device (ops.beam_advance moves it one step):
       tokens int64 / parents int32 / beam_score fp32 [B*W]   the running beams of the last step (slot order = candidate order)
