@@ -1,0 +1,140 @@
+"""The decode loop of generate(), once, for the three language models (MPTForCausalLM under CrossAttentionModel and SelfAttentionModel,
+LlamaNeighborLM): the prompt check, the two selection tails and the loop "logits -> (processors) -> (keep the step's logits) ->
+select -> write the ids column -> one cached decode step".  A model's generate() validates its keywords (sampling.py), checks the
+prompt (check_prompt), picks a tail, runs its prefill and hands decode_loop three things: its _last_logits, a callable for one cached
+decode step (tokens [rows, 1] -> hidden [rows, d]) and the prefill's last hidden row.  Beam search (MPTForCausalLM._generate_beam) has
+a loop of another shape and shares only check_prompt.
+
+Semantics, the same for every model:
+  * Prompts are right-padded to the common width T; every new token is appended at the same column for all rows, and all
+    max_new_tokens steps run (nothing synchronises with the host to stop early).  The result is [rows, T + max_new_tokens] in the
+    prompt's dtype; an embeddings prompt has no ids to repeat, so only the new tokens [rows, max_new_tokens] (int64) come back.
+  * eos_token_id: a row that has emitted it gets pad_token_id (default config.pad_token_id) from then on, as in transformers' loops;
+    None: no end-of-sequence handling.
+  * Greedy (GreedyTail): argmax of the step's logits.  Sampled (SampledTail): transformers' temperature -> top_k -> top_p pipeline
+    and the draw in one ops.sample_tokens launch that writes the ids column and the finished flags in place, from
+    uniform numbers [max_new_tokens, rows] drawn once before the loop (sampling.sampling_u).
+  * R = num_return_sequences > 1: the model prefills B rows and gives its cache a BeamState of R rows per prompt whose parent table
+    stays the identity -- R independent rows that share the prompt's keys.  Step 0 draws R tokens from each of the B logits rows,
+    every later step has B*R rows.  Rows b*R .. b*R + R - 1 of the result belong to prompt b.
+  * proc (sampling.LogitsProcessors, None: off -- then nothing is added): one ops.process_logits call per step rewrites the logits
+    in front of the selection, with the returned row so far -- the prompt without its masked columns, then the new
+    tokens -- as history; on step 0 of R > 1 the R draws of a prompt share its logits row and the prompt as history.  An embeddings
+    prompt may name the ids it stands for (history_ids / history_mask [B, Th]); without them its history is the new tokens.
+  * return_step_logits: also the [rows, max_new_tokens, V] logits the tokens were picked from (the processed ones with proc)."""
+import torch
+
+from .. import ops
+
+
+def check_prompt(input_ids, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, config, max_positions):
+    """The prompt arguments of every generate(): either input_ids [B, T] or inputs_embeds [B, T, d_embed], on the GPU, with
+    T + max_new_tokens - 1 positions inside the model's table.  Returns (B, T, n_new, pad_token_id, attention_mask) with the defaults
+    filled in: pad_token_id from `config` when there is an EOS, a mask of ones."""
+    if (input_ids is None) == (inputs_embeds is None):
+        raise ValueError("generate() takes exactly one of input_ids and inputs_embeds")
+    prompt = input_ids if input_ids is not None else inputs_embeds
+    n_new = int(max_new_tokens)
+    if n_new < 1:
+        raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
+    if not prompt.is_cuda:
+        raise RuntimeError(f"generate() runs on the GPU only (the prompt is on {prompt.device}); there is no CPU path")
+    if prompt.dim() != (2 if input_ids is not None else 3):
+        raise ValueError(f"generate(): input_ids [B, T] or inputs_embeds [B, T, d_embed], got {tuple(prompt.shape)}")
+    B, T = prompt.shape[:2]
+    if T + n_new - 1 > max_positions:
+        raise ValueError(f"generate(): {T} prompt columns + {n_new} new tokens exceed max_position_embeddings {max_positions}")
+    if eos_token_id is not None and pad_token_id is None:
+        pad_token_id = config.pad_token_id
+        if pad_token_id is None:
+            raise ValueError("generate(): eos_token_id needs a pad_token_id")
+    if attention_mask is None:
+        attention_mask = torch.ones(B, T, dtype=torch.int64, device=prompt.device)
+    return B, T, n_new, pad_token_id, attention_mask
+
+
+class GreedyTail:
+    """select(logits, ids, c, s): argmax, the EOS bookkeeping, then the write of column c.  Returns the tokens [rows]."""
+    ids_dtype = None                                           # the column write casts: ids are allocated in the prompt's dtype
+
+    def __init__(self, rows, device, eos_token_id=None, pad_token_id=None):
+        self.eos, self.pad = eos_token_id, pad_token_id
+        self.finished = torch.zeros(rows, dtype=torch.bool, device=device)
+
+    def __call__(self, logits, ids, c, s):
+        tok = torch.argmax(logits, dim=-1)
+        if self.eos is not None:
+            tok = torch.where(self.finished, torch.full_like(tok, self.pad), tok)
+            self.finished = self.finished | (tok == self.eos)
+        ids[:, c] = tok
+        return tok
+
+
+class SampledTail:
+    """select(logits, ids, c, s): one ops.sample_tokens launch on u[s] (u fp32 [n_new, rows], sampling.sampling_u) that writes
+    column c and the finished flags in place.  Returns the column."""
+    ids_dtype = torch.int64                                    # the kernel writes the int64 column itself
+
+    def __init__(self, u, temperature, top_k, top_p, eos_token_id=None, pad_token_id=None):
+        self.u, self.knobs, self.eos, self.pad = u, (temperature, top_k, top_p), eos_token_id, pad_token_id
+        self.finished = torch.zeros(u.shape[1], dtype=torch.uint8, device=u.device) if eos_token_id is not None else None
+
+    def __call__(self, logits, ids, c, s):
+        col = ids[:, c]
+        ops.sample_tokens(logits, self.u[s].view(logits.shape[0], -1), *self.knobs, self.finished, self.eos, self.pad, out=col)
+        return col
+
+
+def _bind_processors(proc, ids, prompt_mask, history_ids, history_mask, repeat=1):
+    """Per-generation setup of the logits processors (sampling.LogitsProcessors) for a result buffer ids [rows, T + n_new].  Returns
+    (hist, ids): hist is the buffer whose leading columns are each step's history -- ids itself, or, for an embeddings prompt with
+    history_ids [B, Th], a new [B, Th + n_new] buffer that starts with them and whose last n_new columns become `ids`."""
+    if history_ids is None:
+        if history_mask is not None:
+            raise ValueError("generate(): history_mask without history_ids")
+        proc.bind(ids.device, prompt_mask, repeat)
+        return ids, ids
+    B, n_new = ids.shape
+    if (not torch.is_tensor(history_ids) or history_ids.dtype != torch.int64 or history_ids.dim() != 2 or history_ids.shape[0] != B
+            or history_ids.device != ids.device):
+        raise ValueError(f"generate(): history_ids must be an int64 [{B}, Th] tensor on {ids.device}")
+    Th = history_ids.shape[1]
+    if history_mask is not None and (tuple(history_mask.shape) != (B, Th) or history_mask.device != ids.device):
+        raise ValueError(f"generate(): history_mask must be a [{B}, {Th}] tensor on {ids.device}")
+    hist = torch.empty(B, Th + n_new, dtype=torch.int64, device=ids.device)
+    hist[:, :Th] = history_ids
+    proc.bind(ids.device, history_mask, repeat)
+    return hist, hist[:, Th:]
+
+
+def decode_loop(last_logits, step, hidden, select, n_new, input_ids=None, prompt_mask=None, R=1, proc=None, history_ids=None,
+                history_mask=None, return_step_logits=False):
+    """The n_new steps behind a prefill whose last row is `hidden` [B, ...]: see the module docstring.  last_logits(hidden) ->
+    [rows, V]; step(tokens [rows, 1]) -> the next hidden, called n_new - 1 times; select: a GreedyTail or a SampledTail over B*R
+    rows; input_ids [B, T]: the prompt to return in front of the new tokens (None: an embeddings prompt); prompt_mask [B, T]: its
+    valid columns, read by proc only.  Returns ids, or (ids, step logits)."""
+    rows = hidden.shape[0] * R
+    T = 0 if input_ids is None else input_ids.shape[1]       # columns of the result in front of the new tokens
+    ids = torch.empty(rows, T + n_new, dtype=select.ids_dtype or (torch.int64 if input_ids is None else input_ids.dtype),
+                      device=hidden.device)
+    if input_ids is not None:
+        ids[:, :T] = input_ids if R == 1 else input_ids.repeat_interleave(R, dim=0)
+    if proc is not None:
+        hist, ids = _bind_processors(proc, ids, prompt_mask if input_ids is not None else None, history_ids, history_mask, R)
+        Th = hist.shape[1] - n_new                             # step s chooses column Th + s of hist
+    steps = []
+    for s in range(n_new):
+        logits = last_logits(hidden)
+        shared = rows // logits.shape[0]                       # R on step 0 of R > 1 (the prefill's B rows, R draws each), else 1
+        if proc is not None:
+            proc(logits, hist[::shared, :Th + s], s, shared)
+        if return_step_logits:
+            steps.append(logits if shared == 1 else logits.repeat_interleave(shared, dim=0))
+        tok = select(logits, ids, T + s, s)
+        if s + 1 < n_new:
+            hidden = step(tok[:, None])
+    if input_ids is not None:
+        ids = ids.to(input_ids.dtype)
+    elif not ids.is_contiguous():
+        ids = ids.contiguous()                                 # the new-token columns of the history buffer (history_ids)
+    return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids

@@ -38,6 +38,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from .. import ops
 from .encoders import ClipTextEncoder, PackedTextEncoder, PackedVisionEncoder
+from .generation import GreedyTail, SampledTail, check_prompt, decode_loop
 from .sampling import check_processors, check_sampling, sampling_u
 
 CROSS_MODES = ("cross_attention", "embedding")
@@ -881,28 +882,6 @@ def lm_head_loss_and_logits(module, lm_head, hidden, next_labels, return_logits=
     return loss, logits
 
 
-def _bind_processors(proc, ids, prompt_mask, history_ids, history_mask, repeat=1):
-    """Per-generation setup of the logits processors (sampling.LogitsProcessors) for a result buffer ids [rows, T + n_new].  Returns
-    (hist, ids): hist is the buffer whose leading columns are each step's history -- ids itself, or, for an embeddings prompt with
-    history_ids [B, Th], a new [B, Th + n_new] buffer that starts with them and whose last n_new columns become `ids`."""
-    if history_ids is None:
-        if history_mask is not None:
-            raise ValueError("generate(): history_mask without history_ids")
-        proc.bind(ids.device, prompt_mask, repeat)
-        return ids, ids
-    B, n_new = ids.shape
-    if (not torch.is_tensor(history_ids) or history_ids.dtype != torch.int64 or history_ids.dim() != 2 or history_ids.shape[0] != B
-            or history_ids.device != ids.device):
-        raise ValueError(f"generate(): history_ids must be an int64 [{B}, Th] tensor on {ids.device}")
-    Th = history_ids.shape[1]
-    if history_mask is not None and (tuple(history_mask.shape) != (B, Th) or history_mask.device != ids.device):
-        raise ValueError(f"generate(): history_mask must be a [{B}, {Th}] tensor on {ids.device}")
-    hist = torch.empty(B, Th + n_new, dtype=torch.int64, device=ids.device)
-    hist[:, :Th] = history_ids
-    proc.bind(ids.device, history_mask, repeat)
-    return hist, hist[:, Th:]
-
-
 class MPTForCausalLM(MPTPreTrainedModel):
     _tied_weights_keys = ["lm_head.weight"]
 
@@ -987,32 +966,19 @@ class MPTForCausalLM(MPTPreTrainedModel):
                  num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, history_ids=None,
                  history_mask=None):
-        """Greedy decoding (do_sample=False, one beam) with a key/value cache: what the reference's test protocol asks of its
-        wrappers (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of
-        every layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
-        ops.attn_decode); lm_head runs on the last row only.
-        Prompts are right-padded to the common width T (the layout the model is trained on: the summary starts at column
-        max_input_length); every new token is appended at the same column for all samples and the pad keys stay masked.
-        eos_token_id: a row that has emitted it gets pad_token_id (default config.pad_token_id) from then on, as in HF's greedy loop;
-        None: no end-of-sequence handling.  All max_new_tokens steps run (no host synchronisation to stop early).
-        Returns the [B, T + max_new_tokens] ids; with return_step_logits=True also the [B, max_new_tokens, V] logits the tokens
-        were picked from.
+        """Generation with a key/value cache: what the reference's test protocol asks of its wrappers
+        (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of every
+        layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
+        ops.attn_decode); lm_head runs on the last row only.  Prompts are right-padded to the common width T (the layout the model
+        is trained on: the summary starts at column max_input_length) and the pad keys stay masked.
+        The loop and the semantics of eos_token_id / pad_token_id, do_sample with its knobs, num_return_sequences, the logits
+        processors, history_ids / history_mask and return_step_logits are generation.decode_loop's: see that module.  Here:
         inputs_embeds [B, T, d_embed] instead of input_ids (exactly one of the two): the prefill runs on the embeddings (virtual
-        tokens, image or neighbor tokens already in the sequence); there are no prompt ids to repeat, so only the new tokens
-        [B, max_new_tokens] come back (HF's convention for inputs_embeds).
+        tokens, image or neighbor tokens already in the sequence) and only the new tokens come back; history_ids belong to it.
+        num_return_sequences = R (2..8) needs do_sample=True and an input_ids prompt: one prefill of B rows into a cache of
+        capacity T, then steps of B*R rows on the beam-shared cache; sample_u is then [max_new_tokens, B*R].
         num_beams = W > 1 (at most 8): beam search with the semantics of transformers' generate(num_beams=W, do_sample=False,
-        length_penalty, early_stopping in {False, True}) -- see _generate_beam; num_beams = 1 is the greedy path above, untouched.
-        do_sample=True (one beam): every step draws its token with ops.sample_tokens -- transformers' temperature -> top_k -> top_p
-        pipeline and the draw in one launch, see _generate_sample; seed / sample_u fix the uniform numbers; num_return_sequences = R
-        (2..8, input_ids prompts) draws R continuations per prompt on one prefill and returns [B*R, T + max_new_tokens].
-        repetition_penalty, no_repeat_ngram_size, min_new_tokens (needs eos_token_id) and suppress_tokens are transformers' logits
-        processors of those names: with any of them on, every greedy or sampled step makes one ops.process_logits
-        call on its logits in front of the selection, with the returned row so far -- the prompt without its masked columns, then
-        the new tokens -- as history, and return_step_logits returns the processed logits.  At their defaults nothing is added.
-        history_ids / history_mask [B, Th] (with inputs_embeds only): the prompt ids the embeddings stand for, used as history and
-        nothing else; without them the history of an embeddings prompt is the new tokens.  history_mask may have any integer or bool
-        dtype (non-zero: valid).  With every processor at its default there is no history and the two are not read.  num_beams > 1
-        with a processor raises."""
+        length_penalty, early_stopping in {False, True}) -- see _generate_beam; input_ids prompts, no sampling, no processor."""
         W = int(num_beams)
         if W < 1:
             raise ValueError(f"generate(): num_beams = {num_beams} must be positive")
@@ -1036,131 +1002,28 @@ class MPTForCausalLM(MPTPreTrainedModel):
                                        return_sequences_scores, return_beam_trace)
         if return_sequences_scores or return_beam_trace:
             raise ValueError("generate(): return_sequences_scores / return_beam_trace belong to beam search (num_beams > 1)")
-        if do_sample:
-            return self._generate_sample(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
-                                         pad_token_id, return_step_logits, first_key_valid, inputs_embeds, R, temperature, top_k, top_p,
-                                         seed, sample_u, proc, history_ids, history_mask)
-        if (input_ids is None) == (inputs_embeds is None):
-            raise ValueError("generate() takes exactly one of input_ids and inputs_embeds")
-        prompt = input_ids if input_ids is not None else inputs_embeds
-        if not prompt.is_cuda:
-            raise RuntimeError(f"generate() runs on the GPU only (the prompt is on {prompt.device}); there is no CPU path")
-        if prompt.dim() != (2 if input_ids is not None else 3):
-            raise ValueError(f"generate(): input_ids [B, T] or inputs_embeds [B, T, d_embed], got {tuple(prompt.shape)}")
-        B, T = prompt.shape[:2]
-        n_new = int(max_new_tokens)
-        if n_new < 1:
-            raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
-        dec = self.model.decoder
-        if T + n_new - 1 > dec.max_target_positions:
-            raise ValueError(f"generate(): {T} prompt columns + {n_new} new tokens exceed max_position_embeddings {dec.max_target_positions}")
-        if eos_token_id is not None and pad_token_id is None:
-            pad_token_id = self.config.pad_token_id
-            if pad_token_id is None:
-                raise ValueError("generate(): eos_token_id needs a pad_token_id")
-        if attention_mask is None:
-            attention_mask = torch.ones(B, T, dtype=torch.int64, device=prompt.device)
-        if proc is not None:
-            proc.upload(prompt.device)                         # in front of the prefill: see LogitsProcessors
-        out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
-                  neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
-                  cache_capacity=min(T + n_new - 1, dec.max_target_positions))
-        cache = out.past_key_values
-        hidden = out.last_hidden_state[:, -1]
-        T = T if input_ids is not None else 0                  # columns of the result in front of the new tokens
-        ids = torch.empty(B, T + n_new, dtype=torch.int64 if input_ids is None else input_ids.dtype, device=prompt.device)
-        if input_ids is not None:
-            ids[:, :T] = input_ids
-        if proc is not None:
-            hist, ids = _bind_processors(proc, ids, attention_mask if input_ids is not None else None, history_ids, history_mask)
-        finished = torch.zeros(B, dtype=torch.bool, device=prompt.device)
-        steps = []
-        for s in range(n_new):
-            logits = self._last_logits(hidden)
-            if proc is not None:
-                proc(logits, hist[:, :hist.shape[1] - n_new + s], s)
-            if return_step_logits:
-                steps.append(logits)
-            tok = torch.argmax(logits, dim=-1)
-            if eos_token_id is not None:
-                tok = torch.where(finished, torch.full_like(tok, pad_token_id), tok)
-                finished = finished | (tok == eos_token_id)
-            ids[:, T + s] = tok
-            if s + 1 < n_new:
-                hidden = dec(input_ids=tok[:, None], past_key_values=cache).last_hidden_state[:, 0]
-        if not ids.is_contiguous():
-            ids = ids.contiguous()                             # the new-token columns of the history buffer (history_ids)
-        return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
-
-    def _generate_sample(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
-                         pad_token_id, return_step_logits, first_key_valid, inputs_embeds, R, temperature, top_k, top_p, seed, sample_u,
-                         proc=None, history_ids=None, history_mask=None):
-        """generate(do_sample=True): the greedy loop with its argmax / EOS / ids-column tail replaced by one ops.sample_tokens launch
-        that writes the ids column and updates the finished flags in place.  The uniform numbers [max_new_tokens,
-        rows] are drawn once before the loop (sampling_u).
-        R > 1 continuations per prompt: the prompt is prefilled once with B rows into a cache of capacity T, and the cache gets a
-        BeamState of R rows per sample whose parent table stays the identity (nobody calls ops.beam_advance) -- R independent rows
-        that share the prompt's keys.  The first step draws R tokens from each prefill row, every later step runs the decode kernels
-        at M = B*R rows.  Rows b*R .. b*R + R - 1 of the result belong to prompt b; sample_u is then [max_new_tokens, B*R].
-        proc (the logits processors, None: off) rewrites each step's logits in front of the draw; on the first step of R > 1 the R
-        draws of a prompt share its row of logits and the prompt (ids[::R]) as history, afterwards every row has its own."""
-        if (input_ids is None) == (inputs_embeds is None):
-            raise ValueError("generate() takes exactly one of input_ids and inputs_embeds")
-        if R > 1 and input_ids is None:
+        if R > 1 and inputs_embeds is not None:
             raise ValueError(f"generate(): num_return_sequences = {R} takes input_ids prompts, not inputs_embeds")
-        prompt = input_ids if input_ids is not None else inputs_embeds
-        if not prompt.is_cuda:
-            raise RuntimeError(f"generate() runs on the GPU only (the prompt is on {prompt.device}); there is no CPU path")
-        if prompt.dim() != (2 if input_ids is not None else 3):
-            raise ValueError(f"generate(): input_ids [B, T] or inputs_embeds [B, T, d_embed], got {tuple(prompt.shape)}")
-        B, T = prompt.shape[:2]
-        n_new = int(max_new_tokens)
-        if n_new < 1:
-            raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
         dec = self.model.decoder
-        if T + n_new - 1 > dec.max_target_positions:
-            raise ValueError(f"generate(): {T} prompt columns + {n_new} new tokens exceed max_position_embeddings {dec.max_target_positions}")
-        if eos_token_id is not None and pad_token_id is None:
-            pad_token_id = self.config.pad_token_id
-            if pad_token_id is None:
-                raise ValueError("generate(): eos_token_id needs a pad_token_id")
-        dev, rows = prompt.device, B * R
-        u = sampling_u("generate()", n_new, rows, dev, seed, sample_u)
+        B, T, n_new, pad_token_id, attention_mask = check_prompt(input_ids, inputs_embeds, attention_mask, max_new_tokens, eos_token_id,
+                                                                 pad_token_id, self.config, dec.max_target_positions)
+        dev = (input_ids if input_ids is not None else inputs_embeds).device
         if proc is not None:
             proc.upload(dev)                                   # in front of the prefill: see LogitsProcessors
-        if attention_mask is None:
-            attention_mask = torch.ones(B, T, dtype=torch.int64, device=dev)
+        if do_sample:
+            select = SampledTail(sampling_u("generate()", n_new, B * R, dev, seed, sample_u), temperature, top_k, top_p, eos_token_id,
+                                 pad_token_id)
+        else:
+            select = GreedyTail(B, dev, eos_token_id, pad_token_id)
         out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
-                  cache_capacity=T if R > 1 else min(T + n_new - 1, dec.max_target_positions))
+                  cache_capacity=T if R > 1 else T + n_new - 1)
         cache = out.past_key_values
         if R > 1:
-            cache.beam = BeamState(cache, R, n_new - 1)
-        hidden = out.last_hidden_state[:, -1]
-        T = T if input_ids is not None else 0                  # columns of the result in front of the new tokens
-        ids = torch.empty(rows, T + n_new, dtype=torch.int64, device=dev)
-        if input_ids is not None:
-            ids[:, :T] = input_ids if R == 1 else input_ids.repeat_interleave(R, dim=0)
-        if proc is not None:
-            hist, ids = _bind_processors(proc, ids, attention_mask if input_ids is not None else None, history_ids, history_mask, R)
-        finished = torch.zeros(rows, dtype=torch.uint8, device=dev) if eos_token_id is not None else None
-        steps = []
-        for s in range(n_new):
-            logits = self._last_logits(hidden)                 # step 0 of R > 1: the prefill's B rows, R draws each
-            if proc is not None:
-                shared = R if logits.shape[0] != rows else 1
-                proc(logits, hist[::shared, :hist.shape[1] - n_new + s], s, shared)
-            if return_step_logits:
-                steps.append(logits if logits.shape[0] == rows else logits.repeat_interleave(R, dim=0))
-            col = ids[:, T + s]
-            ops.sample_tokens(logits, u[s].view(logits.shape[0], -1), temperature, top_k, top_p, finished, eos_token_id, pad_token_id, out=col)
-            if s + 1 < n_new:
-                hidden = dec(input_ids=col[:, None], past_key_values=cache).last_hidden_state[:, 0]
-        if input_ids is not None:
-            ids = ids.to(input_ids.dtype)
-        elif not ids.is_contiguous():
-            ids = ids.contiguous()                             # the new-token columns of the history buffer (history_ids)
-        return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
+            cache.beam = BeamState(cache, R, n_new - 1)        # the identity parent table: R rows on each prompt's keys
+        return decode_loop(self._last_logits, lambda tok: dec(input_ids=tok, past_key_values=cache).last_hidden_state[:, 0],
+                           out.last_hidden_state[:, -1], select, n_new, input_ids, attention_mask, R, proc, history_ids, history_mask,
+                           return_step_logits)
 
     def _generate_beam(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
                        pad_token_id, first_key_valid, W, length_penalty, early_stopping, return_scores, return_trace):
@@ -1179,26 +1042,14 @@ class MPTForCausalLM(MPTPreTrainedModel):
         candidates cand_index / cand_score [B, 2W]."""
         if input_ids is None or input_ids.dim() != 2:
             raise ValueError("generate(): beam search takes input_ids [B, T]")
-        if not input_ids.is_cuda:
-            raise RuntimeError(f"generate() runs on the GPU only (the prompt is on {input_ids.device}); there is no CPU path")
         if W > ops.MAX_BEAMS:
             raise ValueError(f"generate(): num_beams = {W} (1..{ops.MAX_BEAMS})")
-        B, T = input_ids.shape
-        n_new = int(max_new_tokens)
-        if n_new < 1:
-            raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
         dec = self.model.decoder
-        if T + n_new - 1 > dec.max_target_positions:
-            raise ValueError(f"generate(): {T} prompt columns + {n_new} new tokens exceed max_position_embeddings {dec.max_target_positions}")
-        if pad_token_id is None:
-            pad_token_id = self.config.pad_token_id
-            if pad_token_id is None:
-                if eos_token_id is not None:
-                    raise ValueError("generate(): eos_token_id needs a pad_token_id")
-                pad_token_id = 0                                   # without EOS every hypothesis has all max_new_tokens tokens
+        B, T, n_new, pad_token_id, attention_mask = check_prompt(input_ids, None, attention_mask, max_new_tokens, eos_token_id,
+                                                                 pad_token_id, self.config, dec.max_target_positions)
+        if pad_token_id is None:                               # without EOS every hypothesis has all max_new_tokens tokens
+            pad_token_id = 0 if self.config.pad_token_id is None else self.config.pad_token_id
         dev = input_ids.device
-        if attention_mask is None:
-            attention_mask = torch.ones(B, T, dtype=torch.int64, device=dev)
         out = dec(input_ids=input_ids, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid, cache_capacity=T)
         cache = out.past_key_values

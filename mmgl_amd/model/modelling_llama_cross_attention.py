@@ -21,6 +21,7 @@ from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from .. import ops
 from .modelling_cross_attention import DecodeCache
+from .generation import GreedyTail, SampledTail, check_prompt, decode_loop
 from .sampling import check_processors, check_sampling, sampling_u
 
 
@@ -303,81 +304,32 @@ class LlamaNeighborLM(nn.Module):
                  eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, num_beams=1,
                  num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None):
-        """Greedy decoding with a key/value cache: the contract of MPTForCausalLM.generate (without inputs_embeds).  One prefill over
-        the right-padded prompts [B, T] -- the kernels of forward(), plus the copy of every layer's Hkv key/value heads into a
-        DecodeCache -- then max_new_tokens - 1 decode steps; lm_head runs on the last row only.  Every new token is appended at the
-        same column for all samples (its rotary position), the pad keys stay masked.
-        eos_token_id: a row that has emitted it gets pad_token_id (default config.pad_token_id) from then on; None: no end-of-sequence
-        handling.  All max_new_tokens steps run (no host synchronisation to stop early).
-        Returns the [B, T + max_new_tokens] ids; with return_step_logits=True also the [B, max_new_tokens, V] logits the tokens
-        were picked from.  num_beams > 1 is refused (beam search is implemented for the OPT fork only).
-        do_sample=True: every step draws its token with ops.sample_tokens (temperature -> top_k -> top_p and the draw, one launch that
-        writes the ids column and the finished flags) from uniform numbers [max_new_tokens, B] drawn once before the loop -- sample_u
-        itself, or torch.rand on a generator seeded with `seed` (None: torch's global device generator).  num_return_sequences > 1 is
-        refused (it needs the beam-shared cache of the OPT fork).
-        repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens: with any of them on, one ops.process_logits call
-        per step rewrites the logits in front of the selection, greedy or sampled, with the returned row so far (the prompt without
-        its masked columns, then the new tokens) as history; return_step_logits returns the processed logits."""
+        """The contract of MPTForCausalLM.generate for input_ids prompts: one prefill over the right-padded prompts [B, T] -- the
+        kernels of forward(), plus the copy of every layer's Hkv key/value heads into a DecodeCache -- then max_new_tokens - 1 decode
+        steps; lm_head runs on the last row only.  Every new token is appended at the same column for all samples (its rotary
+        position), the pad keys stay masked.  The loop and the semantics of eos_token_id / pad_token_id, do_sample with its knobs,
+        the logits processors and return_step_logits are generation.decode_loop's: see that module.  Refused here: num_beams > 1
+        (beam search is implemented for the OPT fork only), num_return_sequences > 1 (it needs the beam-shared cache of the OPT
+        fork) and do_sample=True on prompts that are not int64."""
         if int(num_beams) != 1:
             raise ValueError(f"LlamaNeighborLM.generate(): num_beams = {num_beams} is not implemented (beam search runs on the OPT fork "
                              "only); this path is greedy")
         check_sampling("LlamaNeighborLM.generate()", do_sample, temperature, top_k, top_p, seed, sample_u, 1, num_return_sequences)
         proc = check_processors("LlamaNeighborLM.generate()", repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens,
                                 eos_token_id, max_new_tokens, self.config.vocab_size, 1, input_ids.dtype)
-        n_new = int(max_new_tokens)
-        if n_new < 1:
-            raise ValueError(f"max_new_tokens must be positive, got {max_new_tokens}")
-        if not input_ids.is_cuda:
-            raise RuntimeError(f"generate() runs on the GPU only (the prompt is on {input_ids.device}); there is no CPU path")
-        if input_ids.dim() != 2:
-            raise ValueError(f"generate(): input_ids [B, T], got {tuple(input_ids.shape)}")
-        B, T = input_ids.shape
-        limit = self.config.max_position_embeddings
-        if T + n_new - 1 > limit:
-            raise ValueError(f"generate(): {T} prompt columns + {n_new} new tokens exceed max_position_embeddings {limit}")
-        if eos_token_id is not None and pad_token_id is None:
-            pad_token_id = self.config.pad_token_id
-            if pad_token_id is None:
-                raise ValueError("generate(): eos_token_id needs a pad_token_id")
+        if do_sample and input_ids.dtype != torch.int64:
+            raise ValueError(f"generate(do_sample=True): input_ids must be int64, got {input_ids.dtype}")
+        B, T, n_new, pad_token_id, attention_mask = check_prompt(input_ids, None, attention_mask, max_new_tokens, eos_token_id,
+                                                                 pad_token_id, self.config, self.config.max_position_embeddings)
+        dev = input_ids.device
         if proc is not None:
-            proc.upload(input_ids.device)                      # in front of the prefill: see LogitsProcessors
+            proc.upload(dev)                                   # in front of the prefill: see LogitsProcessors
+        if do_sample:
+            select = SampledTail(sampling_u("LlamaNeighborLM.generate()", n_new, B, dev, seed, sample_u), temperature, top_k, top_p,
+                                 eos_token_id, pad_token_id)
+        else:
+            select = GreedyTail(B, dev, eos_token_id, pad_token_id)
         hidden, cache = self._hidden(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid, True,
                                      T + n_new - 1)
-        hidden = hidden[:, -1]
-        ids = torch.empty(B, T + n_new, dtype=input_ids.dtype, device=input_ids.device)
-        ids[:, :T] = input_ids
-        if proc is not None:
-            proc.bind(input_ids.device, attention_mask)
-        if do_sample:
-            if ids.dtype != torch.int64:
-                raise ValueError(f"generate(do_sample=True): input_ids must be int64, got {ids.dtype}")
-            u = sampling_u("LlamaNeighborLM.generate()", n_new, B, input_ids.device, seed, sample_u)
-            done = torch.zeros(B, dtype=torch.uint8, device=input_ids.device) if eos_token_id is not None else None
-            steps = []
-            for s in range(n_new):
-                logits = self._last_logits(hidden)
-                if proc is not None:
-                    proc(logits, ids[:, :T + s], s)
-                if return_step_logits:
-                    steps.append(logits)
-                col = ids[:, T + s]
-                ops.sample_tokens(logits, u[s], temperature, top_k, top_p, done, eos_token_id, pad_token_id, out=col)
-                if s + 1 < n_new:
-                    hidden = self._decode_step(col[:, None], cache)
-            return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
-        finished = torch.zeros(B, dtype=torch.bool, device=input_ids.device)
-        steps = []
-        for s in range(n_new):
-            logits = self._last_logits(hidden)
-            if proc is not None:
-                proc(logits, ids[:, :T + s], s)
-            if return_step_logits:
-                steps.append(logits)
-            tok = torch.argmax(logits, dim=-1)
-            if eos_token_id is not None:
-                tok = torch.where(finished, torch.full_like(tok, pad_token_id), tok)
-                finished = finished | (tok == eos_token_id)
-            ids[:, T + s] = tok
-            if s + 1 < n_new:
-                hidden = self._decode_step(tok[:, None], cache)
-        return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
+        return decode_loop(self._last_logits, lambda tok: self._decode_step(tok, cache), hidden[:, -1], select, n_new, input_ids,
+                           attention_mask, proc=proc, return_step_logits=return_step_logits)

@@ -1,7 +1,7 @@
 """The sampling and logits-processor arguments shared by the three generate() methods (MPTForCausalLM / CrossAttentionModel,
 SelfAttentionModel, LlamaNeighborLM): their checks, which need no device, the uniform numbers a sampled generation consumes and the
 per-generation state of the processors.  The selection itself is ops.sample_tokens, the processors are ops.process_logits, one launch
-per decode step each."""
+per decode step each; the loop that makes those calls is generation.decode_loop."""
 import math
 
 import torch
@@ -62,7 +62,7 @@ MAX_SUPPRESS = ops.MAX_BAN - 1          # the ban array of a generation is suppr
 def check_processors(who, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id, max_new_tokens,
                      vocab_size, num_beams=1, ids_dtype=None):
     """Validates generate()'s logits-processor keywords.  Returns None when all four are at their defaults -- the
-    loops then run exactly as without them -- else a LogitsProcessors that the loop binds to its device and calls once per step."""
+    loop then runs exactly as without them -- else a LogitsProcessors that generation.decode_loop binds and calls once per step."""
     p, n, m = float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens)
     if not (0.0 < p < math.inf):
         raise ValueError(f"{who}: repetition_penalty = {repetition_penalty} must be positive and finite (1: off)")
@@ -95,8 +95,8 @@ class LogitsProcessors:
     """The processors of one generate() call.  The device state is built once: upload() copies the ban array (suppress_tokens
     followed by EOS; the EOS entry counts only while s < min_new_tokens, decided on the host from the step index), bind() makes the
     uint8 mask of the prompt columns.  Step s then makes one ops.process_logits call on the [rows, V] logits with the row so far as
-    history.  upload() is the one host-to-device copy of a generation, and such a copy waits for the work queued before it: the
-    loops call it in FRONT of the prefill, where nothing of this generation is queued yet (behind the prefill it cost the host its
+    history.  upload() is the one host-to-device copy of a generation, and such a copy waits for the work queued before it: every
+    generate() calls it in FRONT of its prefill, where nothing of this generation is queued yet (behind the prefill it cost the host its
     head start over the device, 15 ms per call at B = 16 on the flagship model)."""
 
     def __init__(self, penalty, ngram, min_new, suppress, eos_token_id):
