@@ -329,13 +329,19 @@ extern "C" size_t mmgl_norm_bwd_workspace(int rows, int cols) {
     return parts * cols * 2 * sizeof(float);
 }
 
+// The dtype switch of the eight entry points below: FN is norm_fwd or norm_bwd, RMS its second template argument, the rest its
+// arguments after the entry point's own name.  Ends the entry point: every branch returns.
+#define NORM_BY_DTYPE(FN, RMS, ...)                                                    \
+    do {                                                                               \
+        if (dtype == MMGL_BF16) return FN<bf16, RMS>(__func__, __VA_ARGS__);           \
+        if (dtype == MMGL_F32) return FN<float, RMS>(__func__, __VA_ARGS__);           \
+        MMGL_FAIL(MMGL_ERR_INVALID, "%s: bad dtype %d", __func__, dtype);              \
+    } while (0)
+
 extern "C" int mmgl_layernorm_fwd(const void* x, const void* gamma, const void* beta, void* y, float* mean, float* rstd,
                                   int rows, int cols, float eps, int dtype, void* stream) {
     MMGL_CHECK_ARG(x && y && mean && rstd, "mmgl_layernorm_fwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16) return norm_fwd<bf16, false>("mmgl_layernorm_fwd", x, nullptr, gamma, beta, nullptr, y, mean, rstd, rows, cols, eps, st);
-    if (dtype == MMGL_F32) return norm_fwd<float, false>("mmgl_layernorm_fwd", x, nullptr, gamma, beta, nullptr, y, mean, rstd, rows, cols, eps, st);
-    MMGL_FAIL(MMGL_ERR_INVALID, "mmgl_layernorm_fwd: bad dtype %d", dtype);
+    NORM_BY_DTYPE(norm_fwd, false, x, nullptr, gamma, beta, nullptr, y, mean, rstd, rows, cols, eps, (hipStream_t)stream);
 }
 
 extern "C" int mmgl_add_layernorm_fwd(const void* x, const void* res, const void* gamma, const void* beta, void* sum_out,
@@ -343,12 +349,7 @@ extern "C" int mmgl_add_layernorm_fwd(const void* x, const void* res, const void
                                       uint64_t seed, int dtype, void* stream) {
     MMGL_CHECK_ARG(x && res && y, "mmgl_add_layernorm_fwd: null pointer");
     MMGL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "mmgl_add_layernorm_fwd: dropout p=%g outside [0,1)", p_drop);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16)
-        return norm_fwd<bf16, false>("mmgl_add_layernorm_fwd", x, res, gamma, beta, sum_out, y, mean, rstd, rows, cols, eps, st, p_drop, seed);
-    if (dtype == MMGL_F32)
-        return norm_fwd<float, false>("mmgl_add_layernorm_fwd", x, res, gamma, beta, sum_out, y, mean, rstd, rows, cols, eps, st, p_drop, seed);
-    MMGL_FAIL(MMGL_ERR_INVALID, "mmgl_add_layernorm_fwd: bad dtype %d", dtype);
+    NORM_BY_DTYPE(norm_fwd, false, x, res, gamma, beta, sum_out, y, mean, rstd, rows, cols, eps, (hipStream_t)stream, p_drop, seed);
 }
 
 extern "C" int mmgl_add_layernorm_bwd(const void* dy, const void* dsum, const void* sum, const void* gamma, const float* mean,
@@ -358,64 +359,41 @@ extern "C" int mmgl_add_layernorm_bwd(const void* dy, const void* dsum, const vo
     MMGL_CHECK_ARG(dy && sum && mean && rstd && dres, "mmgl_add_layernorm_bwd: null pointer");
     MMGL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "mmgl_add_layernorm_bwd: dropout p=%g outside [0,1)", p_drop);
     MMGL_CHECK_ARG(p_drop == 0.f || dx, "mmgl_add_layernorm_bwd: dx is required when p_drop > 0");
-    hipStream_t st = (hipStream_t)stream;
-    void* dxd = p_drop > 0.f ? dx : nullptr;
-    if (dtype == MMGL_BF16)
-        return norm_bwd<bf16, false>("mmgl_add_layernorm_bwd", dy, sum, gamma, mean, rstd, dsum, dres, dgamma, dbeta, workspace, workspace_bytes, rows, cols, st, dxd, p_drop, seed);
-    if (dtype == MMGL_F32)
-        return norm_bwd<float, false>("mmgl_add_layernorm_bwd", dy, sum, gamma, mean, rstd, dsum, dres, dgamma, dbeta, workspace, workspace_bytes, rows, cols, st, dxd, p_drop, seed);
-    MMGL_FAIL(MMGL_ERR_INVALID, "mmgl_add_layernorm_bwd: bad dtype %d", dtype);
+    NORM_BY_DTYPE(norm_bwd, false, dy, sum, gamma, mean, rstd, dsum, dres, dgamma, dbeta, workspace, workspace_bytes, rows, cols,
+                  (hipStream_t)stream, p_drop > 0.f ? dx : nullptr, p_drop, seed);
 }
 
 extern "C" int mmgl_layernorm_bwd(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
                                   void* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, int rows,
                                   int cols, int dtype, void* stream) {
     MMGL_CHECK_ARG(dy && x && mean && rstd && dx, "mmgl_layernorm_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16)
-        return norm_bwd<bf16, false>("mmgl_layernorm_bwd", dy, x, gamma, mean, rstd, nullptr, dx, dgamma, dbeta, workspace, workspace_bytes, rows, cols, st);
-    if (dtype == MMGL_F32)
-        return norm_bwd<float, false>("mmgl_layernorm_bwd", dy, x, gamma, mean, rstd, nullptr, dx, dgamma, dbeta, workspace, workspace_bytes, rows, cols, st);
-    MMGL_FAIL(MMGL_ERR_INVALID, "mmgl_layernorm_bwd: bad dtype %d", dtype);
+    NORM_BY_DTYPE(norm_bwd, false, dy, x, gamma, mean, rstd, nullptr, dx, dgamma, dbeta, workspace, workspace_bytes, rows, cols,
+                  (hipStream_t)stream);
 }
 
 extern "C" int mmgl_rmsnorm_fwd(const void* x, const void* gamma, void* y, float* rstd, int rows, int cols, float eps,
                                 int dtype, void* stream) {
     MMGL_CHECK_ARG(x && y && rstd, "mmgl_rmsnorm_fwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16) return norm_fwd<bf16, true>("mmgl_rmsnorm_fwd", x, nullptr, gamma, nullptr, nullptr, y, nullptr, rstd, rows, cols, eps, st);
-    if (dtype == MMGL_F32) return norm_fwd<float, true>("mmgl_rmsnorm_fwd", x, nullptr, gamma, nullptr, nullptr, y, nullptr, rstd, rows, cols, eps, st);
-    MMGL_FAIL(MMGL_ERR_INVALID, "mmgl_rmsnorm_fwd: bad dtype %d", dtype);
+    NORM_BY_DTYPE(norm_fwd, true, x, nullptr, gamma, nullptr, nullptr, y, nullptr, rstd, rows, cols, eps, (hipStream_t)stream);
 }
 
 extern "C" int mmgl_add_rmsnorm_fwd(const void* x, const void* res, const void* gamma, void* sum_out, void* y, float* rstd, int rows,
                                     int cols, float eps, int dtype, void* stream) {
     MMGL_CHECK_ARG(x && res && sum_out && y && rstd, "mmgl_add_rmsnorm_fwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16) return norm_fwd<bf16, true>("mmgl_add_rmsnorm_fwd", x, res, gamma, nullptr, sum_out, y, nullptr, rstd, rows, cols, eps, st);
-    if (dtype == MMGL_F32) return norm_fwd<float, true>("mmgl_add_rmsnorm_fwd", x, res, gamma, nullptr, sum_out, y, nullptr, rstd, rows, cols, eps, st);
-    MMGL_FAIL(MMGL_ERR_INVALID, "mmgl_add_rmsnorm_fwd: bad dtype %d", dtype);
+    NORM_BY_DTYPE(norm_fwd, true, x, res, gamma, nullptr, sum_out, y, nullptr, rstd, rows, cols, eps, (hipStream_t)stream);
 }
 
 extern "C" int mmgl_add_rmsnorm_bwd(const void* dy, const void* dsum, const void* sum, const void* gamma, const float* rstd, void* dres,
                                     float* dgamma, void* workspace, size_t workspace_bytes, int rows, int cols, int dtype, void* stream) {
     MMGL_CHECK_ARG(dy && sum && rstd && dres, "mmgl_add_rmsnorm_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16)
-        return norm_bwd<bf16, true>("mmgl_add_rmsnorm_bwd", dy, sum, gamma, nullptr, rstd, dsum, dres, dgamma, nullptr, workspace, workspace_bytes, rows, cols, st);
-    if (dtype == MMGL_F32)
-        return norm_bwd<float, true>("mmgl_add_rmsnorm_bwd", dy, sum, gamma, nullptr, rstd, dsum, dres, dgamma, nullptr, workspace, workspace_bytes, rows, cols, st);
-    MMGL_FAIL(MMGL_ERR_INVALID, "mmgl_add_rmsnorm_bwd: bad dtype %d", dtype);
+    NORM_BY_DTYPE(norm_bwd, true, dy, sum, gamma, nullptr, rstd, dsum, dres, dgamma, nullptr, workspace, workspace_bytes, rows, cols,
+                  (hipStream_t)stream);
 }
 
 extern "C" int mmgl_rmsnorm_bwd(const void* dy, const void* x, const void* gamma, const float* rstd, void* dx,
                                 float* dgamma, void* workspace, size_t workspace_bytes, int rows, int cols, int dtype,
                                 void* stream) {
     MMGL_CHECK_ARG(dy && x && rstd && dx, "mmgl_rmsnorm_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16)
-        return norm_bwd<bf16, true>("mmgl_rmsnorm_bwd", dy, x, gamma, nullptr, rstd, nullptr, dx, dgamma, nullptr, workspace, workspace_bytes, rows, cols, st);
-    if (dtype == MMGL_F32)
-        return norm_bwd<float, true>("mmgl_rmsnorm_bwd", dy, x, gamma, nullptr, rstd, nullptr, dx, dgamma, nullptr, workspace, workspace_bytes, rows, cols, st);
-    MMGL_FAIL(MMGL_ERR_INVALID, "mmgl_rmsnorm_bwd: bad dtype %d", dtype);
+    NORM_BY_DTYPE(norm_bwd, true, dy, x, gamma, nullptr, rstd, nullptr, dx, dgamma, nullptr, workspace, workspace_bytes, rows, cols,
+                  (hipStream_t)stream);
 }

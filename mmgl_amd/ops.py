@@ -14,6 +14,14 @@ from . import _lib
 from ._lib import dtype_code, lib, ptr, ptr_off, require_cuda, stream_ptr
 
 
+def _dropout(p_drop, training, seed):
+    """(p, seed) for the kernels: p = 0 outside training; a seed is drawn when something is dropped and the caller gave none."""
+    p = float(p_drop) if training else 0.0
+    if p > 0.0 and seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    return p, int(seed or 0)
+
+
 # ------------------------------------------------------------------------------------------ attention core
 def _check_mask(key_valid, shape):
     if key_valid.shape != shape:
@@ -92,8 +100,8 @@ class _AttnGeneral(torch.autograd.Function):
         lse = torch.empty(B, num_heads, T, dtype=torch.float32, device=q.device)
         probs = torch.empty(B, num_heads, T, S, dtype=q.dtype, device=q.device) if want_probs else None
         hm = None if head_mask is None else head_mask.detach().to(device=q.device, dtype=torch.float32).contiguous()
-        _lib.call("mmgl_attn_general_fwd", dict(flops=4.0 * B * T * S * d), ptr(q), ptr(k), ptr(v), ptr(key_valid), ptr(hm) if hm is not None else None,
-                  ptr(out), ptr(probs) if probs is not None else None, ptr(lse), B, num_heads, T, S, D, int(causal), float(p_drop), int(seed),
+        _lib.call("mmgl_attn_general_fwd", dict(flops=4.0 * B * T * S * d), ptr(q), ptr(k), ptr(v), ptr(key_valid), ptr(hm),
+                  ptr(out), ptr(probs), ptr(lse), B, num_heads, T, S, D, int(causal), float(p_drop), int(seed),
                   dtype_code(q), stream_ptr())
         ctx.save_for_backward(q, k, v, key_valid, lse, hm)
         ctx.cfg = (num_heads, int(causal), float(p_drop), int(seed))
@@ -114,7 +122,7 @@ class _AttnGeneral(torch.autograd.Function):
         nbytes = lib().mmgl_attn_general_bwd_workspace(B, H, T)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
         _lib.call("mmgl_attn_general_bwd", dict(flops=10.0 * B * T * S * d), ptr(dout), ptr(q), ptr(k), ptr(v), ptr(lse), ptr(key_valid),
-                  ptr(hm) if hm is not None else None, ptr(dq), ptr(dk), ptr(dv), ptr(ws), nbytes, B, H, T, S, D, causal, p_drop, seed,
+                  ptr(hm), ptr(dq), ptr(dk), ptr(dv), ptr(ws), nbytes, B, H, T, S, D, causal, p_drop, seed,
                   dtype_code(q), stream_ptr())
         return dq, dk, dv, None, None, None, None, None, None, None
 
@@ -133,10 +141,8 @@ def attn_general(q, k, v, key_valid, num_heads, causal=False, head_mask=None, p_
         # This kernel treats it as a constant -- refuse rather than hand back a silent zero gradient
         raise NotImplementedError("attn_general: head_mask.requires_grad is not supported (the kernel computes no gradient for the head "
                                   "mask); detach it, or differentiate a per-head scale applied outside the attention core")
-    p = float(p_drop) if training else 0.0
-    if p > 0.0 and seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    return _AttnGeneral.apply(q, k, v, _key_valid(key_valid), head_mask, num_heads, bool(causal), p, int(seed or 0), bool(output_attentions))
+    p, seed = _dropout(p_drop, training, seed)
+    return _AttnGeneral.apply(q, k, v, _key_valid(key_valid), head_mask, num_heads, bool(causal), p, seed, bool(output_attentions))
 
 
 def attn_dropout_mask(B, H, T, S, p_drop, seed, device):
@@ -347,160 +353,138 @@ def _ws(nbytes, device):
 
 
 # ------------------------------------------------------------------------------------------ LayerNorm / RMSNorm
-class _LayerNorm(torch.autograd.Function):
+# One forward and one backward route over the kernel family of csrc/rownorm.hip; between them they make every call to the eight
+# mmgl_*norm* entry points.  rms picks RMSNorm (no mean, no beta); tensors are flattened to [rows, cols] here and stay 2-D inside.
+def _norm_fwd(rms, x, res, gamma, beta, eps, p=0.0, seed=0, keep_sum=True, keep_stats=True):
+    """y = norm(s) in one launch, with s = x, or s = res + dropout(x) when `res` is given (the mmgl_add_* entry points, which also
+    write s unless keep_sum is off).  Returns (s, y, gamma as the kernel read it, mean, rstd); mean / rstd are what the backward
+    needs and are not computed with keep_stats off."""
+    require_cuda(x, res)
+    cols = x.shape[-1]
+    x2 = x.contiguous().view(-1, cols)
+    rows = x2.shape[0]
+    y = torch.empty_like(x2)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device) if keep_stats and not rms else None
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if keep_stats else None
+    g = None if gamma is None else gamma.to(x.dtype).contiguous()
+    b = None if beta is None else beta.to(x.dtype).contiguous()
+    if res is None:
+        s = x2
+        work = dict(bytes=2.0 * rows * cols * x.element_size())
+        if rms:
+            _lib.call("mmgl_rmsnorm_fwd", work, ptr(x2), ptr(g), ptr(y), ptr(rstd), rows, cols, eps, dtype_code(x), stream_ptr())
+        else:
+            _lib.call("mmgl_layernorm_fwd", work, ptr(x2), ptr(g), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, cols, eps, dtype_code(x),
+                      stream_ptr())
+    else:
+        r2 = res.contiguous().view(-1, cols)
+        s = torch.empty_like(x2) if keep_sum else None
+        work = dict(bytes=(3.0 + keep_sum) * rows * cols * x.element_size())
+        if rms:
+            _lib.call("mmgl_add_rmsnorm_fwd", work, ptr(x2), ptr(r2), ptr(g), ptr(s), ptr(y), ptr(rstd), rows, cols, eps, dtype_code(x),
+                      stream_ptr())
+        else:
+            _lib.call("mmgl_add_layernorm_fwd", work, ptr(x2), ptr(r2), ptr(g), ptr(b), ptr(s), ptr(y), ptr(mean), ptr(rstd), rows, cols,
+                      eps, p, seed, dtype_code(x), stream_ptr())
+    return s, y, g, mean, rstd
+
+
+def _norm_bwd(rms, fused, dy, dsum, s, g, mean, rstd, pgrad, pdtype, p=0.0, seed=0):
+    """The backward of _norm_fwd in one launch (plus the column reduction when a parameter gradient is wanted).  fused: the
+    mmgl_add_* entry points, which add `dsum` (the gradient arriving on s, or None) inside the kernel and with p > 0 also write the
+    gradient of the dropped-out x.  pgrad = (gamma, beta) need a gradient: LayerNorm computes both when either does; only the needed
+    ones come back, in the parameters' dtype.  Returns (ds, dx | None, dgamma | None, dbeta | None) with ds, dx [rows, cols]."""
+    rows, cols = s.shape
+    dy = dy.contiguous().view(rows, cols)
+    dsum = None if dsum is None else dsum.contiguous().view(rows, cols)
+    ds = torch.empty_like(s)
+    dx = torch.empty_like(s) if p > 0.0 else None
+    want = any(pgrad)
+    dgamma = torch.empty(cols, dtype=torch.float32, device=s.device) if want else None
+    dbeta = torch.empty(cols, dtype=torch.float32, device=s.device) if want and not rms else None
+    nbytes = lib().mmgl_norm_bwd_workspace(rows, cols) if want else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device) if want else None
+    work = dict(bytes=(3.0 + (dsum is not None) + (dx is not None)) * rows * cols * s.element_size())
+    if not fused:
+        if rms:
+            _lib.call("mmgl_rmsnorm_bwd", work, ptr(dy), ptr(s), ptr(g), ptr(rstd), ptr(ds), ptr(dgamma), ptr(ws), nbytes, rows, cols,
+                      dtype_code(s), stream_ptr())
+        else:
+            _lib.call("mmgl_layernorm_bwd", work, ptr(dy), ptr(s), ptr(g), ptr(mean), ptr(rstd), ptr(ds), ptr(dgamma), ptr(dbeta), ptr(ws),
+                      nbytes, rows, cols, dtype_code(s), stream_ptr())
+    elif rms:
+        _lib.call("mmgl_add_rmsnorm_bwd", work, ptr(dy), ptr(dsum), ptr(s), ptr(g), ptr(rstd), ptr(ds), ptr(dgamma), ptr(ws), nbytes, rows,
+                  cols, dtype_code(s), stream_ptr())
+    else:
+        _lib.call("mmgl_add_layernorm_bwd", work, ptr(dy), ptr(dsum), ptr(s), ptr(g), ptr(mean), ptr(rstd), ptr(ds), ptr(dx), ptr(dgamma),
+                  ptr(dbeta), ptr(ws), nbytes, rows, cols, p, seed, dtype_code(s), stream_ptr())
+    return ds, dx, (dgamma.to(pdtype) if pgrad[0] else None), (dbeta.to(pdtype) if pgrad[1] else None)
+
+
+def _norm_ctx(ctx, rms, shape, gamma, beta, p=0.0, seed=0):
+    pgrad = (gamma is not None and gamma.requires_grad, beta is not None and beta.requires_grad)
+    ctx.cfg = (rms, shape, pgrad, None if gamma is None else gamma.dtype, p, seed)
+
+
+class _Norm(torch.autograd.Function):
+    """y = LayerNorm(x) or RMSNorm(x)."""
+
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps):
-        require_cuda(x)
-        shape = x.shape
-        cols = shape[-1]
-        x2 = x.contiguous().view(-1, cols)
-        rows = x2.shape[0]
-        y = torch.empty_like(x2)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        g = None if gamma is None else gamma.to(x.dtype).contiguous()
-        b = None if beta is None else beta.to(x.dtype).contiguous()
-        _lib.call("mmgl_layernorm_fwd", dict(bytes=2.0 * rows * cols * x.element_size()), ptr(x2), ptr(g), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, cols, eps,
-                                       dtype_code(x), stream_ptr())
+    def forward(ctx, x, gamma, beta, eps, rms):
+        x2, y, g, mean, rstd = _norm_fwd(rms, x, None, gamma, beta, eps)
         ctx.save_for_backward(x2, g, mean, rstd)
-        ctx.shape = shape
-        ctx.pgrad = (gamma is not None and gamma.requires_grad, beta is not None and beta.requires_grad)
-        ctx.pdtype = None if gamma is None else gamma.dtype
-        return y.view(shape)
+        _norm_ctx(ctx, rms, x.shape, gamma, beta)
+        return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
         x2, g, mean, rstd = ctx.saved_tensors
-        rows, cols = x2.shape
-        dy2 = dy.contiguous().view(rows, cols)
-        dx = torch.empty_like(x2)
-        want = any(ctx.pgrad)
-        dgamma = torch.empty(cols, dtype=torch.float32, device=x2.device) if want else None
-        dbeta = torch.empty(cols, dtype=torch.float32, device=x2.device) if want else None
-        nbytes = lib().mmgl_norm_bwd_workspace(rows, cols) if want else 0
-        ws = _ws(nbytes, x2.device)
-        _lib.call("mmgl_layernorm_bwd", dict(bytes=3.0 * rows * cols * x2.element_size()), ptr(dy2), ptr(x2), ptr(g), ptr(mean), ptr(rstd), ptr(dx), ptr(dgamma), ptr(dbeta),
-                                       ptr(ws), ws.numel(), rows, cols, dtype_code(x2), stream_ptr())
-        dg = dgamma.to(ctx.pdtype) if ctx.pgrad[0] else None
-        db = dbeta.to(ctx.pdtype) if ctx.pgrad[1] else None
-        return dx.view(ctx.shape), dg, db, None
+        rms, shape, pgrad, pdtype, _, _ = ctx.cfg
+        dx, _, dg, db = _norm_bwd(rms, False, dy, None, x2, g, mean, rstd, pgrad, pdtype)
+        return dx.view(shape), dg, db, None, None
+
+
+class _NormPair(torch.autograd.Function):
+    """(s, y) = (res + dropout(x), norm(s)) in one pass; backward folds the gradient arriving on s into the norm's backward kernel,
+    which writes the gradient of res and (when dropout is active) of x -- no separate residual kernels, no autograd accumulation
+    add.  res=None is the fan-out of a pre-LN block (reference :316-320 `residual = hidden_states; hidden_states =
+    self.self_attn_layer_norm(hidden_states)`, :347-350): s is x itself, returned as an alias of the input, so the gradient of the
+    residual stream meets the norm's inside the kernel instead of in autograd's add over [B, T, d] at every fan-out (10 per step at
+    config 3)."""
+
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta, eps, rms, p, seed):
+        s, y, g, mean, rstd = _norm_fwd(rms, x, res, gamma, beta, eps, p, seed)
+        ctx.save_for_backward(s, g, mean, rstd)
+        ctx.set_materialize_grads(False)                      # an unused output arrives as None, not as a zero tensor to stream
+        _norm_ctx(ctx, rms, x.shape, gamma, beta, p, seed)
+        ctx.fanout = res is None
+        return (x if res is None else s.view(x.shape)), y.view(x.shape)      # autograd wraps the returned input as a view
+
+    @staticmethod
+    def backward(ctx, ds, dy):
+        s, g, mean, rstd = ctx.saved_tensors
+        rms, shape, pgrad, pdtype, p, seed = ctx.cfg
+        if dy is None:                                        # only the residual stream was used downstream
+            if ds is None or p == 0.0:
+                return ds, (None if ctx.fanout else ds), None, None, None, None, None, None
+            dy = torch.zeros_like(ds)                         # dropout: the kernel still has to mask ds into the gradient of x
+        dres, dx, dg, db = _norm_bwd(rms, True, dy, ds, s, g, mean, rstd, pgrad, pdtype, p, seed)
+        dres = dres.view(shape)
+        if ctx.fanout:
+            return dres, None, dg, db, None, None, None, None
+        return (dres if dx is None else dx.view(shape)), dres, dg, db, None, None, None, None
 
 
 def layer_norm(x, gamma, beta, eps=1e-5):
     """nn.LayerNorm over the last dim (reference model/modelling_cross_attention.py:287-294, 319-320, 349-350)."""
-    return _LayerNorm.apply(x, gamma, beta, float(eps))
-
-
-class _LayerNormFanout(torch.autograd.Function):
-    """(x, LayerNorm(x)) for a pre-LN block whose input also feeds the block's residual add (reference :316-320 `residual =
-    hidden_states; hidden_states = self.self_attn_layer_norm(hidden_states)`, :347-350): the gradient arriving on the residual
-    stream is added INSIDE the LayerNorm backward kernel (mmgl_add_layernorm_bwd with the sum = x), instead of autograd's
-    accumulation add over [B, T, d] at every fan-out (10 per step at config 3)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps):
-        require_cuda(x)
-        shape = x.shape
-        cols = shape[-1]
-        x2 = x.contiguous().view(-1, cols)
-        rows = x2.shape[0]
-        y = torch.empty_like(x2)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        g = None if gamma is None else gamma.to(x.dtype).contiguous()
-        b = None if beta is None else beta.to(x.dtype).contiguous()
-        _lib.call("mmgl_layernorm_fwd", dict(bytes=2.0 * rows * cols * x.element_size()), ptr(x2), ptr(g), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, cols, eps,
-                  dtype_code(x), stream_ptr())
-        ctx.save_for_backward(x2, g, mean, rstd)
-        ctx.set_materialize_grads(False)
-        ctx.shape = shape
-        ctx.pgrad = (gamma is not None and gamma.requires_grad, beta is not None and beta.requires_grad)
-        ctx.pdtype = None if gamma is None else gamma.dtype
-        return x, y.view(shape)          # x comes back as an alias of the input (autograd wraps it as a view)
-
-    @staticmethod
-    def backward(ctx, dres, dy):
-        x2, g, mean, rstd = ctx.saved_tensors
-        rows, cols = x2.shape
-        if dy is None:
-            return dres, None, None, None
-        dy2 = dy.contiguous().view(rows, cols)
-        dr2 = None if dres is None else dres.contiguous().view(rows, cols)
-        dx = torch.empty_like(x2)
-        want = any(ctx.pgrad)
-        dgamma = torch.empty(cols, dtype=torch.float32, device=x2.device) if want else None
-        dbeta = torch.empty(cols, dtype=torch.float32, device=x2.device) if want else None
-        nbytes = lib().mmgl_norm_bwd_workspace(rows, cols) if want else 0
-        ws = _ws(nbytes, x2.device)
-        nt = 3.0 + (dr2 is not None)
-        _lib.call("mmgl_add_layernorm_bwd", dict(bytes=nt * rows * cols * x2.element_size()), ptr(dy2), ptr(dr2), ptr(x2), ptr(g), ptr(mean),
-                  ptr(rstd), ptr(dx), None, ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), rows, cols, 0.0, 0, dtype_code(x2), stream_ptr())
-        dg = dgamma.to(ctx.pdtype) if ctx.pgrad[0] else None
-        db = dbeta.to(ctx.pdtype) if ctx.pgrad[1] else None
-        return dx.view(ctx.shape), dg, db, None
+    return _Norm.apply(x, gamma, beta, float(eps), False)
 
 
 def layer_norm_fanout(x, gamma, beta, eps=1e-5):
     """(residual, LayerNorm(x)) with residual == x: use BOTH outputs downstream (the residual add and the normed branch) so that
     the two gradients meet inside the LayerNorm backward kernel."""
-    return _LayerNormFanout.apply(x, gamma, beta, float(eps))
-
-
-class _AddLayerNorm(torch.autograd.Function):
-    """(s, y) = (res + dropout(x), LayerNorm(s)) in one pass; backward folds the gradient arriving on s into the LayerNorm
-    backward kernel, which writes the gradient of res and (when dropout is active) of x -- no separate residual kernels,
-    no autograd accumulation add."""
-
-    @staticmethod
-    def forward(ctx, x, res, gamma, beta, eps, p_drop, seed):
-        require_cuda(x, res)
-        shape = x.shape
-        cols = shape[-1]
-        x2, r2 = x.contiguous().view(-1, cols), res.contiguous().view(-1, cols)
-        rows = x2.shape[0]
-        s, y = torch.empty_like(x2), torch.empty_like(x2)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        g = None if gamma is None else gamma.to(x.dtype).contiguous()
-        b = None if beta is None else beta.to(x.dtype).contiguous()
-        _lib.call("mmgl_add_layernorm_fwd", dict(bytes=4.0 * rows * cols * x.element_size()), ptr(x2), ptr(r2), ptr(g), ptr(b), ptr(s), ptr(y),
-                  ptr(mean), ptr(rstd), rows, cols, eps, p_drop, seed, dtype_code(x), stream_ptr())
-        ctx.save_for_backward(s, g, mean, rstd)
-        ctx.set_materialize_grads(False)                      # an unused output arrives as None, not as a zero tensor to stream
-        ctx.shape, ctx.p, ctx.seed = shape, p_drop, seed
-        ctx.pgrad = (gamma is not None and gamma.requires_grad, beta is not None and beta.requires_grad)
-        ctx.pdtype = None if gamma is None else gamma.dtype
-        return s.view(shape), y.view(shape)
-
-    @staticmethod
-    def backward(ctx, ds, dy):
-        s, g, mean, rstd = ctx.saved_tensors
-        rows, cols = s.shape
-        p = ctx.p
-        if dy is None:                                        # only the residual stream was used downstream
-            if ds is None:
-                return None, None, None, None, None, None, None
-            if p == 0.0:
-                return ds, ds, None, None, None, None, None
-            dy = torch.zeros_like(ds)
-        dy2 = dy.contiguous().view(rows, cols)
-        ds2 = None if ds is None else ds.contiguous().view(rows, cols)
-        dres = torch.empty_like(s)
-        dx = torch.empty_like(s) if p > 0.0 else None
-        want = any(ctx.pgrad)
-        dgamma = torch.empty(cols, dtype=torch.float32, device=s.device) if want else None
-        dbeta = torch.empty(cols, dtype=torch.float32, device=s.device) if want else None
-        nbytes = lib().mmgl_norm_bwd_workspace(rows, cols) if want else 0
-        ws = _ws(nbytes, s.device)
-        nt = 3.0 + (ds2 is not None) + (dx is not None)
-        _lib.call("mmgl_add_layernorm_bwd", dict(bytes=nt * rows * cols * s.element_size()), ptr(dy2), ptr(ds2), ptr(s), ptr(g), ptr(mean),
-                  ptr(rstd), ptr(dres), ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), rows, cols, p, ctx.seed, dtype_code(s),
-                  stream_ptr())
-        dres = dres.view(ctx.shape)
-        dx = dres if dx is None else dx.view(ctx.shape)
-        dg = dgamma.to(ctx.pdtype) if ctx.pgrad[0] else None
-        db = dbeta.to(ctx.pdtype) if ctx.pgrad[1] else None
-        return dx, dres, dg, db, None, None, None
+    return _NormPair.apply(x, None, gamma, beta, float(eps), False, 0.0, 0)
 
 
 def add_layer_norm_pair(x, res, gamma, beta, eps=1e-5, p_drop=0.0, training=False, seed=None):
@@ -509,93 +493,18 @@ def add_layer_norm_pair(x, res, gamma, beta, eps=1e-5, p_drop=0.0, training=Fals
     kernel.  Dropout uses the same counter hash of (seed, element index) as gated_residual."""
     if x.shape != res.shape:
         raise ValueError(f"add_layer_norm_pair: shapes differ {tuple(x.shape)} vs {tuple(res.shape)}")
-    p = float(p_drop) if training else 0.0
-    if p > 0.0 and seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    return _AddLayerNorm.apply(x, res, gamma, beta, float(eps), p, int(seed or 0))
-
-
-class _RMSNorm(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, gamma, eps):
-        require_cuda(x)
-        shape = x.shape
-        cols = shape[-1]
-        x2 = x.contiguous().view(-1, cols)
-        rows = x2.shape[0]
-        y = torch.empty_like(x2)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        g = None if gamma is None else gamma.to(x.dtype).contiguous()
-        _lib.call("mmgl_rmsnorm_fwd", None, ptr(x2), ptr(g), ptr(y), ptr(rstd), rows, cols, eps, dtype_code(x), stream_ptr())
-        ctx.save_for_backward(x2, g, rstd)
-        ctx.shape = shape
-        ctx.pgrad = gamma is not None and gamma.requires_grad
-        ctx.pdtype = None if gamma is None else gamma.dtype
-        return y.view(shape)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, g, rstd = ctx.saved_tensors
-        rows, cols = x2.shape
-        dy2 = dy.contiguous().view(rows, cols)
-        dx = torch.empty_like(x2)
-        dgamma = torch.empty(cols, dtype=torch.float32, device=x2.device) if ctx.pgrad else None
-        nbytes = lib().mmgl_norm_bwd_workspace(rows, cols) if ctx.pgrad else 0
-        ws = _ws(nbytes, x2.device)
-        _lib.call("mmgl_rmsnorm_bwd", None, ptr(dy2), ptr(x2), ptr(g), ptr(rstd), ptr(dx), ptr(dgamma), ptr(ws), ws.numel(), rows,
-                                     cols, dtype_code(x2), stream_ptr())
-        return dx.view(ctx.shape), (dgamma.to(ctx.pdtype) if ctx.pgrad else None), None
+    return _NormPair.apply(x, res, gamma, beta, float(eps), False, *_dropout(p_drop, training, seed))
 
 
 def rms_norm(x, gamma, eps=1e-6):
-    return _RMSNorm.apply(x, gamma, float(eps))
-
-
-class _AddRMSNorm(torch.autograd.Function):
-    """(s, y) = (res + x, RMSNorm(s)) in one pass (a Llama layer's residual add and the norm that follows it); backward folds the
-    gradient arriving on s into the norm's backward kernel: no residual kernel, no autograd accumulation add."""
-
-    @staticmethod
-    def forward(ctx, x, res, gamma, eps):
-        require_cuda(x, res)
-        shape = x.shape
-        cols = shape[-1]
-        x2, r2 = x.contiguous().view(-1, cols), res.contiguous().view(-1, cols)
-        rows = x2.shape[0]
-        s, y = torch.empty_like(x2), torch.empty_like(x2)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        g = None if gamma is None else gamma.to(x.dtype).contiguous()
-        _lib.call("mmgl_add_rmsnorm_fwd", dict(bytes=4.0 * rows * cols * x.element_size()), ptr(x2), ptr(r2), ptr(g), ptr(s), ptr(y), ptr(rstd),
-                  rows, cols, eps, dtype_code(x), stream_ptr())
-        ctx.save_for_backward(s, g, rstd)
-        ctx.set_materialize_grads(False)
-        ctx.shape = shape
-        ctx.pgrad = gamma is not None and gamma.requires_grad
-        ctx.pdtype = None if gamma is None else gamma.dtype
-        return s.view(shape), y.view(shape)
-
-    @staticmethod
-    def backward(ctx, ds, dy):
-        s, g, rstd = ctx.saved_tensors
-        rows, cols = s.shape
-        if dy is None:                                        # only the residual stream was used downstream
-            return ds, ds, None, None
-        dy2 = dy.contiguous().view(rows, cols)
-        ds2 = None if ds is None else ds.contiguous().view(rows, cols)
-        dres = torch.empty_like(s)
-        dgamma = torch.empty(cols, dtype=torch.float32, device=s.device) if ctx.pgrad else None
-        ws = _ws(lib().mmgl_norm_bwd_workspace(rows, cols) if ctx.pgrad else 0, s.device)
-        _lib.call("mmgl_add_rmsnorm_bwd", dict(bytes=(3.0 + (ds2 is not None)) * rows * cols * s.element_size()), ptr(dy2), ptr(ds2), ptr(s), ptr(g),
-                  ptr(rstd), ptr(dres), ptr(dgamma), ptr(ws), ws.numel(), rows, cols, dtype_code(s), stream_ptr())
-        dres = dres.view(ctx.shape)
-        return dres, dres, (dgamma.to(ctx.pdtype) if dgamma is not None else None), None
+    return _Norm.apply(x, gamma, None, float(eps), True)
 
 
 def add_rms_norm_pair(x, res, gamma, eps=1e-6):
     """Differentiable (s, RMSNorm(s)) with s = res + x: one forward and one backward kernel for the pair."""
     if x.shape != res.shape:
         raise ValueError(f"add_rms_norm_pair: shapes differ {tuple(x.shape)} vs {tuple(res.shape)}")
-    return _AddRMSNorm.apply(x, res, gamma, float(eps))
+    return _NormPair.apply(x, res, gamma, None, float(eps), True, 0.0, 0)
 
 
 # ------------------------------------------------------------------------------------------ gated residual
@@ -631,10 +540,7 @@ class _GatedResidual(torch.autograd.Function):
 def gated_residual(residual, x, gate=None, p_drop=0.0, training=False, seed=None):
     """residual + tanh(gate) * dropout(x)  (reference :332-335, :356-359; gate=None is the ungated :337/:361 form).
     The dropout mask is a counter hash of (seed, index) regenerated in backward."""
-    p = float(p_drop) if training else 0.0
-    if p > 0.0 and seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    return _GatedResidual.apply(residual, x, gate, p, int(seed or 0))
+    return _GatedResidual.apply(residual, x, gate, *_dropout(p_drop, training, seed))
 
 
 # ------------------------------------------------------------------------------------------ linear (+bias, scale, ReLU)
@@ -1469,14 +1375,9 @@ def add_layer_norm(x, res, gamma, beta, eps, return_sum=False):
     require_cuda(x, res)
     if x.shape != res.shape:
         raise ValueError(f"add_layer_norm: shapes differ {tuple(x.shape)} vs {tuple(res.shape)}")
-    cols = x.shape[-1]
-    x2, r2 = x.contiguous().view(-1, cols), res.contiguous().view(-1, cols)
-    y = torch.empty_like(x2)
-    s = torch.empty_like(x2) if return_sum else None
-    g, b = gamma.to(x.dtype).contiguous(), beta.to(x.dtype).contiguous()
-    if x2.shape[0]:
-        _lib.call("mmgl_add_layernorm_fwd", dict(bytes=(4.0 if return_sum else 3.0) * x2.numel() * x2.element_size()), ptr(x2), ptr(r2), ptr(g), ptr(b), ptr(s), ptr(y), None, None, x2.shape[0], cols, float(eps),
-                  0.0, 0, dtype_code(x2), stream_ptr())
+    if x.shape[-1] and not x.numel():                      # no rows: nothing to launch
+        return (torch.empty_like(x), torch.empty_like(x)) if return_sum else torch.empty_like(x)
+    s, y, _, _, _ = _norm_fwd(False, x, res, gamma, beta, float(eps), keep_sum=return_sum, keep_stats=False)
     return (s.view(x.shape), y.view(x.shape)) if return_sum else y.view(x.shape)
 
 

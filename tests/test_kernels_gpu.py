@@ -236,6 +236,113 @@ def test_add_rms_norm_pair(rows, cols, dtype, use_sum, gamma_grad):
         assert_close(gd.grad.float(), gr.grad, t, "dgamma")
 
 
+# (9, 64): one wave per row, one chunk per lane; (5, 4096): in fp32 the 256-thread row with 4 chunks per lane
+NORM_SHAPES = [(9, 64), (5, 4096)]
+
+
+def _norm_inputs(rows, cols, n):
+    """n activation-shaped fp32 tensors, then gamma and beta, all from one seed."""
+    g = torch.Generator().manual_seed(rows * 7 + cols)
+    acts = [torch.randn(rows, cols, generator=g) for _ in range(n)]
+    return acts + [torch.randn(cols, generator=g) * 0.2 + 1, torch.randn(cols, generator=g) * 0.1]
+
+
+@pytest.mark.parametrize("rows,cols", NORM_SHAPES)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("op", ["add_layer_norm_pair", "add_rms_norm_pair", "layer_norm_fanout"])
+def test_norm_pair_residual_only(rows, cols, dtype, op):
+    """The loss reads the residual stream and never y: the upstream gradient goes to the inputs unchanged, with no kernel, and the
+    (trainable) parameters get no gradient."""
+    from mmgl_amd import ops
+    x, r, w, gamma, beta = _norm_inputs(rows, cols, 3)
+    xd, rd, gd, bd = dev(x, dtype), dev(r, dtype), dev(gamma, dtype), dev(beta, dtype)
+    wd = w.to(dtype).cuda()
+    if op == "add_layer_norm_pair":
+        s, _ = ops.add_layer_norm_pair(xd, rd, gd, bd, 1e-5)
+    elif op == "add_rms_norm_pair":
+        s, _ = ops.add_rms_norm_pair(xd, rd, gd, 1e-6)
+    else:
+        s, _ = ops.layer_norm_fanout(xd * 1.0, gd, bd, 1e-5)            # a non-leaf input, as in the decoder loop
+    (s * wd).sum().backward()
+    assert torch.equal(xd.grad, wd)
+    if op != "layer_norm_fanout":
+        assert torch.equal(rd.grad, wd)
+    assert gd.grad is None and bd.grad is None
+
+
+@pytest.mark.parametrize("rows,cols", NORM_SHAPES)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_add_layer_norm_pair_residual_only_dropout(rows, cols, dtype):
+    """Residual-only use with dropout: res still gets the upstream gradient itself, x gets it through the dropout mask of
+    (p, seed) -- what gated_residual's backward computes."""
+    from mmgl_amd import ops
+    p, seed = 0.3, 24680
+    x, r, w, gamma, beta = _norm_inputs(rows, cols, 3)
+    wd = w.to(dtype).cuda()
+    xa, ra = dev(x, dtype), dev(r, dtype)
+    s, _ = ops.add_layer_norm_pair(xa, ra, gamma.to(dtype).cuda(), beta.to(dtype).cuda(), 1e-5, p, True, seed=seed)
+    (s * wd).sum().backward()
+    xb, rb = dev(x, dtype), dev(r, dtype)
+    s2 = ops.gated_residual(rb, xb, None, p, True, seed=seed)
+    (s2 * wd).sum().backward()
+    assert torch.equal(s, s2)
+    assert torch.equal(ra.grad, wd)
+    assert_close(xa.grad.float(), xb.grad.float(), tol(dtype), "dx")
+
+
+@pytest.mark.parametrize("rows,cols", NORM_SHAPES)
+@pytest.mark.parametrize("rms", [False, True])
+def test_norm_fp32_params_bf16_activations(rows, cols, rms):
+    """bf16 activations with trainable fp32 gamma / beta: the kernel reads the parameters rounded to bf16, and their gradients come
+    back in fp32."""
+    from mmgl_amd import ops
+    dtype = torch.bfloat16
+    x, w, gamma, beta = _norm_inputs(rows, cols, 2)
+    xd, wd = dev(x, dtype), w.to(dtype).cuda()
+    gd, bd = dev(gamma, torch.float32), dev(beta, torch.float32)
+    y = ops.rms_norm(xd, gd, 1e-6) if rms else ops.layer_norm(xd, gd, bd, 1e-5)
+    (y * wd).sum().backward()
+    xr = xd.detach().float().cpu().requires_grad_()
+    gr, br = (t.detach().to(dtype).float().cpu().requires_grad_() for t in (gd, bd))
+    yr = xr * torch.rsqrt(xr.pow(2).mean(-1, keepdim=True) + 1e-6) * gr if rms else F.layer_norm(xr, (cols,), gr, br, 1e-5)
+    (yr * wd.float().cpu()).sum().backward()
+    t = tol(dtype)
+    assert y.dtype == dtype and gd.grad.dtype == torch.float32
+    assert_close(y.float(), yr, t, "y")
+    assert_close(xd.grad.float(), xr.grad, t, "dx")
+    assert_close(gd.grad, gr.grad, t, "dgamma")
+    if not rms:
+        assert bd.grad.dtype == torch.float32
+        assert_close(bd.grad, br.grad, t, "dbeta")
+
+
+@pytest.mark.parametrize("rows,cols", NORM_SHAPES)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_layernorm_partial_and_no_affine(rows, cols, dtype):
+    """gamma trainable beside a frozen beta: only gamma gets a gradient.  And layer_norm(x, None, None): no affine at all."""
+    from mmgl_amd import ops
+    x, w, gamma, beta = _norm_inputs(rows, cols, 2)
+    wd, t = w.to(dtype).cuda(), tol(dtype)
+    xd, gd, bd = dev(x, dtype), dev(gamma, dtype), beta.to(dtype).cuda()
+    y = ops.layer_norm(xd, gd, bd, 1e-5)
+    (y * wd).sum().backward()
+    xr, gr = (t_.detach().float().cpu().requires_grad_() for t_ in (xd, gd))
+    yr = F.layer_norm(xr, (cols,), gr, bd.float().cpu(), 1e-5)
+    (yr * wd.float().cpu()).sum().backward()
+    assert bd.grad is None
+    assert_close(y.float(), yr, t, "y")
+    assert_close(xd.grad.float(), xr.grad, t, "dx")
+    assert_close(gd.grad.float(), gr.grad, t, "dgamma")
+    xn = dev(x, dtype)
+    yn = ops.layer_norm(xn, None, None, 1e-5)
+    (yn * wd).sum().backward()
+    xr.grad = None
+    ynr = F.layer_norm(xr, (cols,), None, None, 1e-5)
+    (ynr * wd.float().cpu()).sum().backward()
+    assert_close(yn.float(), ynr, t, "y, no affine")
+    assert_close(xn.grad.float(), xr.grad, t, "dx, no affine")
+
+
 @pytest.mark.parametrize("n", [(3, 7, 64), (4, 640, 2048), (1, 5, 13)])
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_gated_residual_eval(n, dtype):
