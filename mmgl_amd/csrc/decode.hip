@@ -328,6 +328,27 @@ template <> struct Vec16<float> { typedef f32x4 type; };
 constexpr int AD_WAVES = 4;
 constexpr int AD_UNROLL = 4;
 
+// The operands every single-query attention entry point shares: q [rows, ldq] and out [rows, H*D] (rows = B, or B*W beam rows), the
+// per-sample keys / values k, v [B, S, ldkv] of Hkv heads (batch stride bs_kv) and their mask valid [B, ld_valid].
+struct AttnPrefix {
+    const void *q, *k, *v;
+    const uint8_t* valid;
+    void* out;
+    int ldq, ldkv, ld_valid, B, H, Hkv, S, D, dtype;
+    size_t bs_kv;
+};
+
+// returns FN<T, D>(...) at the head_dim that check_attn_prefix let through: nothing after it runs
+#define RETURN_BY_HEAD_DIM(FN, T, D, ...)               \
+    do {                                                \
+        switch (D) {                                    \
+            case 16: return FN<T, 16>(__VA_ARGS__);     \
+            case 32: return FN<T, 32>(__VA_ARGS__);     \
+            case 64: return FN<T, 64>(__VA_ARGS__);     \
+            default: return FN<T, 128>(__VA_ARGS__);    \
+        }                                               \
+    } while (0)
+
 template <typename T, int D>
 __global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k,
                                                                       const T* __restrict__ v, int ldkv, size_t bs_kv,
@@ -423,23 +444,11 @@ __global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_kernel(const T* _
 }
 
 template <typename T, int D>
-int launch_attn_decode(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t bs_kv, const uint8_t* valid, int ld_valid,
-                       void* out, int B, int H, int S, hipStream_t st) {
-    hipLaunchKernelGGL((attn_decode_kernel<T, D>), dim3(B * H), dim3(AD_WAVES * WAVE), 0, st, (const T*)q, ldq, (const T*)k, (const T*)v,
-                       ldkv, bs_kv, valid, ld_valid, (T*)out, H, S);
+int launch_attn_decode(const AttnPrefix& a, hipStream_t st) {
+    hipLaunchKernelGGL((attn_decode_kernel<T, D>), dim3(a.B * a.H), dim3(AD_WAVES * WAVE), 0, st, (const T*)a.q, a.ldq, (const T*)a.k,
+                       (const T*)a.v, a.ldkv, a.bs_kv, a.valid, a.ld_valid, (T*)a.out, a.H, a.S);
     MMGL_CHECK_LAUNCH("mmgl_attn_decode_fwd");
     return MMGL_OK;
-}
-
-template <typename T>
-int attn_decode_d(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t bs_kv, const uint8_t* valid, int ld_valid, void* out,
-                  int B, int H, int S, int D, hipStream_t st) {
-    switch (D) {
-        case 16: return launch_attn_decode<T, 16>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, S, st);
-        case 32: return launch_attn_decode<T, 32>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, S, st);
-        case 64: return launch_attn_decode<T, 64>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, S, st);
-        default: return launch_attn_decode<T, 128>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, S, st);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ grouped-query single-query attention
@@ -584,13 +593,12 @@ __global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_gqa_kernel(const 
 }
 
 template <typename T, int D>
-int attn_decode_gqa_nq(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t bs_kv, const uint8_t* valid, int ld_valid,
-                       void* out, int B, int H, int Hkv, int S, hipStream_t st) {
-    const int G = H / Hkv, nblk = cdiv(G, 8), qpb = cdiv(G, nblk);        // G > 8: further blocks, of equal size up to one head
-    const dim3 grid(B * Hkv * nblk), block(AD_WAVES * WAVE);
+int attn_decode_gqa_nq(const AttnPrefix& a, hipStream_t st) {
+    const int G = a.H / a.Hkv, nblk = cdiv(G, 8), qpb = cdiv(G, nblk);    // G > 8: further blocks, of equal size up to one head
+    const dim3 grid(a.B * a.Hkv * nblk), block(AD_WAVES * WAVE);
 #define MMGL_GQA_DECODE(NQ)                                                                                                          \
-    hipLaunchKernelGGL((attn_decode_gqa_kernel<T, D, NQ>), grid, block, 0, st, (const T*)q, ldq, (const T*)k, (const T*)v, ldkv, bs_kv, \
-                       valid, ld_valid, (T*)out, H, Hkv, S, qpb, nblk)
+    hipLaunchKernelGGL((attn_decode_gqa_kernel<T, D, NQ>), grid, block, 0, st, (const T*)a.q, a.ldq, (const T*)a.k, (const T*)a.v, a.ldkv, \
+                       a.bs_kv, a.valid, a.ld_valid, (T*)a.out, a.H, a.Hkv, a.S, qpb, nblk)
     if (qpb == 1) MMGL_GQA_DECODE(1);
     else if (qpb == 2) MMGL_GQA_DECODE(2);
     else if (qpb <= 4) MMGL_GQA_DECODE(4);
@@ -598,17 +606,6 @@ int attn_decode_gqa_nq(const void* q, int ldq, const void* k, const void* v, int
 #undef MMGL_GQA_DECODE
     MMGL_CHECK_LAUNCH("mmgl_attn_decode_gqa_fwd");
     return MMGL_OK;
-}
-
-template <typename T>
-int attn_decode_gqa_d(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t bs_kv, const uint8_t* valid, int ld_valid,
-                      void* out, int B, int H, int Hkv, int S, int D, hipStream_t st) {
-    switch (D) {
-        case 16: return attn_decode_gqa_nq<T, 16>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, Hkv, S, st);
-        case 32: return attn_decode_gqa_nq<T, 32>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, Hkv, S, st);
-        case 64: return attn_decode_gqa_nq<T, 64>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, Hkv, S, st);
-        default: return attn_decode_gqa_nq<T, 128>(q, ldq, k, v, ldkv, bs_kv, valid, ld_valid, out, B, H, Hkv, S, st);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ beam-shared single-query attention
@@ -780,21 +777,21 @@ __global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_beam_kernel(const
 }
 
 struct BeamAttnArgs {
-    const void *q, *kp, *vp, *kt, *vt;
-    const uint8_t* valid;
+    AttnPrefix p;                                  // the sample's shared prefix; q and out have B*W rows
+    const void *kt, *vt;
     const int* src;
-    void* out;
-    int ldq, ld_pre, ld_valid, ld_tail, ld_src, B, W, H, S, n_tail;
-    size_t bs_pre, rs_tail;
+    int ld_tail, ld_src, W, n_tail;
+    size_t rs_tail;
 };
 
 template <typename T, int D>
 int attn_decode_beam_nq(const BeamAttnArgs& a, hipStream_t st) {
-    const dim3 grid(a.B * a.H), block(AD_WAVES * WAVE);
+    const AttnPrefix& p = a.p;
+    const dim3 grid(p.B * p.H), block(AD_WAVES * WAVE);
 #define MMGL_BEAM_DECODE(NQ)                                                                                                            \
-    hipLaunchKernelGGL((attn_decode_beam_kernel<T, D, NQ>), grid, block, 0, st, (const T*)a.q, a.ldq, (const T*)a.kp, (const T*)a.vp,  \
-                       a.ld_pre, a.bs_pre, a.valid, a.ld_valid, (const T*)a.kt, (const T*)a.vt, a.ld_tail, a.rs_tail, a.src, a.ld_src, \
-                       (T*)a.out, a.W, a.H, a.S, a.n_tail)
+    hipLaunchKernelGGL((attn_decode_beam_kernel<T, D, NQ>), grid, block, 0, st, (const T*)p.q, p.ldq, (const T*)p.k, (const T*)p.v,    \
+                       p.ldkv, p.bs_kv, p.valid, p.ld_valid, (const T*)a.kt, (const T*)a.vt, a.ld_tail, a.rs_tail, a.src, a.ld_src,    \
+                       (T*)p.out, a.W, p.H, p.S, a.n_tail)
     if (a.W == 1) MMGL_BEAM_DECODE(1);
     else if (a.W == 2) MMGL_BEAM_DECODE(2);
     else if (a.W <= 4) MMGL_BEAM_DECODE(4);
@@ -802,16 +799,6 @@ int attn_decode_beam_nq(const BeamAttnArgs& a, hipStream_t st) {
 #undef MMGL_BEAM_DECODE
     MMGL_CHECK_LAUNCH("mmgl_attn_decode_beam_fwd");
     return MMGL_OK;
-}
-
-template <typename T>
-int attn_decode_beam_d(const BeamAttnArgs& a, int D, hipStream_t st) {
-    switch (D) {
-        case 16: return attn_decode_beam_nq<T, 16>(a, st);
-        case 32: return attn_decode_beam_nq<T, 32>(a, st);
-        case 64: return attn_decode_beam_nq<T, 64>(a, st);
-        default: return attn_decode_beam_nq<T, 128>(a, st);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ rotary embedding of one new token
@@ -849,15 +836,41 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(T* __restrict__ qkv
     }
 }
 
+// what the two skinny GEMM entry points refuse alike (their sizes and leading dimensions differ by the adapter's).  ptrs: every
+// required pointer is set; hint: the way out of M > 64 that `who` offers
+int check_skinny(const char* who, const char* hint, bool ptrs, int M, int act, int dtype) {
+    if (M > 64) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: M=%d > 64 rows (%s)", who, M, hint);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "%s: bad dtype %d", who, dtype);
+    MMGL_CHECK_ARG(ptrs, "%s: null pointer", who);
+    MMGL_CHECK_ARG(act == MMGL_ACT_NONE || act == MMGL_ACT_RELU, "%s: unknown activation %d", who, act);
+    return MMGL_OK;
+}
+
+// what every single-query attention entry point refuses about its prefix operands, after its own test of the sizes.  kv, rows, s_name
+// and ld_name are the entry point's words for its keys in the messages.
+int check_attn_prefix(const AttnPrefix& a, const char* who, const char* kv = "k and v", const char* rows = "key", const char* s_name = "S",
+                      const char* ld_name = "ldkv") {
+    MMGL_CHECK_ARG(a.dtype == MMGL_BF16 || a.dtype == MMGL_F32, "%s: bad dtype %d", who, a.dtype);
+    if (a.D != 16 && a.D != 32 && a.D != 64 && a.D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: head_dim %d (16, 32, 64, 128)", who, a.D);
+    const int vec = a.dtype == MMGL_BF16 ? 8 : 4;
+    if (a.ldq % vec || a.ldkv % vec || a.bs_kv % vec)
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: strides (%d, %d, %zu) must be multiples of 16 bytes", who, a.ldq, a.ldkv, a.bs_kv);
+    MMGL_CHECK_ARG(a.q && a.k && a.v && a.valid && a.out, "%s: null pointer", who);
+    MMGL_CHECK_ARG(a.ldq >= a.H * a.D && a.ldkv >= a.Hkv * a.D && a.ld_valid >= a.S, "%s: strides (%d, %d, %d) smaller than the rows", who, a.ldq,
+                   a.ldkv, a.ld_valid);
+    if (!aligned16(a.q) || !aligned16(a.k) || !aligned16(a.v)) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: q, %s must be 16-byte aligned", who, kv);
+    if (((size_t)(a.S - 1) * a.ldkv + a.D) * (a.dtype == MMGL_BF16 ? 2 : 4) >= (1ull << 31))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: a sample's %s rows span 2 GiB or more (%s=%d, %s=%d)", who, rows, s_name, a.S, ld_name, a.ldkv);
+    return MMGL_OK;
+}
+
 }  // namespace
 
 extern "C" int mmgl_gemm_skinny(const void* x, int ldx, const void* W, int ldw, const void* bias, const void* residual, void* y, int ldy,
                                 int M, int N, int K, int act, float scale, int dtype, void* stream) {
     MMGL_CHECK_ARG(M >= 1 && N >= 1 && K >= 1, "mmgl_gemm_skinny: bad sizes M=%d N=%d K=%d", M, N, K);
-    if (M > 64) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_gemm_skinny: M=%d > 64 rows (chunk the rows or use mmgl_gemm_nt)", M);
-    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_gemm_skinny: bad dtype %d", dtype);
-    MMGL_CHECK_ARG(x && W && y, "mmgl_gemm_skinny: null pointer");
-    MMGL_CHECK_ARG(act == MMGL_ACT_NONE || act == MMGL_ACT_RELU, "mmgl_gemm_skinny: unknown activation %d", act);
+    const int bad = check_skinny(__func__, "chunk the rows or use mmgl_gemm_nt", x && W && y, M, act, dtype);
+    if (bad) return bad;
     MMGL_CHECK_ARG(ldx >= K && ldw >= K && ldy >= N, "mmgl_gemm_skinny: leading dimensions (%d, %d, %d) smaller than the rows (K=%d, N=%d)",
                    ldx, ldw, ldy, K, N);
     hipStream_t st = (hipStream_t)stream;
@@ -873,11 +886,9 @@ extern "C" int mmgl_gemm_skinny_lora(const void* x, int ldx, const void* W, int 
                                      const void* lora_A, int lda, const void* lora_B, int ldb, int r, float lora_scale, void* workspace,
                                      int M, int N, int K, int act, float scale, int dtype, void* stream) {
     MMGL_CHECK_ARG(M >= 1 && N >= 1 && K >= 1 && r >= 1, "mmgl_gemm_skinny_lora: bad sizes M=%d N=%d K=%d r=%d", M, N, K, r);
-    if (M > 64) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_gemm_skinny_lora: M=%d > 64 rows (chunk the rows)", M);
     if (r > 256) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_gemm_skinny_lora: rank %d > 256", r);
-    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_gemm_skinny_lora: bad dtype %d", dtype);
-    MMGL_CHECK_ARG(x && W && y && lora_A && lora_B && workspace, "mmgl_gemm_skinny_lora: null pointer");
-    MMGL_CHECK_ARG(act == MMGL_ACT_NONE || act == MMGL_ACT_RELU, "mmgl_gemm_skinny_lora: unknown activation %d", act);
+    const int bad = check_skinny(__func__, "chunk the rows", x && W && y && lora_A && lora_B && workspace, M, act, dtype);
+    if (bad) return bad;
     MMGL_CHECK_ARG(ldx >= K && ldw >= K && ldy >= N && lda >= K && ldb >= r,
                    "mmgl_gemm_skinny_lora: leading dimensions (%d, %d, %d, %d, %d) smaller than the rows (K=%d, N=%d, r=%d)", ldx, ldw, ldy, lda,
                    ldb, K, N, r);
@@ -901,20 +912,12 @@ extern "C" int mmgl_gemm_skinny_lora(const void* x, int ldx, const void* W, int 
 extern "C" int mmgl_attn_decode_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,
                                     const uint8_t* key_valid, int ld_valid, void* out, int B, int H, int S, int D, int dtype, void* stream) {
     MMGL_CHECK_ARG(B >= 1 && H >= 1 && S >= 1, "mmgl_attn_decode_fwd: bad sizes B=%d H=%d S=%d", B, H, S);
-    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_attn_decode_fwd: bad dtype %d", dtype);
-    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_fwd: head_dim %d (16, 32, 64, 128)", D);
-    const int vec = dtype == MMGL_BF16 ? 8 : 4;
-    if (ldq % vec || ldkv % vec || batch_stride_kv % vec)
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_fwd: strides (%d, %d, %zu) must be multiples of 16 bytes", ldq, ldkv, batch_stride_kv);
-    MMGL_CHECK_ARG(q && k && v && key_valid && out, "mmgl_attn_decode_fwd: null pointer");
-    MMGL_CHECK_ARG(ldq >= H * D && ldkv >= H * D && ld_valid >= S, "mmgl_attn_decode_fwd: strides (%d, %d, %d) smaller than the rows", ldq, ldkv, ld_valid);
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v))
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_fwd: q, k and v must be 16-byte aligned");
-    if (((size_t)(S - 1) * ldkv + D) * (dtype == MMGL_BF16 ? 2 : 4) >= (1ull << 31))
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_fwd: a sample's key rows span 2 GiB or more (S=%d, ldkv=%d)", S, ldkv);
+    const AttnPrefix a{q, k, v, key_valid, out, ldq, ldkv, ld_valid, B, H, H, S, D, dtype, batch_stride_kv};
+    const int bad = check_attn_prefix(a, __func__);
+    if (bad) return bad;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16) return attn_decode_d<bf16>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, S, D, st);
-    return attn_decode_d<float>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, S, D, st);
+    if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(launch_attn_decode, bf16, D, a, st);
+    RETURN_BY_HEAD_DIM(launch_attn_decode, float, D, a, st);
 }
 
 extern "C" int mmgl_attn_decode_gqa_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,
@@ -922,21 +925,12 @@ extern "C" int mmgl_attn_decode_gqa_fwd(const void* q, int ldq, const void* k, c
                                         void* stream) {
     MMGL_CHECK_ARG(B >= 1 && H >= 1 && Hkv >= 1 && S >= 1, "mmgl_attn_decode_gqa_fwd: bad sizes B=%d H=%d Hkv=%d S=%d", B, H, Hkv, S);
     MMGL_CHECK_ARG(H % Hkv == 0, "mmgl_attn_decode_gqa_fwd: %d query heads are no multiple of %d key/value heads", H, Hkv);
-    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_attn_decode_gqa_fwd: bad dtype %d", dtype);
-    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_gqa_fwd: head_dim %d (16, 32, 64, 128)", D);
-    const int vec = dtype == MMGL_BF16 ? 8 : 4;
-    if (ldq % vec || ldkv % vec || batch_stride_kv % vec)
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_gqa_fwd: strides (%d, %d, %zu) must be multiples of 16 bytes", ldq, ldkv, batch_stride_kv);
-    MMGL_CHECK_ARG(q && k && v && key_valid && out, "mmgl_attn_decode_gqa_fwd: null pointer");
-    MMGL_CHECK_ARG(ldq >= H * D && ldkv >= Hkv * D && ld_valid >= S, "mmgl_attn_decode_gqa_fwd: strides (%d, %d, %d) smaller than the rows", ldq, ldkv,
-                   ld_valid);
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v))
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_gqa_fwd: q, k and v must be 16-byte aligned");
-    if (((size_t)(S - 1) * ldkv + D) * (dtype == MMGL_BF16 ? 2 : 4) >= (1ull << 31))
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_gqa_fwd: a sample's key rows span 2 GiB or more (S=%d, ldkv=%d)", S, ldkv);
+    const AttnPrefix a{q, k, v, key_valid, out, ldq, ldkv, ld_valid, B, H, Hkv, S, D, dtype, batch_stride_kv};
+    const int bad = check_attn_prefix(a, __func__);
+    if (bad) return bad;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16) return attn_decode_gqa_d<bf16>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, Hkv, S, D, st);
-    return attn_decode_gqa_d<float>(q, ldq, k, v, ldkv, batch_stride_kv, key_valid, ld_valid, out, B, H, Hkv, S, D, st);
+    if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(attn_decode_gqa_nq, bf16, D, a, st);
+    RETURN_BY_HEAD_DIM(attn_decode_gqa_nq, float, D, a, st);
 }
 
 extern "C" int mmgl_attn_decode_beam_fwd(const void* q, int ldq, const void* k_pre, const void* v_pre, int ld_pre, size_t batch_stride_pre,
@@ -946,19 +940,12 @@ extern "C" int mmgl_attn_decode_beam_fwd(const void* q, int ldq, const void* k_p
     MMGL_CHECK_ARG(B >= 1 && W >= 1 && H >= 1 && S_pre >= 1 && n_tail >= 0, "mmgl_attn_decode_beam_fwd: bad sizes B=%d W=%d H=%d S_pre=%d n_tail=%d",
                    B, W, H, S_pre, n_tail);
     if (W > 8) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: %d beams per sample (1..8)", W);
-    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_attn_decode_beam_fwd: bad dtype %d", dtype);
-    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: head_dim %d (16, 32, 64, 128)", D);
-    const int vec = dtype == MMGL_BF16 ? 8 : 4, esz = dtype == MMGL_BF16 ? 2 : 4;
-    if (ldq % vec || ld_pre % vec || batch_stride_pre % vec)
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: strides (%d, %d, %zu) must be multiples of 16 bytes", ldq, ld_pre, batch_stride_pre);
-    MMGL_CHECK_ARG(q && k_pre && v_pre && key_valid && out, "mmgl_attn_decode_beam_fwd: null pointer");
-    MMGL_CHECK_ARG(ldq >= H * D && ld_pre >= H * D && ld_valid >= S_pre, "mmgl_attn_decode_beam_fwd: strides (%d, %d, %d) smaller than the rows", ldq,
-                   ld_pre, ld_valid);
-    if (!aligned16(q) || !aligned16(k_pre) || !aligned16(v_pre))
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: q, k_pre and v_pre must be 16-byte aligned");
-    if (((size_t)(S_pre - 1) * ld_pre + D) * esz >= (1ull << 31))
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: a sample's prefix rows span 2 GiB or more (S_pre=%d, ld_pre=%d)", S_pre, ld_pre);
+    const BeamAttnArgs a{{q, k_pre, v_pre, key_valid, out, ldq, ld_pre, ld_valid, B, H, H, S_pre, D, dtype, batch_stride_pre},
+                         k_tail, v_tail, src, ld_tail, ld_src, W, n_tail, row_stride_tail};
+    const int bad = check_attn_prefix(a.p, __func__, "k_pre and v_pre", "prefix", "S_pre", "ld_pre");
+    if (bad) return bad;
     if (n_tail > 0) {
+        const int vec = dtype == MMGL_BF16 ? 8 : 4, esz = dtype == MMGL_BF16 ? 2 : 4;
         MMGL_CHECK_ARG(k_tail && v_tail && src, "mmgl_attn_decode_beam_fwd: null tail pointer with n_tail=%d", n_tail);
         if (ld_tail % vec || row_stride_tail % vec || !aligned16(k_tail) || !aligned16(v_tail) || ((uintptr_t)src & 3))
             MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_beam_fwd: tail strides (%d, %zu) must be multiples of 16 bytes, k_tail and v_tail 16-byte "
@@ -979,11 +966,9 @@ extern "C" int mmgl_attn_decode_beam_fwd(const void* q, int ldq, const void* k_p
                 }
         }
     }
-    const BeamAttnArgs a{q, k_pre, v_pre, k_tail, v_tail, key_valid, src, out, ldq, ld_pre, ld_valid, ld_tail, ld_src, B, W, H, S_pre, n_tail,
-                         batch_stride_pre, row_stride_tail};
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MMGL_BF16) return attn_decode_beam_d<bf16>(a, D, st);
-    return attn_decode_beam_d<float>(a, D, st);
+    if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(attn_decode_beam_nq, bf16, D, a, st);
+    RETURN_BY_HEAD_DIM(attn_decode_beam_nq, float, D, a, st);
 }
 
 extern "C" int mmgl_rope_kv_append(void* qkv, int ldqkv, const float* cos_sin_row, void* kv_col, size_t batch_stride_kv, int B, int H, int Hkv,

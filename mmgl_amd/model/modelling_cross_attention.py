@@ -127,6 +127,11 @@ def _lin(module: nn.Module, x):
     return ops.frozen_linear(x, module.weight, module.bias)
 
 
+def _plain(*mods):
+    if any(type(m) is not nn.Linear for m in mods):
+        raise ValueError("the decode step runs plain nn.Linear projections only (adapted projections, e.g. LoRA, have no decode path)")
+
+
 class MPTAttention(nn.Module):
     """Multi-head attention; cross_attention=True attends over the neighbor tokens (reference :148-275)."""
 
@@ -178,45 +183,40 @@ class MPTAttention(nn.Module):
             o = ops.xattn_core(q, k, v, key_valid, self.num_heads)
         return ops.linear(o, self.out_proj.weight, self.out_proj.bias), attn_w, None
 
-    def _frozen_qkv(self):
-        """[3d, d] weight / [3d] bias = (q_proj * scaling | k_proj | v_proj) when the three projections are frozen (the
-        reference freezes the whole LM outside the cross-attention layers, :731-737), else None.  A derived copy: the
-        module's own parameters and state_dict stay as loaded; rebuilt when they change (load_state_dict, .bfloat16())."""
-        if any(type(m) is not nn.Linear for m in (self.q_proj, self.k_proj, self.v_proj)):
-            return None                      # adapted projections (LoRA): each one runs its own forward
-        ps = (self.q_proj.weight, self.k_proj.weight, self.v_proj.weight, self.q_proj.bias, self.k_proj.bias, self.v_proj.bias)
+    def _fused_qkv(self, ps, slot):
+        """[3d, d] weight / [3d] bias = (q * scaling | k | v) of the frozen parameters ps = (three weights, three biases), else None.
+        A derived copy kept in self.__dict__[slot]: the module's own parameters and state_dict stay as loaded; rebuilt when they change
+        (load_state_dict, .bfloat16())."""
         if any(p is None or p.requires_grad for p in ps):
             return None
         key = tuple((p.data_ptr(), p._version, p.dtype) for p in ps)
-        cache = self.__dict__.get("_qkv_cache")
+        cache = self.__dict__.get(slot)
         if cache is None or cache[0] != key:
             with torch.no_grad():
                 w = torch.cat([ps[0].float() * self.scaling, ps[1].float(), ps[2].float()], 0).to(ps[0].dtype).contiguous()
                 b = torch.cat([ps[3].float() * self.scaling, ps[4].float(), ps[5].float()], 0).to(ps[0].dtype).contiguous()
             cache = (key, (w, b))
-            self.__dict__["_qkv_cache"] = cache
+            self.__dict__[slot] = cache
         return cache[1]
 
+    def _frozen_qkv(self):
+        """The fused weight / bias (_fused_qkv) when the three projections are frozen (the reference freezes the whole LM outside
+        the cross-attention layers, :731-737), else None."""
+        q, k, v = self.q_proj, self.k_proj, self.v_proj
+        if any(type(m) is not nn.Linear for m in (q, k, v)):
+            return None                      # adapted projections (LoRA): each one runs its own forward
+        return self._fused_qkv((q.weight, k.weight, v.weight, q.bias, k.bias, v.bias), "_qkv_cache")
+
     def _lora_qkv(self):
-        """The fused frozen [3d, d] weight / [3d] bias under LoRA adapters on q_proj and v_proj (peft's OPT targets) with a plain
-        frozen k_proj, else None.  Same derived-copy cache as _frozen_qkv."""
+        """The fused frozen weight / bias (_fused_qkv) under LoRA adapters on q_proj and v_proj (peft's OPT targets) with a plain
+        frozen k_proj, else None."""
         q, k, v = self.q_proj, self.k_proj, self.v_proj
         if not (hasattr(q, "lora_A") and hasattr(v, "lora_A") and type(k) is nn.Linear) or q.r != v.r or q.scaling != v.scaling:
             return None
         if self.training and (getattr(q, "lora_dropout", 0.0) > 0.0 or getattr(v, "lora_dropout", 0.0) > 0.0):
             return None                      # lora_dropout: each adapted projection runs its own (unfused) forward
-        ps = (q.base_layer.weight, k.weight, v.base_layer.weight, q.base_layer.bias, k.bias, v.base_layer.bias)
-        if any(p is None or p.requires_grad for p in ps):
-            return None
-        key = tuple((p.data_ptr(), p._version, p.dtype) for p in ps)
-        cache = self.__dict__.get("_lora_qkv_cache")
-        if cache is None or cache[0] != key:
-            with torch.no_grad():
-                w = torch.cat([ps[0].float() * self.scaling, ps[1].float(), ps[2].float()], 0).to(ps[0].dtype).contiguous()
-                b = torch.cat([ps[3].float() * self.scaling, ps[4].float(), ps[5].float()], 0).to(ps[0].dtype).contiguous()
-            cache = (key, (w, b))
-            self.__dict__["_lora_qkv_cache"] = cache
-        return cache[1]
+        return self._fused_qkv((q.base_layer.weight, k.weight, v.base_layer.weight, q.base_layer.bias, k.bias, v.base_layer.bias),
+                               "_lora_qkv_cache")
 
     # -- causal self-attention of the (frozen) OPT layers: HIP flash kernels, no [B,1,T,T] mask, no [B,H,T,T] scores
     def _forward_self(self, hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value=None, kv_out=None):
@@ -292,19 +292,14 @@ class MPTAttention(nn.Module):
         return self._forward_self(hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value, kv_out)
 
     # -- one decode step of generate(): M = batch rows, weight-streaming GEMMs and single-query attention (csrc/decode.hip)
-    def _plain(self, *mods):
-        if any(type(m) is not nn.Linear for m in mods):
-            raise ValueError("the decode step runs plain nn.Linear projections only (adapted projections, e.g. LoRA, have no decode path)")
-
     @staticmethod
     def _decode_proj(mod, x, out_scale=1.0, out=None):
         """One of q / k / v on the rows of a decode step: a plain nn.Linear, or a LoRA-adapted one through its own decode()
         (model/modelling_self_attention.LoRALinear: the rank-r term rides in the skinny GEMM's epilogue)."""
-        if type(mod) is nn.Linear:
-            return ops.decode_linear(x, mod.weight, mod.bias, out_scale=out_scale, out=out)
-        if hasattr(mod, "lora_A") and hasattr(mod, "decode"):
+        if type(mod) is not nn.Linear and hasattr(mod, "lora_A") and hasattr(mod, "decode"):
             return mod.decode(x, out_scale=out_scale, out=out)
-        raise ValueError("the decode step runs plain nn.Linear projections only (adapted projections, e.g. LoRA, have no decode path)")
+        _plain(mod)
+        return ops.decode_linear(x, mod.weight, mod.bias, out_scale=out_scale, out=out)
 
     def decode_self(self, x, kv, key_mask, col, beam=None, tail=None):
         """x [B, d]: the new token's layer input.  Projects q and writes k|v into column `col` of the layer's cache rows kv
@@ -314,34 +309,29 @@ class MPTAttention(nn.Module):
         the rows attend over the sample's `col` prompt columns of kv (shared, never copied) plus their own n_tail + 1 tail keys,
         addressed through beam.book.src (ops.attn_decode_beam).  Plain nn.Linear projections only."""
         d = self.embed_dim
-        self._plain(self.k_proj, self.out_proj)
-        if beam is not None:
-            self._plain(self.q_proj, self.v_proj)
-            j = beam.n_tail
-            fused = self._frozen_qkv()
-            if fused is not None:
-                w, b = fused
-                q = ops.decode_linear(x, w[:d], b[:d])
-                ops.decode_linear(x, w[d:], b[d:], out=tail[:, j])
-            else:
-                q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
-                ops.decode_linear(x, self.k_proj.weight, self.k_proj.bias, out=tail[:, j, :d])
-                ops.decode_linear(x, self.v_proj.weight, self.v_proj.bias, out=tail[:, j, d:])
-            return ops.attn_decode_beam(q, kv[:, :col, :d], kv[:, :col, d:], key_mask[:, :col], self.num_heads, beam.W,
-                                        tail[:, :j + 1, :d], tail[:, :j + 1, d:], beam.book.src)
+        _plain(self.k_proj, self.out_proj)
+        if beam is None:
+            dst = kv[:, col]
+        else:
+            _plain(self.q_proj, self.v_proj)
+            dst = tail[:, beam.n_tail]
         fused = self._frozen_qkv()
         if fused is not None:
             w, b = fused
             q = ops.decode_linear(x, w[:d], b[:d])
-            ops.decode_linear(x, w[d:], b[d:], out=kv[:, col])
+            ops.decode_linear(x, w[d:], b[d:], out=dst)
         else:
             q = self._decode_proj(self.q_proj, x, out_scale=self.scaling)
-            ops.decode_linear(x, self.k_proj.weight, self.k_proj.bias, out=kv[:, col, :d])
-            self._decode_proj(self.v_proj, x, out=kv[:, col, d:])
-        return ops.attn_decode(q, kv[:, :col + 1, :d], kv[:, :col + 1, d:], key_mask[:, :col + 1], self.num_heads)
+            ops.decode_linear(x, self.k_proj.weight, self.k_proj.bias, out=dst[:, :d])
+            self._decode_proj(self.v_proj, x, out=dst[:, d:])
+        if beam is None:
+            return ops.attn_decode(q, kv[:, :col + 1, :d], kv[:, :col + 1, d:], key_mask[:, :col + 1], self.num_heads)
+        n = beam.n_tail + 1
+        return ops.attn_decode_beam(q, kv[:, :col, :d], kv[:, :col, d:], key_mask[:, :col], self.num_heads, beam.W,
+                                    tail[:, :n, :d], tail[:, :n, d:], beam.book.src)
 
     def decode_cross(self, x, k, v, key_valid, beam=None):
-        self._plain(self.q_proj, self.out_proj)
+        _plain(self.q_proj, self.out_proj)
         q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
         if beam is not None:                  # the W beams of a sample read its neighbor tokens once: k, v stay at B rows
             return ops.attn_decode_beam(q, k, v, key_valid, self.num_heads, beam.W)
@@ -489,28 +479,25 @@ class MPTDecoderLayer(nn.Module):
         pre = self.do_layer_norm_before
         attn = self.self_attn
         ln1, ln2 = self.self_attn_layer_norm, self.final_layer_norm
-        if type(self.fc1) is not nn.Linear or type(self.fc2) is not nn.Linear or type(attn.out_proj) is not nn.Linear:
-            raise ValueError("the decode step runs plain nn.Linear projections only (adapted projections, e.g. LoRA, have no decode path)")
+        _plain(self.fc1, self.fc2, attn.out_proj)
         x = self._ln(ln1, h) if pre else h
-        if self.cross_attention:
-            gated = self.peft_type == "flamingo"
+        gated = self.cross_attention
+        if gated:                             # residual adds through ops.gated_residual (the gate is None outside flamingo)
+            g1, g2 = (self.gating1, self.gating2) if self.peft_type == "flamingo" else (None, None)
             k, v = cache.cross[idx]
             a = attn.decode_cross(x, k, v, cache.cross_valid, cache.beam)
-            a = ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias)
-            h = ops.gated_residual(h, a, self.gating1 if gated else None, 0.0, False)
-            if not pre:
-                h = self._ln(ln1, h)
-            x = self._ln(ln2, h) if pre else h
-            x = ops.decode_linear(self._decode_ffn(x), self.fc2.weight, self.fc2.bias)
-            h = ops.gated_residual(h, x, self.gating2 if gated else None, 0.0, False)
-            return h if pre else self._ln(ln2, h)
-        beam = cache.beam
-        a = attn.decode_self(x, cache.kv[idx], cache.mask, cache.col, beam, None if beam is None else beam.tail[idx])
-        h = ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias, residual=h)
+            h = ops.gated_residual(h, ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias), g1, 0.0, False)
+        else:                                 # frozen layer: the residual adds ride in the GEMM epilogues
+            beam = cache.beam
+            a = attn.decode_self(x, cache.kv[idx], cache.mask, cache.col, beam, None if beam is None else beam.tail[idx])
+            h = ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias, residual=h)
         if not pre:
             h = self._ln(ln1, h)
-        x = self._ln(ln2, h) if pre else h
-        h = ops.decode_linear(self._decode_ffn(x), self.fc2.weight, self.fc2.bias, residual=h)
+        x = self._decode_ffn(self._ln(ln2, h) if pre else h)
+        if gated:
+            h = ops.gated_residual(h, ops.decode_linear(x, self.fc2.weight, self.fc2.bias), g2, 0.0, False)
+        else:
+            h = ops.decode_linear(x, self.fc2.weight, self.fc2.bias, residual=h)
         return h if pre else self._ln(ln2, h)
 
 

@@ -1398,6 +1398,31 @@ def _no_grad_inputs(op, *ts):
         raise ValueError(f"{op} is forward only (the decode step of generate()): run it under torch.no_grad() or detach its inputs")
 
 
+def _as_uint8(mask):
+    """A bool mask viewed as uint8 (no launch, unlike _key_valid); any other dtype passes through."""
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _decode_gemm_operands(op, x, weight, bias, out):
+    """The operands of a decode GEMM x [M, K] x weight [N, K]^T as the skinny kernels take them: x and weight with unit column stride,
+    bias in x's dtype, and y -- `out` [M, N] (any row stride) checked, or a new dense tensor."""
+    M, N = x.shape[0], weight.shape[0]
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    weight = weight if weight.stride(1) == 1 else weight.contiguous()
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+    if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.dtype != x.dtype or weight.dtype != x.dtype:
+        raise ValueError(f"{op}: out{tuple(y.shape)} {y.dtype} for x{tuple(x.shape)} {x.dtype} weight{tuple(weight.shape)} {weight.dtype}")
+    if bias is not None and bias.dtype != x.dtype:
+        bias = bias.to(x.dtype)
+    return x, weight, bias, y
+
+
+def _row_chunks(M):
+    """The rows of a decode GEMM as slices of at most 64: what one mmgl_gemm_skinny / mmgl_gemm_skinny_lora call takes."""
+    return [slice(m0, min(M, m0 + 64)) for m0 in range(0, M, 64)]
+
+
 _SKINNY_MAX_N = 32768
 
 
@@ -1435,24 +1460,16 @@ def decode_linear(x, weight, bias=None, act="none", out_scale=1.0, residual=None
     M, K = x.shape
     N = weight.shape[0]
     code = _act_code("decode_linear", act)
-    if x.stride(1) != 1:
-        x = x.contiguous()
-    weight = weight if weight.stride(1) == 1 else weight.contiguous()
-    y = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
-    if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.dtype != x.dtype or weight.dtype != x.dtype:
-        raise ValueError(f"decode_linear: out{tuple(y.shape)} {y.dtype} for x{tuple(x.shape)} {x.dtype} weight{tuple(weight.shape)} {weight.dtype}")
+    x, weight, bias, y = _decode_gemm_operands("decode_linear", x, weight, bias, out)
     if residual is not None and (tuple(residual.shape) != (M, N) or residual.stride(1) != 1 or residual.stride(0) != y.stride(0)):
         raise ValueError("decode_linear: residual must have the output's shape and row stride")
-    if bias is not None and bias.dtype != x.dtype:
-        bias = bias.to(x.dtype)
     if M == 0:
         return y
     dense = y.stride(0) == N and x.stride(0) == K and weight.stride(0) == K
     if dense and x.dtype == torch.bfloat16 and K % 8 == 0 and N % 8 == 0 and not _skinny_route(M, N, K, x.dtype):
         return gemm_nt(x, weight, bias, residual, None, code, out_scale, K, y)
-    for m0 in range(0, M, 64):
-        m1 = min(M, m0 + 64)
-        gemm_skinny(x[m0:m1], weight, bias, None if residual is None else residual[m0:m1], code, out_scale, y[m0:m1])
+    for rows in _row_chunks(M):
+        gemm_skinny(x[rows], weight, bias, None if residual is None else residual[rows], code, out_scale, y[rows])
     return y
 
 
@@ -1489,26 +1506,44 @@ def decode_lora_linear(x, weight, bias, lora_A, lora_B, scaling, out_scale=1.0, 
     N, r = lora_B.shape
     if not 1 <= r <= 256:
         raise ValueError(f"decode_lora_linear: rank {r} (1..256)")
-    if x.stride(1) != 1:
-        x = x.contiguous()
-    weight = weight if weight.stride(1) == 1 else weight.contiguous()
+    x, weight, bias, y = _decode_gemm_operands("decode_lora_linear", x, weight, bias, out)
     A = lora_A.detach().to(x.dtype)
     B = lora_B.detach().to(x.dtype)
     A = A if A.stride(1) == 1 else A.contiguous()
     B = B if B.stride(1) == 1 else B.contiguous()
-    y = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
-    if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.dtype != x.dtype or weight.dtype != x.dtype:
-        raise ValueError(f"decode_lora_linear: out{tuple(y.shape)} {y.dtype} for x{tuple(x.shape)} {x.dtype} weight{tuple(weight.shape)} "
-                         f"{weight.dtype}")
-    if bias is not None and bias.dtype != x.dtype:
-        bias = bias.to(x.dtype)
     if M == 0:
         return y
     ws = torch.empty(min(M, 64) * r, dtype=torch.float32, device=x.device)       # t = x A^T of one chunk
-    for m0 in range(0, M, 64):
-        m1 = min(M, m0 + 64)
-        gemm_skinny_lora(x[m0:m1], weight, A, B, scaling, bias, None, 0, out_scale, y[m0:m1], ws)
+    for rows in _row_chunks(M):
+        gemm_skinny_lora(x[rows], weight, A, B, scaling, bias, None, 0, out_scale, y[rows], ws)
     return y
+
+
+def _decode_attn_operands(op, q, k, v, key_valid, num_heads, out, q_rows=1, key_cols=None, names=("k", "v", "keys"), tail=""):
+    """The operands of single-query attention: q [B * q_rows, d] against the per-sample views k, v [B, S, key_cols] (None: d columns)
+    with unit column stride and common strides, and key_valid [B, S].  Returns (B, S, d, the mask as uint8 with unit column stride
+    and its own row stride, `out` checked or a new dense [B * q_rows, d]).  names and tail only word the messages."""
+    if (q.dim() != 2 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] * q_rows
+            or (q.shape[1] if key_cols is None else key_cols) != k.shape[2] or k.stride() != v.stride() or k.stride(2) != 1 or q.stride(1) != 1
+            or k.dtype != q.dtype or v.dtype != q.dtype):
+        raise ValueError(f"{op}: incompatible q{tuple(q.shape)} {names[0]}{tuple(k.shape)}/{k.stride()} {names[1]}{tuple(v.shape)}/{v.stride()}{tail}")
+    R, d = q.shape
+    B, S = k.shape[:2]
+    if d % num_heads:
+        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {d} and `num_heads`: {num_heads}).")
+    _check_mask(key_valid, (B, S))
+    if S == 0:
+        raise ValueError(f"{op}: no {names[2]}")
+    key_valid = _as_uint8(key_valid)
+    if key_valid.dtype != torch.uint8:
+        key_valid = key_valid.to(torch.uint8)
+    if key_valid.stride(1) != 1:
+        key_valid = key_valid.contiguous()
+    if out is None:
+        out = torch.empty(R, d, dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (R, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError(f"{op}: out{tuple(out.shape)} {out.dtype} must be a dense [{R}, {d}] {q.dtype} tensor on {q.device}")
+    return B, S, d, key_valid, out
 
 
 def attn_decode(q, k, v, key_valid, num_heads, out=None, num_kv_heads=None):
@@ -1523,27 +1558,8 @@ def attn_decode(q, k, v, key_valid, num_heads, out=None, num_kv_heads=None):
     _no_grad_inputs("attn_decode", q, k, v)
     Hkv = _kv_heads("attn_decode", num_heads, num_kv_heads)
     kd = q.shape[-1] if Hkv is None or q.shape[-1] % num_heads else q.shape[-1] // num_heads * Hkv     # columns of a key row
-    if (q.dim() != 2 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or kd != k.shape[2] or k.stride() != v.stride()
-            or k.stride(2) != 1 or q.stride(1) != 1 or k.dtype != q.dtype or v.dtype != q.dtype):
-        raise ValueError(f"attn_decode: incompatible q{tuple(q.shape)} k{tuple(k.shape)}/{k.stride()} v{tuple(v.shape)}/{v.stride()}"
-                         + ("" if Hkv is None else f" for H={num_heads}, Hkv={Hkv}"))
-    B, d = q.shape
-    S = k.shape[1]
-    if d % num_heads:
-        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {d} and `num_heads`: {num_heads}).")
-    _check_mask(key_valid, (B, S))
-    if S == 0:
-        raise ValueError("attn_decode: no keys")
-    if key_valid.dtype == torch.bool:
-        key_valid = key_valid.view(torch.uint8)
-    elif key_valid.dtype != torch.uint8:
-        key_valid = key_valid.to(torch.uint8)
-    if key_valid.stride(1) != 1:
-        key_valid = key_valid.contiguous()
-    if out is None:
-        out = torch.empty(B, d, dtype=q.dtype, device=q.device)
-    elif tuple(out.shape) != (B, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
-        raise ValueError(f"attn_decode: out{tuple(out.shape)} {out.dtype} must be a dense [{B}, {d}] {q.dtype} tensor on {q.device}")
+    B, S, d, key_valid, out = _decode_attn_operands("attn_decode", q, k, v, key_valid, num_heads, out, key_cols=kd,
+                                                    tail="" if Hkv is None else f" for H={num_heads}, Hkv={Hkv}")
     if Hkv is None:
         _lib.call("mmgl_attn_decode_fwd", dict(bytes=2.0 * B * S * d * q.element_size()), ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(1), k.stride(0),
                   ptr(key_valid), key_valid.stride(0), ptr(out), B, num_heads, S, d // num_heads, dtype_code(q), stream_ptr())
@@ -1605,17 +1621,9 @@ def attn_decode_beam(q, k_pre, v_pre, key_valid, num_heads, num_beams, k_tail=No
     require_cuda(q, k_pre, v_pre, key_valid, k_tail, v_tail, src)
     _no_grad_inputs("attn_decode_beam", q, k_pre, v_pre, k_tail, v_tail)
     W = _beams("attn_decode_beam", num_beams)
-    if (q.dim() != 2 or k_pre.dim() != 3 or k_pre.shape != v_pre.shape or q.shape[0] != k_pre.shape[0] * W or q.shape[1] != k_pre.shape[2]
-            or k_pre.stride() != v_pre.stride() or k_pre.stride(2) != 1 or q.stride(1) != 1 or k_pre.dtype != q.dtype or v_pre.dtype != q.dtype):
-        raise ValueError(f"attn_decode_beam: incompatible q{tuple(q.shape)} k_pre{tuple(k_pre.shape)}/{k_pre.stride()} "
-                         f"v_pre{tuple(v_pre.shape)}/{v_pre.stride()} for {W} beams")
-    R, d = q.shape
-    B, S = k_pre.shape[:2]
-    if d % num_heads:
-        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {d} and `num_heads`: {num_heads}).")
-    _check_mask(key_valid, (B, S))
-    if S == 0:
-        raise ValueError("attn_decode_beam: no prefix keys")
+    B, S, d, key_valid, out = _decode_attn_operands("attn_decode_beam", q, k_pre, v_pre, key_valid, num_heads, out, q_rows=W,
+                                                    names=("k_pre", "v_pre", "prefix keys"), tail=f" for {W} beams")
+    R = B * W
     n_tail = 0 if k_tail is None else k_tail.shape[1] if k_tail.dim() == 3 else -1
     if (k_tail is None) != (v_tail is None) or n_tail < 0:
         raise ValueError("attn_decode_beam: k_tail and v_tail come together, as [B*W, n_tail, d] views")
@@ -1626,16 +1634,6 @@ def attn_decode_beam(q, k_pre, v_pre, key_valid, num_heads, num_beams, k_tail=No
                              f"{v_tail.stride()} for q{tuple(q.shape)}")
         if src is None or src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != R or src.shape[1] < n_tail or src.stride(1) != 1:
             raise ValueError(f"attn_decode_beam: src must be an int32 [{R}, >= {n_tail}] view with unit column stride")
-    if key_valid.dtype == torch.bool:
-        key_valid = key_valid.view(torch.uint8)
-    elif key_valid.dtype != torch.uint8:
-        key_valid = key_valid.to(torch.uint8)
-    if key_valid.stride(1) != 1:
-        key_valid = key_valid.contiguous()
-    if out is None:
-        out = torch.empty(R, d, dtype=q.dtype, device=q.device)
-    elif tuple(out.shape) != (R, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
-        raise ValueError(f"attn_decode_beam: out{tuple(out.shape)} {out.dtype} must be a dense [{R}, {d}] {q.dtype} tensor on {q.device}")
     tail = (ptr(k_tail), ptr(v_tail), k_tail.stride(1), k_tail.stride(0), ptr(src), src.stride(0)) if n_tail else (None, None, 0, 0, None, 0)
     _lib.call("mmgl_attn_decode_beam_fwd", dict(bytes=2.0 * (B * S + R * n_tail) * d * q.element_size()), ptr(q), q.stride(0), ptr(k_pre),
               ptr(v_pre), k_pre.stride(1), k_pre.stride(0), ptr(key_valid), key_valid.stride(0), *tail, ptr(out), B, W, num_heads, S, n_tail,
@@ -1677,6 +1675,17 @@ def beam_topk(logits, beam_score, num_beams, rows_in=None, out=None):
     return cs, ci
 
 
+def _logits_operand(op, logits):
+    """(rows, V, dtype code) of logits [rows, V]: unit column stride, not empty, V <= 131072 (sample_tokens, process_logits)."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] == 0 or logits.shape[1] == 0:
+        raise ValueError(f"{op}: logits{tuple(logits.shape)}/{logits.stride()} must be [rows, V] with unit column stride")
+    rows, V = logits.shape
+    code = dtype_code(logits)
+    if V > 131072:
+        raise ValueError(f"{op}: V = {V} (at most 131072)")
+    return rows, V, code
+
+
 def sample_tokens(logits, u, temperature=1.0, top_k=0, top_p=1.0, finished=None, eos_token_id=None, pad_token_id=None, out=None,
                   return_kept=False):
     """The selection step of generate(do_sample=True) in one launch (mmgl_sample_tokens): transformers' temperature -> top-k -> top-p
@@ -1690,12 +1699,7 @@ def sample_tokens(logits, u, temperature=1.0, top_k=0, top_p=1.0, finished=None,
     column of the ids tensor).  Returns the tokens (int64 [rows * n_draws], or `out`), with return_kept=True also the size of each
     row's kept set (int32 [rows]).  No [rows, V] intermediate, no host synchronisation, bitwise reproducible.  Forward only; GPU only."""
     require_cuda(logits, u, finished, out)
-    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] == 0 or logits.shape[1] == 0:
-        raise ValueError(f"sample_tokens: logits{tuple(logits.shape)}/{logits.stride()} must be [rows, V] with unit column stride")
-    rows, V = logits.shape
-    code = dtype_code(logits)
-    if V > 131072:
-        raise ValueError(f"sample_tokens: V = {V} (at most 131072)")
+    rows, V, code = _logits_operand("sample_tokens", logits)
     if u.dtype != torch.float32 or u.dim() not in (1, 2) or u.shape[0] != rows or not u.is_contiguous() or u.device != logits.device:
         raise ValueError(f"sample_tokens: u {u.dtype}{tuple(u.shape)} must be a dense fp32 [{rows}, n_draws] tensor on {logits.device}")
     n_draws = 1 if u.dim() == 1 else u.shape[1]
@@ -1710,8 +1714,7 @@ def sample_tokens(logits, u, temperature=1.0, top_k=0, top_p=1.0, finished=None,
         raise ValueError(f"sample_tokens: top_p = {top_p} outside (0, 1]")
     n = rows * n_draws
     if finished is not None:
-        if finished.dtype == torch.bool:
-            finished = finished.view(torch.uint8)
+        finished = _as_uint8(finished)
         if finished.dtype != torch.uint8 or tuple(finished.shape) != (n,) or not finished.is_contiguous() or finished.device != logits.device:
             raise ValueError(f"sample_tokens: finished must be a dense uint8 / bool [{n}] tensor on {logits.device}")
         if eos_token_id is not None and pad_token_id is None:
@@ -1746,12 +1749,7 @@ def process_logits(logits, history, history_valid=None, n_masked=None, repetitio
     in this order (-inf wins).  A token outside [0, V) is never an address.  Every other element keeps its bits.  Returns `logits`.
     Nothing is launched when everything is off.  No host synchronisation, bitwise reproducible.  Forward only; GPU only."""
     require_cuda(logits, history, history_valid, ban)
-    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] == 0 or logits.shape[1] == 0:
-        raise ValueError(f"process_logits: logits{tuple(logits.shape)}/{logits.stride()} must be [rows, V] with unit column stride")
-    rows, V = logits.shape
-    code = dtype_code(logits)
-    if V > 131072:
-        raise ValueError(f"process_logits: V = {V} (at most 131072)")
+    rows, V, code = _logits_operand("process_logits", logits)
     p, n = float(repetition_penalty), int(no_repeat_ngram_size)
     if not (0.0 < p < float("inf")):
         raise ValueError(f"process_logits: repetition_penalty = {repetition_penalty} must be positive and finite")
@@ -1771,8 +1769,7 @@ def process_logits(logits, history, history_valid=None, n_masked=None, repetitio
             raise ValueError(f"process_logits: n_masked = {n_masked} without history_valid")
         n_masked = 0
     else:
-        if history_valid.dtype == torch.bool:
-            history_valid = history_valid.view(torch.uint8)
+        history_valid = _as_uint8(history_valid)
         if (history_valid.dtype != torch.uint8 or history_valid.dim() != 2 or history_valid.shape[0] != rows
                 or (history_valid.shape[1] > 1 and history_valid.stride(1) != 1) or history_valid.stride(0) < 0
                 or history_valid.device != logits.device):
