@@ -204,7 +204,7 @@ int mmgl_linear_fwd(const void* x, const void* W, const void* bias, void* y,
  * none), then dx[M,K] = dyp @ W, dW[N,K] (+)= dyp^T @ x, dbias[N] (+)= colsum(dyp), each in the activation dtype and each
  * optional (NULL); accumulate != 0 adds dW / dbias to the existing contents (gradient accumulation across micro-batches).
  * N must be a multiple of 8; the fp32 path needs dW whenever dbias is requested.
- * mask_dx != 0: x is itself the output of a ReLU (fc2 after fc1+ReLU, modelling_cross_attention.py:352-355) and that ReLU's
+ * mask_dx != 0: x is itself the output of a ReLU (fc2 after fc1+ReLU: the trainable route of ops.relu_ffn) and that ReLU's
  * backward is folded into this call: dx is zeroed where x <= 0 (in the dgrad GEMM's epilogue for the large-shape kernel), so
  * the producing linear can be differentiated with act = none on the already-masked gradient. */
 size_t mmgl_linear_bwd_workspace(int M, int N, int K, int act, int dtype);

@@ -388,6 +388,13 @@ class MPTDecoderLayer(nn.Module):
             return ops.layer_norm_fanout(x, ln.weight, ln.bias, ln.eps)
         return x, ops.layer_norm(x, ln.weight, ln.bias, ln.eps)
 
+    def _ffn(self, x, frozen):
+        """fc2(act(fc1(x))) (reference :352-355); frozen=False: on ops.linear whatever the parameters say, None: as they say."""
+        if self.activation_name == "relu":
+            return ops.relu_ffn(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, frozen=frozen)
+        lin = _lin if frozen is None else lambda m, t: ops.linear(t, m.weight, m.bias)
+        return lin(self.fc2, self.activation_fn(lin(self.fc1, x)))
+
     def _forward_cross(self, h, neighbor_embeds, neighbor_attention_mask, layer_head_mask, output_attentions, kv_out=None):
         gated = self.peft_type == "flamingo"
         # pre-LN: the block input feeds the LayerNorm AND the residual add -- both gradients meet inside the LayerNorm backward kernel
@@ -398,13 +405,7 @@ class MPTDecoderLayer(nn.Module):
         if not self.do_layer_norm_before:
             h = self._ln(self.self_attn_layer_norm, h)
         residual, x = self._ln_fanout(self.final_layer_norm, h) if self.do_layer_norm_before else (h, h)
-        if self.activation_name == "relu":
-            # fc1's ReLU backward rides in the epilogue of fc2's dgrad GEMM (mask_dx) instead of a separate pass over [M, ffn]
-            x = ops.linear(x, self.fc1.weight, self.fc1.bias, act="relu", bwd_premasked=True)
-            x = ops.linear(x, self.fc2.weight, self.fc2.bias, mask_dx=True)
-        else:
-            x = self.activation_fn(ops.linear(x, self.fc1.weight, self.fc1.bias))
-            x = ops.linear(x, self.fc2.weight, self.fc2.bias)
+        x = self._ffn(x, frozen=False)
         h = ops.gated_residual(residual, x, self.gating2 if gated else None, self.dropout, self.training)
         if not self.do_layer_norm_before:
             h = self._ln(self.final_layer_norm, h)
@@ -436,13 +437,7 @@ class MPTDecoderLayer(nn.Module):
             _, h = pair(a, residual, ln1)                                                   # post-LN: h = LN(residual + a)
             x = h
         residual = h
-        if self.activation_name == "relu":
-            # fc1's ReLU backward rides in the epilogue of fc2's dgrad GEMM (mask_dx): no pass over [M, ffn], nothing kept twice
-            frozen = not any(p.requires_grad for p in (*self.fc1.parameters(), *self.fc2.parameters()))
-            lin = ops.frozen_linear if frozen else ops.linear
-            x = lin(lin(x, self.fc1.weight, self.fc1.bias, act="relu", bwd_premasked=True), self.fc2.weight, self.fc2.bias, mask_dx=True)
-        else:
-            x = _lin(self.fc2, self.activation_fn(_lin(self.fc1, x)))
+        x = self._ffn(x, frozen=None)
         if pre and defer_residual:
             return _Deferred(residual, x, self.dropout, self.training), attn_w
         if not pre:

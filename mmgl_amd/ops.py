@@ -625,16 +625,17 @@ class _Linear(torch.autograd.Function):
         return dx, dw, db, None, None, None, None
 
 
-def linear(x, weight, bias=None, act="none", out_scale=1.0, mask_dx=False, bwd_premasked=False):
+def _linear(x, weight, bias, act, out_scale=1.0, mask_dx=False, premasked=False):
+    return _mfma_aligned(lambda a, w, b, _r, _z, act_, scale, _K, _out: _Linear.apply(a, w, b, act_, scale, mask_dx, premasked),
+                         x, weight, bias, act=act, out_scale=out_scale)
+
+
+def linear(x, weight, bias=None, act="none", out_scale=1.0):
     """act((x @ weight.T + bias) * out_scale); weight is nn.Linear layout [out, in].
-    (reference q/k/v/out_proj :194-199, :273; fc1+ReLU / fc2 :352-355)
-    mask_dx / bwd_premasked: a ReLU linear followed directly by another linear can hand its ReLU backward to the consumer:
-    `h = linear(x, W1, b1, act="relu", bwd_premasked=True); y = linear(h, W2, b2, mask_dx=True)` -- the second call zeroes
-    its dx where h <= 0 inside the dgrad GEMM, the first one then skips the separate mask pass.  Use the two flags together."""
+    (reference q/k/v/out_proj :194-199, :273; the fc1+ReLU / fc2 pair :352-355 is relu_ffn's)"""
     if x.shape[-1] != weight.shape[1]:
         raise ValueError(f"linear: x has {x.shape[-1]} features, weight expects {weight.shape[1]}")
-    return _mfma_aligned(lambda a, w, b, _r, _z, act_, scale, _K, _out: _Linear.apply(a, w, b, act_, scale, bool(mask_dx), bool(bwd_premasked)),
-                         x, weight, bias, act=_act_code("linear", act), out_scale=float(out_scale))
+    return _linear(x, weight, bias, _act_code("linear", act), float(out_scale))
 
 
 class _LoraLinear(torch.autograd.Function):
@@ -1068,19 +1069,15 @@ def relu_bits_bytes(M, N, K, ldx, ldw, ldy, dtype):
     return lib().mmgl_gemm_nt_relu_bits_bytes(M, N, K, ldx, ldw, ldy, _lib.BF16)
 
 
-def gemm_nt_relu_bits(x2, w, bias, out, K=None, bits=None):
+def gemm_nt_relu_bits(x2, w, bias, out, K=None):
     """out = relu(x2[:, :K] @ w^T + bias) plus one bit per element (out > 0), lane-private to the persistent GEMM's tiling:
-    (out, bits uint8 [nbytes]).  Callers check relu_bits_bytes() > 0 first; `bits`: that many bytes of their own, else allocated
-    here.  No autograd."""
+    (out, bits uint8 [nbytes]).  Callers check relu_bits_bytes() > 0 first.  No autograd."""
     M, N = x2.shape[0], w.shape[0]
     K = x2.shape[1] if K is None else K
     nb = relu_bits_bytes(M, N, K, x2.stride(0), w.stride(0), out.stride(0), x2.dtype)
     if not nb:
         raise ValueError("gemm_nt_relu_bits: shape not eligible (relu_bits_bytes == 0)")
-    if bits is None:
-        bits = torch.empty(nb, dtype=torch.uint8, device=x2.device)
-    elif bits.numel() != nb:
-        raise ValueError(f"gemm_nt_relu_bits: bits hold {bits.numel()} bytes, the shape writes {nb}")
+    bits = torch.empty(nb, dtype=torch.uint8, device=x2.device)
     _lib.call("mmgl_gemm_nt_relu_bits", dict(flops=2.0 * M * N * K, bytes=float(M * K + N * K + M * N) * x2.element_size(), tag=f"{M}x{N}x{K}+b+a1+bits"),
               ptr(x2), x2.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(out), out.stride(0), ptr(bits), M, N, K, 1.0, dtype_code(x2), stream_ptr())
     return out, bits
@@ -1170,99 +1167,114 @@ def _row_strided(t2, cols, n_out):
 
 class _FrozenLinear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, act, mask_dx, premasked, pitch, relu_out, relu_in):
-        require_cuda(x, weight)
-        K, N = weight.shape[1], weight.shape[0]
+    def forward(ctx, x, weight, bias, act):
+        N, K = weight.shape
         x2 = _row_strided(x.reshape(-1, K), K, N)
-        w = (weight if weight.dtype == x.dtype else weight.to(x.dtype)).contiguous()
-        b = None if bias is None else (bias if bias.dtype == x.dtype else bias.to(x.dtype))
         # the output is allocated here, in its final shape, and returned as is: consumers such as the in-place rotary embedding may
-        # then modify it (a tensor the caller passed in would come back as a view of an input).  pitch != N: fc1 of a frozen FFN,
-        # which the consumer (fc2, mask_dx) reads with its row stride
-        out = torch.empty(*x.shape[:-1], pitch, dtype=x.dtype, device=x.device)
-        out = out[..., :N] if pitch != N else out
-        y = out.view(-1, N)
-        if relu_out is None:
-            _mfma_aligned(gemm_nt, x2, w, b, act=act, out=y)
-        else:
-            # fc1 planned by frozen_linear: the ReLU mask leaves as bits beside the activation -- fc2's backward applies those (16 bytes
-            # per lane and tile) instead of re-reading and keeping the [M, ffn] activation -- for the rows that run as whole rounds of
-            # the persistent kernel; a short tail runs on the few-tile kernel and its activation rows stay the mask
-            bits, _, rows = relu_out
-            gemm_nt_relu_bits(x2[:rows], w, b, y[:rows], bits=bits)
-            if rows < y.shape[0]:
-                gemm_nt(x2[rows:], w, b, act=act, out=y[rows:])
-        # premasked: the consumer folds this layer's ReLU backward into its own dgrad (mask_dx there): differentiate as a plain
-        # linear and keep nothing.  mask_dx: x2 is a ReLU output whose backward rides in this layer's dgrad epilogue -- as the
-        # producer's mask bits when it left some and the dgrad's shape takes them (then x2 itself is not kept), else as x2.
-        ctx.mask_bits = None
-        xkeep = x2 if mask_dx else None
-        if mask_dx and relu_in is not None:
-            bits, rpitch, mrows = relu_in                     # bits cover rows [0, mrows), the rest: the activation rows themselves
-            if x2.dtype == torch.bfloat16 and x2.stride(0) == rpitch and N % 128 == 0 and 0 < mrows <= x2.shape[0] and \
-                    relu_bits_bytes(mrows, K, N, N, N, rpitch, x2.dtype) == bits.numel():
-                ctx.mask_bits = relu_in
-                xkeep = None
-                if mrows < x2.shape[0]:      # a short tail, copied (a view would keep the [M, ffn] buffer) with the row pitch the dgrad's output has
-                    xkeep = torch.empty(x2.shape[0] - mrows, rpitch, dtype=x2.dtype, device=x2.device)[:, :K]
-                    xkeep.copy_(x2[mrows:])
-        ctx.save_for_backward(weight, out if (act == 1 and not premasked) else None, xkeep)
-        ctx.act = 0 if premasked else act
-        ctx.xshape = x.shape
+        # then modify it (a tensor the caller passed in would come back as a view of an input)
+        out = torch.empty(*x.shape[:-1], N, dtype=x.dtype, device=x.device)
+        _mfma_aligned(gemm_nt, x2, weight.to(x.dtype).contiguous(), None if bias is None else bias.to(x.dtype), act=act, out=out.view(-1, N))
+        ctx.save_for_backward(weight, out if act == 1 else None)
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        weight, y, xmask = ctx.saved_tensors
+        weight, y = ctx.saved_tensors
         N, K = weight.shape
         g = dy.reshape(-1, N)
-        g = _row_strided(g, N, K) if ctx.act == 0 else g.contiguous()
-        if ctx.act == 1:
+        g = _row_strided(g, N, K) if y is None else g.contiguous()
+        if y is not None:                                     # a stand-alone act="relu": its own pass over the gradient
             gm = torch.empty_like(g)
             _lib.call("mmgl_relu_bwd", dict(bytes=3.0 * g.numel() * g.element_size()), ptr(g), ptr(y), ptr(gm), g.numel(), dtype_code(g), stream_ptr())
             g = gm
-        if ctx.mask_bits is not None:
-            bits, pitch, mrows = ctx.mask_bits
-            dx = torch.empty(g.shape[0], pitch, dtype=g.dtype, device=g.device)[:, :K]
-            frozen_dgrad(g[:mrows], weight, out=dx[:mrows], bits=bits)
-            if mrows < g.shape[0]:                            # the tail rows with their activation rows as the mask
-                frozen_dgrad(g[mrows:], weight, zmask=xmask, out=dx[mrows:])
-        else:
-            dx = frozen_dgrad(g, weight, zmask=xmask)
-        return dx.reshape(ctx.xshape), None, None, None, None, None, None, None, None
+        return frozen_dgrad(g, weight).reshape(*dy.shape[:-1], K), None, None, None
 
 
-def frozen_linear(x, weight, bias, act="none", mask_dx=False, bwd_premasked=False):
-    """act(x W^T + b) for a FROZEN nn.Linear (reference :194-199, :273, :352-355 inside the frozen LM layers, lm_head :826),
-    act "none" | "relu".  mask_dx / bwd_premasked: as in `linear` -- `h = frozen_linear(x, W1, b1, act="relu", bwd_premasked=True);
-    y = frozen_linear(h, W2, b2, mask_dx=True)` puts fc1's ReLU backward into the epilogue of fc2's dgrad GEMM."""
+def frozen_linear(x, weight, bias, act="none"):
+    """act(x W^T + b) for a FROZEN nn.Linear (reference :194-199, :273 inside the frozen LM layers, lm_head :826), act "none" |
+    "relu".  The fc1 + ReLU / fc2 pair of a frozen layer (:352-355) is relu_ffn's."""
     if weight.requires_grad or (bias is not None and bias.requires_grad):
         raise ValueError("frozen_linear: weight and bias must be frozen (requires_grad=False)")
     if x.shape[-1] != weight.shape[1]:
         raise ValueError(f"frozen_linear: x has {x.shape[-1]} features, weight expects {weight.shape[1]}")
-    code = _act_code("frozen_linear", act)
-    if bwd_premasked and code != _lib.ACT_RELU:
-        raise ValueError("frozen_linear: bwd_premasked needs the ReLU epilogue")
-    N, K = weight.shape
-    pitch, relu_out = N, None
-    if bwd_premasked:
-        # fc1 of a frozen FFN: its row pitch, and the rows whose ReLU mask leaves as bits -- whole rounds of the persistent kernel
-        # when the rest is a short tail, else all of them where the shape runs as whole tiles.  The plan reads x's rows densely.
-        x = x.contiguous()
-        M = x.numel() // K
-        pitch = _ffn_pitch(M, N, K, x.dtype)
-        if pitch != N:
-            rows = _round_split_rows(M, N, x.device)
-            nb = relu_bits_bytes(rows, N, K, K, K, pitch, x.dtype) if rows else 0
+    return _FrozenLinear.apply(x, weight, bias, _act_code("frozen_linear", act))
+
+
+class _FrozenReluFFN(torch.autograd.Function):
+    """y = fc2(relu(fc1(x))), w1 [ffn, d_in] and w2 [d_out, ffn] frozen, as one node that owns the hidden buffer h [M, ffn] and the plan
+    of its ReLU mask: fc1's ReLU backward rides in the epilogue of fc2's dgrad GEMM -- no pass over [M, ffn] -- and where the shapes
+    allow it the mask leaves fc1 as bits (16 bytes per lane and tile), so that h is not kept for backward."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2):
+        (F_, K), N = w1.shape, w2.shape[0]
+        x2 = x.contiguous().reshape(-1, K)                    # the plan reads x's rows densely
+        M = x2.shape[0]
+        # h's row pitch and the rows whose mask leaves as bits: whole rounds of the persistent kernel when the rest is a short tail
+        # (it runs on the few-tile kernel, its activation rows stay the mask), else all rows where the shape runs as whole tiles
+        pitch = _ffn_pitch(M, F_, K, x.dtype)
+        rows = nb = 0
+        if pitch != F_:
+            rows = _round_split_rows(M, F_, x.device)
+            nb = relu_bits_bytes(rows, F_, K, K, K, pitch, x.dtype) if rows else 0
             if not nb:
-                rows, nb = M, relu_bits_bytes(M, N, K, K, K, pitch, x.dtype)
-            if nb:
-                relu_out = (torch.empty(nb, dtype=torch.uint8, device=x.device), pitch, rows)
-    y = _FrozenLinear.apply(x, weight, bias, code, bool(mask_dx), bool(bwd_premasked), pitch, relu_out,
-                            getattr(x, "_mmgl_relu_bits", None) if mask_dx else None)
-    if relu_out is not None:         # fc2 (mask_dx) finds them here; one that does not (a wrapper or view dropped it) masks with y
-        y._mmgl_relu_bits = relu_out
-    return y
+                rows, nb = M, relu_bits_bytes(M, F_, K, K, K, pitch, x.dtype)
+        w, b = w1.to(x.dtype).contiguous(), None if b1 is None else b1.to(x.dtype)
+        h = x.new_empty(M, pitch)[:, :F_]
+        if nb:
+            _, bits = gemm_nt_relu_bits(x2[:rows], w, b, h[:rows])
+            if rows < M:
+                gemm_nt(x2[rows:], w, b, act=1, out=h[rows:])
+        else:
+            _mfma_aligned(gemm_nt, x2, w, b, act=1, out=h)
+        hx = _row_strided(h, F_, N)                           # fc2 reads h with its row pitch
+        y = x.new_empty(*x.shape[:-1], N)
+        _mfma_aligned(gemm_nt, hx, w2.to(x.dtype).contiguous(), None if b2 is None else b2.to(x.dtype), out=y.view(-1, N))
+        # kept for fc2's dgrad: nothing when the bits cover every row and the dgrad's shape takes them, the tail rows when they cover
+        # some -- copied (a view would keep the [M, ffn] buffer) with the row pitch the dgrad's output has -- else the activation
+        mask, ctx.mask_bits = hx, None
+        if nb and hx.stride(0) == pitch and N % 128 == 0 and relu_bits_bytes(rows, F_, N, N, N, pitch, x.dtype) == nb:
+            mask, ctx.mask_bits = None, (bits, pitch, rows)
+            if rows < M:
+                mask = x.new_empty(M - rows, pitch)[:, :F_].copy_(hx[rows:])
+        ctx.save_for_backward(w1, w2, mask)
+        h = h.view(*x.shape[:-1], F_)
+        ctx.mark_non_differentiable(h)
+        ctx.set_materialize_grads(False)                      # no zero tensor [M, ffn] for h's gradient
+        return y, h
+
+    @staticmethod
+    def backward(ctx, dy, _dh=None):
+        w1, w2, mask = ctx.saved_tensors
+        (F_, K), N = w1.shape, w2.shape[0]
+        g = _row_strided(dy.reshape(-1, N), N, F_)
+        if ctx.mask_bits is None:
+            dh = frozen_dgrad(g, w2, zmask=mask)
+        else:
+            bits, pitch, rows = ctx.mask_bits
+            dh = g.new_empty(g.shape[0], pitch)[:, :F_]
+            frozen_dgrad(g[:rows], w2, out=dh[:rows], bits=bits)
+            if rows < g.shape[0]:                             # the tail rows with their activation rows as the mask
+                frozen_dgrad(g[rows:], w2, zmask=mask, out=dh[rows:])
+        return frozen_dgrad(_row_strided(dh, F_, K), w1).reshape(*dy.shape[:-1], K), None, None, None, None
+
+
+def relu_ffn(x, w1, b1, w2, b2, frozen=None, return_hidden=False):
+    """fc2(relu(fc1(x))) (reference :352-355): w1 [ffn, d_in], w2 [d_out, ffn] in nn.Linear layout, biases optional; fc1's ReLU backward
+    is folded into fc2's dgrad GEMM.  frozen=None takes the frozen route (_FrozenReluFFN: dgrads only, cached W^T) exactly when none
+    of the four parameters requires grad, frozen=False forces the trainable one (two _Linear nodes).  return_hidden: (y, h) with
+    h = relu(fc1(x)), which carries a gradient on the trainable route only (the frozen node hands it out non-differentiable)."""
+    if x.shape[-1] != w1.shape[1] or w1.shape[0] != w2.shape[1]:
+        raise ValueError(f"relu_ffn: x has {x.shape[-1]} features, fc1 maps {w1.shape[1]} to {w1.shape[0]}, fc2 expects {w2.shape[1]}")
+    trainable = any(p is not None and p.requires_grad for p in (w1, b1, w2, b2))
+    if frozen and trainable:
+        raise ValueError("relu_ffn: weight and bias must be frozen (requires_grad=False)")
+    if trainable or frozen is False:
+        h = _linear(x, w1, b1, _lib.ACT_RELU, premasked=True)
+        y = _linear(h, w2, b2, _lib.ACT_NONE, mask_dx=True)
+    else:
+        y, h = _FrozenReluFFN.apply(x, w1, b1, w2, b2)
+    return (y, h) if return_hidden else y
 
 
 # ------------------------------------------------------------------------------------------ Llama-family elementwise ops

@@ -53,8 +53,8 @@ def core_shape(name, B):
 
 @dataclass(frozen=True)
 class Lin:
-    """One trainable linear as the model calls ops.linear.  kind: "plain", "relu_pair" (fc1 with act="relu", bwd_premasked=True
-    feeding fc2 with mask_dx=True, modelling_cross_attention.py:343-344) or "swiglu" (Llama: fused gate|up, ops.swiglu, down_proj)."""
+    """One trainable linear as the model calls ops.linear.  kind: "plain", "relu_pair" (ops.relu_ffn's trainable route: fc1 with the ReLU
+    epilogue feeding fc2, whose dgrad carries fc1's ReLU backward, MPTDecoderLayer._ffn) or "swiglu" (Llama: fused gate|up, ops.swiglu, down_proj)."""
     label: str
     M: int
     K: int                 # in features
@@ -245,9 +245,8 @@ def test_trainable_linear_at_bench_batch(name, B, row):
         b2 = (torch.randn(K, generator=gen, device="cuda") * 0.3).bfloat16()
         dy = torch.randn(M, K, generator=gen, device="cuda").bfloat16()
         ps = [t.clone().requires_grad_() for t in (x, W1, b1, W2, b2)]
-        h = ops.linear(ps[0], ps[1], ps[2], act="relu", bwd_premasked=True)
+        y, h = ops.relu_ffn(*ps, frozen=False, return_hidden=True)          # exactly as the gated layer's MPTDecoderLayer._ffn
         h.retain_grad()
-        y = ops.linear(h, ps[3], ps[4], mask_dx=True)          # exactly as modelling_cross_attention.py:343-344
         y.backward(dy)
         x64, W164, W264, dy64 = x.double(), W1.double(), W2.double(), dy.double()
         hh, dh = h.detach().double(), h.grad.double()
@@ -327,7 +326,7 @@ def _census(name, B=4):
 
 
 def _expected(name, B=4):
-    """The same records as the table predicts them (bf16 = dtype code 1; ops.linear passes act 0 backward for bwd_premasked)."""
+    """The same records as the table predicts them (bf16 = dtype code 1; relu_ffn's fc1 passes act 0 backward: its ReLU backward is fc2's mask_dx)."""
     Bc, H, T, S, D = core_shape(name, B)
     exp = {("mmgl_xattn_fwd", Bc, H, T, S, D, 1), ("mmgl_xattn_bwd", Bc, H, T, S, D, 1)}
     for r in linears(name, B):

@@ -121,7 +121,8 @@ def test_gemm_nt_padded_contraction_on_the_128_kernel():
 
 @pytest.mark.parametrize("M,d,ffn", [(40960, 2048, 8192), (2560, 2048, 8192), (200, 64, 128)])
 def test_frozen_ffn_pair_mask_dx(M, d, ffn):
-    """fc1 + ReLU (bwd_premasked) -> fc2 (mask_dx): forward and dx against fp32 torch autograd (reference :352-355 frozen)."""
+    """relu_ffn's frozen route (fc1's ReLU backward in fc2's dgrad): forward and dx against fp32 torch autograd (reference :352-355
+    frozen), and what the node keeps for backward."""
     from mmgl_amd import ops
     g = torch.Generator(device="cuda").manual_seed(11)
     x = torch.randn(M, d, device="cuda", generator=g).bfloat16().requires_grad_()
@@ -130,17 +131,17 @@ def test_frozen_ffn_pair_mask_dx(M, d, ffn):
     W2 = (torch.randn(d, ffn, device="cuda", generator=g) * ffn ** -0.5).bfloat16()
     b2 = (torch.randn(d, device="cuda", generator=g) * 0.1).bfloat16()
     w = torch.randn(M, d, device="cuda", generator=g).bfloat16()
-    h = ops.frozen_linear(x, W1, b1, act="relu", bwd_premasked=True)
+    y, h = ops.relu_ffn(x, W1, b1, W2, b2, return_hidden=True)
+    assert not h.requires_grad
+    kept = [t for t in y.grad_fn.saved_tensors if t is not None and t.shape[-1] == ffn and t.data_ptr() != W2.data_ptr()]
     if M >= 2560:                    # whole tiles of the persistent kernel: the ReLU mask travels as bits, h is not kept for backward
-        assert getattr(h, "_mmgl_relu_bits", None) is not None
-    y = ops.frozen_linear(h, W2, b2, mask_dx=True)
-    if M >= 2560:
         assert y.grad_fn.mask_bits is not None
-        kept = y.grad_fn.saved_tensors[2]
         if M == 2560:                # 320 tiles on 256 CUs: 2048 rows as one round of the persistent kernel (mask bits), 512 tail rows on the few-tile
-            assert y.grad_fn.mask_bits[2] == 2048 and tuple(kept.shape) == (512, ffn)      # kernel with their activation rows as the mask
+            assert y.grad_fn.mask_bits[2] == 2048 and [tuple(t.shape) for t in kept] == [(512, ffn)]      # kernel with their activation rows as the mask
         else:
-            assert kept is None
+            assert kept == []
+    else:                            # no bits at this shape: the activation itself is the mask
+        assert y.grad_fn.mask_bits is None and len(kept) == 1 and torch.equal(kept[0], h)
     (y.float() * w.float()).sum().backward()
     xr = x.detach().float().requires_grad_()
     hr = torch.relu(F.linear(xr, W1.float(), b1.float()))
@@ -375,7 +376,7 @@ def test_dynamic_tile_schedule_ffn_relu_bits():
     w2 = (torch.randn(2048, 8192, device="cuda") * 0.02).bfloat16()
 
     def run():
-        y = ops.frozen_linear(ops.frozen_linear(x, w1, b1, act="relu", bwd_premasked=True), w2, None, mask_dx=True)
+        y = ops.relu_ffn(x, w1, b1, w2, None)
         (g,) = torch.autograd.grad(y.float().square().mean(), x)
         return y.detach(), g
     y0, g0 = run()

@@ -455,8 +455,9 @@ def test_linear_big_tile_kernels(act, M, N, K):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("M,K,F_", [(300, 64, 136), (8192, 2048, 4096)])
 def test_linear_relu_pair_with_folded_mask(dtype, M, K, F_):
-    """fc1+ReLU -> fc2 with fc1's ReLU backward folded into fc2's dgrad (bwd_premasked / mask_dx) must give the same
-    gradients as the plain pair (in bf16 the large case runs the 256x256 kernels' mask epilogue, the small one the in-place pass)."""
+    """ops.relu_ffn's trainable route (fc1's ReLU backward folded into fc2's dgrad) must give the same gradients as the plain
+    pair, ops.linear(act="relu") then ops.linear (in bf16 the large case runs the 256x256 kernels' mask epilogue, the small one the
+    in-place pass)."""
     from mmgl_amd import ops
     g = torch.Generator().manual_seed(M + F_)
     x = (torch.randn(M, K, generator=g)).to(dtype).cuda()
@@ -468,8 +469,7 @@ def test_linear_relu_pair_with_folded_mask(dtype, M, K, F_):
     grads = []
     for folded in (False, True):
         ps = [t.detach().clone().requires_grad_() for t in (x, W1, b1, W2, b2)]
-        h = ops.linear(ps[0], ps[1], ps[2], act="relu", bwd_premasked=folded)
-        y = ops.linear(h, ps[3], ps[4], mask_dx=folded)
+        y = ops.relu_ffn(*ps, frozen=False) if folded else ops.linear(ops.linear(ps[0], ps[1], ps[2], act="relu"), ps[3], ps[4])
         (y * w).sum().backward()
         grads.append([y.detach()] + [p.grad for p in ps])
     t = 1e-5 if dtype == torch.float32 else 1e-2
