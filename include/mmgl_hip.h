@@ -568,6 +568,53 @@ int mmgl_logits_process(void* logits, size_t ld_logits, const int64_t* history, 
                         size_t ld_valid, int n_masked, int hist_len, const int* ban, int n_ban, int rows, int V,
                         float repetition_penalty, int no_repeat_ngram_size, int dtype, void* stream);
 
+/* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens = K), 1 <= K <= 7; csrc/decode.hip, csrc/lookup.hip) ---------------
+ * replaces: transformers' PromptLookupCandidateGenerator + the assisted-decoding verification behind generate(
+ *           prompt_lookup_num_tokens=K), which re-runs a [B = 1, K + 1] forward through the dynamic cache and crops it afterwards.
+ *           Forward only; deterministic (no atomics).
+ *
+ * mmgl_attn_decode_block_fwd: causal attention of m = K + 1 <= 8 new tokens per sample against a cache whose length differs per
+ * sample, and the filing of the new keys / values into that cache, one launch; row b*m + i is new token i of sample b.
+ *   q, out      [B*m, H*D] (q: row stride ldq, already scaled by D^-0.5; out dense)
+ *   k_new,v_new [B*m, H*D], row stride ld_new: the keys / values of the new tokens (the halves of a dense [B*m, 2 H D] projection)
+ *   k, v        the cache slabs: `capacity` rows of H*D per sample, row stride ldkv, sample stride batch_stride_kv (elements)
+ *   key_valid   [B, capacity] uint8, row stride ld_valid
+ *   len         int32 [B], device memory: the columns sample b has filed.  Clamped into [0, capacity] by the kernel; keeping it
+ *               there is the caller's contract (as src of mmgl_attn_decode_beam_fwd).
+ *   Row (b, i) attends the cache columns s < len[b] with key_valid set and the new keys j <= i (always valid).  New key / value j
+ *   is written to cache column len[b] + j when that column is below `capacity`, else dropped (it belongs to an input whose output
+ *   the caller discards); no other cache byte is written, and only columns below len[b] are read.
+ *   One workgroup per (sample, head), the m queries in registers; softmax and accumulation in fp32, one rescale per loop trip, partial
+ *   states merged in a fixed order.  D in {16,32,64,128} and m <= 8 (else MMGL_ERR_UNSUPPORTED); strides multiples of 16 bytes,
+ *   q / k_new / v_new / k / v 16-byte aligned.  Plain vector stores only.
+ *
+ * mmgl_lookup_accept: the tail of a verify step, one launch, one workgroup per sample.
+ *   logits      [B*m_in, V] bf16 / fp32, row stride ld_logits: m_in = 1 (the prefill's row per sample) or K + 1 (the rows of `block`)
+ *   block       int64 [B, K+1], n_draft int32 [B]: read (m_in > 1) as the inputs of those rows -- [t_last, d_1 .. d_nd, filler] --
+ *               then overwritten with the next step's; positions int64 [B, K+1]: the next block's position ids, written
+ *   ids         int64 [B, >= T + n_new], row stride ld_ids: columns [0, T) hold the prompt, the new tokens are appended behind
+ *   prompt_mask uint8 [B, T], row stride ld_mask: the prompt columns that count as history
+ *   gen, len    int32 [B]: tokens the row has (pads behind an EOS included) / its cache columns;  finished uint8 [B];  all read and written
+ *   emitted     int32 [B], written: the tokens this call appended to the row
+ *   Accept rule, with a_i the argmax of row i (ties to the lowest index, NaN never chosen): e_0 = a_0; e_i = a_i while i <= nd and
+ *   d_i == e_{i-1}; stop behind eos_token_id (< 0: none; the rest of the row gets pad_token_id at once and gen = n_new) and at n_new
+ *   tokens; either finishes the row.  gen grows by the k tokens emitted, and so does len unless m_in = 1.  A finished row emits
+ *   nothing and keeps its state.
+ *   Draft rule, on the history h = the valid prompt tokens followed by the row's new tokens, L of them: for n = min(N, L - 1) down to
+ *   1, the largest p <= L - n - 1 with h[p .. p+n) == h[L-n .. L) gives the drafts h[p+n .. min(p+n+K, L)); no match: no drafts.
+ *   A history token outside [0, V) equals nothing and ends a draft list.  Next block = [e_{k-1}, drafts, e_{k-1} ...]; a finished
+ *   row has no drafts and repeats the first token of its block.  positions[b][i] = min(valid prompt tokens + pos_offset + gen - 1 + i,
+ *   pos_max).
+ *   T + n_new <= 8192 (the history lives in LDS), 1 <= K <= 7, 1 <= N <= 4, else MMGL_ERR_UNSUPPORTED.  A refused call writes nothing.
+ *   No workspace, no atomics, no host synchronisation; two runs are bitwise equal.  Plain vector stores only. */
+int mmgl_attn_decode_block_fwd(const void* q, int ldq, const void* k_new, const void* v_new, int ld_new, void* k, void* v, int ldkv,
+                               size_t batch_stride_kv, int capacity, const uint8_t* key_valid, int ld_valid, const int* len, void* out,
+                               int B, int m, int H, int D, int dtype, void* stream);
+int mmgl_lookup_accept(const void* logits, size_t ld_logits, int m_in, int64_t* block, int* n_draft, int64_t* positions, int64_t* ids,
+                       size_t ld_ids, const uint8_t* prompt_mask, size_t ld_mask, int* gen, int* len, uint8_t* finished, int* emitted,
+                       int B, int T, int n_new, int V, int K, int N, int64_t eos_token_id, int64_t pad_token_id, int pos_offset,
+                       int pos_max, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

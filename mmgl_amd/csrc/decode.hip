@@ -42,6 +42,10 @@
 // W queries from registers, as the grouped-query kernel does for its group) and differ only in the few keys generated so far, which a
 // per-row int32 parent table addresses in a [B*W, n_cap, 2d] tail buffer.  No cache row is copied when the beams are reordered.
 //
+// mmgl_attn_decode_block_fwd (attn_decode_block_kernel).  Prompt-lookup decoding: m <= 8 new tokens per sample in one step, causal among
+// themselves, against a cache whose length differs per sample (int32 len[b] on the device).  The beam kernel's prefix loop bounded by
+// len[b], then the m new keys from the projection's output, which the same launch files at cache columns len[b] .. len[b] + m - 1.
+//
 // mmgl_rope_kv_append (rope_kv_append_kernel).  The new token's q | k | v row: q rotated in place, k rotated into the token's cache column,
 // v copied there -- one launch where separate projections and rotations would take four (the step is launch-bound).
 #include "common.h"
@@ -801,6 +805,186 @@ int attn_decode_beam_nq(const BeamAttnArgs& a, hipStream_t st) {
     return MMGL_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ causal block of m new tokens per sample
+// One workgroup per (sample, head) serves the W <= NQ new tokens b*W + i of the sample (a verify step of prompt-lookup decoding).  Phase 1
+// is phase 1 of attn_decode_beam_kernel over the L = len[b] cache columns the sample has filed so far -- L is clamped into [0, capacity]
+// and is uniform over the workgroup, so every wave makes the same trips.  Phase 2 scores the W new keys, read from the dense projection
+// output [B*W, ld_new]: 4 waves x KPI >= 2 lane groups hold one new key each, so one trip covers them; row i folds key t only for t <= i
+// (new keys are always valid).  The lane group that holds new key t then files it, and its value, at cache column L + t of head h, unless
+// that column is at or past `capacity`: such a key belongs to an input whose output the caller discards.  Phase 1 reads only columns below
+// L and every (sample, head, column) has one writer, so nothing races.  Same state, rescale per trip and merge as the beam kernel; surplus
+// rows (i >= W) repeat row W - 1 and are not stored.
+template <typename T, int D, int NQ>
+__global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_block_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ kn,
+                                                                            const T* __restrict__ vn, int ld_new, T* kc, T* vc, int ldkv,
+                                                                            size_t bs_kv, int capacity, const uint8_t* __restrict__ valid,
+                                                                            int ld_valid, const int* __restrict__ len, T* __restrict__ out,
+                                                                            int W, int H) {
+    typedef typename Vec16<T>::type V;
+    constexpr int VEC = 16 / sizeof(T);
+    constexpr int LPK = D / VEC;                    // lanes per key
+    constexpr int KPI = WAVE / LPK;                 // keys per wave and load instruction
+    constexpr float NEG = -FLT_MAX;
+    __shared__ float sm_m[AD_WAVES][NQ], sm_l[AD_WAVES][NQ], sm_o[AD_WAVES][NQ][D];
+
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane % LPK, kk = lane / LPK;
+    const size_t row0 = (size_t)b * W;
+    const int S = min(max(len[b], 0), capacity);    // the caller's contract; clamped, never trusted as an address
+
+    float qf[NQ][VEC];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const V qv = *(const V*)(q + (row0 + min(j, W - 1)) * ldq + h * D + c * VEC);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) qf[j][e] = Elem<T>::to_f(qv[e]);
+    }
+    float m[NQ], l[NQ], acc[NQ][VEC];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        m[j] = NEG;
+        l[j] = 0.f;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[j][e] = 0.f;
+    }
+    // the keys of a trip enter row j's online softmax together: one rescale of the state per trip
+    auto fold = [&](int j, const auto& kr, const auto& vr, const auto& ok, const auto& in) {
+        constexpr int U = sizeof(ok) / sizeof(bool);
+        float sc[U], mn = m[j];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) dot += qf[j][e] * Elem<T>::to_f(kr[u][e]);
+            dot = group_sum<LPK>(dot);
+            sc[u] = ok[u] ? dot : NEG;
+            if (in[u]) mn = fmaxf(mn, sc[u]);
+        }
+        const float corr = __expf(m[j] - mn);
+        float pu[U], ps = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            pu[u] = in[u] ? __expf(sc[u] - mn) : 0.f;                 // a key the row does not see weighs nothing
+            ps += pu[u];
+        }
+        l[j] = l[j] * corr + ps;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            float a = acc[j][e] * corr;
+#pragma unroll
+            for (int u = 0; u < U; ++u) a += pu[u] * Elem<T>::to_f(vr[u][e]);
+            acc[j][e] = a;
+        }
+        m[j] = mn;
+    };
+
+    T* kb = kc + b * bs_kv + h * D;
+    T* vb = vc + b * bs_kv + h * D;
+    // ---- phase 1: the cache columns below L (branch-free loads: keys past L fall outside the descriptors)
+    if (S > 0) {
+        const uint32_t slab = (uint32_t)(((size_t)(S - 1) * ldkv + D) * sizeof(T)), row_bytes = (uint32_t)(ldkv * sizeof(T));
+        const __amdgpu_buffer_rsrc_t rk = make_rsrc(kb, slab);
+        const __amdgpu_buffer_rsrc_t rv = make_rsrc(vb, slab);
+        const uint8_t* mb = valid + (size_t)b * ld_valid;
+        for (int base = w * KPI; base < S; base += AD_WAVES * KPI * AD_UNROLL) {          // wave-uniform trip count
+            V kr[AD_UNROLL], vr[AD_UNROLL];
+            bool ok[AD_UNROLL], in[AD_UNROLL];
+#pragma unroll
+            for (int u = 0; u < AD_UNROLL; ++u) {
+                const int s = base + u * AD_WAVES * KPI + kk;
+                in[u] = s < S;
+                const uint32_t off = in[u] ? (uint32_t)s * row_bytes + (uint32_t)(c * 16) : OOB;
+                kr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+                vr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+                ok[u] = mb[min(s, S - 1)] != 0;
+            }
+#pragma unroll
+            for (int j = 0; j < NQ; ++j) fold(j, kr, vr, ok, in);
+        }
+    }
+    // ---- phase 2: the W new keys, causal among themselves, then their way into the cache
+    if (w * KPI < W) {                                                                     // wave-uniform
+        const uint32_t span = (uint32_t)(((size_t)(W - 1) * ld_new + D) * sizeof(T)), new_bytes = (uint32_t)(ld_new * sizeof(T));
+        const __amdgpu_buffer_rsrc_t rk = make_rsrc(kn + row0 * ld_new + h * D, span);
+        const __amdgpu_buffer_rsrc_t rv = make_rsrc(vn + row0 * ld_new + h * D, span);
+        const int t = w * KPI + kk;
+        const bool mine = t < W;
+        const uint32_t off = mine ? (uint32_t)t * new_bytes + (uint32_t)(c * 16) : OOB;
+        V kr[1], vr[1];
+        kr[0] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+        vr[0] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+        const bool ok[1] = {true};
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const bool in[1] = {mine && t <= j};
+            fold(j, kr, vr, ok, in);
+        }
+        if (mine && S + t < capacity) {
+            const size_t at = (size_t)(S + t) * ldkv + c * VEC;
+            *(V*)(kb + at) = kr[0];
+            *(V*)(vb + at) = vr[0];
+        }
+    }
+    // per row: merge the lane groups of the wave (fixed butterfly), then the waves in order
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+#pragma unroll
+        for (int o = LPK; o < WAVE; o <<= 1) {
+            const float m2 = __shfl_xor(m[j], o), l2 = __shfl_xor(l[j], o);
+            const float mn = fmaxf(m[j], m2);
+            const float c1 = __expf(m[j] - mn), c2 = __expf(m2 - mn);
+            l[j] = l[j] * c1 + l2 * c2;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[j][e] = acc[j][e] * c1 + __shfl_xor(acc[j][e], o) * c2;
+            m[j] = mn;
+        }
+        if (lane < LPK) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) sm_o[w][j][c * VEC + e] = acc[j][e];
+            if (lane == 0) { sm_m[w][j] = m[j]; sm_l[w][j] = l[j]; }
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < W * D; idx += AD_WAVES * WAVE) {
+        const int j = idx / D, x = idx % D;
+        float mm = sm_m[0][j];
+#pragma unroll
+        for (int i = 1; i < AD_WAVES; ++i) mm = fmaxf(mm, sm_m[i][j]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int i = 0; i < AD_WAVES; ++i) {
+            const float ci = __expf(sm_m[i][j] - mm);
+            ll += sm_l[i][j] * ci;
+            o += sm_o[i][j][x] * ci;
+        }
+        out[((row0 + j) * H + h) * D + x] = Elem<T>::from_f(o / ll);
+    }
+}
+
+struct BlockAttnArgs {
+    AttnPrefix p;                                  // the sample's cache slabs (S = capacity); q and out have B*W rows
+    const void *kn, *vn;
+    const int* len;
+    int ld_new, W;
+};
+
+template <typename T, int D>
+int attn_decode_block_nq(const BlockAttnArgs& a, hipStream_t st) {
+    const AttnPrefix& p = a.p;
+    const dim3 grid(p.B * p.H), block(AD_WAVES * WAVE);
+#define MMGL_BLOCK_DECODE(NQ)                                                                                                          \
+    hipLaunchKernelGGL((attn_decode_block_kernel<T, D, NQ>), grid, block, 0, st, (const T*)p.q, p.ldq, (const T*)a.kn, (const T*)a.vn, \
+                       a.ld_new, (T*)p.k, (T*)p.v, p.ldkv, p.bs_kv, p.S, p.valid, p.ld_valid, a.len, (T*)p.out, a.W, p.H)
+    if (a.W == 1) MMGL_BLOCK_DECODE(1);
+    else if (a.W == 2) MMGL_BLOCK_DECODE(2);
+    else if (a.W <= 4) MMGL_BLOCK_DECODE(4);
+    else MMGL_BLOCK_DECODE(8);
+#undef MMGL_BLOCK_DECODE
+    MMGL_CHECK_LAUNCH("mmgl_attn_decode_block_fwd");
+    return MMGL_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ rotary embedding of one new token
 // qkv [B, ldqkv] = [q: H heads | k: Hkv | v: Hkv] x D of the new token; cs [D/2] float2 (cos, sin) of its position.  One thread = VN
 // consecutive i of one (sample, head): the pair (i, i + D/2) of a q head is rotated in place, that of a k head is rotated into the
@@ -969,6 +1153,27 @@ extern "C" int mmgl_attn_decode_beam_fwd(const void* q, int ldq, const void* k_p
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(attn_decode_beam_nq, bf16, D, a, st);
     RETURN_BY_HEAD_DIM(attn_decode_beam_nq, float, D, a, st);
+}
+
+extern "C" int mmgl_attn_decode_block_fwd(const void* q, int ldq, const void* k_new, const void* v_new, int ld_new, void* k, void* v, int ldkv,
+                                          size_t batch_stride_kv, int capacity, const uint8_t* key_valid, int ld_valid, const int* len,
+                                          void* out, int B, int m, int H, int D, int dtype, void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && m >= 1 && H >= 1 && capacity >= 1, "mmgl_attn_decode_block_fwd: bad sizes B=%d m=%d H=%d capacity=%d", B, m, H, capacity);
+    if (m > 8) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_block_fwd: %d new tokens per sample (1..8)", m);
+    const BlockAttnArgs a{{q, k, v, key_valid, out, ldq, ldkv, ld_valid, B, H, H, capacity, D, dtype, batch_stride_kv}, k_new, v_new, len, ld_new, m};
+    const int bad = check_attn_prefix(a.p, __func__, "k and v", "cache", "capacity");
+    if (bad) return bad;
+    MMGL_CHECK_ARG(k_new && v_new && len, "mmgl_attn_decode_block_fwd: null pointer");
+    if (ld_new % (dtype == MMGL_BF16 ? 8 : 4) || !aligned16(k_new) || !aligned16(v_new) || ((uintptr_t)len & 3))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_block_fwd: ld_new %d must be a multiple of 16 bytes, k_new and v_new 16-byte aligned, len 4-byte",
+                  ld_new);
+    MMGL_CHECK_ARG(ld_new >= H * D && (B == 1 || batch_stride_kv >= (size_t)(capacity - 1) * ldkv + (size_t)H * D),
+                   "mmgl_attn_decode_block_fwd: strides (%d, %zu) smaller than the rows", ld_new, batch_stride_kv);
+    if (((size_t)(m - 1) * ld_new + D) * (dtype == MMGL_BF16 ? 2 : 4) >= (1ull << 31))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_block_fwd: a sample's new rows span 2 GiB or more (m=%d, ld_new=%d)", m, ld_new);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(attn_decode_block_nq, bf16, D, a, st);
+    RETURN_BY_HEAD_DIM(attn_decode_block_nq, float, D, a, st);
 }
 
 extern "C" int mmgl_rope_kv_append(void* qkv, int ldqkv, const float* cos_sin_row, void* kv_col, size_t batch_stride_kv, int B, int H, int Hkv,

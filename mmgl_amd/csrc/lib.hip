@@ -77,4 +77,5 @@ int mmgl_num_cu() {
 // mmgl_sample_tokens (sampling for generate()) was added at 110 without a bump: no existing signature changed, and the binding
 // resolves every declared symbol at load, so a library built without it is refused all the same.
 // mmgl_logits_process (repetition penalty, n-gram and token bans for generate()) was added at 110 the same way.
+// mmgl_attn_decode_block_fwd / mmgl_lookup_accept (prompt-lookup decoding for generate()) were added at 110 the same way.
 extern "C" int mmgl_version(void) { return 110; }

@@ -41,7 +41,7 @@ def _f(default, help_):
 class Arguments:
     """Same field names and defaults as the reference's Arguments (:66-229) + `neighbor_layer_wise` + `num_beams` + the sampling knobs
     `do_sample` / `temperature` / `top_k` / `top_p` + the logits processors `repetition_penalty` / `no_repeat_ngram_size` /
-    `min_new_tokens`."""
+    `min_new_tokens` + prompt-lookup decoding's `prompt_lookup_num_tokens` / `max_matching_ngram_size`."""
     overwrite_cache: Optional[bool] = _f(False, "Overwrite the cached preprocessed datasets or not.")
     dataset: Optional[str] = _f("wikiweb2m", "The name of the dataset to use.")
     task: Optional[str] = _f("section", "One of three generation tasks in WikiWeb2M")
@@ -106,6 +106,9 @@ class Arguments:
     repetition_penalty: float = _f(1.0, "repetition penalty of the test protocol's generate(); 1 = off")
     no_repeat_ngram_size: int = _f(0, "no n-gram of this size occurs twice in the test protocol's generations; 0 = off")
     min_new_tokens: int = _f(0, "the end-of-sequence token is banned for this many new tokens in the test protocol's generate()")
+    prompt_lookup_num_tokens: int = _f(0, "tokens drafted from the prompt and verified per step of the test protocol's greedy generate() "
+                                          "(1..7; same captions in fewer steps); 0 = off")
+    max_matching_ngram_size: int = _f(2, "longest n-gram prompt-lookup decoding matches when it drafts (1..4)")
     peft_type: str = _f("none", "peft type: none, prefix, prompt, lora, flamingo")
     lora_r: int = _f(64, "lora row rank")
     lora_alpha: float = _f(1, "lora scaling factor")
@@ -640,6 +643,11 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                     fields["no_repeat_ngram_size"] = int(args.no_repeat_ngram_size)
                 if int(getattr(args, "min_new_tokens", 0)) != 0:
                     fields["min_new_tokens"] = int(args.min_new_tokens)
+                if (int(getattr(args, "prompt_lookup_num_tokens", 0)) > 0 and "prompt_lookup_num_tokens" in named
+                        and _plain_projections(model)) and not (
+                        {"num_beams", "do_sample", "repetition_penalty", "no_repeat_ngram_size", "min_new_tokens"} & set(fields)):
+                    fields.update(prompt_lookup_num_tokens=int(args.prompt_lookup_num_tokens),      # greedy runs only: the same ids
+                                  max_matching_ngram_size=int(getattr(args, "max_matching_ngram_size", 2)))
                 generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),
                                                attention_mask=batch["attention_mask"][:, :L_in].contiguous(), **fields,
                                                host_meta=extra.get("host_meta"), max_new_tokens=32,
@@ -687,6 +695,13 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
     evaluate_loop.last = meters
     evaluate_loop.samples_per_sec = n_samples / max(t_loop, 1e-9)
     return meters["bleu4"]
+
+
+def _plain_projections(model):
+    """Whether no linear of the wrapper's LM is adapted (LoRA): prompt-lookup decoding verifies on plain projections only, and it
+    changes no caption, so a run with adapters keeps the plain greedy loop instead of failing in the middle of the evaluation."""
+    lm = getattr(model, "lm", model)
+    return not any(hasattr(m, "lora_A") for m in lm.modules())
 
 
 # =============================================================================================== main / worker

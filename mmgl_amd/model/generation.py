@@ -2,8 +2,8 @@
 LlamaNeighborLM): the prompt check, the two selection tails and the loop "logits -> (processors) -> (keep the step's logits) ->
 select -> write the ids column -> one cached decode step".  A model's generate() validates its keywords (sampling.py), checks the
 prompt (check_prompt), picks a tail, runs its prefill and hands decode_loop three things: its _last_logits, a callable for one cached
-decode step (tokens [rows, 1] -> hidden [rows, d]) and the prefill's last hidden row.  Beam search (MPTForCausalLM._generate_beam) has
-a loop of another shape and shares only check_prompt.
+decode step (tokens [rows, 1] -> hidden [rows, d]) and the prefill's last hidden row.  Beam search (MPTForCausalLM._generate_beam) and
+prompt-lookup decoding (lookup_loop, below) have loops of another shape and share only check_prompt.
 
 Semantics, the same for every model:
   * Prompts are right-padded to the common width T; every new token is appended at the same column for all rows, and all
@@ -138,3 +138,35 @@ def decode_loop(last_logits, step, hidden, select, n_new, input_ids=None, prompt
     elif not ids.is_contiguous():
         ids = ids.contiguous()                                 # the new-token columns of the history buffer (history_ids)
     return (ids, torch.stack(steps, dim=1)) if return_step_logits else ids
+
+
+def lookup_loop(last_logits, verify, hidden, lookup, input_ids, prompt_mask, n_new, eos_token_id, pad_token_id, pos_offset, pos_max,
+                return_stats=False):
+    """Greedy generation by prompt-lookup decoding behind a prefill whose last row is `hidden` [B, ...]: the result
+    of decode_loop with a GreedyTail -- [B, T + n_new] in the prompt's dtype, EOS followed by pad_token_id -- in fewer steps.
+    lookup: the cache's LookupState; verify() -> hidden [B*(K+1), d]: one verify step on lookup.block; last_logits as in decode_loop.
+    Call 0 of ops.lookup_accept takes the prefill's row (m_in = 1) and drafts the first block; every verify step is followed by one
+    call (m_in = K + 1) that keeps the longest prefix of the block greedy decoding would have produced, appends it to ids and drafts
+    the next block.  Rows advance at their own pace, so the number of steps depends on the data: before every verify step the host
+    reads ONE int32 from the device -- the smallest token count over the rows -- and stops when it has reached n_new.  This is the
+    one loop of generate() that reads from the device while it runs (decode_loop and beam search run a fixed number of steps and
+    never do); a finished row waits for the others with its state frozen.  Every verify step gives every unfinished row at least one
+    token and call 0 gave one, so at most n_new - 1 verify steps run.
+    return_stats: also dict(steps = verify steps run, emitted = int32 [steps + 1, B], the tokens each call appended per row)."""
+    B, T = input_ids.shape
+    ids = torch.empty(B, T + n_new, dtype=torch.int64, device=input_ids.device)
+    ids[:, :T] = input_ids
+    mask = (prompt_mask != 0).to(torch.uint8)
+
+    def accept(hid, m_in, call):
+        ops.lookup_accept(last_logits(hid), m_in, lookup.block, lookup.n_draft, lookup.positions, ids, mask, lookup.gen, lookup.len,
+                          lookup.finished, lookup.emitted[call], n_new, lookup.N, eos_token_id, pad_token_id, pos_offset, pos_max)
+
+    accept(hidden, 1, 0)
+    steps = 0
+    while n_new > 1 and int(lookup.gen.min()) < n_new:          # the one 4-byte device read of a step
+        assert steps < n_new - 1, f"prompt-lookup decoding: more than {n_new - 1} verify steps"
+        accept(verify(), lookup.W, steps + 1)
+        steps += 1
+    ids = ids.to(input_ids.dtype)
+    return (ids, dict(steps=steps, emitted=lookup.emitted[:steps + 1].clone())) if return_stats else ids

@@ -38,8 +38,8 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from .. import ops
 from .encoders import ClipTextEncoder, PackedTextEncoder, PackedVisionEncoder
-from .generation import GreedyTail, SampledTail, check_prompt, decode_loop
-from .sampling import check_processors, check_sampling, sampling_u
+from .generation import GreedyTail, SampledTail, check_prompt, decode_loop, lookup_loop
+from .sampling import check_lookup, check_processors, check_sampling, sampling_u
 
 CROSS_MODES = ("cross_attention", "embedding")
 
@@ -330,10 +330,30 @@ class MPTAttention(nn.Module):
         return ops.attn_decode_beam(q, kv[:, :col, :d], kv[:, :col, d:], key_mask[:, :col], self.num_heads, beam.W,
                                     tail[:, :n, :d], tail[:, :n, d:], beam.book.src)
 
+    def decode_block(self, x, kv, key_mask, lookup, scratch):
+        """x [B*m, d]: the layer input of the m = lookup.W new tokens per sample of a verify step (prompt-lookup decoding).  Projects
+        q, and k|v into the dense `scratch` [B*m, 2d]; ops.attn_decode_block then attends over the sample's lookup.len cache columns
+        of kv plus the new keys at or before each token, and files the new keys and values at columns lookup.len .. of kv -- the
+        launches of decode_self.  Plain nn.Linear projections only."""
+        d = self.embed_dim
+        _plain(self.q_proj, self.k_proj, self.v_proj, self.out_proj)
+        fused = self._frozen_qkv()
+        if fused is not None:
+            w, b = fused
+            q = ops.decode_linear(x, w[:d], b[:d])
+            ops.decode_linear(x, w[d:], b[d:], out=scratch)
+        else:
+            q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
+            ops.decode_linear(x, self.k_proj.weight, self.k_proj.bias, out=scratch[:, :d])
+            ops.decode_linear(x, self.v_proj.weight, self.v_proj.bias, out=scratch[:, d:])
+        return ops.attn_decode_block(q, scratch[:, :d], scratch[:, d:], kv[:, :, :d], kv[:, :, d:], key_mask, lookup.len, self.num_heads,
+                                     lookup.W)
+
     def decode_cross(self, x, k, v, key_valid, beam=None):
+        """beam: the cache's BeamState, or its LookupState -- beam.W rows per sample (beams, or the tokens of a verify step)."""
         _plain(self.q_proj, self.out_proj)
         q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
-        if beam is not None:                  # the W beams of a sample read its neighbor tokens once: k, v stay at B rows
+        if beam is not None:                  # the W rows of a sample read its neighbor tokens once: k, v stay at B rows
             return ops.attn_decode_beam(q, k, v, key_valid, self.num_heads, beam.W)
         return ops.attn_decode(q, k, v, key_valid, self.num_heads)
 
@@ -470,7 +490,9 @@ class MPTDecoderLayer(nn.Module):
         """The layer on the one new token of a decode step, h [B, d]: the existing LayerNorm / gated-residual kernels at M = B,
         ops.decode_linear for every projection (residual adds in the GEMM epilogue of the frozen layers) and ops.attn_decode over
         the cache -- layer idx's K|V rows (frozen layer) or neighbor layer idx's projected neighbor tokens (gated layer).
-        With cache.beam set h is [B*W, d]: the same kernels at M = B*W rows, the attention through ops.attn_decode_beam."""
+        With cache.beam set h is [B*W, d]: the same kernels at M = B*W rows, the attention through ops.attn_decode_beam.
+        With cache.lookup set h is [B*m, d], m new tokens per sample (a verify step of prompt-lookup decoding): the same kernels at
+        M = B*m rows, ops.attn_decode_block in the frozen layers, ops.attn_decode_beam (m queries per sample) in the gated ones."""
         pre = self.do_layer_norm_before
         attn = self.self_attn
         ln1, ln2 = self.self_attn_layer_norm, self.final_layer_norm
@@ -480,11 +502,14 @@ class MPTDecoderLayer(nn.Module):
         if gated:                             # residual adds through ops.gated_residual (the gate is None outside flamingo)
             g1, g2 = (self.gating1, self.gating2) if self.peft_type == "flamingo" else (None, None)
             k, v = cache.cross[idx]
-            a = attn.decode_cross(x, k, v, cache.cross_valid, cache.beam)
+            a = attn.decode_cross(x, k, v, cache.cross_valid, cache.beam if cache.lookup is None else cache.lookup)
             h = ops.gated_residual(h, ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias), g1, 0.0, False)
         else:                                 # frozen layer: the residual adds ride in the GEMM epilogues
-            beam = cache.beam
-            a = attn.decode_self(x, cache.kv[idx], cache.mask, cache.col, beam, None if beam is None else beam.tail[idx])
+            beam, lookup = cache.beam, cache.lookup
+            if lookup is not None:
+                a = attn.decode_block(x, cache.kv[idx], cache.mask, lookup, lookup.scratch[idx])
+            else:
+                a = attn.decode_self(x, cache.kv[idx], cache.mask, cache.col, beam, None if beam is None else beam.tail[idx])
             h = ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias, residual=h)
         if not pre:
             h = self._ln(ln1, h)
@@ -505,7 +530,9 @@ class DecodeCache:
       col         the column the next token is written to -- the same for every sample (prompts are right-padded to a common width)
       next_pos    [B] position id of the next token, counted from the mask as HF does (valid tokens so far + OPT's offset 2)
       beam        None (greedy), or the BeamState of a beam search: then kv / mask / cross / cross_valid / next_pos stay at B rows --
-                  the prompt is prefilled once per sample and col stays at the prompt width -- and the decode steps run B*W rows"""
+                  the prompt is prefilled once per sample and col stays at the prompt width -- and the decode steps run B*W rows
+      lookup      None, or the LookupState of prompt-lookup decoding: then col / next_pos stand still at the prompt's and the verify steps
+                  (MPTDecoder._verify_step) run B*(K+1) rows against per-sample cache lengths lookup.len"""
 
     def __init__(self, num_layers, batch_size, capacity, hidden_size, dtype, device):
         self.capacity = int(capacity)
@@ -516,6 +543,31 @@ class DecodeCache:
         self.col = 0
         self.next_pos = None
         self.beam = None
+        self.lookup = None
+
+
+class LookupState:
+    """What prompt-lookup decoding adds to a prefilled DecodeCache (cache.lookup): per sample a cache length of its own and the block
+    of W = K + 1 tokens the next verify step feeds.  All of it lives on the device and is advanced by ops.lookup_accept.
+      len        int32 [B] cache columns filed (starts at the prompt width T: pad keys stay masked), gen int32 [B] tokens the row has,
+                 finished uint8 [B], n_draft int32 [B] drafts in the block
+      block      int64 [B, W] = [last token, drafts, filler], positions int64 [B, W] its position ids (clamped to the table)
+      scratch    per frozen layer the dense [B*W, 2d] output of the k|v projection; ops.attn_decode_block files it into the cache
+      emitted    int32 [n_new, B]: row c holds the tokens call c of ops.lookup_accept appended (call 0: the prefill's row)"""
+
+    def __init__(self, cache, num_tokens, ngram_size, n_new):
+        B, _, two_d = cache.kv[0].shape
+        dev = cache.mask.device
+        self.K, self.N, self.W = int(num_tokens), int(ngram_size), int(num_tokens) + 1
+        self.len = torch.full((B,), cache.col, dtype=torch.int32, device=dev)
+        self.gen = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.finished = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self.n_draft = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.block = torch.zeros(B, self.W, dtype=torch.int64, device=dev)
+        self.positions = torch.zeros(B, self.W, dtype=torch.int64, device=dev)
+        self.scratch = [torch.empty(B * self.W, two_d, dtype=kv.dtype, device=dev) for kv in cache.kv]
+        self.emitted = torch.zeros(max(int(n_new), 1), B, dtype=torch.int32, device=dev)
+        cache.mask[:, cache.col:] = 1                            # once: lookup.len bounds what a sample reads
 
 
 class BeamState:
@@ -798,6 +850,34 @@ class MPTDecoder(MPTPreTrainedModel):
         return BaseModelOutputWithPast(last_hidden_state=h, past_key_values=cache, hidden_states=all_hidden_states, attentions=None)
 
 
+    def _verify_step(self, cache):
+        """A verify step of prompt-lookup decoding: the W = K + 1 tokens cache.lookup.block [B, W] of every sample -- its last token,
+        then the drafts -- at the positions cache.lookup.positions, causally against the sample's lookup.len cache columns.  The layers
+        run decode_step at M = B*W rows and file the block's keys and values at columns lookup.len .. lookup.len + W - 1 (below the
+        capacity); which of them count is decided afterwards by ops.lookup_accept, which advances lookup.len.  Returns the hidden
+        rows [B*W, d] in front of lm_head.  _decode_step is not involved: it keeps refusing more than one token per sample."""
+        lookup = cache.lookup
+        if lookup is None or cache.beam is not None or cache.next_pos is None:
+            raise ValueError("a verify step needs a prefilled DecodeCache with a LookupState (cache.lookup) and no BeamState")
+        ops.require_cuda(cache.mask)
+        with torch.no_grad():
+            emb = self.embed_tokens(lookup.block.view(-1))
+            if self.project_in is not None:
+                emb = ops.decode_linear(emb.contiguous(), self.project_in.weight, self.project_in.bias)
+            h = emb + F.embedding(lookup.positions.view(-1), self.embed_positions.weight)
+            for idx, layer in enumerate(self.layers):
+                h = layer.decode_step(h, cache, idx)
+                if cache.cross and (idx + 1) % self.neighbor_layer_wise == 0:
+                    nb = (idx + 1) // self.neighbor_layer_wise - 1
+                    h = self.neighbor_layers[nb].decode_step(h, cache, nb)
+            if self.final_layer_norm is not None:
+                fln = self.final_layer_norm
+                h = ops.layer_norm(h, fln.weight, fln.bias, fln.eps)
+            if self.project_out is not None:
+                h = ops.decode_linear(h, self.project_out.weight, self.project_out.bias)
+        return h
+
+
 class MPTModel(MPTPreTrainedModel):
     def __init__(self, config: MPTConfig):
         super().__init__(config)
@@ -947,7 +1027,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
                  num_beams=1, length_penalty=1.0, early_stopping=False, return_sequences_scores=False, return_beam_trace=False,
                  num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, history_ids=None,
-                 history_mask=None):
+                 history_mask=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False):
         """Generation with a key/value cache: what the reference's test protocol asks of its wrappers
         (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of every
         layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
@@ -960,7 +1040,12 @@ class MPTForCausalLM(MPTPreTrainedModel):
         num_return_sequences = R (2..8) needs do_sample=True and an input_ids prompt: one prefill of B rows into a cache of
         capacity T, then steps of B*R rows on the beam-shared cache; sample_u is then [max_new_tokens, B*R].
         num_beams = W > 1 (at most 8): beam search with the semantics of transformers' generate(num_beams=W, do_sample=False,
-        length_penalty, early_stopping in {False, True}) -- see _generate_beam; input_ids prompts, no sampling, no processor."""
+        length_penalty, early_stopping in {False, True}) -- see _generate_beam; input_ids prompts, no sampling, no processor.
+        prompt_lookup_num_tokens = K (1..7; 0: off) with max_matching_ngram_size = N (1..4): transformers' prompt-lookup decoding.
+        Each step drafts up to K tokens -- what followed the latest earlier occurrence of the row's last N (or fewer) tokens -- and
+        verifies them in one step of B*(K+1) rows (generation.lookup_loop).  The result is the greedy result; only the
+        number of steps changes.  Greedy, input_ids prompts and plain projections only.  return_lookup_stats: also a dict of `steps`
+        (verify steps run) and `emitted` (int32 [steps + 1, B]: tokens appended per call and row, call 0 the prefill's)."""
         W = int(num_beams)
         if W < 1:
             raise ValueError(f"generate(): num_beams = {num_beams} must be positive")
@@ -974,6 +1059,12 @@ class MPTForCausalLM(MPTPreTrainedModel):
                                 max_new_tokens, self.config.vocab_size, W, None if input_ids is None else input_ids.dtype)
         if history_ids is not None and input_ids is not None:
             raise ValueError("generate(): history_ids / history_mask belong to inputs_embeds prompts; input_ids are their own history")
+        K, N = check_lookup("generate()", prompt_lookup_num_tokens, max_matching_ngram_size, return_lookup_stats, do_sample, W,
+                            num_return_sequences, proc is not None, return_step_logits, inputs_embeds)
+        if K > 0:                                              # with the other refusals, before any work: a verify step has no adapter path
+            _plain(self.lm_head, *(m for layer in list(self.model.decoder.layers) + list(self.model.decoder.neighbor_layers)
+                                   for m in (layer.self_attn.q_proj, layer.self_attn.k_proj, layer.self_attn.v_proj,
+                                             layer.self_attn.out_proj, layer.fc1, layer.fc2)))
         if W > 1:
             if inputs_embeds is not None:
                 raise ValueError("generate(): beam search (num_beams > 1) takes input_ids prompts, not inputs_embeds")
@@ -1001,6 +1092,11 @@ class MPTForCausalLM(MPTPreTrainedModel):
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
                   cache_capacity=T if R > 1 else T + n_new - 1)
         cache = out.past_key_values
+        if K > 0:
+            cache.lookup = LookupState(cache, K, N, n_new)
+            return lookup_loop(self._last_logits, lambda: dec._verify_step(cache), out.last_hidden_state[:, -1], cache.lookup, input_ids,
+                               attention_mask, n_new, eos_token_id, pad_token_id, dec.embed_positions.offset,
+                               dec.embed_positions.weight.shape[0] - 1, return_lookup_stats)
         if R > 1:
             cache.beam = BeamState(cache, R, n_new - 1)        # the identity parent table: R rows on each prompt's keys
         return decode_loop(self._last_logits, lambda tok: dec(input_ids=tok, past_key_values=cache).last_hidden_state[:, 0],
@@ -1372,7 +1468,7 @@ class CrossAttentionModel(nn.Module):
                  pad_token_id=None, return_step_logits=False, num_beams=1, length_penalty=1.0, early_stopping=False,
                  return_sequences_scores=False, return_beam_trace=False, num_return_sequences=1, do_sample=False, temperature=1.0,
                  top_k=0, top_p=1.0, seed=None, sample_u=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
-                 suppress_tokens=None):
+                 suppress_tokens=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded): the neighbors are encoded and interleaved once, exactly
         as forward does, then MPTForCausalLM.generate runs the prefill and the cached decode steps.  Returns [B, T + max_new_tokens]
         ids (and the step logits with return_step_logits=True).  num_beams, length_penalty, early_stopping, return_sequences_scores and
@@ -1380,12 +1476,15 @@ class CrossAttentionModel(nn.Module):
         sample and their tokens stay at B rows.  So are its sampling keywords do_sample, temperature, top_k, top_p, seed, sample_u and
         num_return_sequences (R continuations per prompt also read the prompt's neighbor tokens once), and its logits processors
         repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens (history: input_ids without the masked columns,
-        then the new tokens)."""
+        then the new tokens), and its prompt-lookup keywords prompt_lookup_num_tokens, max_matching_ngram_size and
+        return_lookup_stats (drafts come from input_ids and the new tokens, never from the neighbors)."""
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the OPT fork only, not for {type(self.lm).__name__}")
         check_sampling("generate()", do_sample, temperature, top_k, top_p, seed, sample_u, num_beams, num_return_sequences, multi=True)
-        check_processors("generate()", repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id,
-                         max_new_tokens, self.lm.config.vocab_size, num_beams, input_ids.dtype)
+        proc = check_processors("generate()", repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id,
+                                max_new_tokens, self.lm.config.vocab_size, num_beams, input_ids.dtype)
+        check_lookup("generate()", prompt_lookup_num_tokens, max_matching_ngram_size, return_lookup_stats, do_sample, num_beams,
+                     num_return_sequences, proc is not None, return_step_logits)
         if not input_ids.is_cuda:
             raise RuntimeError(f"generate() runs on the GPU only (input_ids is on {input_ids.device}); there is no CPU path")
         neighbor_embeds, key_valid = self._neighbor_tokens(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, text_locations,
@@ -1398,4 +1497,6 @@ class CrossAttentionModel(nn.Module):
                                 return_sequences_scores=return_sequences_scores, return_beam_trace=return_beam_trace,
                                 num_return_sequences=num_return_sequences, do_sample=do_sample, temperature=temperature, top_k=top_k,
                                 top_p=top_p, seed=seed, sample_u=sample_u, repetition_penalty=repetition_penalty,
-                                no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens)
+                                no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
+                                prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
+                                return_lookup_stats=return_lookup_stats)

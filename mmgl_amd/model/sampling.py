@@ -1,4 +1,4 @@
-"""The sampling and logits-processor arguments shared by the three generate() methods (MPTForCausalLM / CrossAttentionModel,
+"""The sampling, logits-processor and prompt-lookup arguments shared by the three generate() methods (MPTForCausalLM / CrossAttentionModel,
 SelfAttentionModel, LlamaNeighborLM): their checks, which need no device, the uniform numbers a sampled generation consumes and the
 per-generation state of the processors.  The selection itself is ops.sample_tokens, the processors are ops.process_logits, one launch
 per decode step each; the loop that makes those calls is generation.decode_loop."""
@@ -54,6 +54,36 @@ def sampling_u(who, n_new, rows, device, seed, sample_u):
         gen = torch.Generator(device=device)
         gen.manual_seed(int(seed))
     return torch.rand(n_new, rows, generator=gen, device=device, dtype=torch.float32)
+
+
+def check_lookup(who, prompt_lookup_num_tokens, max_matching_ngram_size, return_lookup_stats, do_sample=False, num_beams=1,
+                 num_return_sequences=1, processors=False, return_step_logits=False, inputs_embeds=None):
+    """Validates generate()'s prompt-lookup keywords; returns (K, N).  K = prompt_lookup_num_tokens = 0: off -- the
+    greedy loop runs exactly as without the keywords.  K > 0 verifies K drafted tokens per step and returns the greedy result, so it
+    combines with nothing that changes or observes the per-step selection."""
+    K, N = int(prompt_lookup_num_tokens), int(max_matching_ngram_size)
+    if not 0 <= K <= ops.MAX_LOOKUP_TOKENS:
+        raise ValueError(f"{who}: prompt_lookup_num_tokens = {prompt_lookup_num_tokens} (0: off, 1..{ops.MAX_LOOKUP_TOKENS})")
+    if K == 0:
+        if return_lookup_stats:
+            raise ValueError(f"{who}: return_lookup_stats belongs to prompt_lookup_num_tokens > 0")
+        return 0, N
+    if not 1 <= N <= ops.MAX_LOOKUP_NGRAM:
+        raise ValueError(f"{who}: max_matching_ngram_size = {max_matching_ngram_size} (1..{ops.MAX_LOOKUP_NGRAM})")
+    if do_sample:
+        raise ValueError(f"{who}: prompt_lookup_num_tokens = {K} with do_sample=True is not implemented (the drafts are verified against "
+                         "the greedy choice)")
+    if int(num_beams) != 1 or int(num_return_sequences) != 1:
+        raise ValueError(f"{who}: prompt_lookup_num_tokens = {K} with num_beams = {num_beams} / num_return_sequences = "
+                         f"{num_return_sequences} is not implemented")
+    if processors:
+        raise ValueError(f"{who}: prompt_lookup_num_tokens = {K} is not implemented with repetition_penalty / no_repeat_ngram_size / "
+                         "min_new_tokens / suppress_tokens (they rewrite each step's logits from the tokens before it)")
+    if return_step_logits:
+        raise ValueError(f"{who}: prompt_lookup_num_tokens = {K} has no per-step logits to return (return_step_logits)")
+    if inputs_embeds is not None:
+        raise ValueError(f"{who}: prompt_lookup_num_tokens = {K} takes input_ids prompts, not inputs_embeds (the drafts are looked up in the ids)")
+    return K, N
 
 
 MAX_SUPPRESS = ops.MAX_BAN - 1          # the ban array of a generation is suppress_tokens followed by the EOS entry

@@ -1653,6 +1653,97 @@ def attn_decode_beam(q, k_pre, v_pre, key_valid, num_heads, num_beams, k_tail=No
     return out
 
 
+# ------------------------------------------------------------------------------------------ prompt-lookup decoding (csrc/decode.hip, csrc/lookup.hip)
+MAX_LOOKUP_TOKENS = 7                   # K: drafted tokens per verify step (K + 1 <= 8 rows per sample)
+MAX_LOOKUP_NGRAM = 4                    # N: longest n-gram matched
+MAX_LOOKUP_HISTORY = 8192               # T + n_new: the row's history lives in LDS
+
+
+def _state_vector(op, name, t, rows, dtype, device):
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (rows,) or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{op}: {name} must be a dense {dtype} [{rows}] tensor on {device}")
+
+
+def attn_decode_block(q, k_new, v_new, k, v, key_valid, lens, num_heads, m, out=None):
+    """Causal attention of m <= 8 new tokens per sample against the cache, and their filing into it, one launch; row b*m + i is new
+    token i of sample b.
+      q [B*m, d] already scaled; k_new, v_new [B*m, d]: views with unit column stride and a common row stride (the halves of the
+      k|v projection's dense [B*m, 2d] output); k, v [B, capacity, d]: the column slabs of the cache rows [B, capacity, 2d], read
+      below lens[b] and WRITTEN at columns lens[b] .. lens[b] + m - 1 (a column at or past capacity is dropped); key_valid
+      [B, capacity] bool/uint8; lens int32 [B] on the device, 0 <= lens[b] <= capacity: the caller's contract (the kernel clamps,
+      nothing is checked on the device).
+    Row (b, i) attends the valid cache columns below lens[b] and the new keys j <= i.  Returns [B*m, d] (`out`, a dense tensor of
+    q's dtype, when given: a refused call leaves it and the cache as they were).  Forward only; GPU only."""
+    require_cuda(q, k_new, v_new, k, v, key_valid, lens)
+    _no_grad_inputs("attn_decode_block", q, k_new, v_new, k, v)
+    m = int(m)
+    if not 1 <= m <= MAX_LOOKUP_TOKENS + 1:
+        raise ValueError(f"attn_decode_block: m = {m} new tokens per sample (1..{MAX_LOOKUP_TOKENS + 1})")
+    B, S, d, key_valid, out = _decode_attn_operands("attn_decode_block", q, k, v, key_valid, num_heads, out, q_rows=m,
+                                                    names=("k", "v", "cache columns"), tail=f" for {m} new tokens per sample")
+    if (k_new.dim() != 2 or tuple(k_new.shape) != (B * m, d) or k_new.shape != v_new.shape or k_new.stride() != v_new.stride()
+            or k_new.stride(1) != 1 or k_new.dtype != q.dtype or v_new.dtype != q.dtype or k_new.device != q.device or v_new.device != q.device):
+        raise ValueError(f"attn_decode_block: incompatible k_new{tuple(k_new.shape)}/{k_new.stride()} v_new{tuple(v_new.shape)}/"
+                         f"{v_new.stride()} for q{tuple(q.shape)}")
+    _state_vector("attn_decode_block", "lens", lens, B, torch.int32, q.device)
+    if k.device != q.device or key_valid.device != q.device:
+        raise ValueError("attn_decode_block: the operands are on different devices")
+    _lib.call("mmgl_attn_decode_block_fwd", dict(bytes=2.0 * B * (S + m) * d * q.element_size()), ptr(q), q.stride(0), ptr(k_new), ptr(v_new),
+              k_new.stride(0), ptr(k), ptr(v), k.stride(1), k.stride(0), S, ptr(key_valid), key_valid.stride(0), ptr(lens), ptr(out), B, m,
+              num_heads, d // num_heads, dtype_code(q), stream_ptr())
+    return out
+
+
+def lookup_accept(logits, m_in, block, n_draft, positions, ids, prompt_mask, gen, lens, finished, emitted, n_new, ngram_size,
+                  eos_token_id=None, pad_token_id=None, pos_offset=0, pos_max=None):
+    """The tail of a prompt-lookup verify step for B samples, one launch, everything in place (mmgl_lookup_accept in
+    include/mmgl_hip.h states the accept and the draft rule):
+      logits [B*m_in, V] bf16 / fp32 (unit column stride): m_in = 1 -- the prefill's row per sample -- or K + 1, the rows of `block`;
+      block int64 [B, K+1], n_draft int32 [B]: the inputs of those rows as the previous call wrote them, replaced by the next
+      step's; positions int64 [B, K+1]: the next block's position ids = min(valid prompt tokens + pos_offset + gen - 1 + i, pos_max);
+      ids int64 [B, T + n_new] (unit column stride): the prompt, then the new tokens, appended here; prompt_mask uint8 [B, T];
+      gen, lens int32 [B], finished uint8 [B]: the rows' state; emitted int32 [B]: the tokens this call appended.
+    K = block.shape[1] - 1 in 1..7, ngram_size N in 1..4, T + n_new <= 8192.  eos_token_id None: no end-of-sequence handling.
+    A refused call leaves every tensor as it was.  Forward only; GPU only."""
+    op = "lookup_accept"
+    require_cuda(logits, block, n_draft, positions, ids, prompt_mask, gen, lens, finished, emitted)
+    rows, V, code = _logits_operand(op, logits)
+    m_in, n_new, N = int(m_in), int(n_new), int(ngram_size)
+    if not torch.is_tensor(block) or block.dim() != 2 or block.dtype != torch.int64 or not block.is_contiguous():
+        raise ValueError(f"{op}: block must be a dense int64 [B, K + 1] tensor")
+    B, K = block.shape[0], block.shape[1] - 1
+    if not 1 <= K <= MAX_LOOKUP_TOKENS:
+        raise ValueError(f"{op}: K = {K} drafted tokens (1..{MAX_LOOKUP_TOKENS})")
+    if not 1 <= N <= MAX_LOOKUP_NGRAM:
+        raise ValueError(f"{op}: ngram_size = {N} (1..{MAX_LOOKUP_NGRAM})")
+    if m_in not in (1, K + 1) or rows != B * m_in:
+        raise ValueError(f"{op}: {rows} logits rows for B = {B}, m_in = {m_in} (1 for the prefill's row, else K + 1 = {K + 1})")
+    dev = logits.device
+    if block.device != dev or tuple(positions.shape) != (B, K + 1) or positions.dtype != torch.int64 or not positions.is_contiguous() or positions.device != dev:
+        raise ValueError(f"{op}: block and positions must be dense int64 [{B}, {K + 1}] tensors on {dev}")
+    if n_new < 1 or ids.dim() != 2 or ids.dtype != torch.int64 or ids.shape[0] != B or ids.shape[1] < n_new or ids.stride(1) != 1 or ids.device != dev:
+        raise ValueError(f"{op}: ids must be an int64 [{B}, T + n_new] tensor with unit column stride on {dev}, n_new = {n_new} >= 1")
+    T = ids.shape[1] - n_new
+    if T + n_new > MAX_LOOKUP_HISTORY:
+        raise ValueError(f"{op}: a history of T + n_new = {T + n_new} tokens (at most {MAX_LOOKUP_HISTORY})")
+    if (prompt_mask.dtype not in (torch.uint8, torch.bool) or tuple(prompt_mask.shape) != (B, T) or (T > 0 and prompt_mask.stride(1) != 1)
+            or prompt_mask.device != dev):
+        raise ValueError(f"{op}: prompt_mask must be a uint8 [{B}, {T}] tensor with unit column stride on {dev}")
+    for name, t, dt in (("n_draft", n_draft, torch.int32), ("gen", gen, torch.int32), ("lens", lens, torch.int32),
+                        ("finished", finished, torch.uint8), ("emitted", emitted, torch.int32)):
+        _state_vector(op, name, t, B, dt, dev)
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    pad = 0 if pad_token_id is None else int(pad_token_id)
+    if eos_token_id is not None and (eos < 0 or pad_token_id is None or not 0 <= pad < V):
+        raise ValueError(f"{op}: eos_token_id = {eos_token_id} needs a pad_token_id in [0, {V}), got {pad_token_id}")
+    pos_max = 2 ** 31 - 1 if pos_max is None else int(pos_max)
+    if pos_max < 0 or not 0 <= int(pos_offset) < 2 ** 20:
+        raise ValueError(f"{op}: pos_offset = {pos_offset} / pos_max = {pos_max}")
+    _lib.call("mmgl_lookup_accept", dict(bytes=float(rows) * V * logits.element_size()), ptr(logits), logits.stride(0), m_in, ptr(block), ptr(n_draft),
+              ptr(positions), ptr(ids), ids.stride(0), ptr(_as_uint8(prompt_mask)), prompt_mask.stride(0) if T > 0 else 0, ptr(gen), ptr(lens),
+              ptr(finished), ptr(emitted), B, T, n_new, V, K, N, eos, pad, int(pos_offset), pos_max, code, stream_ptr())
+
+
 def beam_topk(logits, beam_score, num_beams, rows_in=None, out=None):
     """Per sample the 2W best continuations of its rows: logits [B*rows_in, V] (bf16 / fp32, unit column stride, any row stride) with
     rows_in = W = num_beams (the default) or 1 (the first step: the prefill's one row per sample); beam_score fp32 [B*rows_in].
