@@ -120,6 +120,21 @@ int mmgl_selfattn_gqa_bwd(const void* dout, const void* q, const void* k, const 
                           const uint8_t* key_valid, void* dq, void* dk, void* dv, void* workspace, size_t workspace_bytes,
                           int B, int H, int Hkv, int T, int D, int ld_q, int ld_kv, int ld_dq, int ld_dkv, int dtype, void* stream);
 
+/* Live key tiles only: mmgl_selfattn_fwd / _bwd for a batch whose padded keys fill whole 64-key tiles (bf16, D = 64, T a multiple of
+ * 64 up to 4096, multi-head; anything else returns MMGL_ERR_UNSUPPORTED).  A key tile (keys 64 j .. 64 j + 63 of a sample) is live
+ * when any of its keys is valid.  k, v hold the live tiles and nothing else: [m_live, ld_kv] rows for the whole batch, m_live = 64 x
+ * live tiles, tiles numbered sample by sample in key order.  key_tiles [B, T / 64] int32 gives the compact tile of every key tile,
+ * -1 for a dead one.  q, out, lse and dq, dk, dv keep their dense [B, T, ld] layout (dk, dv of a dead tile are zero).  The arithmetic
+ * is that of the dense entry points (a dead tile contributes nothing there either), so out, lse, dq, dk and dv are bitwise theirs.
+ * Every index read from key_tiles is clamped to the m_live rows.  Workspace: mmgl_selfattn_bwd_workspace(B, H, T). */
+int mmgl_selfattn_tiles_fwd(const void* q, const void* k, const void* v, const uint8_t* key_valid, const int32_t* key_tiles,
+                            void* out, float* lse, int B, int H, int T, int D, int m_live, int ld_q, int ld_kv, int dtype,
+                            void* stream);
+int mmgl_selfattn_tiles_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
+                            const uint8_t* key_valid, const int32_t* key_tiles, void* dq, void* dk, void* dv, void* workspace,
+                            size_t workspace_bytes, int B, int H, int T, int D, int m_live, int ld_q, int ld_kv, int ld_dq,
+                            int ld_dkv, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * General attention core: the options of MPTAttention.forward the fused kernels above leave out -- attention-probability dropout,
  * layer_head_mask, output_attentions -- for both call sites of the class (causal = 0: the gated cross-attention layers, key mask only;
@@ -367,6 +382,17 @@ int mmgl_add_layernorm_bwd(const void* dy, const void* dsum, const void* sum, co
                            const float* rstd, void* dres, void* dx, float* dgamma, float* dbeta, void* workspace,
                            size_t workspace_bytes, int rows, int cols, float p_drop, uint64_t seed, int dtype,
                            void* stream);
+/* The LayerNorm in front of a frozen layer's self-attention when only the live key tiles are projected to keys and values
+ * (mmgl_selfattn_tiles_*).  mmgl_layernorm_tiles_fwd / mmgl_add_layernorm_tiles_fwd are mmgl_layernorm_fwd / mmgl_add_layernorm_fwd
+ * (same y, sum_out, mean, rstd, same dropout hash, keyed by the full row index) plus a compact copy: row r of y is also stored to
+ * row rowmap[r] of yc [crows, cols] when 0 <= rowmap[r] < crows.  rowmap [rows] int32 maps every row of a live 64-key tile,
+ * its padding rows included, to its compact row and every other row to -1.  yc is a copy for the frozen K | V projection, whose
+ * gradient reaches y through the dense fused dgrad: the backward is mmgl_layernorm_bwd / mmgl_add_layernorm_bwd as it is. */
+int mmgl_layernorm_tiles_fwd(const void* x, const void* gamma, const void* beta, void* y, void* yc, const int32_t* rowmap,
+                             float* mean, float* rstd, int rows, int cols, int crows, float eps, int dtype, void* stream);
+int mmgl_add_layernorm_tiles_fwd(const void* x, const void* res, const void* gamma, const void* beta, void* sum_out, void* y,
+                                 void* yc, const int32_t* rowmap, float* mean, float* rstd, int rows, int cols, int crows,
+                                 float eps, float p_drop, uint64_t seed, int dtype, void* stream);
 int mmgl_activation_fwd(const void* x, void* y, size_t n, int act, int dtype, void* stream);
 /* y[i] = x[i] * (*scale), product in fp32, scale read from device memory (x == y allowed).  The upstream gradient of a scalar
  * loss -- `loss / args.grad_accumulation_steps` at reference language_modelling/run_generation.py:483 -- applied to a saved

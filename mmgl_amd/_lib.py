@@ -32,6 +32,8 @@ SIGNATURES = {
     "mmgl_selfattn_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, P]),
     "mmgl_selfattn_prefix_fwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "mmgl_selfattn_prefix_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, I, I, I, P]),
+    "mmgl_selfattn_tiles_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "mmgl_selfattn_tiles_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, I, I, I, P]),
     "mmgl_selfattn_gqa_fwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "mmgl_selfattn_gqa_bwd_workspace": (Z, [I, I, I, I, I, I]),
     "mmgl_selfattn_gqa_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, I, I, I, P]),
@@ -64,6 +66,8 @@ SIGNATURES = {
     "mmgl_encattn_fwd": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "mmgl_add_layernorm_fwd": (I, [P, P, P, P, P, P, P, P, I, I, F, F, U, I, P]),
     "mmgl_add_layernorm_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, Z, I, I, F, U, I, P]),
+    "mmgl_layernorm_tiles_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, F, I, P]),
+    "mmgl_add_layernorm_tiles_fwd": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, F, F, U, I, P]),
     "mmgl_activation_fwd": (I, [P, P, Z, I, I, P]),
     "mmgl_scale": (I, [P, P, P, Z, I, P]),
     "mmgl_gemm_nt_fast": (I, [I, I, I, I, I, I, I]),

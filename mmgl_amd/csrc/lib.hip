@@ -78,4 +78,6 @@ int mmgl_num_cu() {
 // resolves every declared symbol at load, so a library built without it is refused all the same.
 // mmgl_logits_process (repetition penalty, n-gram and token bans for generate()) was added at 110 the same way.
 // mmgl_attn_decode_block_fwd / mmgl_lookup_accept (prompt-lookup decoding for generate()) were added at 110 the same way.
+// mmgl_selfattn_tiles_fwd / _bwd and mmgl_layernorm_tiles_fwd / mmgl_add_layernorm_tiles_fwd (keys and values of the live key
+// tiles only in the frozen layers) were added at 110 the same way.
 extern "C" int mmgl_version(void) { return 110; }

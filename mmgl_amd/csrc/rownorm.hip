@@ -30,12 +30,16 @@ template <int TPR> __device__ __forceinline__ float row_sum(float v, float* red,
     }
 }
 
-template <typename T, int TPR, int NV, bool RMS>
+// MODE bit 0: RMSNorm (no mean); bit 2: compact copy -- a row whose rowmap entry r is in [0, crows) is also stored to yc row r
+// (the normed rows of the live key tiles, the operand of the frozen layers' K | V projection); everything else is untouched
+template <typename T, int TPR, int NV, int MODE>
 __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
                                                        const T* __restrict__ gamma, const T* __restrict__ beta,
                                                        T* __restrict__ sum_out, T* __restrict__ y,
                                                        float* __restrict__ mean, float* __restrict__ rstd, int rows,
-                                                       int cols, float eps, float p, uint64_t seed) {
+                                                       int cols, float eps, float p, uint64_t seed,
+                                                       const int* __restrict__ rowmap, T* __restrict__ yc, int crows) {
+    constexpr bool RMS = (MODE & 1) != 0, COMPACT = (MODE & 4) != 0;
     typedef typename Vec<T>::type V;
     constexpr int VN = Vec<T>::N;
     __shared__ float red[4];
@@ -47,6 +51,8 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* __restrict__ x, 
     for (int row0 = blockIdx.x * rpb; row0 < rows; row0 += gridDim.x * rpb) {
         const int row = row0 + rib;
         const bool live = row < rows;
+        int crow = -1;
+        if constexpr (COMPACT) crow = live ? rowmap[row] : -1;
         float xv[NV][VN];
         float s = 0.f;
 #pragma unroll
@@ -109,6 +115,9 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* __restrict__ x, 
                     o[j] = (T)t;
                 }
                 *(V*)(y + (size_t)row * cols + c * VN) = o;
+                if constexpr (COMPACT) {
+                    if ((unsigned)crow < (unsigned)crows) *(V*)(yc + (size_t)crow * cols + c * VN) = o;
+                }
             }
         }
     }
@@ -276,14 +285,19 @@ int bwd_blocks(int rows, int rpb) {
 
 template <typename T, bool RMS>
 int norm_fwd(const char* who, const void* x, const void* res, const void* gamma, const void* beta, void* sum_out, void* y,
-             float* mean, float* rstd, int rows, int cols, float eps, hipStream_t st, float p = 0.f, uint64_t seed = 0) {
+             float* mean, float* rstd, int rows, int cols, float eps, hipStream_t st, float p = 0.f, uint64_t seed = 0,
+             const int* rowmap = nullptr, void* yc = nullptr, int crows = 0) {
     Geo g;
     int rc = geometry<T>(who, rows, cols, g);
     if (rc) return rc;
     int blocks = (rows + g.rpb - 1) / g.rpb;
     if (blocks > 8192) blocks = 8192;
-    NORM_DISPATCH(norm_fwd_kernel, T, RMS, g, dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)res, (const T*)gamma,
-                  (const T*)beta, (T*)sum_out, (T*)y, mean, rstd, rows, cols, eps, p, seed);
+    if (!RMS && rowmap)                                // (the compact copy exists for LayerNorm only)
+        NORM_DISPATCH(norm_fwd_kernel, T, (RMS ? 1 : 4), g, dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)res, (const T*)gamma,
+                      (const T*)beta, (T*)sum_out, (T*)y, mean, rstd, rows, cols, eps, p, seed, rowmap, (T*)yc, crows);
+    else
+        NORM_DISPATCH(norm_fwd_kernel, T, (RMS ? 1 : 0), g, dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)res, (const T*)gamma,
+                      (const T*)beta, (T*)sum_out, (T*)y, mean, rstd, rows, cols, eps, p, seed, (const int*)nullptr, (T*)nullptr, 0);
     MMGL_CHECK_LAUNCH(who);
     return MMGL_OK;
 }
@@ -350,6 +364,30 @@ extern "C" int mmgl_add_layernorm_fwd(const void* x, const void* res, const void
     MMGL_CHECK_ARG(x && res && y, "mmgl_add_layernorm_fwd: null pointer");
     MMGL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "mmgl_add_layernorm_fwd: dropout p=%g outside [0,1)", p_drop);
     NORM_BY_DTYPE(norm_fwd, false, x, res, gamma, beta, sum_out, y, mean, rstd, rows, cols, eps, (hipStream_t)stream, p_drop, seed);
+}
+
+// ---- the LayerNorm in front of a frozen layer's attention, with the compact copy of its output (see the header)
+static int compact_check(const char* who, const int32_t* rowmap, const void* yc, int rows, int crows) {
+    MMGL_CHECK_ARG(rowmap && yc && crows > 0 && crows <= rows, "%s: rowmap / compact buffer missing or crows = %d outside (0, rows]", who, crows);
+    return MMGL_OK;
+}
+
+extern "C" int mmgl_layernorm_tiles_fwd(const void* x, const void* gamma, const void* beta, void* y, void* yc, const int32_t* rowmap,
+                                        float* mean, float* rstd, int rows, int cols, int crows, float eps, int dtype, void* stream) {
+    MMGL_CHECK_ARG(x && y && mean && rstd, "mmgl_layernorm_tiles_fwd: null pointer");
+    if (int rc = compact_check("mmgl_layernorm_tiles_fwd", rowmap, yc, rows, crows)) return rc;
+    NORM_BY_DTYPE(norm_fwd, false, x, nullptr, gamma, beta, nullptr, y, mean, rstd, rows, cols, eps, (hipStream_t)stream, 0.f, 0, rowmap, yc,
+                  crows);
+}
+
+extern "C" int mmgl_add_layernorm_tiles_fwd(const void* x, const void* res, const void* gamma, const void* beta, void* sum_out, void* y,
+                                            void* yc, const int32_t* rowmap, float* mean, float* rstd, int rows, int cols, int crows,
+                                            float eps, float p_drop, uint64_t seed, int dtype, void* stream) {
+    MMGL_CHECK_ARG(x && res && y, "mmgl_add_layernorm_tiles_fwd: null pointer");
+    MMGL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "mmgl_add_layernorm_tiles_fwd: dropout p=%g outside [0,1)", p_drop);
+    if (int rc = compact_check("mmgl_add_layernorm_tiles_fwd", rowmap, yc, rows, crows)) return rc;
+    NORM_BY_DTYPE(norm_fwd, false, x, res, gamma, beta, sum_out, y, mean, rstd, rows, cols, eps, (hipStream_t)stream, p_drop, seed, rowmap,
+                  yc, crows);
 }
 
 extern "C" int mmgl_add_layernorm_bwd(const void* dy, const void* dsum, const void* sum, const void* gamma, const float* mean,

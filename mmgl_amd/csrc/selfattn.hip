@@ -939,6 +939,43 @@ extern "C" int mmgl_selfattn_bwd(const void* dout, const void* q, const void* k,
                                     ld_qkv, ld_dqkv, ld_dqkv, dtype, stream);
 }
 
+// ---- live key tiles only: k, v compact [m_live, ld_kv] (the 64-key tiles that hold a valid key), see the header
+static int tiles_check(const char* who, int B, int H, int T, int D, int m_live, int ld_kv, int dtype) {
+    int rc = sa_check(who, B, H, T, D, dtype);
+    if (rc) return rc;
+    if (dtype != MMGL_BF16 || D != 64 || T % 64 || !sa32_supported(dtype, D, T))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: bf16, head_dim 64 and T a multiple of 64 up to 4096 only (got dtype %d, D=%d, T=%d)", who, dtype, D, T);
+    MMGL_CHECK_ARG(m_live > 0 && m_live % 64 == 0 && (long long)m_live <= (long long)B * T,
+                   "%s: m_live = %d must be a positive multiple of 64 up to B*T", who, m_live);
+    MMGL_CHECK_ARG((long long)m_live * (ld_kv ? ld_kv : (long long)H * D) * 2 < (1ll << 31), "%s: the compact buffer must stay below 2 GiB", who);
+    return MMGL_OK;
+}
+
+extern "C" int mmgl_selfattn_tiles_fwd(const void* q, const void* k, const void* v, const uint8_t* key_valid, const int32_t* key_tiles,
+                                       void* out, float* lse, int B, int H, int T, int D, int m_live, int ld_q, int ld_kv, int dtype,
+                                       void* stream) {
+    int rc = tiles_check("mmgl_selfattn_tiles_fwd", B, H, T, D, m_live, ld_kv, dtype);
+    if (rc) return rc;
+    MMGL_CHECK_ARG(q && k && v && key_valid && key_tiles && out && lse, "mmgl_selfattn_tiles_fwd: null pointer");
+    if ((rc = sa_ld("mmgl_selfattn_tiles_fwd", ld_q, H, D)) || (rc = sa_ld("mmgl_selfattn_tiles_fwd", ld_kv, H, D))) return rc;
+    return sa32_tiles_fwd(q, k, v, key_valid, key_tiles, out, lse, B, H, T, m_live / 64, ld_q, ld_kv, (hipStream_t)stream);
+}
+
+extern "C" int mmgl_selfattn_tiles_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                       const uint8_t* key_valid, const int32_t* key_tiles, void* dq, void* dk, void* dv, void* workspace,
+                                       size_t workspace_bytes, int B, int H, int T, int D, int m_live, int ld_q, int ld_kv, int ld_dq,
+                                       int ld_dkv, int dtype, void* stream) {
+    int rc = tiles_check("mmgl_selfattn_tiles_bwd", B, H, T, D, m_live, ld_kv, dtype);
+    if (rc) return rc;
+    if ((rc = sa_ld("mmgl_selfattn_tiles_bwd", ld_q, H, D)) || (rc = sa_ld("mmgl_selfattn_tiles_bwd", ld_kv, H, D)) ||
+        (rc = sa_ld("mmgl_selfattn_tiles_bwd", ld_dq, H, D)) || (rc = sa_ld("mmgl_selfattn_tiles_bwd", ld_dkv, H, D))) return rc;
+    MMGL_CHECK_ARG(dout && q && k && v && out && lse && key_valid && key_tiles && dq && dk && dv && workspace,
+                   "mmgl_selfattn_tiles_bwd: null pointer");
+    MMGL_CHECK_ARG(workspace_bytes >= mmgl_selfattn_bwd_workspace(B, H, T), "mmgl_selfattn_tiles_bwd: workspace too small");
+    return sa32_tiles_bwd(dout, q, k, v, out, lse, key_valid, key_tiles, dq, dk, dv, (float*)workspace, B, H, T, m_live / 64, ld_q, ld_kv,
+                          ld_dq, ld_dkv, (hipStream_t)stream);
+}
+
 // ---- grouped-query attention: k, v, dk, dv [B, T, Hkv*D]; query head h reads key / value head h / (H / Hkv)
 static int gqa_check(const char* who, int B, int H, int Hkv, int T, int D, int dtype) {
     MMGL_CHECK_ARG(Hkv >= 1 && H >= Hkv && H % Hkv == 0, "%s: H = %d must be a positive multiple of Hkv = %d", who, H, Hkv);

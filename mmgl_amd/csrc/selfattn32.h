@@ -12,6 +12,14 @@ SA32_HIDDEN bool sa32_supported(int dtype, int D, int Tk);
 // H / G heads and query head h reads head h / G (mmgl_selfattn_gqa_fwd); G = 1 launches the multi-head kernels
 SA32_HIDDEN int sa32_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, void* out, float* lse, int B, int H, int T,
                          int P, int D, int ldq, int ldk, hipStream_t st, int G = 1);
+// live key tiles only (mmgl_selfattn_tiles_fwd / _bwd): bf16, head_dim 64, T a multiple of 64, no prefix, multi-head.  k, v are
+// compact [64 ntc, ldk]: the 64-key tiles with a valid key, `tiles` [B, T / 64] maps a key tile to its compact tile (-1: dead);
+// dq, dk, dv are dense [B, T, ldg | ldgk]
+SA32_HIDDEN int sa32_tiles_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, const int* tiles, void* out, float* lse,
+                               int B, int H, int T, int ntc, int ldq, int ldk, hipStream_t st);
+SA32_HIDDEN int sa32_tiles_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
+                               const uint8_t* valid, const int* tiles, void* dq, void* dk, void* dv, float* delta, int B, int H, int T,
+                               int ntc, int ldq, int ldk, int ldg, int ldgk, hipStream_t st);
 // packed bidirectional forward; same argument meaning as mmgl_encattn_fwd
 SA32_HIDDEN int sa32_enc_fwd(const void* q, const void* k, const void* v, const int* cu, void* out, int nseq, int H, int D, int ld_in,
                              int ld_out, int max_len, int q_rows, hipStream_t st);

@@ -88,6 +88,8 @@ struct SA32Args {
     int B, H, T, P, nqb, ldq, ldk, ldo, q_rows;
     long long* trace;          // SA32_TRACE builds (timing experiments): 8 x int64 per workgroup
     int G;                     // grouped-query attention (GQA instantiations only): query head h reads key / value head h / G
+    const int* tiles;          // TILES instantiations only: [B, T / 64] compact tile of key tile j, -1 = dead (no such rows in k / v)
+    int ntc;                   // ... and the compact tiles in k / v ([64 ntc, ldk] rows for the whole batch)
 };
 
 __device__ __forceinline__ f32x16 mma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
@@ -100,9 +102,31 @@ __device__ __forceinline__ void swap32_u32(uint32_t& a, uint32_t& b) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
 }
 
+// TILES = true (live key tiles only): k / v hold the 64-key tiles that have a valid key and nothing else, [64 ntc, ldk] for the whole
+// batch.  A lane keeps its sample's row of the tile table (lane j: compact tile of key tile j, at most 64 tiles per sequence), so a
+// tile's base row is one v_readlane.  Masks, causal tests and valid words keep using j.  A dead tile that is requested all the same
+// (the prologue's, before the mask is known) reads the sample's first live tile; every index is clamped to the buffer's tiles, as
+// the scalar offset of a buffer access is outside the descriptor's range check.
+struct TileRow {
+    int tv, first, last;
+    __device__ __forceinline__ void load(const int* tiles, int b, int ntl, int ntc, int lane) {
+        const __amdgpu_buffer_rsrc_t rt = make_rsrc(tiles + (size_t)b * ntl, (uint32_t)ntl * 4u);
+        const int t = (int)__builtin_amdgcn_raw_buffer_load_b32(rt, (uint32_t)lane * 4u, 0, 0);
+        tv = lane < ntl ? t : -1;
+        last = ntc - 1;
+        const uint64_t lv = __builtin_amdgcn_ballot_w64(tv >= 0);
+        first = lv != 0ull ? __builtin_amdgcn_readlane(tv, __builtin_ctzll(lv)) : 0;
+        first = max(min(first, last), 0);
+    }
+    __device__ __forceinline__ int row(int j) const {                   // j wave-uniform, < 64
+        const int t = __builtin_amdgcn_readlane(tv, j);
+        return (t < 0 ? first : min(t, last)) * 64;
+    }
+};
+
 // GQA = true: k, v [B, Tk, (H / G) * D], query head h reads key / value head h / a.G (HF's repeat_kv); nothing else differs, and the
 // GQA = false instantiations are the multi-head kernels as they were
-template <int D, bool CAUSAL, bool GQA = false>
+template <int D, bool CAUSAL, bool GQA = false, bool TILES = false>
 __global__ __launch_bounds__(256, G32<D>::OCC) void sa32_fwd_kernel(SA32Args a) {
     typedef G32<D> G;
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -117,6 +141,8 @@ __global__ __launch_bounds__(256, G32<D>::OCC) void sa32_fwd_kernel(SA32Args a) 
     const int bh = vid / a.nqb;
     const int qblk = CAUSAL ? a.nqb - 1 - vid % a.nqb : vid % a.nqb;      // causal: longest (most key tiles) first
     const int b = bh / a.H, h = bh % a.H;
+    TileRow tr{};
+    if constexpr (TILES) tr.load(a.tiles, b, a.T / G::KT, a.ntc, lane);   // the oldest load of the prologue: the first K / V request waits for it alone
     int Tq, Tk;
     const bf16 *qb, *kb, *vb;
     bf16* ob;
@@ -134,8 +160,8 @@ __global__ __launch_bounds__(256, G32<D>::OCC) void sa32_fwd_kernel(SA32Args a) 
         Tk = a.T + a.P;
         const int hk = GQA ? h / a.G : h;
         qb = a.q + (size_t)b * a.T * a.ldq + h * D;
-        kb = a.k + (size_t)b * Tk * a.ldk + hk * D;
-        vb = a.v + (size_t)b * Tk * a.ldk + hk * D;
+        kb = a.k + (TILES ? (size_t)0 : (size_t)b * Tk * a.ldk) + hk * D;
+        vb = a.v + (TILES ? (size_t)0 : (size_t)b * Tk * a.ldk) + hk * D;
         ob = a.out + (size_t)b * a.T * a.ldo + h * D;
         if (a.valid) valid_row = a.valid + (size_t)b * Tk;
     }
@@ -145,8 +171,9 @@ __global__ __launch_bounds__(256, G32<D>::OCC) void sa32_fwd_kernel(SA32Args a) 
 
     const uint32_t ldqB = (uint32_t)a.ldq * 2u, ldkB = (uint32_t)a.ldk * 2u, ldoB = (uint32_t)a.ldo * 2u;
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(qb, (uint32_t)(Tq - 1) * ldqB + D * 2);
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(kb, (uint32_t)(Tk - 1) * ldkB + D * 2);
-    const __amdgpu_buffer_rsrc_t rv = make_rsrc(vb, (uint32_t)(Tk - 1) * ldkB + D * 2);
+    const int kvrows = TILES ? a.ntc * G::KT : Tk;                      // rows behind the K / V descriptors
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(kb, (uint32_t)(kvrows - 1) * ldkB + D * 2);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(vb, (uint32_t)(kvrows - 1) * ldkB + D * 2);
     const __amdgpu_buffer_rsrc_t ro = make_rsrc(ob, (uint32_t)(Tq - 1) * ldoB + D * 2);
 
     // ---- per-tile key-valid words (bit s of word j: key 64 j + s exists and is attendable).  The bytes of this wave's first four
@@ -174,9 +201,10 @@ __global__ __launch_bounds__(256, G32<D>::OCC) void sa32_fwd_kernel(SA32Args a) 
     }
     auto issue = [&](int j, int slot) __attribute__((always_inline)) {
         char* base = smem + slot * G::SLOTB + wave * 1024;
+        const int jrow = TILES ? tr.row(j) : j * G::KT;
 #pragma unroll
         for (int i = 0; i < G::PIECES / 4; ++i) {
-            const int soff = (int)((uint32_t)(j * G::KT + i * 4 * G::RPP) * ldkB);
+            const int soff = (int)((uint32_t)(jrow + i * 4 * G::RPP) * ldkB);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_void*)(base + i * 4096), 16, kvoff, soff, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_void*)(base + G::TILEB + i * 4096), 16, vvoff, soff, 0, 0);
         }
@@ -470,12 +498,14 @@ struct SA32BwdArgs {
     float* delta;              // [B, H, T]: written by the dQ kernel, read by the dK / dV kernel
     int B, H, T, P, nqb, nkb, ldq, ldk, ldg, ldgk;
     int G;                     // GQA instantiations only: query head h reads key / value head h / G (dk, dv stay per QUERY head)
+    const int* tiles;          // TILES instantiations only (see SA32Args): k, v are compact [64 ntc, ldk]; dq, dk, dv stay dense
+    int ntc;
 };
 
 // 16 transposed fragments' worth of reads for ONE 32-channel block: f[blk][jj][half]; rows 32 blk + 16 jj (+ 8) of the tile at `ad`
 #define SA32_TR_READ(dst, ad, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(ad), "i"(off))
 
-template <int D, bool GQA = false>
+template <int D, bool GQA = false, bool TILES = false>
 __global__ __launch_bounds__(256, SA32_DQ_OCC) void sa32_bwd_dq_kernel(SA32BwdArgs a) {
     typedef G32<D> G;
     constexpr int NS = SA32_NS_DQ, PD = NS - 1;
@@ -490,11 +520,15 @@ __global__ __launch_bounds__(256, SA32_DQ_OCC) void sa32_bwd_dq_kernel(SA32BwdAr
     const int Tq = a.T, Tk = a.T + a.P, HD = a.H * D;
     const int t0 = qblk * 128 + wave * 32, trow = t0 + key;
     const int nkt = (min(Tq, (qblk + 1) * 128) + a.P + G::KT - 1) / G::KT;
+    TileRow tr{};
+    if constexpr (TILES) tr.load(a.tiles, b, a.T / G::KT, a.ntc, lane);   // (see the forward kernel)
 
     const uint32_t ldqB = (uint32_t)a.ldq * 2u, ldkB = (uint32_t)a.ldk * 2u, ldoB = (uint32_t)HD * 2u, ldgB = (uint32_t)a.ldg * 2u;
+    const int kvrows = TILES ? a.ntc * G::KT : Tk;
+    const size_t kvbase = (TILES ? (size_t)0 : (size_t)b * Tk * a.ldk) + hk * D;
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(a.q + (size_t)b * Tq * a.ldq + h * D, (uint32_t)(Tq - 1) * ldqB + D * 2);
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + (size_t)b * Tk * a.ldk + hk * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
-    const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + (size_t)b * Tk * a.ldk + hk * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + kvbase, (uint32_t)(kvrows - 1) * ldkB + D * 2);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + kvbase, (uint32_t)(kvrows - 1) * ldkB + D * 2);
     const __amdgpu_buffer_rsrc_t rg = make_rsrc(a.dout + (size_t)b * Tq * HD + h * D, (uint32_t)(Tq - 1) * ldoB + D * 2);
     const __amdgpu_buffer_rsrc_t ro = make_rsrc(a.out + (size_t)b * Tq * HD + h * D, (uint32_t)(Tq - 1) * ldoB + D * 2);
     const __amdgpu_buffer_rsrc_t rd = make_rsrc(a.dq + (size_t)b * Tq * a.ldg + h * D, (uint32_t)(Tq - 1) * ldgB + D * 2);
@@ -523,9 +557,10 @@ __global__ __launch_bounds__(256, SA32_DQ_OCC) void sa32_bwd_dq_kernel(SA32BwdAr
     }
     auto issue = [&](int j, int slot) __attribute__((always_inline)) {
         char* base = smem + slot * G::SLOTB + wave * 1024;
+        const int jrow = TILES ? tr.row(j) : j * G::KT;
 #pragma unroll
         for (int i = 0; i < G::PIECES / 4; ++i) {
-            const int soff = (int)((uint32_t)(j * G::KT + i * 4 * G::RPP) * ldkB);
+            const int soff = (int)((uint32_t)(jrow + i * 4 * G::RPP) * ldkB);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_void*)(base + i * 4096), 16, tvoff, soff, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_void*)(base + G::TILEB + i * 4096), 16, tvoff, soff, 0, 0);
         }
@@ -721,7 +756,10 @@ template <int D> struct GB32 {
 };
 
 // GQA = true: K / V of head h / a.G, dK / dV still of QUERY head h (the host points dk / dv at the expanded scratch and folds the group)
-template <int D, bool GQA = false>
+// TILES = true: k, v are compact (see the forward kernel).  A wave's 32 keys lie in one key tile: its compact row replaces the key's
+// row in the K / V loads (by the per-lane offset: inside the descriptors' range check), and a wave in a dead tile -- no valid key, so
+// no arithmetic either -- loads zeros.  dK / dV keep the dense layout, zeros in the dead tiles, as the fused dgrad reads them.
+template <int D, bool GQA = false, bool TILES = false>
 __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dkv_kernel(SA32BwdArgs a) {
     typedef G32<D> G;
     typedef GB32<D> GB;
@@ -738,11 +776,21 @@ __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dk
     const int k0 = kblk * 128 + wave * 32, krow = k0 + kl;               // this lane's key
     const int nqt = (Tq + 63) / 64;
     const int i0 = max(kblk * 128 - a.P, 0) / 64;                        // first query tile with a row that sees key kblk * 128
+    int crow = krow;                                                     // this lane's row in k / v
+    bool tile_ok = true;
+    if constexpr (TILES) {
+        const int ntl = Tk / G::KT, jt = k0 >> 6;                        // wave-uniform
+        const int t = jt < ntl ? a.tiles[(size_t)b * ntl + jt] : -1;
+        tile_ok = t >= 0 && t < a.ntc;
+        crow = t * G::KT + (krow & 63);
+    }
 
     const uint32_t ldqB = (uint32_t)a.ldq * 2u, ldkB = (uint32_t)a.ldk * 2u, ldoB = (uint32_t)HD * 2u, ldgB = (uint32_t)a.ldgk * 2u;
+    const int kvrows = TILES ? a.ntc * G::KT : Tk;
+    const size_t kvbase = (TILES ? (size_t)0 : (size_t)b * Tk * a.ldk) + hk * D;
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(a.q + (size_t)b * Tq * a.ldq + h * D, (uint32_t)(Tq - 1) * ldqB + D * 2);
-    const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + (size_t)b * Tk * a.ldk + hk * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
-    const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + (size_t)b * Tk * a.ldk + hk * D, (uint32_t)(Tk - 1) * ldkB + D * 2);
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(a.k + kvbase, (uint32_t)(kvrows - 1) * ldkB + D * 2);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(a.v + kvbase, (uint32_t)(kvrows - 1) * ldkB + D * 2);
     const __amdgpu_buffer_rsrc_t rg = make_rsrc(a.dout + (size_t)b * Tq * HD + h * D, (uint32_t)(Tq - 1) * ldoB + D * 2);
     const __amdgpu_buffer_rsrc_t rdk = make_rsrc(a.dk + (size_t)b * Tk * a.ldgk + h * D, (uint32_t)(Tk - 1) * ldgB + D * 2);
     const __amdgpu_buffer_rsrc_t rdv = make_rsrc(a.dv + (size_t)b * Tk * a.ldgk + h * D, (uint32_t)(Tk - 1) * ldgB + D * 2);
@@ -755,7 +803,7 @@ __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dk
     bf16x8 kf[G::NKS], vf[G::NKS];
 #pragma unroll
     for (int ks = 0; ks < G::NKS; ++ks) {
-        const uint32_t c = (uint32_t)krow * ldkB + (uint32_t)(16 * ks + 8 * hi) * 2u;
+        const uint32_t c = (tile_ok ? (uint32_t)crow * ldkB : OOB) + (uint32_t)(16 * ks + 8 * hi) * 2u;
         kf[ks] = buf_load8<bf16>(rk, c);
         vf[ks] = buf_load8<bf16>(rv, c);
     }
@@ -934,28 +982,28 @@ __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dk
             }
 }
 
-template <int D, bool CAUSAL, bool GQA = false> int launch_fwd(const SA32Args& a, int nblocks, hipStream_t st) {
+template <int D, bool CAUSAL, bool GQA = false, bool TILES = false> int launch_fwd(const SA32Args& a, int nblocks, hipStream_t st) {
     typedef G32<D> G;
-    auto kern = sa32_fwd_kernel<D, CAUSAL, GQA>;
+    auto kern = sa32_fwd_kernel<D, CAUSAL, GQA, TILES>;
     if (int rc = mmgl_set_lds(kern, G::LDS, "sa32_fwd")) return rc;
     hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), G::LDS, st, a);
     MMGL_CHECK_LAUNCH("sa32_fwd");
     return MMGL_OK;
 }
 
-template <int D, bool GQA = false> int launch_bwd_dq(const SA32BwdArgs& a, hipStream_t st) {
+template <int D, bool GQA = false, bool TILES = false> int launch_bwd_dq(const SA32BwdArgs& a, hipStream_t st) {
     typedef G32<D> G;
     constexpr int LDS = SA32_NS_DQ * G::SLOTB + G::MAXT * 8;
-    auto kern = sa32_bwd_dq_kernel<D, GQA>;
+    auto kern = sa32_bwd_dq_kernel<D, GQA, TILES>;
     if (int rc = mmgl_set_lds(kern, LDS, "sa32_bwd_dq")) return rc;
     hipLaunchKernelGGL(kern, dim3(a.B * a.H * a.nqb), dim3(256), LDS, st, a);
     MMGL_CHECK_LAUNCH("sa32_bwd_dq");
     return MMGL_OK;
 }
 
-template <int D, bool GQA = false> int launch_bwd_dkv(const SA32BwdArgs& a, hipStream_t st) {
+template <int D, bool GQA = false, bool TILES = false> int launch_bwd_dkv(const SA32BwdArgs& a, hipStream_t st) {
     typedef GB32<D> GB;
-    auto kern = sa32_bwd_dkv_kernel<D, GQA>;
+    auto kern = sa32_bwd_dkv_kernel<D, GQA, TILES>;
     if (int rc = mmgl_set_lds(kern, GB::LDS, "sa32_bwd_dkv")) return rc;
     hipLaunchKernelGGL(kern, dim3(a.B * a.H * a.nkb), dim3(256), GB::LDS, st, a);
     MMGL_CHECK_LAUNCH("sa32_bwd_dkv");
@@ -978,6 +1026,15 @@ int sa32_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, 
     a.G = G;
     if (G > 1) return D == 64 ? launch_fwd<64, true, true>(a, nblocks, st) : launch_fwd<128, true, true>(a, nblocks, st);
     return D == 64 ? launch_fwd<64, true>(a, nblocks, st) : launch_fwd<128, true>(a, nblocks, st);
+}
+
+int sa32_tiles_fwd(const void* q, const void* k, const void* v, const uint8_t* valid, const int* tiles, void* out, float* lse, int B,
+                   int H, int T, int ntc, int ldq, int ldk, hipStream_t st) {
+    SA32Args a{};
+    a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.valid = valid; a.out = (bf16*)out; a.lse = lse; a.cu = nullptr;
+    a.B = B; a.H = H; a.T = T; a.P = 0; a.nqb = cdiv(T, 128); a.ldq = ldq; a.ldk = ldk; a.ldo = H * 64; a.q_rows = T;
+    a.G = 1; a.tiles = tiles; a.ntc = ntc;
+    return launch_fwd<64, true, false, true>(a, B * H * a.nqb, st);
 }
 
 int sa32_enc_fwd(const void* q, const void* k, const void* v, const int* cu, void* out, int nseq, int H, int D, int ld_in, int ld_out,
@@ -1004,4 +1061,16 @@ int sa32_bwd(const void* dout, const void* q, const void* k, const void* v, cons
     }
     if (int rc = D == 64 ? launch_bwd_dq<64>(a, st) : launch_bwd_dq<128>(a, st)) return rc;
     return D == 64 ? launch_bwd_dkv<64>(a, st) : launch_bwd_dkv<128>(a, st);
+}
+
+int sa32_tiles_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse, const uint8_t* valid,
+                   const int* tiles, void* dq, void* dk, void* dv, float* delta, int B, int H, int T, int ntc, int ldq, int ldk, int ldg,
+                   int ldgk, hipStream_t st) {
+    SA32BwdArgs a{};
+    a.dout = (const bf16*)dout; a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (const bf16*)out; a.lse = lse;
+    a.valid = valid; a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.delta = delta;
+    a.B = B; a.H = H; a.T = T; a.P = 0; a.nqb = cdiv(T, 128); a.nkb = cdiv(T, 128); a.ldq = ldq; a.ldk = ldk; a.ldg = ldg; a.ldgk = ldgk;
+    a.G = 1; a.tiles = tiles; a.ntc = ntc;
+    if (int rc = launch_bwd_dq<64, false, true>(a, st)) return rc;
+    return launch_bwd_dkv<64, false, true>(a, st);
 }

@@ -199,6 +199,16 @@ class MPTAttention(nn.Module):
             self.__dict__[slot] = cache
         return cache[1]
 
+    def key_tiles_route(self, x, key_tiles, layer_head_mask, output_attentions, past_key_value, kv_out):
+        """Whether this layer's self-attention projects keys and values for the live key tiles only (ops.frozen_selfattn_tiles): a
+        frozen fused projection on the bf16 head_dim-64 flash kernels, with the batch's tile table.  Everything else -- the general
+        core, a key / value prefix, a decode cache, adapters -- keeps the dense path."""
+        if key_tiles is None or self.cross_attention or past_key_value is not None or kv_out is not None:
+            return False
+        if layer_head_mask is not None or output_attentions or (self.training and self.dropout > 0):
+            return False
+        return ops.selfattn_tiles_supported(x, self.num_heads, key_tiles) and self._frozen_qkv() is not None
+
     def _frozen_qkv(self):
         """The fused weight / bias (_fused_qkv) when the three projections are frozen (the reference freezes the whole LM outside
         the cross-attention layers, :731-737), else None."""
@@ -219,8 +229,10 @@ class MPTAttention(nn.Module):
                                "_lora_qkv_cache")
 
     # -- causal self-attention of the (frozen) OPT layers: HIP flash kernels, no [B,1,T,T] mask, no [B,H,T,T] scores
-    def _forward_self(self, hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value=None, kv_out=None):
-        """kv_out: the layer's [B, capacity, 2d] K|V buffer of a DecodeCache -- the prefill copies its keys and values there."""
+    def _forward_self(self, hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value=None, kv_out=None,
+                      live=None):
+        """kv_out: the layer's [B, capacity, 2d] K|V buffer of a DecodeCache -- the prefill copies its keys and values there.
+        live = (yc, key_tiles): the caller checked key_tiles_route and brings the compact copy of hidden_states."""
         H = self.num_heads
         if attention_mask is None or attention_mask.dim() != 2:
             raise ValueError("self-attention takes the [bsz, seq_len] key mask (causality is implied); additive 4-D masks are "
@@ -230,6 +242,10 @@ class MPTAttention(nn.Module):
             raise ValueError("layer_head_mask / output_attentions / attention dropout together with a key / value prefix (prefix tuning) "
                              "are not implemented")
         fused = self._frozen_qkv()
+        if live is not None:                 # frozen layer, padded batch: keys and values of the live key tiles only
+            yc, key_tiles = live
+            o = ops.frozen_selfattn_tiles(hidden_states, yc, *fused, attention_mask, key_tiles, H)
+            return _lin(self.out_proj, o), None, None
         if general:
             # reference :237-256 on the self-attention call site: separate q / k / v (the fused-QKV node has no general core), the
             # general HIP core with the causal AND key mask
@@ -285,11 +301,11 @@ class MPTAttention(nn.Module):
         return _lin(self.out_proj, o), None, None
 
     def forward(self, hidden_states, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None,
-                past_key_value=None, layer_head_mask=None, output_attentions=False, kv_out=None):
+                past_key_value=None, layer_head_mask=None, output_attentions=False, kv_out=None, live=None):
         """Input shape: Batch x Time x Channel.  Returns (attn_output, attn_weights-or-None, None)."""
         if self.cross_attention:
             return self._forward_cross(hidden_states, neighbor_embeds, neighbor_attention_mask, layer_head_mask, output_attentions, kv_out)
-        return self._forward_self(hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value, kv_out)
+        return self._forward_self(hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value, kv_out, live)
 
     # -- one decode step of generate(): M = batch rows, weight-streaming GEMMs and single-query attention (csrc/decode.hip)
     @staticmethod
@@ -431,15 +447,26 @@ class MPTDecoderLayer(nn.Module):
             h = self._ln(self.final_layer_norm, h)
         return h, attn_w
 
-    def _forward_self(self, h, attention_mask, layer_head_mask, output_attentions, defer_residual=False, past_key_value=None, kv_out=None):
+    def _forward_self(self, h, attention_mask, layer_head_mask, output_attentions, defer_residual=False, past_key_value=None, kv_out=None,
+                      key_tiles=None):
         """OPT layer (frozen in every peft mode of the reference, :731-737): GEMMs, attention (ops.selfattn_core*), LayerNorm and
         dropout + residual all run on this repo's HIP kernels.  Every `residual + dropout(branch)` is folded into the LayerNorm that
         follows it (ops.add_layer_norm_pair: one forward and one backward kernel per pair); the layer's last add can be
-        left to the next layer's first LayerNorm (`defer_residual`, see _Deferred)."""
+        left to the next layer's first LayerNorm (`defer_residual`, see _Deferred).
+        key_tiles (an ops.KeyTiles): a pre-LN layer whose attention takes the live-key-tile route (MPTAttention.key_tiles_route) has
+        its first LayerNorm write the compact copy of the normed rows as well."""
         pre = self.do_layer_norm_before
         ln1, ln2 = self.self_attn_layer_norm, self.final_layer_norm
         pair = lambda x, r, ln: ops.add_layer_norm_pair(x, r, ln.weight, ln.bias, ln.eps, self.dropout, self.training)
-        if isinstance(h, _Deferred):
+        like = h.residual if isinstance(h, _Deferred) else h
+        live = None
+        if pre and self.self_attn.key_tiles_route(like, key_tiles, layer_head_mask, output_attentions, past_key_value, kv_out):
+            if isinstance(h, _Deferred):
+                h, x, yc = ops.add_layer_norm_tiles(h.branch, h.residual, ln1.weight, ln1.bias, ln1.eps, key_tiles, h.p_drop, h.training)
+            else:
+                h, x, yc = ops.layer_norm_tiles(h, ln1.weight, ln1.bias, ln1.eps, key_tiles)
+            live = (yc, key_tiles)
+        elif isinstance(h, _Deferred):
             if pre:
                 h, x = ops.add_layer_norm_pair(h.branch, h.residual, ln1.weight, ln1.bias, ln1.eps, h.p_drop, h.training)
             else:
@@ -450,7 +477,7 @@ class MPTDecoderLayer(nn.Module):
             x = h
         residual = h
         a, attn_w, _ = self.self_attn(x, attention_mask=attention_mask, layer_head_mask=layer_head_mask,
-                                      output_attentions=output_attentions, past_key_value=past_key_value, kv_out=kv_out)
+                                      output_attentions=output_attentions, past_key_value=past_key_value, kv_out=kv_out, live=live)
         if pre:
             h, x = pair(a, residual, ln2)
         else:
@@ -466,13 +493,14 @@ class MPTDecoderLayer(nn.Module):
         return ops.gated_residual(residual, x, None, self.dropout, self.training), attn_w
 
     def forward(self, hidden_states, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None,
-                layer_head_mask=None, past_key_value=None, output_attentions=False, use_cache=False, defer_residual=False, kv_out=None):
+                layer_head_mask=None, past_key_value=None, output_attentions=False, use_cache=False, defer_residual=False, kv_out=None,
+                key_tiles=None):
         if self.cross_attention:
             h, attn_w = self._forward_cross(_materialize(hidden_states), neighbor_embeds, neighbor_attention_mask, layer_head_mask,
                                             output_attentions, kv_out)
         else:
             h, attn_w = self._forward_self(hidden_states, attention_mask, layer_head_mask, output_attentions, defer_residual, past_key_value,
-                                           kv_out)
+                                           kv_out, key_tiles)
         outputs = (h,)
         if output_attentions:
             outputs += (attn_w,)
@@ -659,8 +687,10 @@ class MPTDecoder(MPTPreTrainedModel):
 
     def forward(self, input_ids=None, attention_mask=None, head_mask=None, past_key_values=None, inputs_embeds=None,
                 neighbor_embeds=None, neighbor_attention_mask=None, use_cache=None, output_attentions=None,
-                output_hidden_states=None, return_dict=None, first_key_valid=False, cache_capacity=None):
-        """use_cache=True: the prefill of greedy generation -- the same kernels as any forward, plus a copy of every layer's keys and
+                output_hidden_states=None, return_dict=None, first_key_valid=False, cache_capacity=None, key_tiles=None):
+        """key_tiles (an ops.KeyTiles of attention_mask, optional): the frozen layers project keys and values for the 64-key tiles that
+        hold a valid key only (MPTAttention.key_tiles_route says where); the result is that of the dense path.
+        use_cache=True: the prefill of greedy generation -- the same kernels as any forward, plus a copy of every layer's keys and
         values into a DecodeCache (capacity `cache_capacity` columns, default max_position_embeddings) returned as past_key_values.
         past_key_values=DecodeCache with input_ids [B, 1]: one decode step (see _decode_step).  Any other past_key_values keeps its
         meaning: a fixed key/value prefix (prefix tuning)."""
@@ -759,7 +789,7 @@ class MPTDecoder(MPTPreTrainedModel):
             layer_outputs = decoder_layer(hidden_states, attention_mask=causal_attention_mask, layer_head_mask=lhm,
                                           output_attentions=output_attentions, defer_residual=defer,
                                           past_key_value=None if past_key_values is None else past_key_values[idx],
-                                          kv_out=None if cache is None else cache.kv[idx])
+                                          kv_out=None if cache is None else cache.kv[idx], key_tiles=key_tiles)
             if self.cross_attention and neighbor_embeds is not None and (idx + 1) % self.neighbor_layer_wise == 0:
                 hidden_states = _materialize(layer_outputs[0])
                 neighbor_idx = (idx + 1) // self.neighbor_layer_wise - 1
@@ -979,8 +1009,9 @@ class MPTForCausalLM(MPTPreTrainedModel):
     def forward(self, input_ids=None, attention_mask=None, head_mask=None, past_key_values=None, inputs_embeds=None,
                 labels=None, neighbor_embeds=None, neighbor_attention_mask=None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, first_key_valid=False, return_logits=None, logits_slice=None,
-                cache_capacity=None):
+                cache_capacity=None, key_tiles=None):
         """return_logits / logits_slice: see lm_head_loss_and_logits (training steps never build the [B, T, V] logits unless asked).
+        key_tiles: see MPTDecoder.forward.
         use_cache / past_key_values=DecodeCache / cache_capacity: see MPTDecoder.forward; a decode step returns [B, 1, V] logits."""
         return_dict = True if return_dict is None else return_dict
         outputs = self.model.decoder(input_ids=input_ids, attention_mask=attention_mask, head_mask=head_mask,
@@ -988,7 +1019,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
                                      neighbor_embeds=neighbor_embeds, neighbor_attention_mask=neighbor_attention_mask,
                                      use_cache=use_cache, output_attentions=output_attentions,
                                      output_hidden_states=output_hidden_states, return_dict=True, first_key_valid=first_key_valid,
-                                     cache_capacity=cache_capacity)
+                                     cache_capacity=cache_capacity, key_tiles=key_tiles)
         hidden = outputs.last_hidden_state
         if isinstance(past_key_values, DecodeCache):
             if labels is not None:
@@ -1237,6 +1268,10 @@ def host_metadata(batch, use_images=True):
     real neighbor text is (the packing of the padding-free encoder), and that every sequence starts with a valid token.
     Passing it as `host_meta=` removes every device->host synchronisation from the training step."""
     meta = {"first_key_valid": bool((batch["attention_mask"][:, 0] != 0).all())}
+    # the 64-key tiles of the decoder's sequences that hold a valid key: the frozen layers project keys and values for those only
+    table, m_live = ops.key_tile_table(batch["attention_mask"])
+    if table is not None:
+        meta["key_tiles"], meta["M_live"] = table, m_live
     npos = batch.get("neighbor_pos_ids")
     ipos = batch.get("neighbor_images_pos_ids") if use_images else None      # context text_only: image slots are not keys
     has_key = None                                     # per sample: a valid neighbor slot in any modality
@@ -1436,9 +1471,12 @@ class CrossAttentionModel(nn.Module):
         `return_logits` / `logits_slice`: see lm_head_loss_and_logits -- a training step does not build the [B, T, V] logits."""
         neighbor_embeds, key_valid = self._neighbor_tokens(neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, text_locations,
                                                            neighbor_images, neighbor_images_pos_ids, image_locations, host_meta)
+        extra = {}
+        if host_meta and host_meta.get("M_live", 0) > 0 and isinstance(self.lm, MPTForCausalLM):
+            extra["key_tiles"] = ops.KeyTiles(host_meta["key_tiles"], host_meta["M_live"], input_ids.device)
         return self.lm(input_ids=input_ids, attention_mask=attention_mask, labels=labels, neighbor_embeds=neighbor_embeds,
                        neighbor_attention_mask=key_valid, first_key_valid=bool(host_meta and host_meta.get("first_key_valid")),
-                       return_logits=return_logits, logits_slice=logits_slice)
+                       return_logits=return_logits, logits_slice=logits_slice, **extra)
 
     def _neighbor_tokens(self, neighbor_input_ids, neighbor_attention_mask, neighbor_pos_ids, text_locations, neighbor_images,
                          neighbor_images_pos_ids, image_locations, host_meta):

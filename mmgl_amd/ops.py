@@ -348,6 +348,129 @@ def selfattn_core_prefix(q, k, v, key_valid, num_heads, prefix_len):
     return _SelfAttn.apply(q, k, v, _key_valid(key_valid), num_heads, int(prefix_len))
 
 
+# ------------------------------------------------------------------------------------------ live key tiles of the frozen layers
+# A padded position is a masked key in every frozen layer: its K and V are never read and its dK, dV are zero.  The flash kernels
+# already skip a 64-key tile without a valid key; here such a tile is not projected either.  The LayerNorm in front of the attention
+# stores the rows of the live tiles a second time, compact (yc); K | V = yc Wkv^T has 64 x (live tiles) rows, the kernels find a
+# tile's rows through a table.  Every element of Q, K and V is the sum the fused [M, 3d] GEMM forms, so the attention output is bitwise
+# the dense path's; dQ | dK | dV keep the dense [B, T, 3d] layout and the fused dgrad, whose one rounding of dQ Wq' + dKV Wkv two
+# GEMMs cannot reproduce.
+KEY_TILE = 64
+
+
+def key_tile_table(attention_mask):
+    """Host side: (table, m_live) of a [B, T] key mask that is still in host memory.  table [B, T // 64] int32: the compact index of
+    a key tile that holds a valid key -- tiles are numbered sample by sample, in key order -- and -1 for a tile of padding;
+    m_live = 64 x the number of live tiles.  (None, 0) when T is no multiple of 64."""
+    am = attention_mask.cpu() != 0
+    B, T = am.shape
+    if T == 0 or T % KEY_TILE:
+        return None, 0
+    live = am.view(B, T // KEY_TILE, KEY_TILE).any(dim=-1).reshape(-1)
+    index = torch.cumsum(live.to(torch.int32), 0, dtype=torch.int32) - 1
+    table = torch.where(live, index, torch.full_like(index, -1)).view(B, T // KEY_TILE).contiguous()
+    return table, KEY_TILE * int(live.sum())
+
+
+class KeyTiles:
+    """key_tile_table's result on the device, for one forward / backward pass: table [B, T // 64] int32, rowmap [B * T] int32 (the
+    compact row of every row of a live tile, -1 elsewhere) and m_live, a host integer -- no synchronisation."""
+    __slots__ = ("table", "rowmap", "m_live")
+
+    def __init__(self, table, m_live, device):
+        self.table = table.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
+        self.m_live = int(m_live)
+        t = self.table.view(-1, 1)
+        rows = t * KEY_TILE + torch.arange(KEY_TILE, dtype=torch.int32, device=self.table.device)
+        self.rowmap = torch.where(t >= 0, rows, torch.full_like(rows, -1)).reshape(-1).contiguous()
+
+    def fits(self, B, T):
+        return self.m_live > 0 and tuple(self.table.shape) == (B, T // KEY_TILE) and T % KEY_TILE == 0
+
+
+def selfattn_tiles_supported(like, num_heads, tiles):
+    """Whether frozen_selfattn_tiles takes activations `like` [B, T, d] with this table: the D = 64 bf16 flash kernels, T a multiple
+    of 64 within their 4096 keys."""
+    B, T, d = like.shape
+    return (tiles is not None and like.is_cuda and like.dtype == torch.bfloat16 and d == 64 * num_heads and T <= 4096
+            and tiles.fits(B, T))
+
+
+def layer_norm_tiles(x, gamma, beta, eps, tiles):
+    """(residual, y, yc): layer_norm_fanout plus the compact copy yc [tiles.m_live, d] of the rows of y in live key tiles.  Without
+    gradients flowing the plain forward kernel runs (no autograd node, no statistics kept)."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _NormPair.apply(x, None, gamma, beta, float(eps), False, 0.0, 0, tiles)
+    yc = x.new_empty(tiles.m_live, x.shape[-1])
+    with torch.no_grad():
+        _, y, _, _, _ = _norm_fwd(False, x, None, gamma, beta, float(eps), compact=(tiles.rowmap, yc))
+    return x, y.view(x.shape), yc
+
+
+def add_layer_norm_tiles(x, res, gamma, beta, eps, tiles, p_drop=0.0, training=False, seed=None):
+    """(s, LayerNorm(s), yc) with s = res + dropout(x): add_layer_norm_pair plus the compact copy (see layer_norm_tiles)."""
+    if x.shape != res.shape:
+        raise ValueError(f"add_layer_norm_tiles: shapes differ {tuple(x.shape)} vs {tuple(res.shape)}")
+    return _NormPair.apply(x, res, gamma, beta, float(eps), False, *_dropout(p_drop, training, seed), tiles)
+
+
+class _FrozenSelfAttnTiles(torch.autograd.Function):
+    """The frozen QKV projection and the causal attention of one layer on live key tiles: Q = y Wq'^T over all rows, K | V = yc Wkv^T
+    over the m_live compact rows (both row blocks of the fused frozen weight w [3d, d] = (q * scaling | k | v), without K splits: the
+    summation order of the fused GEMM), attention through mmgl_selfattn_tiles_*.  Backward: dQ | dK | dV in the dense [B, T, 3d] layout
+    (zeros in the dead tiles) and the fused dgrad of frozen_linear, so the gradient is bitwise the dense path's; yc gets none."""
+
+    @staticmethod
+    def forward(ctx, y, yc, w, b, key_valid, tiles, num_heads):
+        require_cuda(y, yc, key_valid)
+        B, T, d = y.shape
+        m = tiles.m_live
+        y2 = y.contiguous().view(-1, d)
+        q = gemm_nt(y2, w[:d], None if b is None else b[:d], k_splits=False)
+        kv = gemm_nt(yc, w[d:], None if b is None else b[d:], k_splits=False)
+        out = torch.empty(B, T, d, dtype=y.dtype, device=y.device)
+        lse = torch.empty(B, num_heads, T, dtype=torch.float32, device=y.device)
+        es = y.element_size()
+        work = dict(flops=2.0 * B * T * T * d, bytes=(2.0 * B * T * d + 2.0 * m * d) * es)
+        _lib.call("mmgl_selfattn_tiles_fwd", work, ptr(q), ptr(kv), ptr_off(kv, d * es), ptr(key_valid), ptr(tiles.table), ptr(out), ptr(lse),
+                  B, num_heads, T, d // num_heads, m, d, 2 * d, dtype_code(y), stream_ptr())
+        ctx.save_for_backward(q, kv, key_valid, out, lse, w)
+        ctx.tiles, ctx.num_heads = tiles, num_heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, kv, key_valid, out, lse, w = ctx.saved_tensors
+        tiles, H = ctx.tiles, ctx.num_heads
+        B, T, d = out.shape
+        m, es = tiles.m_live, out.element_size()
+        dout = dout.contiguous()
+        dqkv = torch.empty(B, T, 3 * d, dtype=out.dtype, device=out.device)
+        nbytes = lib().mmgl_selfattn_bwd_workspace(B, H, T)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
+        work = dict(flops=5.0 * B * T * T * d, bytes=(6.0 * B * T * d + 2.0 * m * d) * es)
+        _lib.call("mmgl_selfattn_tiles_bwd", work, ptr(dout), ptr(q), ptr(kv), ptr_off(kv, d * es), ptr(out), ptr(lse), ptr(key_valid),
+                  ptr(tiles.table), ptr(dqkv), ptr_off(dqkv, d * es), ptr_off(dqkv, 2 * d * es), ptr(ws), nbytes, B, H, T, d // H, m, d, 2 * d,
+                  3 * d, 3 * d, dtype_code(out), stream_ptr())
+        return frozen_dgrad(dqkv.view(-1, 3 * d), w).view(B, T, d), None, None, None, None, None, None
+
+
+def frozen_selfattn_tiles(y, yc, w, b, key_valid, tiles, num_heads):
+    """Causal self-attention of a frozen layer from its normed input y [B, T, d] and the compact copy yc [tiles.m_live, d] (see
+    layer_norm_tiles): keys and values exist for the live key tiles only.  w [3d, d], b [3d] are the fused frozen projection
+    (q * scaling | k | v); pass the same w object from call to call, as frozen_dgrad caches its transpose per object.  Check
+    selfattn_tiles_supported first."""
+    if not selfattn_tiles_supported(y, num_heads, tiles):
+        raise ValueError(f"frozen_selfattn_tiles: y{tuple(y.shape)} {y.dtype} with {num_heads} heads is not a bf16 head_dim-64 batch "
+                         f"whose [B, T // 64] table and m_live > 0 are given")
+    if w.requires_grad or (b is not None and b.requires_grad) or w.shape != (3 * y.shape[2], y.shape[2]):
+        raise ValueError("frozen_selfattn_tiles: w must be the frozen fused [3d, d] projection")
+    if yc.shape != (tiles.m_live, y.shape[2]):
+        raise ValueError(f"frozen_selfattn_tiles: yc{tuple(yc.shape)} is not [m_live = {tiles.m_live}, d]")
+    _check_mask(key_valid, y.shape[:2])
+    return _FrozenSelfAttnTiles.apply(y, yc, w, b, _key_valid(key_valid), tiles, num_heads)
+
+
 def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
@@ -355,10 +478,11 @@ def _ws(nbytes, device):
 # ------------------------------------------------------------------------------------------ LayerNorm / RMSNorm
 # One forward and one backward route over the kernel family of csrc/rownorm.hip; between them they make every call to the eight
 # mmgl_*norm* entry points.  rms picks RMSNorm (no mean, no beta); tensors are flattened to [rows, cols] here and stay 2-D inside.
-def _norm_fwd(rms, x, res, gamma, beta, eps, p=0.0, seed=0, keep_sum=True, keep_stats=True):
+def _norm_fwd(rms, x, res, gamma, beta, eps, p=0.0, seed=0, keep_sum=True, keep_stats=True, compact=None):
     """y = norm(s) in one launch, with s = x, or s = res + dropout(x) when `res` is given (the mmgl_add_* entry points, which also
     write s unless keep_sum is off).  Returns (s, y, gamma as the kernel read it, mean, rstd); mean / rstd are what the backward
-    needs and are not computed with keep_stats off."""
+    needs and are not computed with keep_stats off.  compact = (rowmap, yc): the LayerNorm entry points that also store the rows
+    of the live key tiles to yc (see KeyTiles)."""
     require_cuda(x, res)
     cols = x.shape[-1]
     x2 = x.contiguous().view(-1, cols)
@@ -368,7 +492,21 @@ def _norm_fwd(rms, x, res, gamma, beta, eps, p=0.0, seed=0, keep_sum=True, keep_
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if keep_stats else None
     g = None if gamma is None else gamma.to(x.dtype).contiguous()
     b = None if beta is None else beta.to(x.dtype).contiguous()
-    if res is None:
+    if compact is not None:
+        rowmap, yc = compact
+        if rms or rowmap.numel() != rows:
+            raise ValueError(f"_norm_fwd: the compact copy is LayerNorm's, with one map entry per row ({rowmap.numel()} for {rows} rows)")
+        work = dict(bytes=((2.0 if res is None else 3.0 + keep_sum) * rows * cols + yc.numel()) * x.element_size())
+        if res is None:
+            s = x2
+            _lib.call("mmgl_layernorm_tiles_fwd", work, ptr(x2), ptr(g), ptr(b), ptr(y), ptr(yc), ptr(rowmap), ptr(mean), ptr(rstd), rows,
+                      cols, yc.shape[0], eps, dtype_code(x), stream_ptr())
+        else:
+            r2 = res.contiguous().view(-1, cols)
+            s = torch.empty_like(x2) if keep_sum else None
+            _lib.call("mmgl_add_layernorm_tiles_fwd", work, ptr(x2), ptr(r2), ptr(g), ptr(b), ptr(s), ptr(y), ptr(yc), ptr(rowmap), ptr(mean),
+                      ptr(rstd), rows, cols, yc.shape[0], eps, p, seed, dtype_code(x), stream_ptr())
+    elif res is None:
         s = x2
         work = dict(bytes=2.0 * rows * cols * x.element_size())
         if rms:
@@ -450,30 +588,38 @@ class _NormPair(torch.autograd.Function):
     add.  res=None is the fan-out of a pre-LN block (reference :316-320 `residual = hidden_states; hidden_states =
     self.self_attn_layer_norm(hidden_states)`, :347-350): s is x itself, returned as an alias of the input, so the gradient of the
     residual stream meets the norm's inside the kernel instead of in autograd's add over [B, T, d] at every fan-out (10 per step at
-    config 3)."""
+    config 3).
+    tiles (a KeyTiles, else None): a third output yc [tiles.m_live, d], the rows of y that lie in a live key tile -- what a frozen layer
+    projects to keys and values (frozen_selfattn_tiles).  It is a copy without a gradient of its own: the fused dgrad of that
+    projection returns everything on y."""
 
     @staticmethod
-    def forward(ctx, x, res, gamma, beta, eps, rms, p, seed):
-        s, y, g, mean, rstd = _norm_fwd(rms, x, res, gamma, beta, eps, p, seed)
+    def forward(ctx, x, res, gamma, beta, eps, rms, p, seed, tiles):
+        yc = None if tiles is None else x.new_empty(tiles.m_live, x.shape[-1])
+        s, y, g, mean, rstd = _norm_fwd(rms, x, res, gamma, beta, eps, p, seed, compact=None if tiles is None else (tiles.rowmap, yc))
         ctx.save_for_backward(s, g, mean, rstd)
         ctx.set_materialize_grads(False)                      # an unused output arrives as None, not as a zero tensor to stream
         _norm_ctx(ctx, rms, x.shape, gamma, beta, p, seed)
         ctx.fanout = res is None
-        return (x if res is None else s.view(x.shape)), y.view(x.shape)      # autograd wraps the returned input as a view
+        outs = (x if res is None else s.view(x.shape)), y.view(x.shape)      # autograd wraps the returned input as a view
+        if tiles is None:
+            return outs
+        ctx.mark_non_differentiable(yc)
+        return outs + (yc,)
 
     @staticmethod
-    def backward(ctx, ds, dy):
+    def backward(ctx, ds, dy, _dyc=None):
         s, g, mean, rstd = ctx.saved_tensors
         rms, shape, pgrad, pdtype, p, seed = ctx.cfg
         if dy is None:                                        # only the residual stream was used downstream
             if ds is None or p == 0.0:
-                return ds, (None if ctx.fanout else ds), None, None, None, None, None, None
+                return ds, (None if ctx.fanout else ds), None, None, None, None, None, None, None
             dy = torch.zeros_like(ds)                         # dropout: the kernel still has to mask ds into the gradient of x
         dres, dx, dg, db = _norm_bwd(rms, True, dy, ds, s, g, mean, rstd, pgrad, pdtype, p, seed)
         dres = dres.view(shape)
         if ctx.fanout:
-            return dres, None, dg, db, None, None, None, None
-        return (dres if dx is None else dx.view(shape)), dres, dg, db, None, None, None, None
+            return dres, None, dg, db, None, None, None, None, None
+        return (dres if dx is None else dx.view(shape)), dres, dg, db, None, None, None, None, None
 
 
 def layer_norm(x, gamma, beta, eps=1e-5):
@@ -484,7 +630,7 @@ def layer_norm(x, gamma, beta, eps=1e-5):
 def layer_norm_fanout(x, gamma, beta, eps=1e-5):
     """(residual, LayerNorm(x)) with residual == x: use BOTH outputs downstream (the residual add and the normed branch) so that
     the two gradients meet inside the LayerNorm backward kernel."""
-    return _NormPair.apply(x, None, gamma, beta, float(eps), False, 0.0, 0)
+    return _NormPair.apply(x, None, gamma, beta, float(eps), False, 0.0, 0, None)
 
 
 def add_layer_norm_pair(x, res, gamma, beta, eps=1e-5, p_drop=0.0, training=False, seed=None):
@@ -493,7 +639,7 @@ def add_layer_norm_pair(x, res, gamma, beta, eps=1e-5, p_drop=0.0, training=Fals
     kernel.  Dropout uses the same counter hash of (seed, element index) as gated_residual."""
     if x.shape != res.shape:
         raise ValueError(f"add_layer_norm_pair: shapes differ {tuple(x.shape)} vs {tuple(res.shape)}")
-    return _NormPair.apply(x, res, gamma, beta, float(eps), False, *_dropout(p_drop, training, seed))
+    return _NormPair.apply(x, res, gamma, beta, float(eps), False, *_dropout(p_drop, training, seed), None)
 
 
 def rms_norm(x, gamma, eps=1e-6):
@@ -504,7 +650,7 @@ def add_rms_norm_pair(x, res, gamma, eps=1e-6):
     """Differentiable (s, RMSNorm(s)) with s = res + x: one forward and one backward kernel for the pair."""
     if x.shape != res.shape:
         raise ValueError(f"add_rms_norm_pair: shapes differ {tuple(x.shape)} vs {tuple(res.shape)}")
-    return _NormPair.apply(x, res, gamma, None, float(eps), True, 0.0, 0)
+    return _NormPair.apply(x, res, gamma, None, float(eps), True, 0.0, 0, None)
 
 
 # ------------------------------------------------------------------------------------------ gated residual
@@ -1036,10 +1182,11 @@ def gemm_dynamic_schedule(enable=True, device=None):
     return c
 
 
-def gemm_nt(x2, w, bias=None, residual=None, zmask=None, act=0, out_scale=1.0, K=None, out=None):
+def gemm_nt(x2, w, bias=None, residual=None, zmask=None, act=0, out_scale=1.0, K=None, out=None, k_splits=True):
     """Raw mmgl_gemm_nt call: act((x2[:, :K] @ w[:, :K]^T + bias) * out_scale) [zeroed where zmask <= 0] [+ residual].
     x2 [M, >=K] and w [N, >=K] are row-major with unit column stride (their row strides are passed as ldx / ldw: K may exceed
-    x2's row length when the matching columns of w are zero padding).  No autograd."""
+    x2's row length when the matching columns of w are zero padding).  k_splits=False brings no K-split scratch: every output element
+    is then one sum over K in tile order, whatever M is (a partial round of tiles is not cut along K).  No autograd."""
     require_cuda(x2, w)
     M, N = x2.shape[0], w.shape[0]
     K = x2.shape[1] if K is None else K
@@ -1051,7 +1198,7 @@ def gemm_nt(x2, w, bias=None, residual=None, zmask=None, act=0, out_scale=1.0, K
     for name, t in (("zmask", zmask), ("residual", residual)):
         if t is not None and (t.stride(1) != 1 or t.stride(0) != y.stride(0)):
             raise ValueError(f"gemm_nt: {name} must share the output's row stride ({t.stride(0)} vs {y.stride(0)})")
-    nws = lib().mmgl_gemm_nt_workspace(M, N, K, x2.stride(0), w.stride(0), y.stride(0), dtype_code(x2))
+    nws = lib().mmgl_gemm_nt_workspace(M, N, K, x2.stride(0), w.stride(0), y.stride(0), dtype_code(x2)) if k_splits else 0
     ws = torch.empty(nws, dtype=torch.uint8, device=x2.device) if nws else None       # K-split partial tiles (few-tile shapes)
     _lib.call("mmgl_gemm_nt", dict(flops=2.0 * M * N * K, bytes=float(M * K + N * K + M * N) * x2.element_size(),
                                    tag=f"{M}x{N}x{K}" + ("+b" if bias is not None else "") + ("+z" if zmask is not None else "")
