@@ -641,6 +641,41 @@ int mmgl_lookup_accept(const void* logits, size_t ld_logits, int m_in, int64_t* 
                        int B, int T, int n_new, int V, int K, int N, int64_t eos_token_id, int64_t pad_token_id, int pos_offset,
                        int pos_max, int dtype, void* stream);
 
+/* The verify step of prompt-lookup decoding on the Llama-family LM (LlamaNeighborLM.generate(prompt_lookup_num_tokens = K)): the cache
+ * holds Hkv <= H heads, and a token's rotary position is its cache column len[b] + i -- per sample, on the device.  Two launches per
+ * layer, in this order; row b*m + i is new token i of sample b, 1 <= m = K + 1 <= 8.  No reference counterpart.  Forward only.
+ *   len         int32 [B], device memory: the columns sample b has filed.  Both kernels clamp it into [0, capacity] and never use it as
+ *               an address unclamped; keeping it there is the caller's contract.
+ *
+ * mmgl_rope_kv_append_block: mmgl_rope_kv_append for the B*m rows of the fused q | k | v projection.
+ *   qkv         [B*m, (H + 2 Hkv) * D], row stride ldqkv: the H query heads of a row are rotated IN PLACE by the angles of position
+ *               p = len[b] + i; the k and v blocks are only read
+ *   cos_sin     fp32 [n_pos, D/2, 2] (cos, sin), dense: the table mmgl_rope_inplace takes, read at row min(p, n_pos - 1)
+ *   kv          the cache rows [B, capacity, 2 Hkv D], row stride ldkv, sample stride batch_stride_kv (elements): the row's rotated Hkv
+ *               key heads and unrotated Hkv value heads go to column p of sample b when p < capacity, else they are dropped (they
+ *               belong to an input whose output the caller discards).  No other byte is written.
+ *   The arithmetic of mmgl_rope_kv_append: m = 1 with every len[b] = col is bitwise that call on column col.
+ *
+ * mmgl_attn_decode_gqa_block_fwd: causal attention of the m new tokens per sample over the cache of Hkv heads, AFTER the append; the
+ *   cache is only read.
+ *   q, out      [B*m, H*D] (q: row stride ldq, the rotated rows of qkv, already scaled by D^-0.5; out dense)
+ *   k, v        the cache slabs: `capacity` rows of Hkv*D per sample, row stride ldkv, sample stride batch_stride_kv (elements)
+ *   key_valid   [B, capacity] uint8, row stride ld_valid
+ *   Row (b, i), query head h, reads key / value head h / (H / Hkv).  With L = len[b] clamped it attends the columns s < L with
+ *   key_valid set, and the new columns L .. min(L + i, capacity - 1), always valid.  A row whose own column L + i is at or past
+ *   `capacity` stays in bounds; its value is unspecified (the caller discards it).
+ *   One workgroup per (sample, key/value head, block of at most 8 (token, query head) pairs of its m * H / Hkv): each 16-byte K / V
+ *   load is issued once for the pairs of the block and nothing is expanded to H heads in memory.  Softmax and accumulation in fp32, one
+ *   rescale per loop trip, partial states merged in a fixed order.
+ * Both: D in {16,32,64,128} and m <= 8 (else MMGL_ERR_UNSUPPORTED); Hkv any divisor of H (else MMGL_ERR_INVALID); strides multiples of
+ * 16 bytes, qkv / q / k / v / kv 16-byte aligned, len 4-byte.  A refused call writes nothing.  No workspace, no atomics, no host
+ * synchronisation; two runs are bitwise equal.  Plain vector stores only. */
+int mmgl_rope_kv_append_block(void* qkv, int ldqkv, const float* cos_sin, int n_pos, void* kv, int ldkv, size_t batch_stride_kv, int capacity,
+                              const int* len, int B, int m, int H, int Hkv, int D, int dtype, void* stream);
+int mmgl_attn_decode_gqa_block_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv, int capacity,
+                                   const uint8_t* key_valid, int ld_valid, const int* len, void* out, int B, int m, int H, int Hkv, int D,
+                                   int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,8 @@ SIGNATURES = {
     "mmgl_logits_process": (I, [P, Z, P, Z, P, Z, I, I, P, I, I, I, F, I, I, P]),
     "mmgl_attn_decode_block_fwd": (I, [P, I, P, P, I, P, P, I, Z, I, P, I, P, P, I, I, I, I, I, P]),
     "mmgl_lookup_accept": (I, [P, Z, I, P, P, P, P, Z, P, Z, P, P, P, P, I, I, I, I, I, I, L, L, I, I, I, P]),
+    "mmgl_rope_kv_append_block": (I, [P, I, P, I, P, I, Z, I, P, I, I, I, I, I, I, P]),
+    "mmgl_attn_decode_gqa_block_fwd": (I, [P, I, P, P, I, Z, I, P, I, P, P, I, I, I, I, I, I, P]),
 }
 
 _lib = None

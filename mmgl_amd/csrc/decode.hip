@@ -985,6 +985,196 @@ int attn_decode_block_nq(const BlockAttnArgs& a, hipStream_t st) {
     return MMGL_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ causal block over a grouped-query cache
+// attn_decode_block_kernel for a cache of Hkv <= H heads whose new columns are filed already (rope_kv_append_block_kernel runs first:
+// this kernel only reads).  The m new tokens of a sample times the G = H / Hkv query heads of a key/value head are m*G (token, head)
+// pairs, p = i*G + g; one workgroup serves one (sample, key/value head) and a block of at most NQ <= 8 consecutive pairs, held in
+// registers as the NQ query heads of attn_decode_gqa_kernel are, so every 16-byte K / V load is issued once for the whole block and
+// nothing is expanded in memory.  Phase 1 walks the L = len[b] columns filed before this step (L clamped into [0, capacity], uniform
+// over the workgroup); phase 2 the new columns L + t, t < m, below the capacity: one per lane group, pair (i, g) folds column t only
+// for t <= i (new columns are always valid).  A pair whose own column L + i is at or past the capacity sees the columns below it: its
+// output is the caller's to discard.  Same state, rescale per trip and merge as the block kernel; surplus pairs (j >= np) repeat pair
+// np - 1 and are not stored.
+template <typename T, int D, int NQ>
+__global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_gqa_block_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ kc,
+                                                                                const T* __restrict__ vc, int ldkv, size_t bs_kv, int capacity,
+                                                                                const uint8_t* __restrict__ valid, int ld_valid,
+                                                                                const int* __restrict__ len, T* __restrict__ out, int W, int H,
+                                                                                int Hkv, int ppb, int nblk) {
+    typedef typename Vec16<T>::type V;
+    constexpr int VEC = 16 / sizeof(T);
+    constexpr int LPK = D / VEC;                    // lanes per key
+    constexpr int KPI = WAVE / LPK;                 // keys per wave and load instruction
+    constexpr float NEG = -FLT_MAX;
+    __shared__ float sm_m[AD_WAVES][NQ], sm_l[AD_WAVES][NQ], sm_o[AD_WAVES][NQ][D];
+
+    const int G = H / Hkv;
+    const int pb = blockIdx.x % nblk, kvh = (blockIdx.x / nblk) % Hkv, b = blockIdx.x / (nblk * Hkv);
+    const int p0 = pb * ppb, np = min(ppb, W * G - p0);                    // pairs p0 .. p0 + np - 1
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane % LPK, kk = lane / LPK;
+    const size_t row0 = (size_t)b * W;
+    const int S = min(max(len[b], 0), capacity);    // the caller's contract; clamped, never trusted as an address
+
+    float qf[NQ][VEC];
+    int tok[NQ];                                    // the pair's token i: wave-uniform
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const int p = p0 + min(j, np - 1);
+        tok[j] = p / G;
+        const V qv = *(const V*)(q + (row0 + tok[j]) * ldq + (kvh * G + p % G) * D + c * VEC);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) qf[j][e] = Elem<T>::to_f(qv[e]);
+    }
+    float m[NQ], l[NQ], acc[NQ][VEC];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        m[j] = NEG;
+        l[j] = 0.f;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[j][e] = 0.f;
+    }
+    // the keys of a trip enter pair j's online softmax together: one rescale of the state per trip
+    auto fold = [&](int j, const auto& kr, const auto& vr, const auto& ok, const auto& in) {
+        constexpr int U = sizeof(ok) / sizeof(bool);
+        float sc[U], mn = m[j];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) dot += qf[j][e] * Elem<T>::to_f(kr[u][e]);
+            dot = group_sum<LPK>(dot);
+            sc[u] = ok[u] ? dot : NEG;
+            if (in[u]) mn = fmaxf(mn, sc[u]);
+        }
+        const float corr = __expf(m[j] - mn);
+        float pu[U], ps = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            pu[u] = in[u] ? __expf(sc[u] - mn) : 0.f;                 // a key the pair does not see weighs nothing
+            ps += pu[u];
+        }
+        l[j] = l[j] * corr + ps;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            float a = acc[j][e] * corr;
+#pragma unroll
+            for (int u = 0; u < U; ++u) a += pu[u] * Elem<T>::to_f(vr[u][e]);
+            acc[j][e] = a;
+        }
+        m[j] = mn;
+    };
+
+    const T* kb = kc + b * bs_kv + kvh * D;
+    const T* vb = vc + b * bs_kv + kvh * D;
+    const uint32_t row_bytes = (uint32_t)(ldkv * sizeof(T));
+    // ---- phase 1: the cache columns below L (branch-free loads: keys past L fall outside the descriptors)
+    if (S > 0) {
+        const uint32_t slab = (uint32_t)(((size_t)(S - 1) * ldkv + D) * sizeof(T));
+        const __amdgpu_buffer_rsrc_t rk = make_rsrc(kb, slab);
+        const __amdgpu_buffer_rsrc_t rv = make_rsrc(vb, slab);
+        const uint8_t* mb = valid + (size_t)b * ld_valid;
+        for (int base = w * KPI; base < S; base += AD_WAVES * KPI * AD_UNROLL) {          // wave-uniform trip count
+            V kr[AD_UNROLL], vr[AD_UNROLL];
+            bool ok[AD_UNROLL], in[AD_UNROLL];
+#pragma unroll
+            for (int u = 0; u < AD_UNROLL; ++u) {
+                const int s = base + u * AD_WAVES * KPI + kk;
+                in[u] = s < S;
+                const uint32_t off = in[u] ? (uint32_t)s * row_bytes + (uint32_t)(c * 16) : OOB;
+                kr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+                vr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+                ok[u] = mb[min(s, S - 1)] != 0;
+            }
+#pragma unroll
+            for (int j = 0; j < NQ; ++j) fold(j, kr, vr, ok, in);
+        }
+    }
+    // ---- phase 2: the new columns L .. L + n_new - 1 (n_new = the tokens filed below the capacity), causal among themselves
+    const int n_new = min(W, capacity - S);
+    if (w * KPI < n_new) {                                                                 // wave-uniform
+        const uint32_t span = (uint32_t)(((size_t)(n_new - 1) * ldkv + D) * sizeof(T));
+        const __amdgpu_buffer_rsrc_t rk = make_rsrc(kb + (size_t)S * ldkv, span);
+        const __amdgpu_buffer_rsrc_t rv = make_rsrc(vb + (size_t)S * ldkv, span);
+        const int t = w * KPI + kk;
+        const bool mine = t < n_new;
+        const uint32_t off = mine ? (uint32_t)t * row_bytes + (uint32_t)(c * 16) : OOB;
+        V kr[1], vr[1];
+        kr[0] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+        vr[0] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+        const bool ok[1] = {true};
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const bool in[1] = {mine && t <= tok[j]};
+            fold(j, kr, vr, ok, in);
+        }
+    }
+    // per pair: merge the lane groups of the wave (fixed butterfly), then the waves in order
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+#pragma unroll
+        for (int o = LPK; o < WAVE; o <<= 1) {
+            const float m2 = __shfl_xor(m[j], o), l2 = __shfl_xor(l[j], o);
+            const float mn = fmaxf(m[j], m2);
+            const float c1 = __expf(m[j] - mn), c2 = __expf(m2 - mn);
+            l[j] = l[j] * c1 + l2 * c2;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[j][e] = acc[j][e] * c1 + __shfl_xor(acc[j][e], o) * c2;
+            m[j] = mn;
+        }
+        if (lane < LPK) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) sm_o[w][j][c * VEC + e] = acc[j][e];
+            if (lane == 0) { sm_m[w][j] = m[j]; sm_l[w][j] = l[j]; }
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < np * D; idx += AD_WAVES * WAVE) {
+        const int j = idx / D, x = idx % D, p = p0 + j;
+        float mm = sm_m[0][j];
+#pragma unroll
+        for (int i = 1; i < AD_WAVES; ++i) mm = fmaxf(mm, sm_m[i][j]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int i = 0; i < AD_WAVES; ++i) {
+            const float ci = __expf(sm_m[i][j] - mm);
+            ll += sm_l[i][j] * ci;
+            o += sm_o[i][j][x] * ci;
+        }
+        out[((row0 + p / G) * H + kvh * G + p % G) * D + x] = Elem<T>::from_f(o / ll);
+    }
+}
+
+struct GqaBlockAttnArgs {
+    AttnPrefix p;                                  // the sample's cache slabs of Hkv heads (S = capacity); q and out have B*W rows
+    const int* len;
+    int W;
+};
+
+template <typename T, int D>
+int attn_decode_gqa_block_nq(const GqaBlockAttnArgs& a, hipStream_t st) {
+    const AttnPrefix& p = a.p;
+    // pairs per block: 8 shares a K / V load among the most pairs, but with 8 states per lane group the loop is ALU-bound and a small
+    // batch leaves most CUs idle.  So the blocks shrink (8 -> 4 -> 2 -> 1) while the grid stays within two workgroups per CU: at
+    // B = 2, Hkv = 8, m = 2 that is 128 workgroups of one pair (17 us) instead of 16 of eight (34 us); at 512 workgroups and more the
+    // blocks of 8 win.  The re-read K / V of a (sample, head) comes from L2.
+    const int P = a.W * (p.H / p.Hkv), room = 2 * mmgl_num_cu();
+    int most = 8;
+    while (most > 1 && (long long)p.B * p.Hkv * cdiv(P, most / 2) <= room) most /= 2;
+    const int nblk = cdiv(P, most), ppb = cdiv(P, nblk);                   // blocks of equal size up to one pair
+    const dim3 grid(p.B * p.Hkv * nblk), block(AD_WAVES * WAVE);
+#define MMGL_GQA_BLOCK_DECODE(NQ)                                                                                                          \
+    hipLaunchKernelGGL((attn_decode_gqa_block_kernel<T, D, NQ>), grid, block, 0, st, (const T*)p.q, p.ldq, (const T*)p.k, (const T*)p.v,   \
+                       p.ldkv, p.bs_kv, p.S, p.valid, p.ld_valid, a.len, (T*)p.out, a.W, p.H, p.Hkv, ppb, nblk)
+    if (ppb == 1) MMGL_GQA_BLOCK_DECODE(1);
+    else if (ppb == 2) MMGL_GQA_BLOCK_DECODE(2);
+    else if (ppb <= 4) MMGL_GQA_BLOCK_DECODE(4);
+    else MMGL_GQA_BLOCK_DECODE(8);
+#undef MMGL_GQA_BLOCK_DECODE
+    MMGL_CHECK_LAUNCH("mmgl_attn_decode_gqa_block_fwd");
+    return MMGL_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ rotary embedding of one new token
 // qkv [B, ldqkv] = [q: H heads | k: Hkv | v: Hkv] x D of the new token; cs [D/2] float2 (cos, sin) of its position.  One thread = VN
 // consecutive i of one (sample, head): the pair (i, i + D/2) of a q head is rotated in place, that of a k head is rotated into the
@@ -1020,6 +1210,45 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(T* __restrict__ qkv
     }
 }
 
+// rope_kv_append_kernel for the rows of a verify step: row b*m + i of qkv is new token i of sample b, at position p = len[b] + i (len
+// clamped into [0, capacity]: never trusted as an address).  Its angles are row min(p, n_pos - 1) of the table cs [n_pos, D/2]; its q
+// heads are rotated in place; its k and v heads go to column p of the sample's cache rows kv [capacity, ldkv] -- or nowhere when p is at
+// or past the capacity.  Same thread layout and arithmetic: m = 1 with equal len is bitwise rope_kv_append_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void rope_kv_append_block_kernel(T* __restrict__ qkv, int ldqkv, const f32x2* __restrict__ cs, int n_pos,
+                                                                   T* __restrict__ kv, int ldkv, size_t bs_kv, int capacity,
+                                                                   const int* __restrict__ len, int rows, int m, int H, int Hkv, int D) {
+    constexpr int VN = 16 / sizeof(T);
+    typedef typename Vec16<T>::type V;
+    const int half = D / 2, per_head = half / VN, heads = H + 2 * Hkv;
+    const int total = rows * heads * per_head;
+    for (int id = blockIdx.x * 256 + threadIdx.x; id < total; id += gridDim.x * 256) {
+        const int r = id / (heads * per_head), rem = id - r * heads * per_head;
+        const int hd = rem / per_head, c = rem - hd * per_head;
+        const int b = r / m;
+        const int p = min(max(len[b], 0), capacity) + (r - b * m);
+        if (hd >= H && p >= capacity) continue;                            // a key / value past the cache: dropped
+        T* src = qkv + (size_t)r * ldqkv + (size_t)hd * D + c * VN;
+        V lo = *(const V*)src, hi = *(const V*)(src + half);
+        if (hd < H + Hkv) {
+            const f32x2* a = cs + (size_t)min(p, n_pos - 1) * half + c * VN;
+            V olo, ohi;
+#pragma unroll
+            for (int e = 0; e < VN; ++e) {
+                const float co = a[e][0], si = a[e][1];
+                const float x0 = (float)lo[e], x1 = (float)hi[e];
+                olo[e] = (T)(x0 * co - x1 * si);
+                ohi[e] = (T)(x1 * co + x0 * si);
+            }
+            lo = olo;
+            hi = ohi;
+        }
+        T* dst = hd < H ? src : kv + b * bs_kv + (size_t)p * ldkv + (size_t)(hd - H) * D + c * VN;
+        *(V*)dst = lo;
+        *(V*)(dst + half) = hi;
+    }
+}
+
 // what the two skinny GEMM entry points refuse alike (their sizes and leading dimensions differ by the adapter's).  ptrs: every
 // required pointer is set; hint: the way out of M > 64 that `who` offers
 int check_skinny(const char* who, const char* hint, bool ptrs, int M, int act, int dtype) {
@@ -1045,6 +1274,24 @@ int check_attn_prefix(const AttnPrefix& a, const char* who, const char* kv = "k 
     if (!aligned16(a.q) || !aligned16(a.k) || !aligned16(a.v)) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: q, %s must be 16-byte aligned", who, kv);
     if (((size_t)(a.S - 1) * a.ldkv + a.D) * (a.dtype == MMGL_BF16 ? 2 : 4) >= (1ull << 31))
         MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: a sample's %s rows span 2 GiB or more (%s=%d, %s=%d)", who, rows, s_name, a.S, ld_name, a.ldkv);
+    return MMGL_OK;
+}
+
+// what the two rotary append entry points refuse alike about the `rows` rows of qkv and the cache they file into, after their own test
+// of the sizes.  kv_name and cs_name are the entry point's words for its cache pointer and its angles in the messages.
+int check_rope_append(const char* who, const char* kv_name, const char* cs_name, const void* qkv, int ldqkv, const void* cs, const void* kv,
+                      size_t bs_kv, int B, int rows, int H, int Hkv, int D, int dtype) {
+    MMGL_CHECK_ARG(H % Hkv == 0, "%s: %d query heads are no multiple of %d key/value heads", who, H, Hkv);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "%s: bad dtype %d", who, dtype);
+    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: head_dim %d (16, 32, 64, 128)", who, D);
+    const int vec = dtype == MMGL_BF16 ? 8 : 4;
+    if (ldqkv % vec || bs_kv % vec) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: strides (%d, %zu) must be multiples of 16 bytes", who, ldqkv, bs_kv);
+    MMGL_CHECK_ARG(qkv && cs && kv, "%s: null pointer", who);
+    MMGL_CHECK_ARG((long long)ldqkv >= (long long)(H + 2 * Hkv) * D && (B == 1 || bs_kv >= (size_t)2 * Hkv * D),
+                   "%s: strides (%d, %zu) smaller than the rows", who, ldqkv, bs_kv);
+    if (!aligned16(qkv) || !aligned16(kv) || ((uintptr_t)cs & 7))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: qkv and %s must be 16-byte aligned, %s 8-byte", who, kv_name, cs_name);
+    MMGL_CHECK_ARG((long long)rows * (H + 2 * Hkv) * (D / 2 / vec) < (1ll << 31), "%s: %d rows of %d heads are too many", who, rows, H + 2 * Hkv);
     return MMGL_OK;
 }
 
@@ -1176,23 +1423,58 @@ extern "C" int mmgl_attn_decode_block_fwd(const void* q, int ldq, const void* k_
     RETURN_BY_HEAD_DIM(attn_decode_block_nq, float, D, a, st);
 }
 
+extern "C" int mmgl_attn_decode_gqa_block_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv, int capacity,
+                                              const uint8_t* key_valid, int ld_valid, const int* len, void* out, int B, int m, int H, int Hkv,
+                                              int D, int dtype, void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && m >= 1 && H >= 1 && Hkv >= 1 && capacity >= 1, "mmgl_attn_decode_gqa_block_fwd: bad sizes B=%d m=%d H=%d Hkv=%d capacity=%d",
+                   B, m, H, Hkv, capacity);
+    if (m > 8) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_gqa_block_fwd: %d new tokens per sample (1..8)", m);
+    MMGL_CHECK_ARG(H % Hkv == 0, "mmgl_attn_decode_gqa_block_fwd: %d query heads are no multiple of %d key/value heads", H, Hkv);
+    const GqaBlockAttnArgs a{{q, k, v, key_valid, out, ldq, ldkv, ld_valid, B, H, Hkv, capacity, D, dtype, batch_stride_kv}, len, m};
+    const int bad = check_attn_prefix(a.p, __func__, "k and v", "cache", "capacity");
+    if (bad) return bad;
+    MMGL_CHECK_ARG(len, "mmgl_attn_decode_gqa_block_fwd: null pointer");
+    if ((uintptr_t)len & 3) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_gqa_block_fwd: len must be 4-byte aligned");
+    MMGL_CHECK_ARG(B == 1 || batch_stride_kv >= (size_t)(capacity - 1) * ldkv + (size_t)Hkv * D,
+                   "mmgl_attn_decode_gqa_block_fwd: batch stride %zu smaller than the rows", batch_stride_kv);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(attn_decode_gqa_block_nq, bf16, D, a, st);
+    RETURN_BY_HEAD_DIM(attn_decode_gqa_block_nq, float, D, a, st);
+}
+
+extern "C" int mmgl_rope_kv_append_block(void* qkv, int ldqkv, const float* cos_sin, int n_pos, void* kv, int ldkv, size_t batch_stride_kv,
+                                         int capacity, const int* len, int B, int m, int H, int Hkv, int D, int dtype, void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && m >= 1 && H >= 1 && Hkv >= 1 && capacity >= 1 && n_pos >= 1,
+                   "mmgl_rope_kv_append_block: bad sizes B=%d m=%d H=%d Hkv=%d capacity=%d n_pos=%d", B, m, H, Hkv, capacity, n_pos);
+    if (m > 8) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_rope_kv_append_block: %d new tokens per sample (1..8)", m);
+    const int bad = check_rope_append(__func__, "kv", "cos_sin", qkv, ldqkv, cos_sin, kv, batch_stride_kv, B, B * m, H, Hkv, D, dtype);
+    if (bad) return bad;
+    MMGL_CHECK_ARG(len, "mmgl_rope_kv_append_block: null pointer");
+    const int vec = dtype == MMGL_BF16 ? 8 : 4;
+    if (ldkv % vec || ((uintptr_t)len & 3))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_rope_kv_append_block: ldkv %d must be a multiple of 16 bytes, len 4-byte aligned", ldkv);
+    MMGL_CHECK_ARG(ldkv >= 2 * Hkv * D && (B == 1 || batch_stride_kv >= (size_t)(capacity - 1) * ldkv + (size_t)2 * Hkv * D),
+                   "mmgl_rope_kv_append_block: strides (%d, %zu) smaller than the rows", ldkv, batch_stride_kv);
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = B * m, total = rows * (H + 2 * Hkv) * (D / 2 / vec);
+    const dim3 grid(min(cdiv(total, 256), 4096)), block(256);
+    if (dtype == MMGL_BF16)
+        hipLaunchKernelGGL(rope_kv_append_block_kernel<bf16>, grid, block, 0, st, (bf16*)qkv, ldqkv, (const f32x2*)cos_sin, n_pos, (bf16*)kv, ldkv,
+                           batch_stride_kv, capacity, len, rows, m, H, Hkv, D);
+    else
+        hipLaunchKernelGGL(rope_kv_append_block_kernel<float>, grid, block, 0, st, (float*)qkv, ldqkv, (const f32x2*)cos_sin, n_pos, (float*)kv, ldkv,
+                           batch_stride_kv, capacity, len, rows, m, H, Hkv, D);
+    MMGL_CHECK_LAUNCH("mmgl_rope_kv_append_block");
+    return MMGL_OK;
+}
+
 extern "C" int mmgl_rope_kv_append(void* qkv, int ldqkv, const float* cos_sin_row, void* kv_col, size_t batch_stride_kv, int B, int H, int Hkv,
                                    int D, int dtype, void* stream) {
     MMGL_CHECK_ARG(B >= 1 && H >= 1 && Hkv >= 1, "mmgl_rope_kv_append: bad sizes B=%d H=%d Hkv=%d", B, H, Hkv);
-    MMGL_CHECK_ARG(H % Hkv == 0, "mmgl_rope_kv_append: %d query heads are no multiple of %d key/value heads", H, Hkv);
-    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_rope_kv_append: bad dtype %d", dtype);
-    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_rope_kv_append: head_dim %d (16, 32, 64, 128)", D);
-    const int vec = dtype == MMGL_BF16 ? 8 : 4;
-    if (ldqkv % vec || batch_stride_kv % vec)
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_rope_kv_append: strides (%d, %zu) must be multiples of 16 bytes", ldqkv, batch_stride_kv);
-    MMGL_CHECK_ARG(qkv && cos_sin_row && kv_col, "mmgl_rope_kv_append: null pointer");
-    MMGL_CHECK_ARG((long long)ldqkv >= (long long)(H + 2 * Hkv) * D && (B == 1 || batch_stride_kv >= (size_t)2 * Hkv * D),
-                   "mmgl_rope_kv_append: strides (%d, %zu) smaller than the rows", ldqkv, batch_stride_kv);
-    if (!aligned16(qkv) || !aligned16(kv_col) || ((uintptr_t)cos_sin_row & 7))
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_rope_kv_append: qkv and kv_col must be 16-byte aligned, cos_sin_row 8-byte");
-    MMGL_CHECK_ARG((long long)B * (H + 2 * Hkv) * (D / 2 / vec) < (1ll << 31), "mmgl_rope_kv_append: B=%d rows of %d heads are too many", B, H + 2 * Hkv);
+    const int bad = check_rope_append(__func__, "kv_col", "cos_sin_row", qkv, ldqkv, cos_sin_row, kv_col, batch_stride_kv, B, B, H, Hkv, D, dtype);
+    if (bad) return bad;
     hipStream_t st = (hipStream_t)stream;
-    const int total = B * (H + 2 * Hkv) * (D / 2 / vec);
+    const int total = B * (H + 2 * Hkv) * (D / 2 / (dtype == MMGL_BF16 ? 8 : 4));
     const dim3 grid(min(cdiv(total, 256), 4096)), block(256);
     if (dtype == MMGL_BF16)
         hipLaunchKernelGGL(rope_kv_append_kernel<bf16>, grid, block, 0, st, (bf16*)qkv, ldqkv, (const f32x2*)cos_sin_row, (bf16*)kv_col, batch_stride_kv, B, H, Hkv, D);

@@ -581,9 +581,10 @@ class LookupState:
                  finished uint8 [B], n_draft int32 [B] drafts in the block
       block      int64 [B, W] = [last token, drafts, filler], positions int64 [B, W] its position ids (clamped to the table)
       scratch    per frozen layer the dense [B*W, 2d] output of the k|v projection; ops.attn_decode_block files it into the cache
+                 (scratch=False: None -- LlamaNeighborLM files the block's keys from its fused q|k|v rows, ops.rope_kv_append_block)
       emitted    int32 [n_new, B]: row c holds the tokens call c of ops.lookup_accept appended (call 0: the prefill's row)"""
 
-    def __init__(self, cache, num_tokens, ngram_size, n_new):
+    def __init__(self, cache, num_tokens, ngram_size, n_new, scratch=True):
         B, _, two_d = cache.kv[0].shape
         dev = cache.mask.device
         self.K, self.N, self.W = int(num_tokens), int(ngram_size), int(num_tokens) + 1
@@ -593,7 +594,7 @@ class LookupState:
         self.n_draft = torch.zeros(B, dtype=torch.int32, device=dev)
         self.block = torch.zeros(B, self.W, dtype=torch.int64, device=dev)
         self.positions = torch.zeros(B, self.W, dtype=torch.int64, device=dev)
-        self.scratch = [torch.empty(B * self.W, two_d, dtype=kv.dtype, device=dev) for kv in cache.kv]
+        self.scratch = [torch.empty(B * self.W, two_d, dtype=kv.dtype, device=dev) for kv in cache.kv] if scratch else None
         self.emitted = torch.zeros(max(int(n_new), 1), B, dtype=torch.int32, device=dev)
         cache.mask[:, cache.col:] = 1                            # once: lookup.len bounds what a sample reads
 

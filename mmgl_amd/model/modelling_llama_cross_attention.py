@@ -13,6 +13,9 @@ Greedy generation (LlamaNeighborLM.generate) keeps a cache of the Hkv key/value 
 each new token on the decode kernels: one skinny GEMM on the fused q|k|v weight, ops.rope_kv_append (q rotated in place, k rotated and
 v copied into the token's cache column), ops.attn_decode with num_kv_heads (one read of a cached key serves its G query heads),
 residual adds in the GEMM epilogues.  The new token's position is its COLUMN, as in forward() and in HF's default position_ids.
+Prompt-lookup decoding (generate(prompt_lookup_num_tokens=K)) verifies K drafted tokens per step: B*(K+1) rows through the same
+GEMMs, ops.rope_kv_append_block (the position of row (b, i) is its column len[b] + i, per sample and on the device) and
+ops.attn_decode_gqa_block (causal over the Hkv-head cache); the loop and the accept kernel are the OPT fork's.
 """
 import torch
 import torch.nn as nn
@@ -20,9 +23,9 @@ import torch.nn.functional as F
 from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from .. import ops
-from .modelling_cross_attention import DecodeCache
-from .generation import GreedyTail, SampledTail, check_prompt, decode_loop
-from .sampling import check_processors, check_sampling, sampling_u
+from .modelling_cross_attention import DecodeCache, LookupState
+from .generation import GreedyTail, SampledTail, check_prompt, decode_loop, lookup_loop
+from .sampling import check_lookup, check_processors, check_sampling, sampling_u
 
 
 class LlamaGatedCrossAttentionLayer(nn.Module):
@@ -61,12 +64,18 @@ class LlamaGatedCrossAttentionLayer(nn.Module):
         m = ops.linear(ops.swiglu(gu), self.down_proj.weight, None)
         return ops.gated_residual(h, m, self.gating2, self.dropout, self.training)
 
-    def decode_step(self, h, k, v, key_valid, w_gu):
+    def decode_step(self, h, k, v, key_valid, w_gu, rows=1):
         """The layer on the one new token of a decode step, h [B, hidden], against the neighbor keys and values projected at the
-        prefill (k, v [B, S, hidden]); w_gu: the [gate | up] weight, concatenated once per generation."""
+        prefill (k, v [B, S, hidden]); w_gu: the [gate | up] weight, concatenated once per generation.
+        rows = W > 1: h [B*W, hidden], the W tokens per sample of a verify step (prompt-lookup decoding) -- the W rows of a sample
+        read its neighbor tokens once (ops.attn_decode_beam without a tail, as MPTAttention.decode_cross): k, v stay at B rows."""
         x = ops.rms_norm(h, self.input_layernorm, self.eps)
         q = ops.decode_linear(x, self.q_proj.weight, None, out_scale=self.head_dim ** -0.5)
-        a = ops.decode_linear(ops.attn_decode(q, k, v, key_valid, self.num_heads), self.o_proj.weight, None)
+        if rows > 1:
+            a = ops.attn_decode_beam(q, k, v, key_valid, self.num_heads, rows)
+        else:
+            a = ops.attn_decode(q, k, v, key_valid, self.num_heads)
+        a = ops.decode_linear(a, self.o_proj.weight, None)
         h = ops.gated_residual(h, a, self.gating1, 0.0, False)
         x = ops.rms_norm(h, self.post_attention_layernorm, self.eps)
         m = ops.decode_linear(ops.swiglu(ops.decode_linear(x, w_gu, None)), self.down_proj.weight, None)
@@ -124,6 +133,22 @@ class _FrozenLlamaLayer:
         x = ops.rms_norm(h, ly.input_layernorm.weight, eps)
         qkv = ops.rope_kv_append(ops.decode_linear(x, w_qkv, None), cos_sin_row, kv[:, col], self.H, self.Hkv)
         a = ops.attn_decode(qkv[:, :nq], kv[:, :col + 1, :nkv], kv[:, :col + 1, nkv:], key_mask[:, :col + 1], self.H, num_kv_heads=self.Hkv)
+        h = ops.decode_linear(a, ly.self_attn.o_proj.weight, None, residual=h)
+        x = ops.rms_norm(h, ly.post_attention_layernorm.weight, eps)
+        return ops.decode_linear(ops.swiglu(ops.decode_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None, residual=h)
+
+    def decode_block(self, h, kv, key_mask, lookup, cos_sin):
+        """decode_step on the B*W rows of a verify step (prompt-lookup decoding), h [B*W, hidden] -> [B*W, hidden]: row b*W + i is
+        new token i of sample b, and its rotary position is its cache column lookup.len[b] + i -- per sample, on the device.  One
+        skinny GEMM per 64 rows on w_qkv; ops.rope_kv_append_block rotates at those positions (cos_sin: the cache's whole table)
+        and files the keys and values at columns lookup.len .. of kv (a column at or past the capacity is dropped);
+        ops.attn_decode_gqa_block then attends causally over the Hkv-head cache.  The launches of decode_step."""
+        ly, eps = self.layer, self.cfg.rms_norm_eps
+        w_qkv, w_gu = self._fused()
+        nq, nkv = self.H * self.D, self.Hkv * self.D
+        x = ops.rms_norm(h, ly.input_layernorm.weight, eps)
+        qkv = ops.rope_kv_append_block(ops.decode_linear(x, w_qkv, None), cos_sin, kv, lookup.len, self.H, self.Hkv, lookup.W)
+        a = ops.attn_decode_gqa_block(qkv[:, :nq], kv[:, :, :nkv], kv[:, :, nkv:], key_mask, lookup.len, self.H, self.Hkv, lookup.W)
         h = ops.decode_linear(a, ly.self_attn.o_proj.weight, None, residual=h)
         x = ops.rms_norm(h, ly.post_attention_layernorm.weight, eps)
         return ops.decode_linear(ops.swiglu(ops.decode_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None, residual=h)
@@ -289,6 +314,28 @@ class LlamaNeighborLM(nn.Module):
             cache.col += 1
         return h
 
+    def _verify_step(self, cache):
+        """A verify step of prompt-lookup decoding: the W = K + 1 tokens cache.lookup.block [B, W] of every sample -- its last token,
+        then the drafts -- causally against the sample's lookup.len cache columns.  The layers run at B*W rows
+        (_FrozenLlamaLayer.decode_block, the gated layers' decode_step with W rows per sample) and file the block's keys and values at
+        columns lookup.len .. lookup.len + W - 1 (below the capacity); which of them count is decided afterwards by
+        ops.lookup_accept, which advances lookup.len.  A token's position is its column, so lookup.positions is not read, and
+        cache.col stands still at the prompt's width.  Returns the final-norm hidden rows [B*W, hidden]."""
+        lookup = cache.lookup
+        if lookup is None or getattr(cache, "cos_sin", None) is None:
+            raise ValueError("a verify step needs a prefilled DecodeCache with a LookupState (cache.lookup)")
+        ops.require_cuda(cache.mask)
+        with torch.no_grad():
+            h = self.llama.get_input_embeddings()(lookup.block.view(-1))
+            k = 0
+            for l, layer in enumerate(self._frozen):
+                h = layer.decode_block(h, cache.kv[l], cache.mask, lookup, cache.cos_sin)
+                if (l + 1) % self.neighbor_layer_wise == 0:
+                    if cache.cross:
+                        h = self.neighbor_layers[k].decode_step(h, *cache.cross[k], cache.cross_valid, cache.cross_gu[k], lookup.W)
+                    k += 1
+            return ops.rms_norm(h, self.llama.model.norm.weight, self.config.rms_norm_eps)
+
     def _last_logits(self, hidden):
         """lm_head on one row per sample, hidden [B, hidden] (any row stride): the [V, hidden] head is read once for the B rows."""
         head = self.llama.lm_head
@@ -303,20 +350,36 @@ class LlamaNeighborLM(nn.Module):
     def generate(self, input_ids, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
                  eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, num_beams=1,
                  num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None,
-                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None):
+                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, **lookup):
         """The contract of MPTForCausalLM.generate for input_ids prompts: one prefill over the right-padded prompts [B, T] -- the
         kernels of forward(), plus the copy of every layer's Hkv key/value heads into a DecodeCache -- then max_new_tokens - 1 decode
         steps; lm_head runs on the last row only.  Every new token is appended at the same column for all samples (its rotary
         position), the pad keys stay masked.  The loop and the semantics of eos_token_id / pad_token_id, do_sample with its knobs,
         the logits processors and return_step_logits are generation.decode_loop's: see that module.  Refused here: num_beams > 1
         (beam search is implemented for the OPT fork only), num_return_sequences > 1 (it needs the beam-shared cache of the OPT
-        fork) and do_sample=True on prompts that are not int64."""
+        fork) and do_sample=True on prompts that are not int64.
+        **lookup takes exactly three keywords, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False (any
+        other name is the TypeError of an unknown keyword).  They are not named parameters: the parameter list above is the greedy
+        and sampled contract, which tests/test_lookup_accept_cpu.py pins by inspecting this signature.
+        prompt_lookup_num_tokens = K (1..7; 0: off, today's loop) with max_matching_ngram_size = N (1..4): prompt-lookup decoding
+        with the keywords, semantics and refusals of MPTForCausalLM.generate -- each step drafts up to K tokens from the row's own
+        text and verifies them in one step of B*(K+1) rows (_verify_step, generation.lookup_loop).  The result is the
+        greedy result in fewer steps.  return_lookup_stats: also the dict of `steps` and `emitted` lookup_loop describes."""
+        who = "LlamaNeighborLM.generate()"
+        prompt_lookup_num_tokens = lookup.pop("prompt_lookup_num_tokens", 0)
+        max_matching_ngram_size = lookup.pop("max_matching_ngram_size", 2)
+        return_lookup_stats = lookup.pop("return_lookup_stats", False)
+        if lookup:
+            raise TypeError(f"{who} got an unexpected keyword argument '{next(iter(lookup))}'")
         if int(num_beams) != 1:
-            raise ValueError(f"LlamaNeighborLM.generate(): num_beams = {num_beams} is not implemented (beam search runs on the OPT fork "
-                             "only); this path is greedy")
-        check_sampling("LlamaNeighborLM.generate()", do_sample, temperature, top_k, top_p, seed, sample_u, 1, num_return_sequences)
-        proc = check_processors("LlamaNeighborLM.generate()", repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens,
-                                eos_token_id, max_new_tokens, self.config.vocab_size, 1, input_ids.dtype)
+            raise ValueError(f"{who}: num_beams = {num_beams} is not implemented (beam search runs on the OPT fork only); this path is greedy")
+        if int(prompt_lookup_num_tokens) != 0:                 # its refusals of do_sample / num_return_sequences come before check_sampling's
+            check_lookup(who, prompt_lookup_num_tokens, max_matching_ngram_size, return_lookup_stats, do_sample, 1, num_return_sequences)
+        check_sampling(who, do_sample, temperature, top_k, top_p, seed, sample_u, 1, num_return_sequences)
+        proc = check_processors(who, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id, max_new_tokens,
+                                self.config.vocab_size, 1, input_ids.dtype)
+        K, N = check_lookup(who, prompt_lookup_num_tokens, max_matching_ngram_size, return_lookup_stats, do_sample, 1, num_return_sequences,
+                            proc is not None, return_step_logits)
         if do_sample and input_ids.dtype != torch.int64:
             raise ValueError(f"generate(do_sample=True): input_ids must be int64, got {input_ids.dtype}")
         B, T, n_new, pad_token_id, attention_mask = check_prompt(input_ids, None, attention_mask, max_new_tokens, eos_token_id,
@@ -331,5 +394,9 @@ class LlamaNeighborLM(nn.Module):
             select = GreedyTail(B, dev, eos_token_id, pad_token_id)
         hidden, cache = self._hidden(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid, True,
                                      T + n_new - 1)
+        if K > 0:
+            cache.lookup = LookupState(cache, K, N, n_new, scratch=False)
+            return lookup_loop(self._last_logits, lambda: self._verify_step(cache), hidden[:, -1], cache.lookup, input_ids, attention_mask,
+                               n_new, eos_token_id, pad_token_id, 0, self.config.max_position_embeddings - 1, return_lookup_stats)
         return decode_loop(self._last_logits, lambda tok: self._decode_step(tok, cache), hidden[:, -1], select, n_new, input_ids,
                            attention_mask, proc=proc, return_step_logits=return_step_logits)

@@ -1841,6 +1841,74 @@ def attn_decode_block(q, k_new, v_new, k, v, key_valid, lens, num_heads, m, out=
     return out
 
 
+def _block_heads(op, num_heads, num_kv_heads, m):
+    H, Hkv, m = int(num_heads), int(num_kv_heads), int(m)
+    if H < 1 or Hkv < 1 or H % Hkv:
+        raise ValueError(f"{op}: num_heads = {H} must be a multiple of num_kv_heads = {Hkv}")
+    if not 1 <= m <= MAX_LOOKUP_TOKENS + 1:
+        raise ValueError(f"{op}: m = {m} new tokens per sample (1..{MAX_LOOKUP_TOKENS + 1})")
+    return H, Hkv, m
+
+
+def rope_kv_append_block(qkv, cos_sin, kv, lens, num_heads, num_kv_heads, m):
+    """rope_kv_append for the B*m rows of a verify step (prompt-lookup decoding on a grouped-query cache); row b*m + i of qkv
+    [B*m, (H + 2*Hkv)*D] (unit column stride) is new token i of sample b, at position p = lens[b] + i -- per sample, on the device.
+      cos_sin fp32 [n_pos, D/2, 2], contiguous: the table rope_qk_ takes, read at row min(p, n_pos - 1);
+      kv [B, capacity, 2*Hkv*D]: the layer's cache rows, a view with unit column stride; lens int32 [B] on the device,
+      0 <= lens[b] <= capacity: the caller's contract (the kernel clamps, nothing is checked on the device).
+    Rotates the H query heads of every row in place and writes its rotated Hkv key heads and unrotated Hkv value heads to column p of
+    kv[b] -- nowhere when p >= capacity; the k and v blocks of qkv stay as they were.  One launch; m = 1 with equal lens is bitwise
+    rope_kv_append.  Returns qkv.  A refused call leaves qkv and kv untouched.  Forward only; GPU only."""
+    op = "rope_kv_append_block"
+    require_cuda(qkv, cos_sin, kv, lens)
+    _no_grad_inputs(op, qkv, kv)
+    H, Hkv, m = _block_heads(op, num_heads, num_kv_heads, m)
+    if qkv.dim() != 2 or qkv.shape[0] % m or qkv.shape[1] % (H + 2 * Hkv) or qkv.stride(1) != 1:
+        raise ValueError(f"{op}: qkv{tuple(qkv.shape)}/{qkv.stride()} is not [B*m, (H+2*Hkv)*D] for H={H}, Hkv={Hkv}, m={m}")
+    B, D = qkv.shape[0] // m, qkv.shape[1] // (H + 2 * Hkv)
+    if (kv.dim() != 3 or kv.shape[0] != B or kv.shape[1] < 1 or kv.shape[2] != 2 * Hkv * D or kv.stride(2) != 1 or kv.dtype != qkv.dtype
+            or kv.device != qkv.device):
+        raise ValueError(f"{op}: kv{tuple(kv.shape)}/{kv.stride()} {kv.dtype} must be a [{B}, capacity, {2 * Hkv * D}] {qkv.dtype} view with "
+                         "unit column stride")
+    if (cos_sin.dtype != torch.float32 or cos_sin.dim() != 3 or cos_sin.shape[0] < 1 or tuple(cos_sin.shape[1:]) != (D // 2, 2)
+            or not cos_sin.is_contiguous() or cos_sin.device != qkv.device):
+        raise ValueError(f"{op}: cos_sin must be contiguous fp32 [n_pos, D/2={D // 2}, 2] on {qkv.device}, got {cos_sin.dtype} "
+                         f"{tuple(cos_sin.shape)}")
+    _state_vector(op, "lens", lens, B, torch.int32, qkv.device)
+    if B == 0:
+        return qkv
+    _lib.call("mmgl_rope_kv_append_block", dict(bytes=float(2 * H + 4 * Hkv) * B * m * D * qkv.element_size()), ptr(qkv), qkv.stride(0),
+              ptr(cos_sin), cos_sin.shape[0], ptr(kv), kv.stride(1), kv.stride(0), kv.shape[1], ptr(lens), B, m, H, Hkv, D, dtype_code(qkv),
+              stream_ptr())
+    return qkv
+
+
+def attn_decode_gqa_block(q, k, v, key_valid, lens, num_heads, num_kv_heads, m, out=None):
+    """Causal attention of m <= 8 new tokens per sample over a grouped-query cache that holds them already (rope_kv_append_block
+    runs first; this call only reads); row b*m + i is new token i of sample b.
+      q [B*m, d] already scaled (the rotated query columns of the qkv rows); k, v [B, capacity, Hkv*D] with D = d / H: the column
+      slabs of the cache rows [B, capacity, 2*Hkv*D], unit column stride and common strides; key_valid [B, capacity] bool/uint8;
+      lens int32 [B] on the device, 0 <= lens[b] <= capacity: the caller's contract (the kernel clamps).
+    Row (b, i), query head h, reads key / value head h // (H / Hkv): the valid cache columns below lens[b] and the new columns
+    lens[b] .. lens[b] + i below the capacity (always valid).  Nothing is expanded to H heads.  A row whose own column is at or past
+    the capacity gets an unspecified value.  Returns [B*m, d] (`out`, a dense tensor of q's dtype, when given: a refused call leaves
+    it as it was).  Forward only; GPU only."""
+    op = "attn_decode_gqa_block"
+    require_cuda(q, k, v, key_valid, lens)
+    _no_grad_inputs(op, q, k, v)
+    H, Hkv, m = _block_heads(op, num_heads, num_kv_heads, m)
+    kd = q.shape[-1] if q.shape[-1] % H else q.shape[-1] // H * Hkv                  # columns of a key row
+    B, S, d, key_valid, out = _decode_attn_operands(op, q, k, v, key_valid, H, out, q_rows=m, key_cols=kd,
+                                                    names=("k", "v", "cache columns"), tail=f" for H={H}, Hkv={Hkv}, {m} new tokens per sample")
+    _state_vector(op, "lens", lens, B, torch.int32, q.device)
+    if k.device != q.device or key_valid.device != q.device:
+        raise ValueError(f"{op}: the operands are on different devices")
+    _lib.call("mmgl_attn_decode_gqa_block_fwd", dict(bytes=2.0 * B * (S + m) * kd * q.element_size()), ptr(q), q.stride(0), ptr(k), ptr(v),
+              k.stride(1), k.stride(0), S, ptr(key_valid), key_valid.stride(0), ptr(lens), ptr(out), B, m, H, Hkv, d // H, dtype_code(q),
+              stream_ptr())
+    return out
+
+
 def lookup_accept(logits, m_in, block, n_draft, positions, ids, prompt_mask, gen, lens, finished, emitted, n_new, ngram_size,
                   eos_token_id=None, pad_token_id=None, pos_offset=0, pos_max=None):
     """The tail of a prompt-lookup verify step for B samples, one launch, everything in place (mmgl_lookup_accept in
