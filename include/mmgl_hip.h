@@ -676,6 +676,44 @@ int mmgl_attn_decode_gqa_block_fwd(const void* q, int ldq, const void* k, const 
                                    const uint8_t* key_valid, int ld_valid, const int* len, void* out, int B, int m, int H, int Hkv, int D,
                                    int dtype, void* stream);
 
+/* ---- contrastive search (generate(penalty_alpha = alpha > 0, top_k = k), 2 <= k <= 8; csrc/contrastive.hip) -------------------------
+ * replaces: transformers' _contrastive_search (penalty_alpha + top_k), which repeats the key/value cache k times and ranks with a
+ *           [B*k, n, d] similarity through aten.  Here the k candidates of a sample run one decode step on the beam-shared cache
+ *           (mmgl_attn_decode_beam_fwd) and this call ranks them.  Forward only; deterministic (no atomics).
+ *
+ * mmgl_contrastive_select: per sample b the candidate c in [0, k) with the largest
+ *     score_c = (1 - alpha) p_c - alpha pen_c,   p_c = exp(cand_score[b][c]),   pen_c = max_j cos(h_c, h_j)
+ * in fp32, and the bookkeeping of the step.  Row b*k + c of cand_hidden is h_c; j runs over the context rows [0, n_ctx) of sample b
+ * with ctx_valid set.  Dot products and squared norms are accumulated in fp32; the cosine is 0 when either vector has norm 0;
+ * pen_c = 0 when no context row is live.  The lowest c among the maxima is selected; a NaN score is never selected (all NaN: c = 0).
+ *   cand_hidden [B*k, d], row stride ld_cand                      read
+ *   ctx         [B, n_cap, d], row stride ld_ctx, sample stride batch_stride_ctx (elements): rows [0, n_ctx) are read where
+ *               ctx_valid is set -- no other row is loaded -- and row n_ctx is written: a copy of the selected candidate row
+ *   ctx_valid   uint8 [B, n_cap], row stride ld_valid: entries [0, n_ctx) read, entry n_ctx set to 1
+ *   cand_score, cand_index   fp32 / int32 rows of stride ld_pair, the pair mmgl_beam_topk writes (rows_in = 1, beam_score = 0): the
+ *               first k entries of a row are the candidates' log-probabilities and token ids
+ *   src         int32 [B*k, ld_src]: column `step` of the sample's k rows := the selected c (the parent table of
+ *               mmgl_attn_decode_beam_fwd: tail column `step` of every row of the sample now names the chosen key)
+ *   ids         int64, row stride ld_ids: ids[b * ld_ids] := the selected token, or pad_token_id if finished[b] was set
+ *   finished    uint8 [B]: set when the row's token is eos_token_id; eos_token_id < 0: no end-of-sequence handling, may be null
+ *   hidden_out  dense [B, d]: the selected candidate row;  selected  int32 [B]: the selected c
+ *   trace_p, trace_pen, trace_score   fp32 [B, k], dense, all three or none: p, pen and score as computed
+ *   workspace   mmgl_contrastive_workspace(B, k, n_cap) bytes, 4-byte aligned: one partial max per (sample, chunk, candidate)
+ * Two launches: one workgroup per (sample, chunk of mmgl_contrastive_chunk() context rows) streams the context once with 16-byte
+ * loads against the k candidate rows held in LDS and writes the chunk's partial maxima (starting at -inf); one workgroup per sample
+ * folds them in chunk order and does the rest.  n_ctx = 0 skips the first launch.
+ * Refused: null pointers, k outside 2..8 (MMGL_ERR_UNSUPPORTED above 8 and below 2), d no multiple of the 16-byte vector, strides
+ * smaller than the rows or no multiples of 16 bytes, misaligned pointers, n_ctx outside [0, n_cap - 1], alpha outside [0, 1], k d
+ * elements beyond 64 KiB of LDS, a bad dtype.  A refused call writes nothing.  No atomics, no host synchronisation; two runs are
+ * bitwise equal.  Plain vector stores only. */
+int mmgl_contrastive_chunk(void);
+size_t mmgl_contrastive_workspace(int B, int k, int n_cap);
+int mmgl_contrastive_select(const void* cand_hidden, size_t ld_cand, void* ctx, size_t ld_ctx, size_t batch_stride_ctx, uint8_t* ctx_valid,
+                            size_t ld_valid, int n_cap, const float* cand_score, const int* cand_index, size_t ld_pair, float alpha, int n_ctx,
+                            int step, int* src, size_t ld_src, int64_t* ids, size_t ld_ids, uint8_t* finished, int64_t eos_token_id,
+                            int64_t pad_token_id, void* hidden_out, int* selected, float* trace_p, float* trace_pen, float* trace_score,
+                            void* workspace, size_t workspace_bytes, int B, int k, int d, int V, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,9 @@ SIGNATURES = {
     "mmgl_lookup_accept": (I, [P, Z, I, P, P, P, P, Z, P, Z, P, P, P, P, I, I, I, I, I, I, L, L, I, I, I, P]),
     "mmgl_rope_kv_append_block": (I, [P, I, P, I, P, I, Z, I, P, I, I, I, I, I, I, P]),
     "mmgl_attn_decode_gqa_block_fwd": (I, [P, I, P, P, I, Z, I, P, I, P, P, I, I, I, I, I, I, P]),
+    "mmgl_contrastive_chunk": (I, []),
+    "mmgl_contrastive_workspace": (Z, [I, I, I]),
+    "mmgl_contrastive_select": (I, [P, Z, P, Z, Z, P, Z, I, P, P, Z, F, I, I, P, Z, P, Z, P, L, L, P, P, P, P, P, P, Z, I, I, I, I, I, P]),
 }
 
 _lib = None

@@ -456,22 +456,6 @@ int launch_attn_decode(const AttnPrefix& a, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------ grouped-query single-query attention
-// sum over the N = 2^n lanes of a lane group (aligned to N), returned in every lane of the group.  Up to 16 lanes the exchange is DPP --
-// quad permutes, then the mirror of a half row and of a row, which pair the two halves once each half holds its sum -- so a dot
-// product costs VALU adds instead of LDS-routed permutes; wider groups finish with the wave shuffle.  A fixed order: deterministic.
-template <int CTRL> __device__ __forceinline__ float dpp_read(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-template <int N> __device__ __forceinline__ float group_sum(float v) {
-    if constexpr (N >= 2) v += dpp_read<0xB1>(v);          // quad_perm [1, 0, 3, 2]
-    if constexpr (N >= 4) v += dpp_read<0x4E>(v);          // quad_perm [2, 3, 0, 1]
-    if constexpr (N >= 8) v += dpp_read<0x141>(v);         // row_half_mirror
-    if constexpr (N >= 16) v += dpp_read<0x140>(v);        // row_mirror
-#pragma unroll
-    for (int o = 16; o < N; o <<= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // One workgroup per (sample, key/value head, block of NQ <= 8 query heads of that head's group): the key and value registers of
 // attn_decode_kernel (same lane layout, same trip constants) feed NQ online-softmax states per lane group, so every 16-byte K / V load
 // is issued once for the whole block and nothing is expanded in memory.  A block with fewer than NQ heads (nq < NQ) computes its last

@@ -81,4 +81,5 @@ int mmgl_num_cu() {
 // mmgl_selfattn_tiles_fwd / _bwd and mmgl_layernorm_tiles_fwd / mmgl_add_layernorm_tiles_fwd (keys and values of the live key
 // tiles only in the frozen layers) were added at 110 the same way.
 // mmgl_rope_kv_append_block / mmgl_attn_decode_gqa_block_fwd (prompt-lookup decoding on the Llama-family LM) were added at 110 the same way.
+// mmgl_contrastive_chunk / mmgl_contrastive_workspace / mmgl_contrastive_select (contrastive search for generate()) were added at 110 the same way.
 extern "C" int mmgl_version(void) { return 110; }

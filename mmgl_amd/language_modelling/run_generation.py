@@ -41,7 +41,8 @@ def _f(default, help_):
 class Arguments:
     """Same field names and defaults as the reference's Arguments (:66-229) + `neighbor_layer_wise` + `num_beams` + the sampling knobs
     `do_sample` / `temperature` / `top_k` / `top_p` + the logits processors `repetition_penalty` / `no_repeat_ngram_size` /
-    `min_new_tokens` + prompt-lookup decoding's `prompt_lookup_num_tokens` / `max_matching_ngram_size`."""
+    `min_new_tokens` + prompt-lookup decoding's `prompt_lookup_num_tokens` / `max_matching_ngram_size` + contrastive search's
+    `penalty_alpha` (with `top_k` as its k)."""
     overwrite_cache: Optional[bool] = _f(False, "Overwrite the cached preprocessed datasets or not.")
     dataset: Optional[str] = _f("wikiweb2m", "The name of the dataset to use.")
     task: Optional[str] = _f("section", "One of three generation tasks in WikiWeb2M")
@@ -101,8 +102,10 @@ class Arguments:
                            "cross-attention wrapper)")
     do_sample: bool = _f(False, "sample in the test protocol's generate() instead of greedy decoding (seeded with `seed`)")
     temperature: float = _f(1.0, "sampling temperature (do_sample)")
-    top_k: int = _f(0, "keep the k most likely tokens (do_sample); 0 = off")
+    top_k: int = _f(0, "keep the k most likely tokens (do_sample); with penalty_alpha: the candidates ranked per step (2..8); 0 = off")
     top_p: float = _f(1.0, "nucleus sampling: the smallest set of tokens with this probability mass (do_sample); 1 = off")
+    penalty_alpha: float = _f(0.0, "contrastive search in the test protocol's generate(): the weight of the degeneration penalty, in "
+                                   "(0, 1), with top_k candidates per step (OPT fork, plain projections; not with do_sample); 0 = off")
     repetition_penalty: float = _f(1.0, "repetition penalty of the test protocol's generate(); 1 = off")
     no_repeat_ngram_size: int = _f(0, "no n-gram of this size occurs twice in the test protocol's generations; 0 = off")
     min_new_tokens: int = _f(0, "the end-of-sequence token is banned for this many new tokens in the test protocol's generate()")
@@ -643,9 +646,11 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                     fields["no_repeat_ngram_size"] = int(args.no_repeat_ngram_size)
                 if int(getattr(args, "min_new_tokens", 0)) != 0:
                     fields["min_new_tokens"] = int(args.min_new_tokens)
+                if float(getattr(args, "penalty_alpha", 0.0)) > 0 and "do_sample" not in fields and "penalty_alpha" in named:
+                    fields.update(penalty_alpha=float(args.penalty_alpha), top_k=int(args.top_k))   # contrastive search: top_k is its k
                 if (int(getattr(args, "prompt_lookup_num_tokens", 0)) > 0 and "prompt_lookup_num_tokens" in named
                         and _plain_projections(model)) and not (
-                        {"num_beams", "do_sample", "repetition_penalty", "no_repeat_ngram_size", "min_new_tokens"} & set(fields)):
+                        {"num_beams", "do_sample", "repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "penalty_alpha"} & set(fields)):
                     fields.update(prompt_lookup_num_tokens=int(args.prompt_lookup_num_tokens),      # greedy runs only: the same ids
                                   max_matching_ngram_size=int(getattr(args, "max_matching_ngram_size", 2)))
                 generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),

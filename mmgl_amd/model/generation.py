@@ -2,8 +2,9 @@
 LlamaNeighborLM): the prompt check, the two selection tails and the loop "logits -> (processors) -> (keep the step's logits) ->
 select -> write the ids column -> one cached decode step".  A model's generate() validates its keywords (sampling.py), checks the
 prompt (check_prompt), picks a tail, runs its prefill and hands decode_loop three things: its _last_logits, a callable for one cached
-decode step (tokens [rows, 1] -> hidden [rows, d]) and the prefill's last hidden row.  Beam search (MPTForCausalLM._generate_beam) and
-prompt-lookup decoding (lookup_loop, below) have loops of another shape and share only check_prompt.
+decode step (tokens [rows, 1] -> hidden [rows, d]) and the prefill's last hidden row.  Beam search (MPTForCausalLM._generate_beam),
+prompt-lookup decoding (lookup_loop, below) and contrastive search (contrastive_loop, below) have loops of another shape; they share
+check_prompt, and contrastive search the processors' binding.
 
 Semantics, the same for every model:
   * Prompts are right-padded to the common width T; every new token is appended at the same column for all rows, and all
@@ -170,3 +171,54 @@ def lookup_loop(last_logits, verify, hidden, lookup, input_ids, prompt_mask, n_n
         steps += 1
     ids = ids.to(input_ids.dtype)
     return (ids, dict(steps=steps, emitted=lookup.emitted[:steps + 1].clone())) if return_stats else ids
+
+
+def contrastive_loop(last_logits, step, prompt_hidden, src, input_ids, prompt_mask, n_new, k, penalty_alpha, vocab_size, eos_token_id=None,
+                     pad_token_id=None, proc=None, return_step_logits=False, return_trace=False):
+    """Contrastive search (Su et al. 2022) behind a prefill whose last_hidden_state is prompt_hidden [B, T, d]: every
+    step ranks the k most likely next tokens by  (1 - alpha) p(token) - alpha max_j cos(h_token, h_j)  over the hidden rows h_j of the
+    row so far, and takes the best.  Deterministic; [B, T + n_new] in the prompt's dtype, EOS followed by pad_token_id as GreedyTail.
+    step(tokens [B*k, 1]) -> hidden [B*k, d]: one decode step of the k candidates of every sample on the beam-shared cache, whose
+    parent table is `src` (BeamBook.src, the identity at first); last_logits as in decode_loop.
+    The context buffer [B, T + n_new, d] starts as the prompt's hidden rows, its mask as the prompt's: a masked prompt column is no
+    context (transformers ranks against it too; here it is the processors' rule, the row without its pad columns).  Step s:
+    last_logits of the last chosen token's hidden row (the prefill's last row at s = 0) -> the processors -> ops.beam_topk (the k
+    candidates and their log-probabilities) -> `step` on the B*k candidate tokens -> ops.contrastive_select, which picks, writes the
+    ids column, the EOS flags, column s of `src` (tail column s of every row of the sample now names the chosen key), context row
+    T + s and the dense [B, d] input of the next last_logits.  All n_new candidate steps run -- the last token's candidates must be
+    forwarded to be ranked -- so T + n_new positions are needed; nothing synchronises with the host.
+    Returns ids, then as asked the step logits [B, n_new, V] and the trace: per step a dict of candidates int32 [B, k], p / penalty /
+    score fp32 [B, k] and selected int32 [B]."""
+    B, T = input_ids.shape
+    dev, d = input_ids.device, prompt_hidden.shape[-1]
+    ids = torch.empty(B, T + n_new, dtype=torch.int64, device=dev)
+    ids[:, :T] = input_ids
+    ctx = torch.empty(B, T + n_new, d, dtype=prompt_hidden.dtype, device=dev)
+    ctx[:, :T] = prompt_hidden
+    valid = torch.zeros(B, T + n_new, dtype=torch.uint8, device=dev)
+    valid[:, :T] = prompt_mask != 0
+    finished = torch.zeros(B, dtype=torch.uint8, device=dev) if eos_token_id is not None else None
+    start = torch.zeros(B, dtype=torch.float32, device=dev)
+    if proc is not None:
+        _bind_processors(proc, ids, prompt_mask, None, None)
+    hidden = prompt_hidden[:, -1]
+    steps, trace = [], []
+    for s in range(n_new):
+        logits = last_logits(hidden)
+        if proc is not None:
+            proc(logits, ids[:, :T + s], s)
+        if return_step_logits:
+            steps.append(logits)
+        cs, ci = ops.beam_topk(logits, start, k, rows_in=1)
+        cand = ci[:, :k].reshape(B * k, 1)
+        res = ops.contrastive_select(step(cand), ctx, valid, cs, ci, penalty_alpha, T + s, s, src, ids[:, T + s], vocab_size, finished,
+                                     eos_token_id, pad_token_id, trace=return_trace)
+        hidden = res[0]
+        if return_trace:
+            trace.append(dict(candidates=cand.view(B, k), p=res[2][0], penalty=res[2][1], score=res[2][2], selected=res[1]))
+    out = (ids.to(input_ids.dtype),)
+    if return_step_logits:
+        out += (torch.stack(steps, dim=1),)
+    if return_trace:
+        out += (trace,)
+    return out[0] if len(out) == 1 else out

@@ -38,8 +38,8 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 
 from .. import ops
 from .encoders import ClipTextEncoder, PackedTextEncoder, PackedVisionEncoder
-from .generation import GreedyTail, SampledTail, check_prompt, decode_loop, lookup_loop
-from .sampling import check_lookup, check_processors, check_sampling, sampling_u
+from .generation import GreedyTail, SampledTail, check_prompt, contrastive_loop, decode_loop, lookup_loop
+from .sampling import check_contrastive, check_lookup, check_processors, check_sampling, sampling_u
 
 CROSS_MODES = ("cross_attention", "embedding")
 
@@ -1059,7 +1059,8 @@ class MPTForCausalLM(MPTPreTrainedModel):
                  num_beams=1, length_penalty=1.0, early_stopping=False, return_sequences_scores=False, return_beam_trace=False,
                  num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, history_ids=None,
-                 history_mask=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False):
+                 history_mask=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False, penalty_alpha=0.0,
+                 return_contrastive_trace=False):
         """Generation with a key/value cache: what the reference's test protocol asks of its wrappers
         (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of every
         layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
@@ -1077,7 +1078,17 @@ class MPTForCausalLM(MPTPreTrainedModel):
         Each step drafts up to K tokens -- what followed the latest earlier occurrence of the row's last N (or fewer) tokens -- and
         verifies them in one step of B*(K+1) rows (generation.lookup_loop).  The result is the greedy result; only the
         number of steps changes.  Greedy, input_ids prompts and plain projections only.  return_lookup_stats: also a dict of `steps`
-        (verify steps run) and `emitted` (int32 [steps + 1, B]: tokens appended per call and row, call 0 the prefill's)."""
+        (verify steps run) and `emitted` (int32 [steps + 1, B]: tokens appended per call and row, call 0 the prefill's).
+        penalty_alpha in (0, 1) with top_k = k (2..8): contrastive search (generation.contrastive_loop) -- each step
+        forwards the k most likely tokens of every sample in one step of B*k rows on the beam-shared cache (one prefill of B rows, a
+        cache of capacity T, a [B*k, max_new_tokens, 2d] tail per layer) and ops.contrastive_select keeps the one that scores best
+        against the hidden rows of the row so far.  top_k is then no sampling knob.  input_ids prompts and plain projections only;
+        T + max_new_tokens positions are needed, one more than greedy.  The processors and return_step_logits combine with it;
+        return_contrastive_trace: also the per-step candidates / p / penalty / score [B, k] and selected [B]."""
+        kc = check_contrastive("generate()", penalty_alpha, top_k, return_contrastive_trace, do_sample, num_beams, num_return_sequences,
+                               prompt_lookup_num_tokens, inputs_embeds, return_beam_trace, return_sequences_scores)
+        if kc:
+            top_k = 0                                          # contrastive search's k, not check_sampling's
         W = int(num_beams)
         if W < 1:
             raise ValueError(f"generate(): num_beams = {num_beams} must be positive")
@@ -1093,7 +1104,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
             raise ValueError("generate(): history_ids / history_mask belong to inputs_embeds prompts; input_ids are their own history")
         K, N = check_lookup("generate()", prompt_lookup_num_tokens, max_matching_ngram_size, return_lookup_stats, do_sample, W,
                             num_return_sequences, proc is not None, return_step_logits, inputs_embeds)
-        if K > 0:                                              # with the other refusals, before any work: a verify step has no adapter path
+        if K > 0 or kc:                                        # with the other refusals, before any work: these steps have no adapter path
             _plain(self.lm_head, *(m for layer in list(self.model.decoder.layers) + list(self.model.decoder.neighbor_layers)
                                    for m in (layer.self_attn.q_proj, layer.self_attn.k_proj, layer.self_attn.v_proj,
                                              layer.self_attn.out_proj, layer.fc1, layer.fc2)))
@@ -1113,6 +1124,9 @@ class MPTForCausalLM(MPTPreTrainedModel):
         B, T, n_new, pad_token_id, attention_mask = check_prompt(input_ids, inputs_embeds, attention_mask, max_new_tokens, eos_token_id,
                                                                  pad_token_id, self.config, dec.max_target_positions)
         dev = (input_ids if input_ids is not None else inputs_embeds).device
+        if kc and T + n_new > dec.max_target_positions:        # every new token's candidates are forwarded, the last one's too
+            raise ValueError(f"generate(): {T} prompt columns + {n_new} new tokens of contrastive search exceed max_position_embeddings "
+                             f"{dec.max_target_positions}")
         if proc is not None:
             proc.upload(dev)                                   # in front of the prefill: see LogitsProcessors
         if do_sample:
@@ -1122,8 +1136,14 @@ class MPTForCausalLM(MPTPreTrainedModel):
             select = GreedyTail(B, dev, eos_token_id, pad_token_id)
         out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
-                  cache_capacity=T if R > 1 else T + n_new - 1)
+                  cache_capacity=T if R > 1 or kc else T + n_new - 1)
         cache = out.past_key_values
+        if kc:
+            cache.beam = BeamState(cache, kc, n_new)           # beam_advance is never called: book.src is the table the select call writes
+            return contrastive_loop(self._last_logits, lambda tok: dec(input_ids=tok, past_key_values=cache).last_hidden_state[:, 0],
+                                    out.last_hidden_state, cache.beam.book.src, input_ids, attention_mask, n_new, kc, float(penalty_alpha),
+                                    self.lm_head.weight.shape[0], eos_token_id, pad_token_id, proc, return_step_logits,
+                                    return_contrastive_trace)
         if K > 0:
             cache.lookup = LookupState(cache, K, N, n_new)
             return lookup_loop(self._last_logits, lambda: dec._verify_step(cache), out.last_hidden_state[:, -1], cache.lookup, input_ids,
@@ -1507,7 +1527,8 @@ class CrossAttentionModel(nn.Module):
                  pad_token_id=None, return_step_logits=False, num_beams=1, length_penalty=1.0, early_stopping=False,
                  return_sequences_scores=False, return_beam_trace=False, num_return_sequences=1, do_sample=False, temperature=1.0,
                  top_k=0, top_p=1.0, seed=None, sample_u=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
-                 suppress_tokens=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False):
+                 suppress_tokens=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False, penalty_alpha=0.0,
+                 return_contrastive_trace=False):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded): the neighbors are encoded and interleaved once, exactly
         as forward does, then MPTForCausalLM.generate runs the prefill and the cached decode steps.  Returns [B, T + max_new_tokens]
         ids (and the step logits with return_step_logits=True).  num_beams, length_penalty, early_stopping, return_sequences_scores and
@@ -1516,10 +1537,15 @@ class CrossAttentionModel(nn.Module):
         num_return_sequences (R continuations per prompt also read the prompt's neighbor tokens once), and its logits processors
         repetition_penalty, no_repeat_ngram_size, min_new_tokens and suppress_tokens (history: input_ids without the masked columns,
         then the new tokens), and its prompt-lookup keywords prompt_lookup_num_tokens, max_matching_ngram_size and
-        return_lookup_stats (drafts come from input_ids and the new tokens, never from the neighbors)."""
+        return_lookup_stats (drafts come from input_ids and the new tokens, never from the neighbors), and its contrastive-search
+        keywords penalty_alpha (with top_k as its k) and return_contrastive_trace (the k candidates of a sample read its neighbor
+        tokens once: they stay at B rows)."""
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the OPT fork only, not for {type(self.lm).__name__}")
-        check_sampling("generate()", do_sample, temperature, top_k, top_p, seed, sample_u, num_beams, num_return_sequences, multi=True)
+        kc = check_contrastive("generate()", penalty_alpha, top_k, return_contrastive_trace, do_sample, num_beams, num_return_sequences,
+                               prompt_lookup_num_tokens, None, return_beam_trace, return_sequences_scores)
+        check_sampling("generate()", do_sample, temperature, 0 if kc else top_k, top_p, seed, sample_u, num_beams, num_return_sequences,
+                       multi=True)
         proc = check_processors("generate()", repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id,
                                 max_new_tokens, self.lm.config.vocab_size, num_beams, input_ids.dtype)
         check_lookup("generate()", prompt_lookup_num_tokens, max_matching_ngram_size, return_lookup_stats, do_sample, num_beams,
@@ -1538,4 +1564,5 @@ class CrossAttentionModel(nn.Module):
                                 top_p=top_p, seed=seed, sample_u=sample_u, repetition_penalty=repetition_penalty,
                                 no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
                                 prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
-                                return_lookup_stats=return_lookup_stats)
+                                return_lookup_stats=return_lookup_stats, penalty_alpha=penalty_alpha,
+                                return_contrastive_trace=return_contrastive_trace)

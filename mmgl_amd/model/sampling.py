@@ -1,4 +1,4 @@
-"""The sampling, logits-processor and prompt-lookup arguments shared by the three generate() methods (MPTForCausalLM / CrossAttentionModel,
+"""The sampling, logits-processor, prompt-lookup and contrastive-search arguments shared by the three generate() methods (MPTForCausalLM / CrossAttentionModel,
 SelfAttentionModel, LlamaNeighborLM): their checks, which need no device, the uniform numbers a sampled generation consumes and the
 per-generation state of the processors.  The selection itself is ops.sample_tokens, the processors are ops.process_logits, one launch
 per decode step each; the loop that makes those calls is generation.decode_loop."""
@@ -84,6 +84,38 @@ def check_lookup(who, prompt_lookup_num_tokens, max_matching_ngram_size, return_
     if inputs_embeds is not None:
         raise ValueError(f"{who}: prompt_lookup_num_tokens = {K} takes input_ids prompts, not inputs_embeds (the drafts are looked up in the ids)")
     return K, N
+
+
+def check_contrastive(who, penalty_alpha, top_k, return_contrastive_trace, do_sample=False, num_beams=1, num_return_sequences=1,
+                      prompt_lookup_num_tokens=0, inputs_embeds=None, return_beam_trace=False, return_sequences_scores=False):
+    """Validates generate()'s contrastive-search keywords; returns k, the candidates ranked per step (0: off -- then
+    every other path and check runs exactly as without the keywords, top_k stays a sampling knob).  penalty_alpha in (0, 1) turns it
+    on and makes top_k its k (2..ops.MAX_BEAMS).  It is a decoding mode of its own: it combines with the logits processors and
+    return_step_logits, and with nothing else that selects tokens."""
+    alpha = float(penalty_alpha)
+    if alpha == 0.0:
+        if return_contrastive_trace:
+            raise ValueError(f"{who}: return_contrastive_trace belongs to penalty_alpha > 0")
+        return 0
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"{who}: penalty_alpha = {penalty_alpha} outside [0, 1) (0: off)")
+    k = int(top_k)
+    if not 2 <= k <= ops.MAX_BEAMS:
+        raise ValueError(f"{who}: penalty_alpha = {penalty_alpha} (contrastive search) needs top_k in 2..{ops.MAX_BEAMS}, got {top_k}")
+    if do_sample:
+        raise ValueError(f"{who}: penalty_alpha = {penalty_alpha} with do_sample=True is not implemented (contrastive search is deterministic)")
+    if int(num_beams) != 1 or int(num_return_sequences) != 1:
+        raise ValueError(f"{who}: penalty_alpha = {penalty_alpha} with num_beams = {num_beams} / num_return_sequences = "
+                         f"{num_return_sequences} is not implemented")
+    if int(prompt_lookup_num_tokens) != 0:
+        raise ValueError(f"{who}: penalty_alpha = {penalty_alpha} with prompt_lookup_num_tokens = {prompt_lookup_num_tokens} is not implemented "
+                         "(the drafts are verified against the greedy choice)")
+    if inputs_embeds is not None:
+        raise ValueError(f"{who}: penalty_alpha = {penalty_alpha} takes input_ids prompts, not inputs_embeds")
+    if return_beam_trace or return_sequences_scores:
+        raise ValueError(f"{who}: return_sequences_scores / return_beam_trace belong to beam search; contrastive search has "
+                         "return_contrastive_trace")
+    return k
 
 
 MAX_SUPPRESS = ops.MAX_BAN - 1          # the ban array of a generation is suppress_tokens followed by the EOS entry

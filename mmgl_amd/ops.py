@@ -1993,6 +1993,89 @@ def beam_topk(logits, beam_score, num_beams, rows_in=None, out=None):
     return cs, ci
 
 
+# ------------------------------------------------------------------------------------------ contrastive search (csrc/contrastive.hip)
+CONTRASTIVE_CTX_CHUNK = 16              # context rows per workgroup of the streaming launch = mmgl_contrastive_chunk()
+
+
+def contrastive_select(cand_hidden, ctx, ctx_valid, cand_score, cand_index, penalty_alpha, n_ctx, step, src, ids_col, vocab_size,
+                       finished=None, eos_token_id=None, pad_token_id=None, hidden_out=None, selected=None, trace=None):
+    """The ranking and the bookkeeping of one contrastive-search step for B samples x k candidates, one call, two launches, everything
+    in place (mmgl_contrastive_select in include/mmgl_hip.h states the rule):
+      cand_hidden [B*k, d] bf16 / fp32 (unit column stride): the candidates' last hidden rows, row b*k + c is candidate c of sample b;
+      ctx [B, n_cap, d] in the same dtype (unit column stride), ctx_valid uint8 [B, n_cap]: the context rows [0, n_ctx) with
+      ctx_valid set are ranked against; row n_ctx becomes the selected candidate's row and ctx_valid[:, n_ctx] = 1;
+      cand_score fp32 / cand_index int32 [B, >= k] with a common row stride: the pair ops.beam_topk(logits, zeros, k, rows_in=1)
+      returns -- the first k of each row are the candidates' log-probabilities and tokens;
+      src int32 [B*k, >= step + 1] (BeamBook.src): column `step` := the selected candidate for the sample's k rows;
+      ids_col int64 [B] (any stride: a column of the result): the selected token, or pad_token_id for a finished row;
+      finished uint8 [B] with eos_token_id (None: no end-of-sequence handling).
+    k = cand_hidden.shape[0] // B in 2..MAX_BEAMS, d a multiple of the 16-byte vector, 0 <= penalty_alpha <= 1.
+    Returns (hidden_out [B, d] dense, selected int32 [B]) -- `hidden_out` / `selected` when given -- and, with trace=True or a
+    preallocated triple, also (p, penalty, score) fp32 [B, k].  A refused call leaves every tensor as it was.  Forward only; GPU only."""
+    op = "contrastive_select"
+    require_cuda(cand_hidden, ctx, ctx_valid, cand_score, cand_index, src, ids_col, finished, hidden_out, selected)
+    _no_grad_inputs(op, cand_hidden, ctx)
+    if ctx.dim() != 3 or cand_hidden.dim() != 2 or ctx.shape[0] == 0 or cand_hidden.shape[0] % max(ctx.shape[0], 1):
+        raise ValueError(f"{op}: cand_hidden{tuple(cand_hidden.shape)} [B*k, d] and ctx{tuple(ctx.shape)} [B, n_cap, d]")
+    B, n_cap, d = ctx.shape
+    k = cand_hidden.shape[0] // B
+    if not 2 <= k <= MAX_BEAMS:
+        raise ValueError(f"{op}: k = {k} candidates per sample (2..{MAX_BEAMS})")
+    code = dtype_code(cand_hidden)
+    dev = cand_hidden.device
+    if (cand_hidden.shape[1] != d or ctx.dtype != cand_hidden.dtype or cand_hidden.stride(1) != 1 or ctx.stride(2) != 1 or ctx.device != dev
+            or n_cap < 1):
+        raise ValueError(f"{op}: incompatible cand_hidden{tuple(cand_hidden.shape)}/{cand_hidden.stride()} {cand_hidden.dtype} and "
+                         f"ctx{tuple(ctx.shape)}/{ctx.stride()} {ctx.dtype}")
+    if ctx_valid.dtype not in (torch.uint8, torch.bool) or tuple(ctx_valid.shape) != (B, n_cap) or ctx_valid.stride(1) != 1 or ctx_valid.device != dev:
+        raise ValueError(f"{op}: ctx_valid must be a uint8 [{B}, {n_cap}] tensor with unit column stride on {dev}")
+    if (cand_score.dtype != torch.float32 or cand_index.dtype != torch.int32 or cand_score.dim() != 2 or cand_score.shape != cand_index.shape
+            or cand_score.shape[0] != B or cand_score.shape[1] < k or cand_score.stride() != cand_index.stride() or cand_score.stride(1) != 1
+            or cand_score.device != dev or cand_index.device != dev):
+        raise ValueError(f"{op}: cand_score / cand_index must be (fp32, int32) [{B}, >= {k}] tensors of one layout with unit column stride on {dev}")
+    n_ctx, step, V = int(n_ctx), int(step), int(vocab_size)
+    if not 0 <= n_ctx <= n_cap - 1:
+        raise ValueError(f"{op}: n_ctx = {n_ctx} outside [0, n_cap - 1 = {n_cap - 1}]")
+    if (src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != B * k or src.stride(1) != 1 or not 0 <= step < src.shape[1]
+            or src.device != dev):
+        raise ValueError(f"{op}: src must be an int32 [{B * k}, > step = {step}] view with unit column stride on {dev}")
+    if ids_col.dtype != torch.int64 or tuple(ids_col.shape) != (B,) or ids_col.device != dev:
+        raise ValueError(f"{op}: ids_col must be an int64 [{B}] view on {dev}")
+    alpha = float(penalty_alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"{op}: penalty_alpha = {penalty_alpha} outside [0, 1]")
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    pad = 0 if pad_token_id is None else int(pad_token_id)
+    if V < k:
+        raise ValueError(f"{op}: vocab_size = {vocab_size} holds fewer than k = {k} candidates")
+    if eos_token_id is not None:
+        if not 0 <= eos < V or pad_token_id is None or not 0 <= pad < V:
+            raise ValueError(f"{op}: eos_token_id = {eos_token_id} needs a pad_token_id, both in [0, {V}), got {pad_token_id}")
+        _state_vector(op, "finished", finished, B, torch.uint8, dev)
+    if hidden_out is None:
+        hidden_out = torch.empty(B, d, dtype=cand_hidden.dtype, device=dev)
+    if tuple(hidden_out.shape) != (B, d) or hidden_out.dtype != cand_hidden.dtype or not hidden_out.is_contiguous() or hidden_out.device != dev:
+        raise ValueError(f"{op}: hidden_out must be a dense {cand_hidden.dtype} [{B}, {d}] tensor on {dev}")
+    if selected is None:
+        selected = torch.empty(B, dtype=torch.int32, device=dev)
+    _state_vector(op, "selected", selected, B, torch.int32, dev)
+    if trace is True:
+        trace = tuple(torch.empty(B, k, dtype=torch.float32, device=dev) for _ in range(3))
+    if trace:
+        if len(trace) != 3 or any(not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (B, k) or not t.is_contiguous()
+                                  or t.device != dev for t in trace):
+            raise ValueError(f"{op}: trace must be three dense fp32 [{B}, {k}] tensors on {dev}")
+    tr = tuple(trace) if trace else (None, None, None)
+    nbytes = _lib.lib().mmgl_contrastive_workspace(B, k, n_cap)
+    ws = _ws(nbytes, dev)
+    _lib.call("mmgl_contrastive_select", dict(bytes=float(B) * (n_ctx + k) * d * ctx.element_size()), ptr(cand_hidden), cand_hidden.stride(0),
+              ptr(ctx), ctx.stride(1), ctx.stride(0), ptr(_as_uint8(ctx_valid)), ctx_valid.stride(0), n_cap, ptr(cand_score), ptr(cand_index),
+              cand_score.stride(0), alpha, n_ctx, step, ptr(src), src.stride(0), ptr(ids_col), ids_col.stride(0),
+              ptr(finished) if eos_token_id is not None else None, eos, pad, ptr(hidden_out), ptr(selected), ptr(tr[0]), ptr(tr[1]), ptr(tr[2]),
+              ptr(ws), nbytes, B, k, d, V, code, stream_ptr())
+    return (hidden_out, selected, tr) if trace else (hidden_out, selected)
+
+
 def _logits_operand(op, logits):
     """(rows, V, dtype code) of logits [rows, V]: unit column stride, not empty, V <= 131072 (sample_tokens, process_logits)."""
     if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] == 0 or logits.shape[1] == 0:
