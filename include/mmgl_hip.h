@@ -714,6 +714,45 @@ int mmgl_contrastive_select(const void* cand_hidden, size_t ld_cand, void* ctx, 
                             int64_t pad_token_id, void* hidden_out, int* selected, float* trace_p, float* trace_pen, float* trace_score,
                             void* workspace, size_t workspace_bytes, int B, int k, int d, int V, int dtype, void* stream);
 
+/* ---- FP8 key/value cache (generate(kv_cache_dtype="fp8"); csrc/decode.hip) -----------------------------------------------------------
+ * replaces: nothing in the reference (its cache holds keys and values in the model's dtype).  Forward only; deterministic (no atomics).
+ *
+ * Format.  A cached key or value row is stored as OCP e4m3fn codes with one power-of-two scale per (sample, column, key-or-value,
+ * head).  For the D elements x of one head (as stored in T), a = max |x|:  e = 0 if a = 0, else with a = m * 2^X, m in [0.5, 1):
+ * e = X - 9 if m <= 0.875 else X - 8 -- the smallest integer with a * 2^-e <= 448 -- clamped to [-120, 120];
+ * code = e4m3fn(x * 2^-e), round to nearest even; value = code * 2^e.  The scaled magnitude lies in (224, 448] unless a = 0 or e is
+ * clamped, and every value is exactly representable in bf16 and fp32.  Inputs are finite; magnitudes outside [2^-100, 2^100] meet the
+ * clamp and -0.0 keeps no promise about its sign.
+ *   codes   [B, capacity, 2 H D] bytes: a row is [key head 0 .. H-1 | value head 0 .. H-1], row stride ld_code, sample stride
+ *           batch_stride_code (bytes)
+ *   scale   [B, capacity, 2 H] int8: a row is [key exponents | value exponents], row stride ld_scale, sample stride batch_stride_scale
+ *
+ * mmgl_kv_quantize: the prefill's filing.  k, v [B, n, H*D] of T with common row stride ld_src and sample stride batch_stride_src
+ * (elements) -- the column views of a fused qkv output, or two tensors -- into rows 0 .. n-1 of `codes` and `scale` (pointers to the
+ * first row written).  One launch; one lane per 16 elements.
+ *
+ * mmgl_attn_decode_q8_fwd: mmgl_attn_decode_fwd over S >= 1 cached columns of codes plus the new token, one launch.
+ *   q, out        [B, H*D] (q: row stride ldq, already scaled by D^-0.5; out dense)
+ *   k_new, v_new  [B, H*D] of T, row stride ld_new: the new token's key and value as projected.  They take part in the attention
+ *                 unquantised and always valid; the launch quantises them and files codes and exponents at column S
+ *   k_codes, v_codes / k_scale, v_scale   the key and the value slab of `codes` / `scale` (v_codes = k_codes + H*D, v_scale =
+ *                 k_scale + H in a cache row); columns [0, S) are read, column S < capacity is written -- one writer per
+ *                 (sample, head, column), no reader of column S in the launch
+ *   key_valid     [B, S] uint8, row stride ld_valid: a masked cached key weighs nothing (the new key is valid: no all-masked case)
+ *   One workgroup per (sample, head); D / 16 lanes share a key, 16-byte loads of 16 codes, keys past S outside the buffer descriptor;
+ *   the key's scale multiplies the dot product, the value's scale the weight; fp32 online softmax, states merged in a fixed order:
+ *   two runs are bitwise equal.  The result equals mmgl_attn_decode_fwd on the dequantised columns followed by the new row, up to
+ *   summation order.
+ * Both: D in {16,32,64,128} (else MMGL_ERR_UNSUPPORTED); strides multiples of 16 bytes and q / k / v / k_new / v_new / codes 16-byte
+ * aligned, a sample's code rows below 2 GiB (else MMGL_ERR_UNSUPPORTED); null pointers, sizes < 1, capacity <= S, strides smaller than
+ * the rows, a bad dtype: MMGL_ERR_INVALID.  A refused call writes nothing.  Plain vector stores only. */
+int mmgl_kv_quantize(const void* k, const void* v, int ld_src, size_t batch_stride_src, void* codes, int ld_code, size_t batch_stride_code,
+                     void* scale, int ld_scale, size_t batch_stride_scale, int B, int n, int H, int D, int dtype, void* stream);
+int mmgl_attn_decode_q8_fwd(const void* q, int ldq, const void* k_new, const void* v_new, int ld_new, void* k_codes, void* v_codes,
+                            int ld_code, size_t batch_stride_code, void* k_scale, void* v_scale, int ld_scale, size_t batch_stride_scale,
+                            int capacity, const uint8_t* key_valid, int ld_valid, void* out, int B, int H, int S, int D, int dtype,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,11 @@
 // themselves, against a cache whose length differs per sample (int32 len[b] on the device).  The beam kernel's prefix loop bounded by
 // len[b], then the m new keys from the projection's output, which the same launch files at cache columns len[b] .. len[b] + m - 1.
 //
+// mmgl_kv_quantize / mmgl_attn_decode_q8_fwd (kv_quantize_kernel, attn_decode_q8_kernel).  The FP8 key/value cache: cache rows of OCP
+// e4m3fn codes with one power-of-two scale per (sample, column, key-or-value, head).  attn_decode_kernel over 16 codes per lane and
+// 16-byte load, the scales folded into the dot product and the softmax weight; the new token's key and value come dense, count
+// unquantised, and are filed as codes by the same launch.
+//
 // mmgl_rope_kv_append (rope_kv_append_kernel).  The new token's q | k | v row: q rotated in place, k rotated into the token's cache column,
 // v copied there -- one launch where separate projections and rotations would take four (the step is launch-bound).
 #include "common.h"
@@ -1233,6 +1238,273 @@ __global__ __launch_bounds__(256) void rope_kv_append_block_kernel(T* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------------ FP8 key/value cache
+// A cached key or value row is stored as OCP e4m3fn codes, 16 per lane and 16-byte access, with one power-of-two scale per (sample,
+// column, key-or-value, head): an int8 exponent e, value = code * 2^e.  A cache row is [k codes: H*D | v codes: H*D] bytes and its
+// scale row [k exponents: H | v exponents: H].  gfx950 converts both ways in hardware (v_cvt_pk_fp8_f32, round to nearest even;
+// v_cvt_pk_f32_fp8), and code * 2^e is exact in fp32, so a dequantised column is the same number in every kernel that reads it.
+constexpr int Q8_VEC = 16;                          // codes per lane
+
+template <typename T> __device__ __forceinline__ void load16(const T* p, float (&f)[Q8_VEC]) {
+    typedef typename Vec16<T>::type V;
+    constexpr int VEC = 16 / sizeof(T);
+#pragma unroll
+    for (int i = 0; i < Q8_VEC / VEC; ++i) {
+        const V x = *(const V*)(p + i * VEC);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) f[i * VEC + e] = Elem<T>::to_f(x[e]);
+    }
+}
+
+// the exponent of a head whose largest magnitude is a: the smallest e with a * 2^-e <= 448 = 0.875 * 2^9, clamped to [-120, 120];
+// 0 for a = 0.  With a = m * 2^x, m in [0.5, 1): e = x - 9 if m <= 0.875 else x - 8.  (A subnormal a lands on the clamp.)
+__device__ __forceinline__ int q8_exponent(float a) {
+    const uint32_t bits = __builtin_bit_cast(uint32_t, a);
+    if (bits == 0) return 0;
+    const int x = (int)(bits >> 23) - 126;
+    const int e = (bits & 0x7fffffu) <= 0x600000u ? x - 9 : x - 8;
+    return min(max(e, -120), 120);
+}
+
+__device__ __forceinline__ float q8_pow2(int e) { return __builtin_bit_cast(float, (uint32_t)(e + 127) << 23); }
+
+__device__ __forceinline__ u32x4 q8_encode(const float (&f)[Q8_VEC], float inv) {
+    u32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * i] * inv, f[4 * i + 1] * inv, 0, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * i + 2] * inv, f[4 * i + 3] * inv, w, true);
+        r[i] = (uint32_t)w;
+    }
+    return r;
+}
+
+__device__ __forceinline__ void q8_decode(const u32x4& c, float (&f)[Q8_VEC]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], true);
+        f[4 * i] = lo[0];
+        f[4 * i + 1] = lo[1];
+        f[4 * i + 2] = hi[0];
+        f[4 * i + 3] = hi[1];
+    }
+}
+
+// max over the N = 2^n <= 8 lanes of an aligned lane group, in every lane of the group
+template <int N> __device__ __forceinline__ float group_max(float v) {
+#pragma unroll
+    for (int o = 1; o < N; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// the 16 elements a lane holds of one head (D / 16 lanes share the head): their codes, and the head's exponent
+template <int LPH> __device__ __forceinline__ u32x4 q8_quantize(const float (&f)[Q8_VEC], int& e) {
+    float a = 0.f;
+#pragma unroll
+    for (int i = 0; i < Q8_VEC; ++i) a = fmaxf(a, fabsf(f[i]));
+    e = q8_exponent(group_max<LPH>(a));
+    return q8_encode(f, q8_pow2(-e));
+}
+
+// mmgl_kv_quantize: one lane per 16 elements of a (sample, row, key-or-value, head); whole lane groups are in or out of `total`.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void kv_quantize_kernel(const T* __restrict__ k, const T* __restrict__ v, int ld_src, size_t bs_src,
+                                                          uint8_t* __restrict__ code, int ld_code, size_t bs_code, int8_t* __restrict__ scale,
+                                                          int ld_scale, size_t bs_scale, int n, int H, long long total) {
+    constexpr int LPH = D / Q8_VEC;
+    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= total) return;                        // total is a multiple of LPH: a lane group leaves together
+    const int c = (int)(id % LPH);
+    long long r = id / LPH;
+    const int hh = (int)(r % (2 * H));              // key heads first, then value heads
+    r /= 2 * H;
+    const int row = (int)(r % n), b = (int)(r / n);
+    const T* src = (hh < H ? k : v) + b * bs_src + (size_t)row * ld_src + (size_t)(hh % H) * D + c * Q8_VEC;
+    float f[Q8_VEC];
+    load16<T>(src, f);
+    int e;
+    const u32x4 q = q8_quantize<LPH>(f, e);
+    *(u32x4*)(code + b * bs_code + (size_t)row * ld_code + (size_t)hh * D + c * Q8_VEC) = q;
+    if (c == 0) scale[b * bs_scale + (size_t)row * ld_scale + hh] = (int8_t)e;
+}
+
+// mmgl_attn_decode_q8_fwd: attn_decode_kernel over a cache of codes.  D / 16 lanes share a key (one 16-byte load of K codes and one
+// of V codes per lane: 16 codes), a wave covers 1024 / D keys per instruction, the 4 waves interleave key blocks and AD_UNROLL blocks
+// are in flight; keys past S fall outside the descriptors.  The key's scale multiplies the dot product, the value's scale multiplies
+// p; the AD_UNROLL keys of a trip enter the fp32 online softmax together.  The new token's key and value come dense, in T, from the
+// projection's output: lane group 0 of the last wave scores the key unquantised (it is always valid, so a row of masked cached keys
+// weighs only it), then quantises both and files codes and exponents at column S -- one writer per (sample, head, column), and no
+// workgroup reads column S.  Merge as attn_decode_kernel: fixed butterfly, then the waves in order through LDS; no atomics.
+template <typename T, int D>
+__global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_q8_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ kn,
+                                                                         const T* __restrict__ vn, int ld_new, uint8_t* kc, uint8_t* vc,
+                                                                         int ld_code, size_t bs_code, int8_t* ks, int8_t* vs, int ld_scale,
+                                                                         size_t bs_scale, const uint8_t* __restrict__ valid, int ld_valid,
+                                                                         T* __restrict__ out, int H, int S) {
+    constexpr int LPK = D / Q8_VEC;                 // lanes per key
+    constexpr int KPI = WAVE / LPK;                 // keys per wave and load instruction
+    constexpr float NEG = -FLT_MAX;
+    __shared__ float sm_m[AD_WAVES], sm_l[AD_WAVES], sm_o[AD_WAVES][D];
+
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane % LPK, kk = lane / LPK;
+
+    float qf[Q8_VEC];
+    load16<T>(q + (size_t)b * ldq + h * D + c * Q8_VEC, qf);
+    uint8_t* kb = kc + b * bs_code + h * D;
+    uint8_t* vb = vc + b * bs_code + h * D;
+    int8_t* ksb = ks + b * bs_scale + h;
+    int8_t* vsb = vs + b * bs_scale + h;
+    // branch-free loads: keys past S fall outside the descriptors
+    const uint32_t slab = (uint32_t)((size_t)(S - 1) * ld_code + D), row_bytes = (uint32_t)ld_code;
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(kb, slab);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(vb, slab);
+    const uint8_t* mb = valid + (size_t)b * ld_valid;
+
+    float m = NEG, l = 0.f, acc[Q8_VEC];
+#pragma unroll
+    for (int e = 0; e < Q8_VEC; ++e) acc[e] = 0.f;
+
+    for (int base = w * KPI; base < S; base += AD_WAVES * KPI * AD_UNROLL) {          // wave-uniform trip count
+        u32x4 kr[AD_UNROLL], vr[AD_UNROLL];
+        int ke[AD_UNROLL], ve[AD_UNROLL];
+        bool ok[AD_UNROLL], in[AD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            const int s = base + u * AD_WAVES * KPI + kk;
+            in[u] = s < S;
+            const uint32_t off = in[u] ? (uint32_t)s * row_bytes + (uint32_t)(c * Q8_VEC) : OOB;
+            kr[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+            vr[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+            const int sc = min(s, S - 1);
+            ok[u] = mb[sc] != 0;
+            ke[u] = ksb[(size_t)sc * ld_scale];
+            ve[u] = vsb[(size_t)sc * ld_scale];
+        }
+        float sc[AD_UNROLL], mn = m;
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            float kf[Q8_VEC], dot = 0.f;
+            q8_decode(kr[u], kf);
+#pragma unroll
+            for (int e = 0; e < Q8_VEC; ++e) dot += qf[e] * kf[e];
+            dot = group_sum<LPK>(dot) * q8_pow2(ke[u]);
+            sc[u] = ok[u] ? dot : NEG;
+            if (in[u]) mn = fmaxf(mn, sc[u]);
+        }
+        const float corr = __expf(m - mn);
+        float pu[AD_UNROLL], ps = 0.f;
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            pu[u] = in[u] ? __expf(sc[u] - mn) : 0.f;                 // a key past S weighs nothing, also in a group of masked keys
+            ps += pu[u];
+        }
+        l = l * corr + ps;
+#pragma unroll
+        for (int e = 0; e < Q8_VEC; ++e) acc[e] *= corr;
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            float vf[Q8_VEC];
+            q8_decode(vr[u], vf);
+            const float pv = in[u] ? pu[u] * q8_pow2(ve[u]) : 0.f;    // the exponent of a key past S is another column's
+#pragma unroll
+            for (int e = 0; e < Q8_VEC; ++e) acc[e] += pv * vf[e];
+        }
+        m = mn;
+    }
+    // the new token: scored and weighed as it came, filed as codes
+    if (w == AD_WAVES - 1 && kk == 0) {
+        float kf[Q8_VEC], vf[Q8_VEC], dot = 0.f;
+        load16<T>(kn + (size_t)b * ld_new + h * D + c * Q8_VEC, kf);
+        load16<T>(vn + (size_t)b * ld_new + h * D + c * Q8_VEC, vf);
+#pragma unroll
+        for (int e = 0; e < Q8_VEC; ++e) dot += qf[e] * kf[e];
+        dot = group_sum<LPK>(dot);
+        const float mn = fmaxf(m, dot);
+        const float corr = __expf(m - mn), p = __expf(dot - mn);
+        l = l * corr + p;
+#pragma unroll
+        for (int e = 0; e < Q8_VEC; ++e) acc[e] = acc[e] * corr + p * vf[e];
+        m = mn;
+        int ek, ev;
+        const u32x4 kq = q8_quantize<LPK>(kf, ek), vq = q8_quantize<LPK>(vf, ev);
+        const size_t at = (size_t)S * ld_code + c * Q8_VEC;
+        *(u32x4*)(kb + at) = kq;
+        *(u32x4*)(vb + at) = vq;
+        if (c == 0) {
+            ksb[(size_t)S * ld_scale] = (int8_t)ek;
+            vsb[(size_t)S * ld_scale] = (int8_t)ev;
+        }
+    }
+    // merge the lane groups of the wave (fixed butterfly), then the waves in order
+#pragma unroll
+    for (int o = LPK; o < WAVE; o <<= 1) {
+        const float m2 = __shfl_xor(m, o), l2 = __shfl_xor(l, o);
+        const float mn = fmaxf(m, m2);
+        const float c1 = __expf(m - mn), c2 = __expf(m2 - mn);
+        l = l * c1 + l2 * c2;
+#pragma unroll
+        for (int e = 0; e < Q8_VEC; ++e) acc[e] = acc[e] * c1 + __shfl_xor(acc[e], o) * c2;
+        m = mn;
+    }
+    if (lane < LPK) {
+#pragma unroll
+        for (int e = 0; e < Q8_VEC; ++e) sm_o[w][c * Q8_VEC + e] = acc[e];
+        if (lane == 0) { sm_m[w] = m; sm_l[w] = l; }
+    }
+    __syncthreads();
+    if (tid < D) {
+        float mm = sm_m[0];
+#pragma unroll
+        for (int i = 1; i < AD_WAVES; ++i) mm = fmaxf(mm, sm_m[i]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int i = 0; i < AD_WAVES; ++i) {
+            const float ci = __expf(sm_m[i] - mm);
+            ll += sm_l[i] * ci;
+            o += sm_o[i][tid] * ci;
+        }
+        out[((size_t)b * H + h) * D + tid] = Elem<T>::from_f(o / ll);
+    }
+}
+
+struct KvQuantArgs {
+    const void *k, *v;
+    uint8_t* code;
+    int8_t* scale;
+    int ld_src, ld_code, ld_scale, B, n, H;
+    size_t bs_src, bs_code, bs_scale;
+};
+
+template <typename T, int D>
+int launch_kv_quantize(const KvQuantArgs& a, hipStream_t st) {
+    const long long total = (long long)a.B * a.n * 2 * a.H * (D / Q8_VEC);
+    hipLaunchKernelGGL((kv_quantize_kernel<T, D>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const T*)a.k, (const T*)a.v, a.ld_src,
+                       a.bs_src, a.code, a.ld_code, a.bs_code, a.scale, a.ld_scale, a.bs_scale, a.n, a.H, total);
+    MMGL_CHECK_LAUNCH("mmgl_kv_quantize");
+    return MMGL_OK;
+}
+
+struct Q8AttnArgs {
+    const void *q, *kn, *vn;
+    uint8_t *kc, *vc;
+    int8_t *ks, *vs;
+    const uint8_t* valid;
+    void* out;
+    int ldq, ld_new, ld_code, ld_scale, ld_valid, B, H, S;
+    size_t bs_code, bs_scale;
+};
+
+template <typename T, int D>
+int launch_attn_decode_q8(const Q8AttnArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL((attn_decode_q8_kernel<T, D>), dim3(a.B * a.H), dim3(AD_WAVES * WAVE), 0, st, (const T*)a.q, a.ldq, (const T*)a.kn,
+                       (const T*)a.vn, a.ld_new, a.kc, a.vc, a.ld_code, a.bs_code, a.ks, a.vs, a.ld_scale, a.bs_scale, a.valid, a.ld_valid,
+                       (T*)a.out, a.H, a.S);
+    MMGL_CHECK_LAUNCH("mmgl_attn_decode_q8_fwd");
+    return MMGL_OK;
+}
+
 // what the two skinny GEMM entry points refuse alike (their sizes and leading dimensions differ by the adapter's).  ptrs: every
 // required pointer is set; hint: the way out of M > 64 that `who` offers
 int check_skinny(const char* who, const char* hint, bool ptrs, int M, int act, int dtype) {
@@ -1466,4 +1738,59 @@ extern "C" int mmgl_rope_kv_append(void* qkv, int ldqkv, const float* cos_sin_ro
         hipLaunchKernelGGL(rope_kv_append_kernel<float>, grid, block, 0, st, (float*)qkv, ldqkv, (const f32x2*)cos_sin_row, (float*)kv_col, batch_stride_kv, B, H, Hkv, D);
     MMGL_CHECK_LAUNCH("mmgl_rope_kv_append");
     return MMGL_OK;
+}
+
+extern "C" int mmgl_kv_quantize(const void* k, const void* v, int ld_src, size_t batch_stride_src, void* codes, int ld_code,
+                                size_t batch_stride_code, void* scale, int ld_scale, size_t batch_stride_scale, int B, int n, int H, int D,
+                                int dtype, void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && n >= 1 && H >= 1, "mmgl_kv_quantize: bad sizes B=%d n=%d H=%d", B, n, H);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_kv_quantize: bad dtype %d", dtype);
+    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_kv_quantize: head_dim %d (16, 32, 64, 128)", D);
+    const int vec = dtype == MMGL_BF16 ? 8 : 4;
+    if (ld_src % vec || batch_stride_src % vec || ld_code % 16 || batch_stride_code % 16)
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_kv_quantize: strides (%d, %zu, %d, %zu) must be multiples of 16 bytes", ld_src, batch_stride_src,
+                  ld_code, batch_stride_code);
+    MMGL_CHECK_ARG(k && v && codes && scale, "mmgl_kv_quantize: null pointer");
+    const long long hd = (long long)H * D;
+    MMGL_CHECK_ARG(ld_src >= hd && ld_code >= 2 * hd && ld_scale >= 2 * H &&
+                       (B == 1 || (batch_stride_src >= (size_t)(n - 1) * ld_src + (size_t)hd &&
+                                   batch_stride_code >= (size_t)(n - 1) * ld_code + (size_t)(2 * hd) &&
+                                   batch_stride_scale >= (size_t)(n - 1) * ld_scale + (size_t)(2 * H))),
+                   "mmgl_kv_quantize: strides (%d, %zu, %d, %zu, %d, %zu) smaller than the rows", ld_src, batch_stride_src, ld_code,
+                   batch_stride_code, ld_scale, batch_stride_scale);
+    if (!aligned16(k) || !aligned16(v) || !aligned16(codes)) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_kv_quantize: k, v and codes must be 16-byte aligned");
+    if ((long long)B * n * 2 * H * (D / 16) >= (1ll << 31)) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_kv_quantize: %d rows of %d heads are too many", B * n, 2 * H);
+    const KvQuantArgs a{k, v, (uint8_t*)codes, (int8_t*)scale, ld_src, ld_code, ld_scale, B, n, H, batch_stride_src, batch_stride_code, batch_stride_scale};
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(launch_kv_quantize, bf16, D, a, st);
+    RETURN_BY_HEAD_DIM(launch_kv_quantize, float, D, a, st);
+}
+
+extern "C" int mmgl_attn_decode_q8_fwd(const void* q, int ldq, const void* k_new, const void* v_new, int ld_new, void* k_codes, void* v_codes,
+                                       int ld_code, size_t batch_stride_code, void* k_scale, void* v_scale, int ld_scale,
+                                       size_t batch_stride_scale, int capacity, const uint8_t* key_valid, int ld_valid, void* out, int B, int H,
+                                       int S, int D, int dtype, void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && H >= 1 && S >= 1 && capacity > S, "mmgl_attn_decode_q8_fwd: bad sizes B=%d H=%d S=%d capacity=%d", B, H, S, capacity);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_attn_decode_q8_fwd: bad dtype %d", dtype);
+    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_q8_fwd: head_dim %d (16, 32, 64, 128)", D);
+    const int vec = dtype == MMGL_BF16 ? 8 : 4;
+    if (ldq % vec || ld_new % vec || ld_code % 16 || batch_stride_code % 16)
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_q8_fwd: strides (%d, %d, %d, %zu) must be multiples of 16 bytes", ldq, ld_new, ld_code,
+                  batch_stride_code);
+    MMGL_CHECK_ARG(q && k_new && v_new && k_codes && v_codes && k_scale && v_scale && key_valid && out, "mmgl_attn_decode_q8_fwd: null pointer");
+    const long long hd = (long long)H * D;
+    MMGL_CHECK_ARG(ldq >= hd && ld_new >= hd && ld_code >= hd && ld_scale >= H && ld_valid >= S &&
+                       (B == 1 || (batch_stride_code >= (size_t)(capacity - 1) * ld_code + (size_t)hd &&
+                                   batch_stride_scale >= (size_t)(capacity - 1) * ld_scale + (size_t)H)),
+                   "mmgl_attn_decode_q8_fwd: strides (%d, %d, %d, %zu, %d, %zu, %d) smaller than the rows", ldq, ld_new, ld_code,
+                   batch_stride_code, ld_scale, batch_stride_scale, ld_valid);
+    if (!aligned16(q) || !aligned16(k_new) || !aligned16(v_new) || !aligned16(k_codes) || !aligned16(v_codes))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_q8_fwd: q, k_new, v_new, k_codes and v_codes must be 16-byte aligned");
+    if ((size_t)(capacity - 1) * ld_code + D >= (1ull << 31))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_q8_fwd: a sample's cache rows span 2 GiB or more (capacity=%d, ld_code=%d)", capacity, ld_code);
+    const Q8AttnArgs a{q, k_new, v_new, (uint8_t*)k_codes, (uint8_t*)v_codes, (int8_t*)k_scale, (int8_t*)v_scale, key_valid, out,
+                       ldq, ld_new, ld_code, ld_scale, ld_valid, B, H, S, batch_stride_code, batch_stride_scale};
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(launch_attn_decode_q8, bf16, D, a, st);
+    RETURN_BY_HEAD_DIM(launch_attn_decode_q8, float, D, a, st);
 }

@@ -42,7 +42,7 @@ class Arguments:
     """Same field names and defaults as the reference's Arguments (:66-229) + `neighbor_layer_wise` + `num_beams` + the sampling knobs
     `do_sample` / `temperature` / `top_k` / `top_p` + the logits processors `repetition_penalty` / `no_repeat_ngram_size` /
     `min_new_tokens` + prompt-lookup decoding's `prompt_lookup_num_tokens` / `max_matching_ngram_size` + contrastive search's
-    `penalty_alpha` (with `top_k` as its k)."""
+    `penalty_alpha` (with `top_k` as its k) + the FP8 key/value cache's `kv_cache_dtype`."""
     overwrite_cache: Optional[bool] = _f(False, "Overwrite the cached preprocessed datasets or not.")
     dataset: Optional[str] = _f("wikiweb2m", "The name of the dataset to use.")
     task: Optional[str] = _f("section", "One of three generation tasks in WikiWeb2M")
@@ -112,6 +112,9 @@ class Arguments:
     prompt_lookup_num_tokens: int = _f(0, "tokens drafted from the prompt and verified per step of the test protocol's greedy generate() "
                                           "(1..7; same captions in fewer steps); 0 = off")
     max_matching_ngram_size: int = _f(2, "longest n-gram prompt-lookup decoding matches when it drafts (1..4)")
+    kv_cache_dtype: Optional[str] = _f(None, "key/value cache of the test protocol's generate(): fp8 keeps the frozen layers' cached keys "
+                                             "and values as e4m3fn codes (OPT fork, greedy or sampled, plain projections); default: the "
+                                             "model's dtype")
     peft_type: str = _f("none", "peft type: none, prefix, prompt, lora, flamingo")
     lora_r: int = _f(64, "lora row rank")
     lora_alpha: float = _f(1, "lora scaling factor")
@@ -653,6 +656,8 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                         {"num_beams", "do_sample", "repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "penalty_alpha"} & set(fields)):
                     fields.update(prompt_lookup_num_tokens=int(args.prompt_lookup_num_tokens),      # greedy runs only: the same ids
                                   max_matching_ngram_size=int(getattr(args, "max_matching_ngram_size", 2)))
+                if getattr(args, "kv_cache_dtype", None) is not None and "kv_cache_dtype" in named:
+                    fields["kv_cache_dtype"] = args.kv_cache_dtype                                   # generate() says what it combines with
                 generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),
                                                attention_mask=batch["attention_mask"][:, :L_in].contiguous(), **fields,
                                                host_meta=extra.get("host_meta"), max_new_tokens=32,

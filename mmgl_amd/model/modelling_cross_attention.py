@@ -39,7 +39,7 @@ from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutpu
 from .. import ops
 from .encoders import ClipTextEncoder, PackedTextEncoder, PackedVisionEncoder
 from .generation import GreedyTail, SampledTail, check_prompt, contrastive_loop, decode_loop, lookup_loop
-from .sampling import check_contrastive, check_lookup, check_processors, check_sampling, sampling_u
+from .sampling import check_contrastive, check_kv_cache, check_lookup, check_processors, check_sampling, sampling_u
 
 CROSS_MODES = ("cross_attention", "embedding")
 
@@ -231,9 +231,10 @@ class MPTAttention(nn.Module):
     # -- causal self-attention of the (frozen) OPT layers: HIP flash kernels, no [B,1,T,T] mask, no [B,H,T,T] scores
     def _forward_self(self, hidden_states, attention_mask, layer_head_mask, output_attentions, past_key_value=None, kv_out=None,
                       live=None):
-        """kv_out: the layer's [B, capacity, 2d] K|V buffer of a DecodeCache -- the prefill copies its keys and values there.
+        """kv_out: the layer's [B, capacity, 2d] K|V buffer of a DecodeCache -- the prefill copies its keys and values there -- or the
+        (codes, scale) pair of an FP8 cache, which one ops.kv_quantize launch fills (_file_kv).
         live = (yc, key_tiles): the caller checked key_tiles_route and brings the compact copy of hidden_states."""
-        H = self.num_heads
+        H, d = self.num_heads, self.embed_dim
         if attention_mask is None or attention_mask.dim() != 2:
             raise ValueError("self-attention takes the [bsz, seq_len] key mask (causality is implied); additive 4-D masks are "
                              f"not materialised on this path (got {None if attention_mask is None else tuple(attention_mask.shape)})")
@@ -249,7 +250,6 @@ class MPTAttention(nn.Module):
         if general:
             # reference :237-256 on the self-attention call site: separate q / k / v (the fused-QKV node has no general core), the
             # general HIP core with the causal AND key mask
-            d = hidden_states.shape[-1]
             if fused is not None:
                 qkv = ops.frozen_linear(hidden_states, *fused)
                 q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
@@ -263,7 +263,7 @@ class MPTAttention(nn.Module):
             # prefix tuning (peft hands the learned per-layer key/value prefix to HF as past_key_values): P extra keys / values in
             # front of the layer's own, visible to every query; attention_mask is the [bsz, P + seq_len] key mask
             kp, vp = past_key_value
-            B, T, d = hidden_states.shape
+            B, T, _ = hidden_states.shape
             P = kp.shape[-2]
             if fused is not None:
                 qkv = ops.frozen_linear(hidden_states, *fused)
@@ -277,14 +277,14 @@ class MPTAttention(nn.Module):
         elif fused is not None:              # frozen layer: one QKV GEMM forward, one dgrad GEMM backward, no gradient adds
             qkv = ops.frozen_linear(hidden_states, *fused)
             if kv_out is not None:
-                kv_out[:, :qkv.shape[1]].copy_(qkv[..., qkv.shape[-1] // 3:])
+                self._file_kv(kv_out, qkv[..., d:2 * d], qkv[..., 2 * d:], qkv[..., d:])
             o = ops.selfattn_core_fused(qkv, attention_mask, H)
         elif (lq := self._lora_qkv()) is not None and ops.lora_qkv_supported(hidden_states, lq[0], self.q_proj.r):
             # LoRA on q_proj / v_proj: one node for the three projections (fused base GEMM, one dgrad GEMM, no gradient adds)
             qkv = ops.lora_qkv(hidden_states, lq[0], lq[1], self.q_proj.lora_A, self.q_proj.lora_B, self.v_proj.lora_A, self.v_proj.lora_B,
                                self.q_proj.scaling, self.scaling)
             if kv_out is not None:
-                kv_out[:, :qkv.shape[1]].copy_(qkv[..., qkv.shape[-1] // 3:])
+                self._file_kv(kv_out, qkv[..., d:2 * d], qkv[..., 2 * d:], qkv[..., d:])
             o = ops.selfattn_core_fused(qkv, attention_mask, H)
         else:
             if type(self.q_proj) is nn.Linear and self.q_proj.weight.requires_grad:
@@ -295,10 +295,21 @@ class MPTAttention(nn.Module):
                 q = _lin(self.q_proj, hidden_states) * self.scaling
             k, v = _lin(self.k_proj, hidden_states), _lin(self.v_proj, hidden_states)
             if kv_out is not None:
-                kv_out[:, :k.shape[1], :k.shape[2]].copy_(k)
-                kv_out[:, :k.shape[1], k.shape[2]:].copy_(v)
+                self._file_kv(kv_out, k, v)
             o = ops.selfattn_core(q, k, v, attention_mask, H)
         return _lin(self.out_proj, o), None, None
+
+    def _file_kv(self, kv_out, k, v, kv=None):
+        """The prefill's keys and values k, v [B, T, d] into the layer's cache columns [0, T).  kv_out a [B, capacity, 2d] buffer in
+        the model's dtype: one copy of `kv` (the k|v columns of a fused projection) or one each of k and v; kv_out the (codes, scale)
+        pair of an FP8 cache: one ops.kv_quantize launch on the same views."""
+        if isinstance(kv_out, tuple):
+            ops.kv_quantize(k, v, kv_out[0], kv_out[1], self.num_heads)
+        elif kv is not None:
+            kv_out[:, :kv.shape[1]].copy_(kv)
+        else:
+            kv_out[:, :k.shape[1], :k.shape[2]].copy_(k)
+            kv_out[:, :k.shape[1], k.shape[2]:].copy_(v)
 
     def forward(self, hidden_states, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None,
                 past_key_value=None, layer_head_mask=None, output_attentions=False, kv_out=None, live=None):
@@ -317,16 +328,24 @@ class MPTAttention(nn.Module):
         _plain(mod)
         return ops.decode_linear(x, mod.weight, mod.bias, out_scale=out_scale, out=out)
 
-    def decode_self(self, x, kv, key_mask, col, beam=None, tail=None):
+    def decode_self(self, x, kv, key_mask, col, beam=None, tail=None, q8=None):
         """x [B, d]: the new token's layer input.  Projects q and writes k|v into column `col` of the layer's cache rows kv
         [B, capacity, 2d], then attends over columns 0..col (all at or before the query: no causal test).  q_proj and v_proj may be
         LoRA-adapted (any other adapter type, and an adapted k_proj / out_proj, is refused).
         beam (a BeamState) with the layer's tail buffer [B*W, n_cap, 2d]: x [B*W, d]; k|v go into column beam.n_tail of `tail`, and
         the rows attend over the sample's `col` prompt columns of kv (shared, never copied) plus their own n_tail + 1 tail keys,
-        addressed through beam.book.src (ops.attn_decode_beam).  Plain nn.Linear projections only."""
+        addressed through beam.book.src (ops.attn_decode_beam).  Plain nn.Linear projections only.
+        q8 = (scale, kv_new) of an FP8 cache (kv then holds e4m3fn codes): k|v go into the dense kv_new [B, 2d] instead of a cache
+        column, and ops.attn_decode_q8 attends over the `col` cached columns plus the new row and files it, quantised, at column
+        `col` -- the launches of the plain step.  Plain nn.Linear projections, no beams."""
         d = self.embed_dim
         _plain(self.k_proj, self.out_proj)
-        if beam is None:
+        if q8 is not None:
+            if beam is not None:
+                raise ValueError("the FP8 key/value cache has no beam step")
+            _plain(self.q_proj, self.v_proj)
+            scale, dst = q8
+        elif beam is None:
             dst = kv[:, col]
         else:
             _plain(self.q_proj, self.v_proj)
@@ -340,6 +359,8 @@ class MPTAttention(nn.Module):
             q = self._decode_proj(self.q_proj, x, out_scale=self.scaling)
             ops.decode_linear(x, self.k_proj.weight, self.k_proj.bias, out=dst[:, :d])
             self._decode_proj(self.v_proj, x, out=dst[:, d:])
+        if q8 is not None:
+            return ops.attn_decode_q8(q, dst[:, :d], dst[:, d:], kv, scale, key_mask[:, :col], self.num_heads)
         if beam is None:
             return ops.attn_decode(q, kv[:, :col + 1, :d], kv[:, :col + 1, d:], key_mask[:, :col + 1], self.num_heads)
         n = beam.n_tail + 1
@@ -535,9 +556,12 @@ class MPTDecoderLayer(nn.Module):
         else:                                 # frozen layer: the residual adds ride in the GEMM epilogues
             beam, lookup = cache.beam, cache.lookup
             if lookup is not None:
+                if cache.kv_scale is not None:
+                    raise ValueError("the FP8 key/value cache has no verify step")
                 a = attn.decode_block(x, cache.kv[idx], cache.mask, lookup, lookup.scratch[idx])
             else:
-                a = attn.decode_self(x, cache.kv[idx], cache.mask, cache.col, beam, None if beam is None else beam.tail[idx])
+                a = attn.decode_self(x, cache.kv[idx], cache.mask, cache.col, beam, None if beam is None else beam.tail[idx],
+                                     None if cache.kv_scale is None else (cache.kv_scale[idx], cache.kv_new))
             h = ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias, residual=h)
         if not pre:
             h = self._ln(ln1, h)
@@ -560,11 +584,23 @@ class DecodeCache:
       beam        None (greedy), or the BeamState of a beam search: then kv / mask / cross / cross_valid / next_pos stay at B rows --
                   the prompt is prefilled once per sample and col stays at the prompt width -- and the decode steps run B*W rows
       lookup      None, or the LookupState of prompt-lookup decoding: then col / next_pos stand still at the prompt's and the verify steps
-                  (MPTDecoder._verify_step) run B*(K+1) rows against per-sample cache lengths lookup.len"""
+                  (MPTDecoder._verify_step) run B*(K+1) rows against per-sample cache lengths lookup.len
+      kv_dtype    None: kv in the model's dtype, as above.  ops.KV_FP8 (with num_heads = H): kv[l] holds e4m3fn codes [B, capacity, 2d],
+                  kv_scale[l] their int8 exponents [B, capacity, 2H] -- one power of two per (sample, column, key-or-value, head),
+                  key heads first -- and kv_new is the one dense [B, 2d] buffer, in the model's dtype, that takes every layer's k|v
+                  projection of a decode step (ops.attn_decode_q8 reads it and files it quantised).  cross stays in the model's dtype"""
 
-    def __init__(self, num_layers, batch_size, capacity, hidden_size, dtype, device):
+    def __init__(self, num_layers, batch_size, capacity, hidden_size, dtype, device, kv_dtype=None, num_heads=None):
         self.capacity = int(capacity)
-        self.kv = [torch.empty(batch_size, self.capacity, 2 * hidden_size, dtype=dtype, device=device) for _ in range(num_layers)]
+        self.kv_dtype = kv_dtype
+        self.kv_scale = self.kv_new = None
+        if kv_dtype is not None:
+            if kv_dtype is not ops.KV_FP8 or not num_heads or hidden_size % int(num_heads):
+                raise ValueError(f"DecodeCache: kv_dtype = {kv_dtype!r} with num_heads = {num_heads} (None, or torch.float8_e4m3fn with the "
+                                 "number of heads)")
+            self.kv_scale = [torch.empty(batch_size, self.capacity, 2 * int(num_heads), dtype=torch.int8, device=device) for _ in range(num_layers)]
+            self.kv_new = torch.empty(batch_size, 2 * hidden_size, dtype=dtype, device=device)
+        self.kv = [torch.empty(batch_size, self.capacity, 2 * hidden_size, dtype=kv_dtype or dtype, device=device) for _ in range(num_layers)]
         self.mask = torch.zeros(batch_size, self.capacity, dtype=torch.uint8, device=device)
         self.cross = []
         self.cross_valid = None
@@ -572,6 +608,10 @@ class DecodeCache:
         self.next_pos = None
         self.beam = None
         self.lookup = None
+
+    def kv_out(self, idx):
+        """What layer idx's prefill files its keys and values into (MPTAttention._file_kv)."""
+        return self.kv[idx] if self.kv_scale is None else (self.kv[idx], self.kv_scale[idx])
 
 
 class LookupState:
@@ -688,11 +728,14 @@ class MPTDecoder(MPTPreTrainedModel):
 
     def forward(self, input_ids=None, attention_mask=None, head_mask=None, past_key_values=None, inputs_embeds=None,
                 neighbor_embeds=None, neighbor_attention_mask=None, use_cache=None, output_attentions=None,
-                output_hidden_states=None, return_dict=None, first_key_valid=False, cache_capacity=None, key_tiles=None):
+                output_hidden_states=None, return_dict=None, first_key_valid=False, cache_capacity=None, key_tiles=None,
+                kv_cache_dtype=None):
         """key_tiles (an ops.KeyTiles of attention_mask, optional): the frozen layers project keys and values for the 64-key tiles that
         hold a valid key only (MPTAttention.key_tiles_route says where); the result is that of the dense path.
         use_cache=True: the prefill of greedy generation -- the same kernels as any forward, plus a copy of every layer's keys and
         values into a DecodeCache (capacity `cache_capacity` columns, default max_position_embeddings) returned as past_key_values.
+        kv_cache_dtype ("fp8" / torch.float8_e4m3fn, with use_cache=True): that cache keeps the frozen layers' keys and values as
+        e4m3fn codes (sampling.check_kv_cache); the prefill's own attention still runs on the unquantised prompt.
         past_key_values=DecodeCache with input_ids [B, 1]: one decode step (see _decode_step).  Any other past_key_values keeps its
         meaning: a fixed key/value prefix (prefix tuning)."""
         output_attentions = bool(output_attentions)
@@ -700,6 +743,13 @@ class MPTDecoder(MPTPreTrainedModel):
         return_dict = True if return_dict is None else return_dict
         decoding = isinstance(past_key_values, DecodeCache)
         cache = None
+        kv_dtype = check_kv_cache("MPTDecoder.forward()", kv_cache_dtype,
+                                  projections=[m for layer in self.layers for m in (layer.self_attn.q_proj, layer.self_attn.k_proj,
+                                                                                      layer.self_attn.v_proj, layer.self_attn.out_proj)]
+                                  if kv_cache_dtype is not None else (),
+                                  past_key_values=None if decoding else past_key_values)
+        if kv_dtype is not None and (decoding or not use_cache):
+            raise ValueError("MPTDecoder.forward(): kv_cache_dtype belongs to the prefill (use_cache=True); a decode step follows its cache")
         if decoding or use_cache:
             if past_key_values is not None and not decoding:
                 raise ValueError("prefix tuning (a key/value prefix in past_key_values) together with a decode cache is not implemented")
@@ -744,7 +794,8 @@ class MPTDecoder(MPTPreTrainedModel):
             if seq_length > capacity or capacity > self.max_target_positions:
                 raise ValueError(f"decode cache: a prompt of {seq_length} columns, capacity {capacity}, max_position_embeddings "
                                  f"{self.max_target_positions}")
-            cache = DecodeCache(len(self.layers), batch_size, capacity, self.config.hidden_size, inputs_embeds.dtype, inputs_embeds.device)
+            cache = DecodeCache(len(self.layers), batch_size, capacity, self.config.hidden_size, inputs_embeds.dtype, inputs_embeds.device,
+                                kv_dtype, self.config.num_attention_heads)
         if attention_mask is None:
             attention_mask = torch.ones(batch_size, seq_length + prefix_len, device=inputs_embeds.device)
         elif attention_mask.shape[1] == seq_length and prefix_len:
@@ -790,7 +841,7 @@ class MPTDecoder(MPTPreTrainedModel):
             layer_outputs = decoder_layer(hidden_states, attention_mask=causal_attention_mask, layer_head_mask=lhm,
                                           output_attentions=output_attentions, defer_residual=defer,
                                           past_key_value=None if past_key_values is None else past_key_values[idx],
-                                          kv_out=None if cache is None else cache.kv[idx], key_tiles=key_tiles)
+                                          kv_out=None if cache is None else cache.kv_out(idx), key_tiles=key_tiles)
             if self.cross_attention and neighbor_embeds is not None and (idx + 1) % self.neighbor_layer_wise == 0:
                 hidden_states = _materialize(layer_outputs[0])
                 neighbor_idx = (idx + 1) // self.neighbor_layer_wise - 1
@@ -1010,17 +1061,18 @@ class MPTForCausalLM(MPTPreTrainedModel):
     def forward(self, input_ids=None, attention_mask=None, head_mask=None, past_key_values=None, inputs_embeds=None,
                 labels=None, neighbor_embeds=None, neighbor_attention_mask=None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, first_key_valid=False, return_logits=None, logits_slice=None,
-                cache_capacity=None, key_tiles=None):
+                cache_capacity=None, key_tiles=None, kv_cache_dtype=None):
         """return_logits / logits_slice: see lm_head_loss_and_logits (training steps never build the [B, T, V] logits unless asked).
         key_tiles: see MPTDecoder.forward.
-        use_cache / past_key_values=DecodeCache / cache_capacity: see MPTDecoder.forward; a decode step returns [B, 1, V] logits."""
+        use_cache / past_key_values=DecodeCache / cache_capacity / kv_cache_dtype: see MPTDecoder.forward; a decode step returns
+        [B, 1, V] logits."""
         return_dict = True if return_dict is None else return_dict
         outputs = self.model.decoder(input_ids=input_ids, attention_mask=attention_mask, head_mask=head_mask,
                                      past_key_values=past_key_values, inputs_embeds=inputs_embeds,
                                      neighbor_embeds=neighbor_embeds, neighbor_attention_mask=neighbor_attention_mask,
                                      use_cache=use_cache, output_attentions=output_attentions,
                                      output_hidden_states=output_hidden_states, return_dict=True, first_key_valid=first_key_valid,
-                                     cache_capacity=cache_capacity, key_tiles=key_tiles)
+                                     cache_capacity=cache_capacity, key_tiles=key_tiles, kv_cache_dtype=kv_cache_dtype)
         hidden = outputs.last_hidden_state
         if isinstance(past_key_values, DecodeCache):
             if labels is not None:
@@ -1053,6 +1105,11 @@ class MPTForCausalLM(MPTPreTrainedModel):
     def can_generate(self):
         return True
 
+    def _self_attn_projections(self):
+        """The q / k / v / out projections of the frozen layers: what reads and writes the self-attention cache."""
+        return [m for layer in self.model.decoder.layers
+                for m in (layer.self_attn.q_proj, layer.self_attn.k_proj, layer.self_attn.v_proj, layer.self_attn.out_proj)]
+
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
                  eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, inputs_embeds=None,
@@ -1060,7 +1117,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
                  num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, history_ids=None,
                  history_mask=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False, penalty_alpha=0.0,
-                 return_contrastive_trace=False):
+                 return_contrastive_trace=False, kv_cache_dtype=None):
         """Generation with a key/value cache: what the reference's test protocol asks of its wrappers
         (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of every
         layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
@@ -1084,7 +1141,16 @@ class MPTForCausalLM(MPTPreTrainedModel):
         cache of capacity T, a [B*k, max_new_tokens, 2d] tail per layer) and ops.contrastive_select keeps the one that scores best
         against the hidden rows of the row so far.  top_k is then no sampling knob.  input_ids prompts and plain projections only;
         T + max_new_tokens positions are needed, one more than greedy.  The processors and return_step_logits combine with it;
-        return_contrastive_trace: also the per-step candidates / p / penalty / score [B, k] and selected [B]."""
+        return_contrastive_trace: also the per-step candidates / p / penalty / score [B, k] and selected [B].
+        kv_cache_dtype = "fp8" (or torch.float8_e4m3fn; None: off, every path as without it): the frozen layers keep their cached keys
+        and values as e4m3fn codes with one power-of-two scale per (sample, column, key-or-value, head) -- about half the bytes the
+        decode attention reads and the cache holds.  The new token's key and value take part in their own step as
+        projected and are filed quantised; the prefill's attention runs on the unquantised prompt; the neighbor tokens of the gated
+        layers stay in the model's dtype.  For the greedy and sampled loop of one row per prompt, with the processors and
+        return_step_logits; refused with beams, num_return_sequences > 1, prompt-lookup decoding, contrastive search and adapted
+        projections (sampling.check_kv_cache)."""
+        kv_dtype = check_kv_cache("generate()", kv_cache_dtype, num_beams, num_return_sequences, prompt_lookup_num_tokens, penalty_alpha,
+                                  self._self_attn_projections() if kv_cache_dtype is not None else ())
         kc = check_contrastive("generate()", penalty_alpha, top_k, return_contrastive_trace, do_sample, num_beams, num_return_sequences,
                                prompt_lookup_num_tokens, inputs_embeds, return_beam_trace, return_sequences_scores)
         if kc:
@@ -1136,7 +1202,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
             select = GreedyTail(B, dev, eos_token_id, pad_token_id)
         out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
-                  cache_capacity=T if R > 1 or kc else T + n_new - 1)
+                  cache_capacity=T if R > 1 or kc else T + n_new - 1, kv_cache_dtype=kv_dtype)
         cache = out.past_key_values
         if kc:
             cache.beam = BeamState(cache, kc, n_new)           # beam_advance is never called: book.src is the table the select call writes
@@ -1528,7 +1594,7 @@ class CrossAttentionModel(nn.Module):
                  return_sequences_scores=False, return_beam_trace=False, num_return_sequences=1, do_sample=False, temperature=1.0,
                  top_k=0, top_p=1.0, seed=None, sample_u=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
                  suppress_tokens=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False, penalty_alpha=0.0,
-                 return_contrastive_trace=False):
+                 return_contrastive_trace=False, kv_cache_dtype=None):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded): the neighbors are encoded and interleaved once, exactly
         as forward does, then MPTForCausalLM.generate runs the prefill and the cached decode steps.  Returns [B, T + max_new_tokens]
         ids (and the step logits with return_step_logits=True).  num_beams, length_penalty, early_stopping, return_sequences_scores and
@@ -1539,9 +1605,12 @@ class CrossAttentionModel(nn.Module):
         then the new tokens), and its prompt-lookup keywords prompt_lookup_num_tokens, max_matching_ngram_size and
         return_lookup_stats (drafts come from input_ids and the new tokens, never from the neighbors), and its contrastive-search
         keywords penalty_alpha (with top_k as its k) and return_contrastive_trace (the k candidates of a sample read its neighbor
-        tokens once: they stay at B rows)."""
+        tokens once: they stay at B rows), and its kv_cache_dtype ("fp8": the frozen layers' cache as e4m3fn codes; the projected
+        neighbor tokens stay in the model's dtype)."""
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the OPT fork only, not for {type(self.lm).__name__}")
+        check_kv_cache("generate()", kv_cache_dtype, num_beams, num_return_sequences, prompt_lookup_num_tokens, penalty_alpha,
+                       self.lm._self_attn_projections() if kv_cache_dtype is not None else ())
         kc = check_contrastive("generate()", penalty_alpha, top_k, return_contrastive_trace, do_sample, num_beams, num_return_sequences,
                                prompt_lookup_num_tokens, None, return_beam_trace, return_sequences_scores)
         check_sampling("generate()", do_sample, temperature, 0 if kc else top_k, top_p, seed, sample_u, num_beams, num_return_sequences,
@@ -1565,4 +1634,4 @@ class CrossAttentionModel(nn.Module):
                                 no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
                                 prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
                                 return_lookup_stats=return_lookup_stats, penalty_alpha=penalty_alpha,
-                                return_contrastive_trace=return_contrastive_trace)
+                                return_contrastive_trace=return_contrastive_trace, kv_cache_dtype=kv_cache_dtype)

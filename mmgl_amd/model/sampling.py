@@ -1,5 +1,5 @@
-"""The sampling, logits-processor, prompt-lookup and contrastive-search arguments shared by the three generate() methods (MPTForCausalLM / CrossAttentionModel,
-SelfAttentionModel, LlamaNeighborLM): their checks, which need no device, the uniform numbers a sampled generation consumes and the
+"""The sampling, logits-processor, prompt-lookup, contrastive-search and key/value-cache arguments shared by the three generate()
+methods (MPTForCausalLM / CrossAttentionModel, SelfAttentionModel, LlamaNeighborLM): their checks, which need no device, the uniform numbers a sampled generation consumes and the
 per-generation state of the processors.  The selection itself is ops.sample_tokens, the processors are ops.process_logits, one launch
 per decode step each; the loop that makes those calls is generation.decode_loop."""
 import math
@@ -118,7 +118,37 @@ def check_contrastive(who, penalty_alpha, top_k, return_contrastive_trace, do_sa
     return k
 
 
-MAX_SUPPRESS = ops.MAX_BAN - 1          # the ban array of a generation is suppress_tokens followed by the EOS entry
+def check_kv_cache(who, kv_cache_dtype, num_beams=1, num_return_sequences=1, prompt_lookup_num_tokens=0, penalty_alpha=0.0, projections=(),
+                   past_key_values=None):
+    """Validates generate()'s kv_cache_dtype; returns None (off: every path runs exactly as without the keyword) or
+    ops.KV_FP8.  "fp8" / torch.float8_e4m3fn keeps the frozen layers' self-attention cache as e4m3fn codes with power-of-two scales.
+    It belongs to the greedy and sampled loop of one row per prompt (generation.decode_loop: the processors and return_step_logits
+    combine with it); the beam, block and candidate steps read the cache through kernels that have no FP8 form.  `projections`: the
+    q / k / v / out projections of the frozen layers, which must be plain nn.Linear."""
+    if kv_cache_dtype is None:
+        return None
+    if not (kv_cache_dtype == "fp8" or kv_cache_dtype is ops.KV_FP8):
+        raise ValueError(f"{who}: kv_cache_dtype = {kv_cache_dtype!r} is unknown: None (the model's dtype), 'fp8' or torch.float8_e4m3fn "
+                         "(the FP8 key/value cache)")
+    fp8 = f"{who}: kv_cache_dtype = 'fp8' (the FP8 key/value cache)"
+    if int(num_beams) != 1:
+        raise ValueError(f"{fp8} with num_beams = {num_beams} is not implemented (the beam steps read the cache through a kernel of their own)")
+    if int(num_return_sequences) != 1:
+        raise ValueError(f"{fp8} with num_return_sequences = {num_return_sequences} is not implemented (the continuations share the "
+                         "prompt's cache rows through the beam kernel)")
+    if int(prompt_lookup_num_tokens) != 0:
+        raise ValueError(f"{fp8} with prompt_lookup_num_tokens = {prompt_lookup_num_tokens} is not implemented (the verify steps read the "
+                         "cache through the block kernel)")
+    if float(penalty_alpha) != 0.0:
+        raise ValueError(f"{fp8} with penalty_alpha = {penalty_alpha} is not implemented (contrastive search runs on the beam-shared cache)")
+    if any(type(m) is not torch.nn.Linear for m in projections):
+        raise ValueError(f"{fp8} runs plain nn.Linear q / k / v / out projections only (adapted projections, e.g. LoRA, are not implemented)")
+    if past_key_values is not None:
+        raise ValueError(f"{fp8} with a prefix-tuning past_key_values (a key/value prefix) is not implemented")
+    return ops.KV_FP8
+
+
+MAX_SUPPRESS = ops.MAX_BAN - 1         # the ban array of a generation is suppress_tokens followed by the EOS entry
 
 
 def check_processors(who, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id, max_new_tokens,

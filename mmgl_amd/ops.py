@@ -1754,6 +1754,88 @@ def rope_kv_append(qkv, cos_sin_row, kv_col, num_heads, num_kv_heads):
     return qkv
 
 
+# ------------------------------------------------------------------------------------------ FP8 key/value cache (csrc/decode.hip)
+KV_FP8 = torch.float8_e4m3fn            # the code dtype of a quantised cache row; its scales are int8 exponents (include/mmgl_hip.h)
+
+
+def _q8_cache_operands(op, kvq, scale, B, d, num_heads, dtype_like):
+    """The two tensors of a quantised cache for rows of B samples, d = H*D channels: kvq [B, capacity, 2d] e4m3fn codes (or uint8)
+    and scale [B, capacity, 2H] int8, unit column stride, on one device.  Returns (capacity, D)."""
+    if d % num_heads:
+        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {d} and `num_heads`: {num_heads}).")
+    H = int(num_heads)
+    if (kvq.dim() != 3 or scale.dim() != 3 or kvq.dtype not in (KV_FP8, torch.uint8) or scale.dtype != torch.int8
+            or tuple(kvq.shape[::2]) != (B, 2 * d) or tuple(scale.shape) != (B, kvq.shape[1], 2 * H) or kvq.stride(2) != 1 or scale.stride(2) != 1
+            or kvq.device != dtype_like.device or scale.device != dtype_like.device):
+        raise ValueError(f"{op}: incompatible codes{tuple(kvq.shape)}/{kvq.stride()} {kvq.dtype} scale{tuple(scale.shape)}/{scale.stride()} "
+                         f"{scale.dtype} for {B} samples of {H} heads, {d} channels: codes [B, capacity, 2d] {KV_FP8} and scale "
+                         f"[B, capacity, 2H] int8 on {dtype_like.device}")
+    return kvq.shape[1], d // H
+
+
+def kv_quantize(k, v, kvq, scale, num_heads):
+    """Files n key and value rows into columns [0, n) of a quantised cache: k, v [B, n, d] views with unit column stride and common
+    strides (the column slabs of a fused qkv output, or two tensors), kvq [B, capacity, 2d] e4m3fn codes, scale [B, capacity, 2H] int8
+    exponents (key heads first; the format is include/mmgl_hip.h's).  One launch.  Returns (kvq, scale); a refused call leaves them as
+    they were.  Forward only; GPU only."""
+    require_cuda(k, v, kvq, scale)
+    _no_grad_inputs("kv_quantize", k, v)
+    if (k.dim() != 3 or k.shape != v.shape or k.stride() != v.stride() or k.stride(2) != 1 or k.dtype != v.dtype or k.device != v.device):
+        raise ValueError(f"kv_quantize: incompatible k{tuple(k.shape)}/{k.stride()} {k.dtype} v{tuple(v.shape)}/{v.stride()} {v.dtype}")
+    B, n, d = k.shape
+    capacity, D = _q8_cache_operands("kv_quantize", kvq, scale, B, d, num_heads, k)
+    if n > capacity:
+        raise ValueError(f"kv_quantize: {n} rows for a cache of {capacity} columns")
+    code = dtype_code(k)
+    if B == 0 or n == 0:
+        return kvq, scale
+    _lib.call("mmgl_kv_quantize", dict(bytes=2.0 * B * n * d * (k.element_size() + 1)), ptr(k), ptr(v), k.stride(1), k.stride(0), ptr(kvq),
+              kvq.stride(1), kvq.stride(0), ptr(scale), scale.stride(1), scale.stride(0), B, n, int(num_heads), D, code, stream_ptr())
+    return kvq, scale
+
+
+def attn_decode_q8(q, k_new, v_new, kvq, scale, key_valid, num_heads, out=None):
+    """ops.attn_decode on a quantised cache, and the filing of the new token into it, one launch (mmgl_attn_decode_q8_fwd).
+      q [B, d] already scaled; k_new, v_new [B, d]: views with unit column stride and a common row stride (the halves of the k|v
+      projection's dense [B, 2d] output), the new token's key and value: they take part unquantised and always valid;
+      kvq [B, capacity, 2d] e4m3fn codes and scale [B, capacity, 2H] int8 exponents (ops.kv_quantize): columns [0, S) are read,
+      column S < capacity is WRITTEN with the new token's codes and exponents; key_valid [B, S] bool/uint8 view of the cached
+      columns, S >= 1 (a masked cached key weighs nothing).
+    The result equals ops.attn_decode on the dequantised columns followed by the new row, up to summation order.  Returns [B, d]
+    (`out`, a dense tensor of q's dtype, when given: a refused call leaves it and the cache as they were).  Forward only; GPU only."""
+    require_cuda(q, k_new, v_new, kvq, scale, key_valid)
+    _no_grad_inputs("attn_decode_q8", q, k_new, v_new)
+    if (q.dim() != 2 or q.stride(1) != 1 or k_new.dim() != 2 or k_new.shape != q.shape or k_new.shape != v_new.shape
+            or k_new.stride() != v_new.stride() or k_new.stride(1) != 1 or k_new.dtype != q.dtype or v_new.dtype != q.dtype
+            or k_new.device != q.device or v_new.device != q.device):
+        raise ValueError(f"attn_decode_q8: incompatible q{tuple(q.shape)}/{q.stride()} {q.dtype} k_new{tuple(k_new.shape)}/{k_new.stride()} "
+                         f"{k_new.dtype} v_new{tuple(v_new.shape)}/{v_new.stride()} {v_new.dtype}")
+    B, d = q.shape
+    capacity, D = _q8_cache_operands("attn_decode_q8", kvq, scale, B, d, num_heads, q)
+    H = int(num_heads)
+    if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.device != q.device:
+        raise ValueError(f"attn_decode_q8: key_valid{tuple(key_valid.shape)} must be a [{B}, S] mask on {q.device}")
+    S = key_valid.shape[1]
+    if S == 0:
+        raise ValueError("attn_decode_q8: no cached columns")
+    if S >= capacity:
+        raise ValueError(f"attn_decode_q8: the cache is full ({S} cached columns of capacity {capacity}): no column for the new token")
+    code = dtype_code(q)
+    if out is None:
+        out = torch.empty(B, d, dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (B, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError(f"attn_decode_q8: out{tuple(out.shape)} {out.dtype} must be a dense [{B}, {d}] {q.dtype} tensor on {q.device}")
+    key_valid = _as_uint8(key_valid)
+    if key_valid.dtype != torch.uint8:
+        key_valid = key_valid.to(torch.uint8)
+    if key_valid.stride(1) != 1:
+        key_valid = key_valid.contiguous()
+    _lib.call("mmgl_attn_decode_q8_fwd", dict(bytes=2.0 * B * S * (d + H) + 4.0 * B * d * q.element_size()), ptr(q), q.stride(0), ptr(k_new),
+              ptr(v_new), k_new.stride(0), ptr(kvq), ptr_off(kvq, d), kvq.stride(1), kvq.stride(0), ptr(scale), ptr_off(scale, H),
+              scale.stride(1), scale.stride(0), capacity, ptr(key_valid), key_valid.stride(0), ptr(out), B, H, S, D, code, stream_ptr())
+    return out
+
+
 # ------------------------------------------------------------------------------------------ beam search (csrc/decode.hip, csrc/beam.hip)
 MAX_BEAMS = 8
 
