@@ -51,7 +51,15 @@ __device__ __forceinline__ void online_softmax_row(f32x4 (&s)[4], float& m, f32x
     tm = xg_max(tm);
     const float mn = fmaxf(m, tm);
     const float mn2 = (guard_empty && mn == -INFINITY) ? 0.f : mn * LOG2E;      // row without any allowed key yet: keep p = 0
-    const float alpha = __builtin_amdgcn_exp2f(m * LOG2E - mn2);                // m = -inf -> 0
+    // The old maximum scaled as mn2 is -- the ROUNDED product, which the empty asm keeps out of an fma: the p of the earlier tiles
+    // were formed against fl(m LOG2E), so this is their rescale, and exactly 1 while the maximum stands.  Contracted into
+    // fma(m, LOG2E, -mn2) the exponent was the rounding residual of m LOG2E instead of 0: l and o drifted by 2^residual per key
+    // tile (out = o / l did not see it, lse = m + log l did: 1.5e-5 at 65 tiles).
+    float mo2 = m * LOG2E;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(mo2));
+#endif
+    const float alpha = __builtin_amdgcn_exp2f(mo2 - mn2);                      // m = -inf -> 0
     m = mn;
     const f32x4 nm = {-mn2, -mn2, -mn2, -mn2};
 #pragma unroll

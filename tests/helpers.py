@@ -199,6 +199,164 @@ def attn_decode_ref(q, k, v, valid, num_heads):
     return torch.einsum("bhs,bshd->bhd", torch.softmax(sc, -1), v.double().reshape(B, S, num_heads, D)).reshape(B, d)
 
 
+# ------------------------------------------------------------------------------------------ causal self-attention (csrc/selfattn*.hip)
+class SelfAttnRef:
+    """fp64 reference of causal self-attention, forward and backward, on the device the (storage-rounded) operands live on, with the
+    arguments of the kernels: q [B,T,H*D] already scaled, k, v [B,P+T,Hkv*D], key_valid [B,P+T], dout [B,T,H*D].  Key s is allowed
+    for query t iff s <= t + P and key_valid[b,s] (key 0 is always valid: include/mmgl_hip.h); query head h reads kv head h // G.
+    One (sample, head) at a time: T = 4097 needs one set of T x T fp64 matrices at once.
+
+    With p = softmax over the allowed keys, dp = dO V^T, delta = sum_d dO O, Delta_i = sum_d |dO_id| |O_id| and
+    S_i = max_j sum_d |q_id| |k_jd| over the allowed keys, `want` and `mag` of out, lse, dq, dk, dv are
+        out = p V                       mag_out_i = sum_j p_ij |v_j|
+        dv  = p^T dO                    mag_dv_j  = sum_i p_ij |dO_i|
+        dq  = (p (dp - delta)) K        mag_dq_i  = sum_j p_ij (|dp_ij| + Delta_i) |k_j|
+        dk  = (p (dp - delta))^T Q      mag_dk_j  = sum_i p_ij (|dp_ij| + Delta_i) |q_i|      (GQA: summed over the group's query heads)
+
+    Per-element bound (every element is checked), a function of the reference alone, never of the kernel's output:
+        |got - want| <= u |want| + (c + n 2^-24 S_i) mag            u = 2^-8 (bf16), 2^-23 (fp32)
+        |lse_got - lse_want| <= n 2^-24 S_i + 2^-20                 (lse is fp32 for both dtypes)
+    For dk, dv S_i is the largest S of the rows that reach key j (with GQA taken per query head, so the term is the group's sum of
+    S mag), and GQA dk, dv also get u sum_g |per-head want|: each query head's gradient is stored once in the operand dtype before
+    gqa_fold_kernel sums the group.  The count behind the constants:
+      * u |want| is the half ulp of the one round-to-nearest store of the fp32 result.
+      * c counts the roundings of the matrix operands.  bf16, c = 2^-7: P (forward, dV) and dS (dQ, dK) enter the second MFMA rounded
+        to bf16, 2^-8 each, and delta is formed from the bf16-stored `out`, 2^-8 on Delta (hence Delta in mag_dq, mag_dk): 2^-8, counted
+        with a factor 2 of room.  fp32, c = 2^-16: 256 fp32 roundings of 2^-24 on the magnitude sum, SkinnyRef's rationale.
+      * n 2^-24 S_i mag is the fp32 error of a score, which reaches p through the exponent: n roundings of 2^-24 relative to
+        sum_d |q||k| <= S_i.  n = 8 + D / kb: 8 for the LOG2E scale, the subtraction of the scaled maximum (itself a rounded
+        product), exp2 (1 ulp), the sum and the logarithm of l, lse's own store and its LOG2E scale in the backward; D / kb for the
+        fp32 accumulator, rounded once per MFMA k-block of kb products -- kb = 4 for mfma_f32_16x16x4f32 (fp32 operands: 32 chained
+        accumulations at D = 128), kb = 16 for the bf16 MFMAs (32x32x16; a 16x16x32 counts as two).  (The first statement of this
+        bound had n = 8 for every kernel; the fp32 kernels at D >= 32 reached 1.3-1.7 times that in lse on an MI355X, which is the
+        accumulation chain it left out.)
+    The constants are derived, not fitted to a GPU run; c may grow to 2^-6 (bf16) for a rounding that is found and counted, no
+    further.  `allowed` [B,T,P+T] (bool) and `kv_head` (h -> kv head) replace the mask and the head mapping: the deliberately wrong
+    references of tests/test_selfattn_ref_cpu.py."""
+    NAMES = ("out", "lse", "dq", "dk", "dv")
+    RAMP = 0.5                                        # slope of the recency ramp (inputs)
+    U = {torch.bfloat16: 2.0 ** -8, torch.float32: 2.0 ** -23}
+    C = {torch.bfloat16: 2.0 ** -7, torch.float32: 2.0 ** -16}
+
+    @staticmethod
+    def inputs(dtype, B, T, H, D, Hkv=None, P=0, seed=0, ramp=True, device="cpu"):
+        """q, k, v, dout in `dtype`: randn, q scaled by 2 D^-0.5.  ramp: q[..., 0] = 1 in every head and k[..., 0] = 0.5 s for key
+        position s (prefix included): the newest allowed key carries about 40 % of every row's weight at any T, so a key that leaks
+        in or drops out at an edge moves the row far outside the bound (plain randn: weight 1 / t), and the running maximum of the
+        online softmax lies in the last tile."""
+        Hkv = Hkv or H
+        g = torch.Generator().manual_seed(seed)
+        q = torch.randn(B, T, H, D, generator=g) * (2 * D ** -0.5)
+        k, v = torch.randn(B, P + T, Hkv, D, generator=g), torch.randn(B, P + T, Hkv, D, generator=g)
+        dout = torch.randn(B, T, H, D, generator=g)
+        if ramp:
+            q[..., 0] = 1.0
+            k[..., 0] = SelfAttnRef.RAMP * torch.arange(P + T, dtype=torch.float32)[None, :, None]
+        return tuple(t.reshape(B, t.shape[1], -1).to(dtype).to(device) for t in (q, k, v, dout))
+
+    @staticmethod
+    def mask(B, T, layout="M0", L=None, P=0):
+        """key_valid [B,P+T] uint8 (host), the P prefix keys and key 0 always valid.  M0: all valid.  M1: the last sample right-padded
+        to valid length L.  M2: the WikiWeb2M layout prompt | pad | summary | pad in sample 0, hole edges at 70 and T - T // 5."""
+        am = torch.ones(B, P + T, dtype=torch.uint8)
+        if layout == "M1":
+            assert 1 <= L < T
+            am[B - 1, P + L:] = 0
+        elif layout == "M2":
+            assert 70 < T - T // 5 < T - T // 10
+            am[0, P + 70:P + T - T // 5] = 0
+            am[0, P + T - T // 10:] = 0
+            if B > 1:
+                am[1, P + T // 3:] = 0
+        else:
+            assert layout == "M0"
+        return am
+
+    @staticmethod
+    def allowed(key_valid, T, P=0):
+        """[B,T,P+T] bool: key s is allowed for query t iff s <= t + P and key_valid[b,s]."""
+        s = torch.arange(P + T, device=key_valid.device)[None, :]
+        t = torch.arange(T, device=key_valid.device)[:, None]
+        return (s <= t + P)[None] & key_valid.bool()[:, None, :]
+
+    def __init__(self, q, k, v, key_valid, dout, num_heads, num_kv_heads=None, prefix_len=0, allowed=None, kv_head=None):
+        B, T, d = q.shape
+        H, Hkv, P = num_heads, num_kv_heads or num_heads, prefix_len
+        D, G, Tk = d // H, H // Hkv, k.shape[1]
+        assert Tk == P + T and k.shape[2] == Hkv * D
+        kv_head = kv_head or (lambda h: h // G)
+        ok = (SelfAttnRef.allowed(key_valid, T, P) if allowed is None else allowed).to(q.device)
+        q4, k4, v4, g4 = q.reshape(B, T, H, D), k.reshape(B, Tk, Hkv, D), v.reshape(B, Tk, Hkv, D), dout.reshape(B, T, H, D)
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=q.device)
+        self.B, self.T, self.Tk, self.H, self.Hkv, self.D, self.P = B, T, Tk, H, Hkv, D, P
+        self.S = z(B, H, T)
+        self.want = dict(out=z(B, T, H, D), lse=z(B, H, T), dq=z(B, T, H, D), dk=z(B, Tk, Hkv, D), dv=z(B, Tk, Hkv, D))
+        self.mag = {n: torch.zeros_like(self.want[n]) for n in ("out", "dq", "dk", "dv")}
+        self.smag = {n: torch.zeros_like(self.want[n]) for n in ("out", "dq", "dk", "dv")}       # sum of S mag
+        self.habs = {n: torch.zeros_like(self.want[n]) for n in ("dk", "dv")}                    # sum_g |per-head want|
+        for b in range(B):
+            A = ok[b]
+            for h in range(H):
+                hk = kv_head(h)
+                Q, K, V, dO = q4[b, :, h].double(), k4[b, :, hk].double(), v4[b, :, hk].double(), g4[b, :, h].double()
+                S = (Q.abs() @ K.abs().t()).masked_fill_(~A, 0.0).amax(1)
+                p = (Q @ K.t()).masked_fill_(~A, float("-inf"))
+                lse = torch.logsumexp(p, 1)
+                p = p.sub_(lse[:, None]).exp_()
+                O = p @ V
+                dp = dO @ V.t()
+                delta, Delta = (dO * O).sum(1), (dO.abs() * O.abs()).sum(1)
+                w = p * dp.abs().add_(Delta[:, None])
+                ds = dp.sub_(delta[:, None]).mul_(p)
+                Sk = torch.where(A, S[:, None], S.new_zeros(())).amax(0)[:, None]
+                self.S[b, h], self.want["lse"][b, h] = S, lse
+                for n, x, m in (("out", O, p @ V.abs()), ("dq", ds @ K, w @ K.abs())):
+                    self.want[n][b, :, h], self.mag[n][b, :, h], self.smag[n][b, :, h] = x, m, S[:, None] * m
+                for n, x, m in (("dk", ds.t() @ Q, w.t() @ Q.abs()), ("dv", p.t() @ dO, p.t() @ dO.abs())):
+                    self.want[n][b, :, hk] += x
+                    self.mag[n][b, :, hk] += m
+                    self.smag[n][b, :, hk] += Sk * m
+                    self.habs[n][b, :, hk] += x.abs()
+                del p, dp, w, ds
+
+    def bound(self, name, dtype):
+        """The bound of tensor `name`, shaped like want[name] ([B,rows,heads,D]; lse [B,H,T])."""
+        n = (8 + self.D // (16 if dtype == torch.bfloat16 else 4)) * 2.0 ** -24
+        if name == "lse":
+            return n * self.S + 2.0 ** -20
+        b = SelfAttnRef.U[dtype] * self.want[name].abs() + SelfAttnRef.C[dtype] * self.mag[name] + n * self.smag[name]
+        if name in self.habs and self.Hkv < self.H:
+            b = b + SelfAttnRef.U[dtype] * self.habs[name]
+        return b
+
+    def outside(self, other, name, dtype):
+        """From two references alone: the elements (bool, shaped like want[name]) at which `other` -- a deliberately wrong reference
+        of the same call -- leaves this one's bound."""
+        return (other.want[name] - self.want[name]).abs() > self.bound(name, dtype)
+
+    def check(self, got, what, group="", dtype=None):
+        """Asserts the bound on every element of got = (out, lse, dq, dk, dv) (any may be None: skipped); prints the largest
+        err / bound of each and returns them by name."""
+        dtype = dtype or got[0].dtype
+        ratios, failed = {}, []
+        for name, x in zip(SelfAttnRef.NAMES, got):
+            if x is None:
+                continue
+            want = self.want[name]
+            assert torch.isfinite(x.float()).all(), f"{what} {name}: non-finite result"
+            err, bound = (x.detach().double().reshape(want.shape) - want).abs(), self.bound(name, dtype)
+            ratios[name] = (err / bound.clamp_min(1e-300)).max().item()
+            print(f"[bound {group}] {what} {name}: max err/bound {ratios[name]:.3f}")
+            bad = (err > bound).nonzero()
+            if bad.numel():
+                # (sample, head, row): lse is [B,H,T], the others [B,rows,heads,D]
+                at = bad[:, :3] if name == "lse" else bad[:, [0, 2, 1]]
+                failed.append(f"{what} {name}: {bad.shape[0]} of {err.numel()} elements outside the bound (max err/bound "
+                              f"{ratios[name]:.2f}); (sample, head, row) {at.unique(dim=0).tolist()[:12]}")
+        assert not failed, "\n".join(failed)
+        return ratios
+
+
 # ------------------------------------------------------------------------------------------ tiny model builders
 def tiny_opt_config(pre_ln=True, proj=None, dropout=0.1):
     from transformers import OPTConfig
