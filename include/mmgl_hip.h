@@ -54,7 +54,10 @@ int mmgl_version(void);
  *   out       [B,T,H*D]
  *   lse       [B,H,T] fp32 log-sum-exp of the masked scores (saved for backward)
  * A sample with no valid key yields the uniform distribution over its S keys (the reference's
- * finfo.min clamp, :226-228), never NaN.  D in {16,32,64,128}; S <= 256.
+ * finfo.min clamp, :226-228), never NaN; its lse is m + log l with m = 0, i.e. log S (the backward
+ * never reads it for such a sample).  D in {16,32,64,128}; S <= 256; fp32 with D = 128 serves
+ * S <= 128 (K and V of 256 keys would be 256 KiB of LDS): beyond, both entry points return
+ * MMGL_ERR_UNSUPPORTED before any launch.
  * No attention dropout here (:256): OPT's attention_dropout is 0.0, where it is the identity; a config that asks for it (or for a
  * head mask / output_attentions) is routed to mmgl_attn_general_* below by the host mirror.
  */

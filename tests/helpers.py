@@ -357,6 +357,134 @@ class SelfAttnRef:
         return ratios
 
 
+# ------------------------------------------------------------------------------------------ masked cross-attention (csrc/xattn.hip)
+class XAttnRef(SelfAttnRef):
+    """fp64 reference of mmgl_xattn_fwd / mmgl_xattn_bwd on the device the (storage-rounded) operands live on, with the arguments of
+    the ABI: q [B,T,H*D] already scaled, k, v [B,S,H*D], key_valid [B,S], dout [B,T,H*D].  One (sample, head) at a time.
+
+    Semantics (oracle.lm_ref.expand_mask + attention_core):
+      * a sample with a valid key: p = softmax over its valid keys; a masked key gets exactly zero dk and dv.
+      * a sample with no valid key: p = 1 / S on all S keys (every score clamps to finfo.min), and dS is multiplied by 0.5 -- autograd's
+        split at the torch.maximum tie -- so dq and dk are halved, dv is not.  lse is the kernel's m + log l with m = 0: log S
+        (include/mmgl_hip.h; the oracle's finfo.min + log S is another convention for the same row).
+
+    With dp = dO V^T, delta = sum_j p dp, Delta_i = sum_j p_ij |dp_ij| and S_i = max_j sum_d |q_id| |k_jd| over the valid keys (0 for a
+    sample with none: no score is formed), `want` and `mag` of out, lse, dq, dk, dv are those of SelfAttnRef with the weight
+    w = tie p (|dp| + Delta):
+        out = p V                 mag_out = p |V|              dq = (tie p (dp - delta)) K        mag_dq = w |K|
+        dv  = p^T dO              mag_dv  = p^T |dO|           dk = (tie p (dp - delta))^T Q      mag_dk = w^T |Q|
+    (Delta is sum p |dp| here, not sum |dO| |O|: these kernels form delta from p and dP in fp32 and never read `out` back.)
+
+    Per-element bound (every element is checked), a function of the reference alone, never of the kernel's output:
+        |got - want| <= u |want| + (c + n 2^-24 (S_i + ln S)) mag
+        |lse_got - lse_want| <= n 2^-24 (S_i + ln S) + 2^-20
+    u, c and n = 8 + D / kb are SelfAttnRef's, for its reasons: P and dS enter the second MFMA rounded to bf16, the score's fp32 error
+    reaches p through the exponent, the accumulator rounds once per MFMA k-block.  The ln S term is this file's: the backward forms
+    p = exp2(s LOG2E - lse LOG2E), two rounded products whose error is relative to |lse| <= S_i + ln S, not to the score alone.
+    For dk / dv, S_i is the largest of the rows that reach the key: every row of the (sample, head).
+
+    The keyword arguments build the deliberately wrong references of tests/test_xattn_ref_cpu.py: `allowed` [B,S] replaces the mask;
+    `exists` [B,S] the keys a sample without a valid key spreads over; `uniform_n` (sample -> int) the count it divides by; `tie` the
+    factor on dS there; `kv_head` (h -> head whose keys and values head h reads); `rows_kv` [T] the query rows that reach dk / dv."""
+    EDGES = (0, 15, 16, 31, 32, 63, 64, 127, 128)
+    BOOST, FACTOR = 4.0, 16.0        # k[edge key, 0] and the factor on dout's edge rows
+
+    @staticmethod
+    def edges(n):
+        """The edge indices of a dimension of n: EDGES, n - 2, n - 1 and the first index of the last group of 32 (192 at n = 200: no
+        member of EDGES, and the first key of the last dK / dV wave or key block), where they exist."""
+        return sorted({e for e in XAttnRef.EDGES + (n - 2, n - 1, 32 * ((n - 1) // 32)) if 0 <= e < n})
+
+    @staticmethod
+    def inputs(dtype, B, T, S, H, D, seed=0, edge=True, device="cpu"):
+        """q, k, v, dout in `dtype`: randn, q scaled by 2 D^-0.5.  edge: q[..., 0] = 1 in every head, k[s, 0] = BOOST on the edge keys
+        and 0 elsewhere -- at most 12 keys share e^4 : 1 against the others, so an edge key carries several percent of every row at any
+        S (plain randn at S = 256: 0.4 %) -- and dout times FACTOR on the edge rows, so a query row lost from dk / dv shows."""
+        g = torch.Generator().manual_seed(seed)
+        q = torch.randn(B, T, H, D, generator=g) * (2 * D ** -0.5)
+        k, v = torch.randn(B, S, H, D, generator=g), torch.randn(B, S, H, D, generator=g)
+        dout = torch.randn(B, T, H, D, generator=g)
+        if edge:
+            q[..., 0] = 1.0
+            k[..., 0] = 0.0
+            k[:, XAttnRef.edges(S), :, 0] = XAttnRef.BOOST
+            dout[:, XAttnRef.edges(T)] *= XAttnRef.FACTOR
+        return tuple(t.reshape(B, t.shape[1], -1).to(dtype).to(device) for t in (q, k, v, dout))
+
+    @staticmethod
+    def mask(B, S, first=0):
+        """key_valid [B,S] uint8 (host).  Sample b has layout (first + b) % 3:  0 all valid;  1 holed: key S - 1, the edge keys 15, 32,
+        64 and 128 and every key s % 5 == 3 masked (key 0 stays, and S = 1 keeps its one key);  2 no valid key."""
+        am = torch.ones(B, S, dtype=torch.uint8)
+        s = torch.arange(S)
+        for b in range(B):
+            lay = (first + b) % 3
+            if lay == 1 and S > 1:
+                am[b, (s % 5 == 3) | (s == S - 1) | (s == 15) | (s == 32) | (s == 64) | (s == 128)] = 0
+                am[b, 0] = 1
+            elif lay == 2:
+                am[b] = 0
+        return am
+
+    def __init__(self, q, k, v, key_valid, dout, num_heads, allowed=None, exists=None, uniform_n=None, tie=0.5, kv_head=None, rows_kv=None):
+        B, T, d = q.shape
+        H, S = num_heads, k.shape[1]
+        D = d // H
+        assert k.shape == v.shape == (B, S, d) and dout.shape == q.shape and key_valid.shape == (B, S)
+        dev = q.device
+        ok = (key_valid if allowed is None else allowed).to(dev).bool()
+        ex = torch.ones(B, S, dtype=torch.bool, device=dev) if exists is None else exists.to(dev).bool()
+        uniform_n = uniform_n or (lambda b: S)
+        kv_head = kv_head or (lambda h: h)
+        rk = torch.ones(T, dtype=torch.float64, device=dev) if rows_kv is None else rows_kv.to(dev).double()
+        q4, k4, v4, g4 = q.reshape(B, T, H, D), k.reshape(B, S, H, D), v.reshape(B, S, H, D), dout.reshape(B, T, H, D)
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
+        self.B, self.T, self.Tk, self.H, self.Hkv, self.D, self.P = B, T, S, H, H, D, 0
+        self.S = z(B, H, T)                               # S_i + ln S: what a score rounding is relative to
+        self.want = dict(out=z(B, T, H, D), lse=z(B, H, T), dq=z(B, T, H, D), dk=z(B, S, H, D), dv=z(B, S, H, D))
+        self.mag = {n: torch.zeros_like(self.want[n]) for n in ("out", "dq", "dk", "dv")}
+        self.smag = {n: torch.zeros_like(self.want[n]) for n in ("out", "dq", "dk", "dv")}
+        self.habs = {}
+        lnS = float(np.log(S))
+        for b in range(B):
+            A = ok[b]
+            live = bool(A.any())
+            for h in range(H):
+                hk = kv_head(h)
+                Q, K, V, dO = q4[b, :, h].double(), k4[b, :, hk].double(), v4[b, :, hk].double(), g4[b, :, h].double()
+                if live:
+                    Si = (Q.abs() @ K.abs().t())[:, A].amax(1) + lnS
+                    sc = (Q @ K.t()).masked_fill_(~A[None, :], float("-inf"))
+                    lse = torch.logsumexp(sc, 1)
+                    p, f = sc.sub_(lse[:, None]).exp_(), 1.0
+                else:
+                    n = uniform_n(b)
+                    Si = z(T) + lnS
+                    lse = z(T) + float(np.log(n))
+                    p, f = (ex[b].double() / n)[None, :].expand(T, S).contiguous(), tie
+                O = p @ V
+                dp = dO @ V.t()
+                delta, Delta = (p * dp).sum(1), (p * dp.abs()).sum(1)
+                w = p * dp.abs().add(Delta[:, None]) * f
+                ds = dp.sub(delta[:, None]).mul_(p).mul_(f)
+                Sk = Si.max()
+                self.S[b, h], self.want["lse"][b, h] = Si, lse
+                for n, x, m in (("out", O, p @ V.abs()), ("dq", ds @ K, w @ K.abs())):
+                    self.want[n][b, :, h], self.mag[n][b, :, h], self.smag[n][b, :, h] = x, m, Si[:, None] * m
+                pk, dsk, wk = p * rk[:, None], ds * rk[:, None], w * rk[:, None]
+                for n, x, m in (("dk", dsk.t() @ Q, wk.t() @ Q.abs()), ("dv", pk.t() @ dO, pk.t() @ dO.abs())):
+                    self.want[n][b, :, hk] += x
+                    self.mag[n][b, :, hk] += m
+                    self.smag[n][b, :, hk] += Sk * m
+
+    def bound(self, name, dtype):
+        """The bound of tensor `name`, shaped like want[name] ([B,rows,H,D]; lse [B,H,T])."""
+        n = (8 + self.D // (16 if dtype == torch.bfloat16 else 4)) * 2.0 ** -24
+        if name == "lse":
+            return n * self.S + 2.0 ** -20
+        return SelfAttnRef.U[dtype] * self.want[name].abs() + SelfAttnRef.C[dtype] * self.mag[name] + n * self.smag[name]
+
+
 # ------------------------------------------------------------------------------------------ tiny model builders
 def tiny_opt_config(pre_ln=True, proj=None, dropout=0.1):
     from transformers import OPTConfig
