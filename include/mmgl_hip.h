@@ -756,6 +756,23 @@ int mmgl_attn_decode_q8_fwd(const void* q, int ldq, const void* k_new, const voi
                             int capacity, const uint8_t* key_valid, int ld_valid, void* out, int B, int H, int S, int D, int dtype,
                             void* stream);
 
+/* mmgl_attn_decode_gqa_q8_fwd: mmgl_attn_decode_q8_fwd over a cache of Hkv <= H key/value heads (the Llama-family LM; H % Hkv == 0,
+ * query head h reads key/value head h / (H / Hkv)).  The code and scale rows are the format above with H replaced by Hkv:
+ * codes [B, capacity, 2 Hkv D] bytes, scale [B, capacity, 2 Hkv] int8 (v_codes = k_codes + Hkv*D, v_scale = k_scale + Hkv in a row).
+ *   q, out        [B, H*D] as above;  k_new, v_new  [B, Hkv*D] of T, row stride ld_new: unquantised and always valid in the
+ *                 attention, filed as codes and exponents at column S by the same launch
+ *   One workgroup per (sample, key/value head, block of at most 4 query heads of that head's group): every 16-byte load of 16 codes
+ *   is issued once per block, dequantised once and scored against the block's query heads from registers; nothing is expanded to H
+ *   heads in memory.  G = H / Hkv > 4 takes ceil(G / 4) blocks: every block folds the new key and value unquantised, block 0 alone
+ *   files column S -- exactly one writer per (sample, key/value head), and no workgroup reads column S.  A sample whose cached keys
+ *   are all masked returns the new value row of its key/value head for every query head of the group, bitwise.  Scales, softmax,
+ *   merge order, determinism and every refusal as mmgl_attn_decode_q8_fwd (the strides are measured against Hkv-head rows), plus
+ *   Hkv < 1 and H % Hkv != 0: MMGL_ERR_INVALID.  A refused call writes nothing.  Plain vector stores only. */
+int mmgl_attn_decode_gqa_q8_fwd(const void* q, int ldq, const void* k_new, const void* v_new, int ld_new, void* k_codes, void* v_codes,
+                                int ld_code, size_t batch_stride_code, void* k_scale, void* v_scale, int ld_scale,
+                                size_t batch_stride_scale, int capacity, const uint8_t* key_valid, int ld_valid, void* out, int B, int H,
+                                int Hkv, int S, int D, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

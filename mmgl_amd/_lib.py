@@ -109,6 +109,7 @@ SIGNATURES = {
     "mmgl_contrastive_select": (I, [P, Z, P, Z, Z, P, Z, I, P, P, Z, F, I, I, P, Z, P, Z, P, L, L, P, P, P, P, P, P, Z, I, I, I, I, I, P]),
     "mmgl_kv_quantize": (I, [P, P, I, Z, P, I, Z, P, I, Z, I, I, I, I, I, P]),
     "mmgl_attn_decode_q8_fwd": (I, [P, I, P, P, I, P, P, I, Z, P, P, I, Z, I, P, I, P, I, I, I, I, I, P]),
+    "mmgl_attn_decode_gqa_q8_fwd": (I, [P, I, P, P, I, P, P, I, Z, P, P, I, Z, I, P, I, P, I, I, I, I, I, I, P]),
 }
 
 _lib = None

@@ -51,6 +51,11 @@
 // 16-byte load, the scales folded into the dot product and the softmax weight; the new token's key and value come dense, count
 // unquantised, and are filed as codes by the same launch.
 //
+// mmgl_attn_decode_gqa_q8_fwd (attn_decode_gqa_q8_kernel).  The FP8 cache of the Llama-family LM: code rows of Hkv <= H key/value heads.
+// attn_decode_q8_kernel with the workgroups of attn_decode_gqa_kernel -- one per (sample, key/value head, block of at most 4 query heads
+// of its group): a 16-byte load of codes is issued and dequantised once and scored against the block's query heads from registers.
+// Every block folds the new token unquantised; block 0 of a group alone files it as codes.
+//
 // mmgl_rope_kv_append (rope_kv_append_kernel).  The new token's q | k | v row: q rotated in place, k rotated into the token's cache column,
 // v copied there -- one launch where separate projections and rotations would take four (the step is launch-bound).
 #include "common.h"
@@ -1505,6 +1510,225 @@ int launch_attn_decode_q8(const Q8AttnArgs& a, hipStream_t st) {
     return MMGL_OK;
 }
 
+// mmgl_attn_decode_gqa_q8_fwd: attn_decode_q8_kernel over a cache of Hkv <= H key/value heads, with the workgroups of
+// attn_decode_gqa_kernel: one per (sample, key/value head, block of NQ <= Q8_GQA_HEADS of the G = H / Hkv query heads that read it).
+// Lane layout, trip constants and descriptors are attn_decode_q8_kernel's (16 codes per lane and 16-byte load).  A trip decodes each of
+// its AD_UNROLL keys ONCE into 16 fp32 registers and scores it against the NQ queries from registers, then does the same with the
+// values: the 16 conversions per load are paid once per NQ dot products.  The block is capped at 4 heads, not the bf16 kernel's 8:
+// qf and acc cost 32 registers per head at 16 codes per lane (DESIGN.md 4.19 has the table).  A block with nq < NQ heads repeats its
+// last head and stores nq rows.  The new token: lane group 0 of the last wave of EVERY block folds the unquantised key and value of the
+// kv head into its NQ states; block 0 of the group alone quantises them and files column S -- one writer per (sample, kv head).
+constexpr int Q8_GQA_HEADS = 4;
+
+// The second launch bound (waves per SIMD) holds the allocation to 168 registers for NQ = 1 and to 256 for NQ = 2, where the compiler
+// left alone spends 257 (fp32, D = 64) and halves the waves that keep loads in flight.  NQ = 4 is left alone: it fits 2 waves
+// everywhere but bf16 D = 16 (260 registers, 1 wave), and a bound there costs scratch.
+template <typename T, int D, int NQ>
+__global__ __launch_bounds__(AD_WAVES * WAVE, NQ == 1 ? 3 : NQ == 2 ? 2 : 1) void attn_decode_gqa_q8_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ kn,
+                                                                             const T* __restrict__ vn, int ld_new, uint8_t* kc, uint8_t* vc,
+                                                                             int ld_code, size_t bs_code, int8_t* ks, int8_t* vs, int ld_scale,
+                                                                             size_t bs_scale, const uint8_t* __restrict__ valid, int ld_valid,
+                                                                             T* __restrict__ out, int H, int Hkv, int S, int qpb, int nblk) {
+    constexpr int LPK = D / Q8_VEC;                 // lanes per key
+    constexpr int KPI = WAVE / LPK;                 // keys per wave and load instruction
+    constexpr float NEG = -FLT_MAX;
+    __shared__ float sm_m[AD_WAVES][NQ], sm_l[AD_WAVES][NQ], sm_o[AD_WAVES][NQ][D];
+
+    const int G = H / Hkv;
+    const int qb = blockIdx.x % nblk, kvh = (blockIdx.x / nblk) % Hkv, b = blockIdx.x / (nblk * Hkv);
+    const int h0 = kvh * G + qb * qpb, nq = min(qpb, G - qb * qpb);        // query heads h0 .. h0 + nq - 1
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane % LPK, kk = lane / LPK;
+
+    float qf[NQ][Q8_VEC];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) load16<T>(q + (size_t)b * ldq + (h0 + min(j, nq - 1)) * D + c * Q8_VEC, qf[j]);
+    uint8_t* kb = kc + b * bs_code + kvh * D;
+    uint8_t* vb = vc + b * bs_code + kvh * D;
+    int8_t* ksb = ks + b * bs_scale + kvh;
+    int8_t* vsb = vs + b * bs_scale + kvh;
+    // branch-free loads: keys past S fall outside the descriptors
+    const uint32_t slab = (uint32_t)((size_t)(S - 1) * ld_code + D), row_bytes = (uint32_t)ld_code;
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(kb, slab);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(vb, slab);
+    const uint8_t* mb = valid + (size_t)b * ld_valid;
+
+    float m[NQ], l[NQ], acc[NQ][Q8_VEC];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        m[j] = NEG;
+        l[j] = 0.f;
+#pragma unroll
+        for (int e = 0; e < Q8_VEC; ++e) acc[j][e] = 0.f;
+    }
+
+    for (int base = w * KPI; base < S; base += AD_WAVES * KPI * AD_UNROLL) {          // wave-uniform trip count
+        u32x4 kr[AD_UNROLL], vr[AD_UNROLL];
+        int ke[AD_UNROLL], ve[AD_UNROLL];
+        bool ok[AD_UNROLL], in[AD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            const int s = base + u * AD_WAVES * KPI + kk;
+            in[u] = s < S;
+            const uint32_t off = in[u] ? (uint32_t)s * row_bytes + (uint32_t)(c * Q8_VEC) : OOB;
+            kr[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+            vr[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+            const int sc = min(s, S - 1);
+            ok[u] = mb[sc] != 0;
+            ke[u] = ksb[(size_t)sc * ld_scale];
+            ve[u] = vsb[(size_t)sc * ld_scale];
+        }
+        // each key is dequantised once and scored against the NQ queries
+        float sc[NQ][AD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            float kf[Q8_VEC];
+            q8_decode(kr[u], kf);
+            const float kscale = q8_pow2(ke[u]);
+#pragma unroll
+            for (int j = 0; j < NQ; ++j) {
+                float dot = 0.f;
+#pragma unroll
+                for (int e = 0; e < Q8_VEC; ++e) dot += qf[j][e] * kf[e];
+                dot = group_sum<LPK>(dot) * kscale;
+                sc[j][u] = ok[u] ? dot : NEG;
+            }
+        }
+        // the trip's AD_UNROLL keys enter each online softmax together: one rescale of a state per trip
+        float pv[NQ][AD_UNROLL];
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            float mn = m[j];
+#pragma unroll
+            for (int u = 0; u < AD_UNROLL; ++u)
+                if (in[u]) mn = fmaxf(mn, sc[j][u]);
+            const float corr = __expf(m[j] - mn);
+            float ps = 0.f;
+#pragma unroll
+            for (int u = 0; u < AD_UNROLL; ++u) {
+                const float p = in[u] ? __expf(sc[j][u] - mn) : 0.f;  // a key past S weighs nothing, also in a group of masked keys
+                ps += p;
+                pv[j][u] = in[u] ? p * q8_pow2(ve[u]) : 0.f;          // the exponent of a key past S is another column's
+            }
+            l[j] = l[j] * corr + ps;
+#pragma unroll
+            for (int e = 0; e < Q8_VEC; ++e) acc[j][e] *= corr;
+            m[j] = mn;
+        }
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            float vf[Q8_VEC];
+            q8_decode(vr[u], vf);
+#pragma unroll
+            for (int j = 0; j < NQ; ++j)
+#pragma unroll
+                for (int e = 0; e < Q8_VEC; ++e) acc[j][e] += pv[j][u] * vf[e];
+        }
+    }
+    // the new token: scored and weighed as it came by every block, filed as codes by block 0 of the group
+    if (w == AD_WAVES - 1 && kk == 0) {
+        float kf[Q8_VEC], vf[Q8_VEC];
+        load16<T>(kn + (size_t)b * ld_new + kvh * D + c * Q8_VEC, kf);
+        load16<T>(vn + (size_t)b * ld_new + kvh * D + c * Q8_VEC, vf);
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < Q8_VEC; ++e) dot += qf[j][e] * kf[e];
+            dot = group_sum<LPK>(dot);
+            const float mn = fmaxf(m[j], dot);
+            const float corr = __expf(m[j] - mn), p = __expf(dot - mn);
+            l[j] = l[j] * corr + p;
+#pragma unroll
+            for (int e = 0; e < Q8_VEC; ++e) acc[j][e] = acc[j][e] * corr + p * vf[e];
+            m[j] = mn;
+        }
+        if (qb == 0) {
+            int ek, ev;
+            const u32x4 kq = q8_quantize<LPK>(kf, ek), vq = q8_quantize<LPK>(vf, ev);
+            const size_t at = (size_t)S * ld_code + c * Q8_VEC;
+            *(u32x4*)(kb + at) = kq;
+            *(u32x4*)(vb + at) = vq;
+            if (c == 0) {
+                ksb[(size_t)S * ld_scale] = (int8_t)ek;
+                vsb[(size_t)S * ld_scale] = (int8_t)ev;
+            }
+        }
+    }
+    // per query head: merge the lane groups of the wave (fixed butterfly), then the waves in order
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+#pragma unroll
+        for (int o = LPK; o < WAVE; o <<= 1) {
+            const float m2 = __shfl_xor(m[j], o), l2 = __shfl_xor(l[j], o);
+            const float mn = fmaxf(m[j], m2);
+            const float c1 = __expf(m[j] - mn), c2 = __expf(m2 - mn);
+            l[j] = l[j] * c1 + l2 * c2;
+#pragma unroll
+            for (int e = 0; e < Q8_VEC; ++e) acc[j][e] = acc[j][e] * c1 + __shfl_xor(acc[j][e], o) * c2;
+            m[j] = mn;
+        }
+        if (lane < LPK) {
+#pragma unroll
+            for (int e = 0; e < Q8_VEC; ++e) sm_o[w][j][c * Q8_VEC + e] = acc[j][e];
+            if (lane == 0) { sm_m[w][j] = m[j]; sm_l[w][j] = l[j]; }
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < nq * D; idx += AD_WAVES * WAVE) {
+        const int j = idx / D, x = idx % D;
+        float mm = sm_m[0][j];
+#pragma unroll
+        for (int i = 1; i < AD_WAVES; ++i) mm = fmaxf(mm, sm_m[i][j]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int i = 0; i < AD_WAVES; ++i) {
+            const float ci = __expf(sm_m[i][j] - mm);
+            ll += sm_l[i][j] * ci;
+            o += sm_o[i][j][x] * ci;
+        }
+        out[((size_t)b * H + h0 + j) * D + x] = Elem<T>::from_f(o / ll);
+    }
+}
+
+template <typename T, int D>
+int attn_decode_gqa_q8_nq(const Q8AttnArgs& a, int Hkv, hipStream_t st) {
+    const int G = a.H / Hkv, nblk = cdiv(G, Q8_GQA_HEADS), qpb = cdiv(G, nblk);     // G > 4: further blocks, of equal size up to one head
+    const dim3 grid(a.B * Hkv * nblk), block(AD_WAVES * WAVE);
+#define MMGL_GQA_Q8_DECODE(NQ)                                                                                                            \
+    hipLaunchKernelGGL((attn_decode_gqa_q8_kernel<T, D, NQ>), grid, block, 0, st, (const T*)a.q, a.ldq, (const T*)a.kn, (const T*)a.vn,   \
+                       a.ld_new, a.kc, a.vc, a.ld_code, a.bs_code, a.ks, a.vs, a.ld_scale, a.bs_scale, a.valid, a.ld_valid, (T*)a.out, a.H, \
+                       Hkv, a.S, qpb, nblk)
+    if (qpb == 1) MMGL_GQA_Q8_DECODE(1);
+    else if (qpb == 2) MMGL_GQA_Q8_DECODE(2);
+    else MMGL_GQA_Q8_DECODE(4);
+#undef MMGL_GQA_Q8_DECODE
+    MMGL_CHECK_LAUNCH("mmgl_attn_decode_gqa_q8_fwd");
+    return MMGL_OK;
+}
+
+// what every single-query attention entry point over a cache of codes refuses (Hkv key/value heads in the cache rows, H query heads),
+// after its own test of the sizes
+int check_attn_q8(const char* who, const Q8AttnArgs& a, int Hkv, int capacity, int D, int dtype) {
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "%s: bad dtype %d", who, dtype);
+    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: head_dim %d (16, 32, 64, 128)", who, D);
+    const int vec = dtype == MMGL_BF16 ? 8 : 4;
+    if (a.ldq % vec || a.ld_new % vec || a.ld_code % 16 || a.bs_code % 16)
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: strides (%d, %d, %d, %zu) must be multiples of 16 bytes", who, a.ldq, a.ld_new, a.ld_code, a.bs_code);
+    MMGL_CHECK_ARG(a.q && a.kn && a.vn && a.kc && a.vc && a.ks && a.vs && a.valid && a.out, "%s: null pointer", who);
+    const long long hd = (long long)a.H * D, kd = (long long)Hkv * D;
+    MMGL_CHECK_ARG(a.ldq >= hd && a.ld_new >= kd && a.ld_code >= kd && a.ld_scale >= Hkv && a.ld_valid >= a.S &&
+                       (a.B == 1 || (a.bs_code >= (size_t)(capacity - 1) * a.ld_code + (size_t)kd &&
+                                     a.bs_scale >= (size_t)(capacity - 1) * a.ld_scale + (size_t)Hkv)),
+                   "%s: strides (%d, %d, %d, %zu, %d, %zu, %d) smaller than the rows", who, a.ldq, a.ld_new, a.ld_code, a.bs_code, a.ld_scale,
+                   a.bs_scale, a.ld_valid);
+    if (!aligned16(a.q) || !aligned16(a.kn) || !aligned16(a.vn) || !aligned16(a.kc) || !aligned16(a.vc))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: q, k_new, v_new, k_codes and v_codes must be 16-byte aligned", who);
+    if ((size_t)(capacity - 1) * a.ld_code + D >= (1ull << 31))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "%s: a sample's cache rows span 2 GiB or more (capacity=%d, ld_code=%d)", who, capacity, a.ld_code);
+    return MMGL_OK;
+}
+
 // what the two skinny GEMM entry points refuse alike (their sizes and leading dimensions differ by the adapter's).  ptrs: every
 // required pointer is set; hint: the way out of M > 64 that `who` offers
 int check_skinny(const char* who, const char* hint, bool ptrs, int M, int act, int dtype) {
@@ -1771,26 +1995,27 @@ extern "C" int mmgl_attn_decode_q8_fwd(const void* q, int ldq, const void* k_new
                                        size_t batch_stride_scale, int capacity, const uint8_t* key_valid, int ld_valid, void* out, int B, int H,
                                        int S, int D, int dtype, void* stream) {
     MMGL_CHECK_ARG(B >= 1 && H >= 1 && S >= 1 && capacity > S, "mmgl_attn_decode_q8_fwd: bad sizes B=%d H=%d S=%d capacity=%d", B, H, S, capacity);
-    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_attn_decode_q8_fwd: bad dtype %d", dtype);
-    if (D != 16 && D != 32 && D != 64 && D != 128) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_q8_fwd: head_dim %d (16, 32, 64, 128)", D);
-    const int vec = dtype == MMGL_BF16 ? 8 : 4;
-    if (ldq % vec || ld_new % vec || ld_code % 16 || batch_stride_code % 16)
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_q8_fwd: strides (%d, %d, %d, %zu) must be multiples of 16 bytes", ldq, ld_new, ld_code,
-                  batch_stride_code);
-    MMGL_CHECK_ARG(q && k_new && v_new && k_codes && v_codes && k_scale && v_scale && key_valid && out, "mmgl_attn_decode_q8_fwd: null pointer");
-    const long long hd = (long long)H * D;
-    MMGL_CHECK_ARG(ldq >= hd && ld_new >= hd && ld_code >= hd && ld_scale >= H && ld_valid >= S &&
-                       (B == 1 || (batch_stride_code >= (size_t)(capacity - 1) * ld_code + (size_t)hd &&
-                                   batch_stride_scale >= (size_t)(capacity - 1) * ld_scale + (size_t)H)),
-                   "mmgl_attn_decode_q8_fwd: strides (%d, %d, %d, %zu, %d, %zu, %d) smaller than the rows", ldq, ld_new, ld_code,
-                   batch_stride_code, ld_scale, batch_stride_scale, ld_valid);
-    if (!aligned16(q) || !aligned16(k_new) || !aligned16(v_new) || !aligned16(k_codes) || !aligned16(v_codes))
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_q8_fwd: q, k_new, v_new, k_codes and v_codes must be 16-byte aligned");
-    if ((size_t)(capacity - 1) * ld_code + D >= (1ull << 31))
-        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_q8_fwd: a sample's cache rows span 2 GiB or more (capacity=%d, ld_code=%d)", capacity, ld_code);
     const Q8AttnArgs a{q, k_new, v_new, (uint8_t*)k_codes, (uint8_t*)v_codes, (int8_t*)k_scale, (int8_t*)v_scale, key_valid, out,
                        ldq, ld_new, ld_code, ld_scale, ld_valid, B, H, S, batch_stride_code, batch_stride_scale};
+    const int bad = check_attn_q8(__func__, a, H, capacity, D, dtype);
+    if (bad) return bad;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(launch_attn_decode_q8, bf16, D, a, st);
     RETURN_BY_HEAD_DIM(launch_attn_decode_q8, float, D, a, st);
+}
+
+extern "C" int mmgl_attn_decode_gqa_q8_fwd(const void* q, int ldq, const void* k_new, const void* v_new, int ld_new, void* k_codes, void* v_codes,
+                                           int ld_code, size_t batch_stride_code, void* k_scale, void* v_scale, int ld_scale,
+                                           size_t batch_stride_scale, int capacity, const uint8_t* key_valid, int ld_valid, void* out, int B,
+                                           int H, int Hkv, int S, int D, int dtype, void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && H >= 1 && Hkv >= 1 && S >= 1 && capacity > S, "mmgl_attn_decode_gqa_q8_fwd: bad sizes B=%d H=%d Hkv=%d S=%d capacity=%d",
+                   B, H, Hkv, S, capacity);
+    MMGL_CHECK_ARG(H % Hkv == 0, "mmgl_attn_decode_gqa_q8_fwd: %d query heads are no multiple of %d key/value heads", H, Hkv);
+    const Q8AttnArgs a{q, k_new, v_new, (uint8_t*)k_codes, (uint8_t*)v_codes, (int8_t*)k_scale, (int8_t*)v_scale, key_valid, out,
+                       ldq, ld_new, ld_code, ld_scale, ld_valid, B, H, S, batch_stride_code, batch_stride_scale};
+    const int bad = check_attn_q8(__func__, a, Hkv, capacity, D, dtype);
+    if (bad) return bad;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(attn_decode_gqa_q8_nq, bf16, D, a, Hkv, st);
+    RETURN_BY_HEAD_DIM(attn_decode_gqa_q8_nq, float, D, a, Hkv, st);
 }

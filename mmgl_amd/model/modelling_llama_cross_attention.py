@@ -13,6 +13,9 @@ Greedy generation (LlamaNeighborLM.generate) keeps a cache of the Hkv key/value 
 each new token on the decode kernels: one skinny GEMM on the fused q|k|v weight, ops.rope_kv_append (q rotated in place, k rotated and
 v copied into the token's cache column), ops.attn_decode with num_kv_heads (one read of a cached key serves its G query heads),
 residual adds in the GEMM epilogues.  The new token's position is its COLUMN, as in forward() and in HF's default position_ids.
+generate(kv_cache_dtype="fp8") keeps those Hkv heads as e4m3fn codes with one power-of-two scale per (sample, column, key-or-value,
+kv head): the prefill files the prompt with one ops.kv_quantize launch per layer, a step rotates k|v into the cache's dense kv_new row
+and ops.attn_decode_q8 with num_kv_heads reads the codes, counts the new row unquantised and files it.
 Prompt-lookup decoding (generate(prompt_lookup_num_tokens=K)) verifies K drafted tokens per step: B*(K+1) rows through the same
 GEMMs, ops.rope_kv_append_block (the position of row (b, i) is its column len[b] + i, per sample and on the device) and
 ops.attn_decode_gqa_block (causal over the Hkv-head cache); the loop and the accept kernel are the OPT fork's.
@@ -25,7 +28,7 @@ from transformers.modeling_outputs import CausalLMOutputWithPast
 from .. import ops
 from .modelling_cross_attention import DecodeCache, LookupState
 from .generation import GreedyTail, SampledTail, check_prompt, decode_loop, lookup_loop
-from .sampling import check_lookup, check_processors, check_sampling, sampling_u
+from .sampling import check_kv_cache, check_lookup, check_processors, check_sampling, sampling_u
 
 
 class LlamaGatedCrossAttentionLayer(nn.Module):
@@ -107,7 +110,8 @@ class _FrozenLlamaLayer:
     def __call__(self, h, pending, key_valid, cos_sin, kv_out=None):
         """(h, pending) -> (h', pending'): the residual stream and the MLP output NOT yet added to it -- the add runs inside the
         RMSNorm kernel of whoever consumes the sum next (this layer's successor, the final norm), forward and backward.
-        kv_out: the layer's [B, capacity, 2*Hkv*D] rows of a DecodeCache -- the prefill copies its rotated keys and its values there."""
+        kv_out: the layer's [B, capacity, 2*Hkv*D] rows of a DecodeCache -- the prefill copies its rotated keys and its values there --
+        or the (codes, scale) pair of an FP8 cache (DecodeCache.kv_out), which one ops.kv_quantize launch fills instead of the copy."""
         ly, eps = self.layer, self.cfg.rms_norm_eps
         w_qkv, w_gu = self._fused()
         if pending is None:
@@ -116,23 +120,34 @@ class _FrozenLlamaLayer:
             h, x = ops.add_rms_norm_pair(pending, h, ly.input_layernorm.weight, eps)
         # w_qkv is [(H + 2 Hkv) * D, hidden]: the HF q | k | v weights as loaded, so k and v come out with Hkv heads
         qkv = ops.rope_qk_(ops.frozen_linear(x, w_qkv, None), cos_sin, self.H, self.Hkv)
-        if kv_out is not None:
+        if isinstance(kv_out, tuple):
+            nq, nkv = self.H * self.D, self.Hkv * self.D
+            ops.kv_quantize(qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:], kv_out[0], kv_out[1], self.Hkv)
+        elif kv_out is not None:
             kv_out[:, :qkv.shape[1]].copy_(qkv[:, :, self.H * self.D:])
         a = ops.frozen_linear(ops.selfattn_core_fused(qkv, key_valid, self.H, self.Hkv), ly.self_attn.o_proj.weight, None)
         h, x = ops.add_rms_norm_pair(a, h, ly.post_attention_layernorm.weight, eps)
         m = ops.frozen_linear(ops.swiglu(ops.frozen_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None)
         return h, m
 
-    def decode_step(self, h, kv, key_mask, col, cos_sin_row):
+    def decode_step(self, h, kv, key_mask, col, cos_sin_row, q8=None):
         """The layer on the one new token of a decode step, h [B, hidden] -> [B, hidden]: the token's q|k|v row from one skinny GEMM,
         rotated and filed into column `col` of kv [B, capacity, 2*Hkv*D] by one kernel, single-query attention over columns 0..col
-        (all at or before the query: no causal test), both residual adds in GEMM epilogues."""
+        (all at or before the query: no causal test), both residual adds in GEMM epilogues.
+        q8 = (scale, kv_new) of an FP8 cache (kv then holds e4m3fn codes): the rotated k and the v go into the dense kv_new
+        [B, 2*Hkv*D] instead of a cache column, and ops.attn_decode_q8 attends over the `col` cached columns plus the new row and
+        files it, quantised, at column `col` -- the launches of the plain step."""
         ly, eps = self.layer, self.cfg.rms_norm_eps
         w_qkv, w_gu = self._fused()
         nq, nkv = self.H * self.D, self.Hkv * self.D
         x = ops.rms_norm(h, ly.input_layernorm.weight, eps)
-        qkv = ops.rope_kv_append(ops.decode_linear(x, w_qkv, None), cos_sin_row, kv[:, col], self.H, self.Hkv)
-        a = ops.attn_decode(qkv[:, :nq], kv[:, :col + 1, :nkv], kv[:, :col + 1, nkv:], key_mask[:, :col + 1], self.H, num_kv_heads=self.Hkv)
+        if q8 is None:
+            qkv = ops.rope_kv_append(ops.decode_linear(x, w_qkv, None), cos_sin_row, kv[:, col], self.H, self.Hkv)
+            a = ops.attn_decode(qkv[:, :nq], kv[:, :col + 1, :nkv], kv[:, :col + 1, nkv:], key_mask[:, :col + 1], self.H, num_kv_heads=self.Hkv)
+        else:
+            scale, new = q8
+            qkv = ops.rope_kv_append(ops.decode_linear(x, w_qkv, None), cos_sin_row, new, self.H, self.Hkv)
+            a = ops.attn_decode_q8(qkv[:, :nq], new[:, :nkv], new[:, nkv:], kv, scale, key_mask[:, :col], self.H, num_kv_heads=self.Hkv)
         h = ops.decode_linear(a, ly.self_attn.o_proj.weight, None, residual=h)
         x = ops.rms_norm(h, ly.post_attention_layernorm.weight, eps)
         return ops.decode_linear(ops.swiglu(ops.decode_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None, residual=h)
@@ -210,11 +225,18 @@ class LlamaNeighborLM(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, labels=None, neighbor_embeds=None, neighbor_attention_mask=None,
                 first_key_valid=False, return_logits=None, logits_slice=None, use_cache=False, cache_capacity=None, past_key_values=None,
-                **kw):
+                kv_cache_dtype=None, **kw):
         """use_cache=True: the prefill of greedy generation -- the same kernels as any forward, plus a copy of every frozen layer's
         rotated keys and its values into a DecodeCache with rows [B, capacity, 2*Hkv*D] (capacity `cache_capacity` columns, default
         max_position_embeddings) and of every gated layer's projected neighbor tokens; returned as past_key_values.
-        past_key_values=DecodeCache with input_ids [B, 1]: one decode step (see _decode_step), logits [B, 1, V]."""
+        past_key_values=DecodeCache with input_ids [B, 1]: one decode step (see _decode_step), logits [B, 1, V].
+        kv_cache_dtype ("fp8" / torch.float8_e4m3fn, with use_cache=True): that cache keeps the frozen layers' keys and values as
+        e4m3fn codes [B, capacity, 2*Hkv*D] with int8 exponents [B, capacity, 2*Hkv]; the gated layers' neighbor tokens stay in the
+        model's dtype.  A decode step follows its cache."""
+        kv_dtype = check_kv_cache("LlamaNeighborLM.forward()", kv_cache_dtype,
+                                  projections=() if kv_cache_dtype is None else self._self_attn_projections())
+        if kv_dtype is not None and (past_key_values is not None or not use_cache):
+            raise ValueError("LlamaNeighborLM.forward(): kv_cache_dtype belongs to the prefill (use_cache=True); a decode step follows its cache")
         if past_key_values is not None:
             if not isinstance(past_key_values, DecodeCache):
                 raise ValueError("LlamaNeighborLM: past_key_values must be the DecodeCache of a forward(use_cache=True)")
@@ -223,7 +245,7 @@ class LlamaNeighborLM(nn.Module):
             logits = self._last_logits(self._decode_step(input_ids, past_key_values))[:, None]
             return CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=past_key_values)
         hidden, cache = self._hidden(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid, use_cache,
-                                     cache_capacity)
+                                     cache_capacity, kv_dtype)
         nxt = None
         if labels is not None:
             nxt = torch.full_like(labels, -100)
@@ -232,9 +254,14 @@ class LlamaNeighborLM(nn.Module):
         loss, logits = lm_head_loss_and_logits(self, self.llama.lm_head, hidden, nxt, return_logits, logits_slice)
         return CausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=cache)
 
+    def _self_attn_projections(self):
+        """What check_kv_cache looks at: the q / k / v / o projections of the frozen layers."""
+        return [getattr(ly.self_attn, n) for ly in self.llama.model.layers for n in ("q_proj", "k_proj", "v_proj", "o_proj")]
+
     def _hidden(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid=False, use_cache=False,
-                cache_capacity=None):
-        """(final-norm hidden states [B, T, hidden], the filled DecodeCache or None)."""
+                cache_capacity=None, kv_dtype=None):
+        """(final-norm hidden states [B, T, hidden], the filled DecodeCache or None).  kv_dtype: None, or ops.KV_FP8 as
+        check_kv_cache returned it -- the cache then holds codes and exponents of the Hkv heads (DecodeCache)."""
         emb = self.llama.get_input_embeddings()
         B, T = input_ids.shape
         cache = None
@@ -248,7 +275,8 @@ class LlamaNeighborLM(nn.Module):
                 raise ValueError(f"decode cache: a prompt of {T} columns, capacity {capacity}, max_position_embeddings {limit}")
             ops.require_cuda(input_ids)
             fr = self._frozen[0]
-            cache = DecodeCache(len(self._frozen), B, capacity, fr.Hkv * fr.D, emb.weight.dtype, input_ids.device)
+            cache = DecodeCache(len(self._frozen), B, capacity, fr.Hkv * fr.D, emb.weight.dtype, input_ids.device, kv_dtype=kv_dtype,
+                                num_heads=None if kv_dtype is None else fr.Hkv)
             table = capacity
         h = emb(input_ids)
         if attention_mask is None:
@@ -267,7 +295,7 @@ class LlamaNeighborLM(nn.Module):
         k = 0
         pending = None                            # a frozen layer's MLP output, added inside the next RMSNorm kernel
         for l, layer in enumerate(self._frozen):
-            h, pending = layer(h, pending, key_mask, cos_sin, None if cache is None else cache.kv[l])
+            h, pending = layer(h, pending, key_mask, cos_sin, None if cache is None else cache.kv_out(l))
             if (l + 1) % self.neighbor_layer_wise == 0:
                 if ne is not None:
                     h, pending = ops.gated_residual(h, pending), None
@@ -305,7 +333,7 @@ class LlamaNeighborLM(nn.Module):
             row = cache.cos_sin[col]
             k = 0
             for l, layer in enumerate(self._frozen):
-                h = layer.decode_step(h, cache.kv[l], cache.mask, col, row)
+                h = layer.decode_step(h, cache.kv[l], cache.mask, col, row, None if cache.kv_scale is None else (cache.kv_scale[l], cache.kv_new))
                 if (l + 1) % self.neighbor_layer_wise == 0:
                     if cache.cross:
                         h = self.neighbor_layers[k].decode_step(h, *cache.cross[k], cache.cross_valid, cache.cross_gu[k])
@@ -358,21 +386,29 @@ class LlamaNeighborLM(nn.Module):
         the logits processors and return_step_logits are generation.decode_loop's: see that module.  Refused here: num_beams > 1
         (beam search is implemented for the OPT fork only), num_return_sequences > 1 (it needs the beam-shared cache of the OPT
         fork) and do_sample=True on prompts that are not int64.
-        **lookup takes exactly three keywords, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False (any
-        other name is the TypeError of an unknown keyword).  They are not named parameters: the parameter list above is the greedy
-        and sampled contract, which tests/test_lookup_accept_cpu.py pins by inspecting this signature.
+        **lookup takes exactly four keywords, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False and
+        kv_cache_dtype=None (any other name is the TypeError of an unknown keyword).  They are not named parameters: the parameter
+        list above is the greedy and sampled contract, which tests/test_lookup_accept_cpu.py pins by inspecting this signature.
         prompt_lookup_num_tokens = K (1..7; 0: off, today's loop) with max_matching_ngram_size = N (1..4): prompt-lookup decoding
         with the keywords, semantics and refusals of MPTForCausalLM.generate -- each step drafts up to K tokens from the row's own
         text and verifies them in one step of B*(K+1) rows (_verify_step, generation.lookup_loop).  The result is the
-        greedy result in fewer steps.  return_lookup_stats: also the dict of `steps` and `emitted` lookup_loop describes."""
+        greedy result in fewer steps.  return_lookup_stats: also the dict of `steps` and `emitted` lookup_loop describes.
+        kv_cache_dtype = "fp8" (or torch.float8_e4m3fn; None: off, every call as without it): the frozen layers keep the Hkv cached
+        key/value heads as e4m3fn codes with power-of-two scales, (D + 1) / 2D of the bf16 cache's bytes; the steps read them through
+        ops.attn_decode_q8 with num_kv_heads.  Greedy, do_sample, the processors, return_step_logits and EOS handling
+        combine with it; prompt_lookup_num_tokens > 0 is refused (the verify kernel has no FP8 form), adapted projections too."""
         who = "LlamaNeighborLM.generate()"
         prompt_lookup_num_tokens = lookup.pop("prompt_lookup_num_tokens", 0)
         max_matching_ngram_size = lookup.pop("max_matching_ngram_size", 2)
         return_lookup_stats = lookup.pop("return_lookup_stats", False)
+        kv_cache_dtype = lookup.pop("kv_cache_dtype", None)
         if lookup:
             raise TypeError(f"{who} got an unexpected keyword argument '{next(iter(lookup))}'")
         if int(num_beams) != 1:
             raise ValueError(f"{who}: num_beams = {num_beams} is not implemented (beam search runs on the OPT fork only); this path is greedy")
+        # num_beams and num_return_sequences keep this model's own refusals (above, and check_sampling's)
+        kv_dtype = check_kv_cache(who, kv_cache_dtype, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
+                                  projections=() if kv_cache_dtype is None else self._self_attn_projections())
         if int(prompt_lookup_num_tokens) != 0:                 # its refusals of do_sample / num_return_sequences come before check_sampling's
             check_lookup(who, prompt_lookup_num_tokens, max_matching_ngram_size, return_lookup_stats, do_sample, 1, num_return_sequences)
         check_sampling(who, do_sample, temperature, top_k, top_p, seed, sample_u, 1, num_return_sequences)
@@ -393,7 +429,7 @@ class LlamaNeighborLM(nn.Module):
         else:
             select = GreedyTail(B, dev, eos_token_id, pad_token_id)
         hidden, cache = self._hidden(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid, True,
-                                     T + n_new - 1)
+                                     T + n_new - 1, kv_dtype)
         if K > 0:
             cache.lookup = LookupState(cache, K, N, n_new, scratch=False)
             return lookup_loop(self._last_logits, lambda: self._verify_step(cache), hidden[:, -1], cache.lookup, input_ids, attention_mask,

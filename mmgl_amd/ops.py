@@ -1794,7 +1794,7 @@ def kv_quantize(k, v, kvq, scale, num_heads):
     return kvq, scale
 
 
-def attn_decode_q8(q, k_new, v_new, kvq, scale, key_valid, num_heads, out=None):
+def attn_decode_q8(q, k_new, v_new, kvq, scale, key_valid, num_heads, out=None, num_kv_heads=None):
     """ops.attn_decode on a quantised cache, and the filing of the new token into it, one launch (mmgl_attn_decode_q8_fwd).
       q [B, d] already scaled; k_new, v_new [B, d]: views with unit column stride and a common row stride (the halves of the k|v
       projection's dense [B, 2d] output), the new token's key and value: they take part unquantised and always valid;
@@ -1802,17 +1802,26 @@ def attn_decode_q8(q, k_new, v_new, kvq, scale, key_valid, num_heads, out=None):
       column S < capacity is WRITTEN with the new token's codes and exponents; key_valid [B, S] bool/uint8 view of the cached
       columns, S >= 1 (a masked cached key weighs nothing).
     The result equals ops.attn_decode on the dequantised columns followed by the new row, up to summation order.  Returns [B, d]
-    (`out`, a dense tensor of q's dtype, when given: a refused call leaves it and the cache as they were).  Forward only; GPU only."""
+    (`out`, a dense tensor of q's dtype, when given: a refused call leaves it and the cache as they were).  Forward only; GPU only.
+    Grouped-query attention (num_kv_heads = Hkv < num_heads = H, Hkv a divisor of H; mmgl_attn_decode_gqa_q8_fwd): the cache holds
+    Hkv heads -- kvq [B, capacity, 2*Hkv*D], scale [B, capacity, 2*Hkv], k_new, v_new [B, Hkv*D] with D = d / H (the k and v columns
+    of DecodeCache.kv_new after ops.rope_kv_append) -- and query head h reads key / value head h // (H / Hkv): one read and one
+    dequantisation of a cached key serves the query heads of its group; nothing is expanded."""
     require_cuda(q, k_new, v_new, kvq, scale, key_valid)
     _no_grad_inputs("attn_decode_q8", q, k_new, v_new)
-    if (q.dim() != 2 or q.stride(1) != 1 or k_new.dim() != 2 or k_new.shape != q.shape or k_new.shape != v_new.shape
+    Hkv = _kv_heads("attn_decode_q8", num_heads, num_kv_heads)
+    H = int(num_heads)
+    kd = q.shape[-1] if Hkv is None or q.shape[-1] % H else q.shape[-1] // H * Hkv              # columns of a key row
+    if (q.dim() != 2 or q.stride(1) != 1 or k_new.dim() != 2 or tuple(k_new.shape) != (q.shape[0], kd) or k_new.shape != v_new.shape
             or k_new.stride() != v_new.stride() or k_new.stride(1) != 1 or k_new.dtype != q.dtype or v_new.dtype != q.dtype
             or k_new.device != q.device or v_new.device != q.device):
         raise ValueError(f"attn_decode_q8: incompatible q{tuple(q.shape)}/{q.stride()} {q.dtype} k_new{tuple(k_new.shape)}/{k_new.stride()} "
-                         f"{k_new.dtype} v_new{tuple(v_new.shape)}/{v_new.stride()} {v_new.dtype}")
+                         f"{k_new.dtype} v_new{tuple(v_new.shape)}/{v_new.stride()} {v_new.dtype}"
+                         + ("" if Hkv is None else f" for H={H}, Hkv={Hkv}"))
     B, d = q.shape
-    capacity, D = _q8_cache_operands("attn_decode_q8", kvq, scale, B, d, num_heads, q)
-    H = int(num_heads)
+    if d % H:
+        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {d} and `num_heads`: {num_heads}).")
+    capacity, D = _q8_cache_operands("attn_decode_q8", kvq, scale, B, kd, H if Hkv is None else Hkv, q)
     if key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.device != q.device:
         raise ValueError(f"attn_decode_q8: key_valid{tuple(key_valid.shape)} must be a [{B}, S] mask on {q.device}")
     S = key_valid.shape[1]
@@ -1830,9 +1839,15 @@ def attn_decode_q8(q, k_new, v_new, kvq, scale, key_valid, num_heads, out=None):
         key_valid = key_valid.to(torch.uint8)
     if key_valid.stride(1) != 1:
         key_valid = key_valid.contiguous()
-    _lib.call("mmgl_attn_decode_q8_fwd", dict(bytes=2.0 * B * S * (d + H) + 4.0 * B * d * q.element_size()), ptr(q), q.stride(0), ptr(k_new),
-              ptr(v_new), k_new.stride(0), ptr(kvq), ptr_off(kvq, d), kvq.stride(1), kvq.stride(0), ptr(scale), ptr_off(scale, H),
-              scale.stride(1), scale.stride(0), capacity, ptr(key_valid), key_valid.stride(0), ptr(out), B, H, S, D, code, stream_ptr())
+    if Hkv is None:
+        _lib.call("mmgl_attn_decode_q8_fwd", dict(bytes=2.0 * B * S * (d + H) + 4.0 * B * d * q.element_size()), ptr(q), q.stride(0), ptr(k_new),
+                  ptr(v_new), k_new.stride(0), ptr(kvq), ptr_off(kvq, d), kvq.stride(1), kvq.stride(0), ptr(scale), ptr_off(scale, H),
+                  scale.stride(1), scale.stride(0), capacity, ptr(key_valid), key_valid.stride(0), ptr(out), B, H, S, D, code, stream_ptr())
+    else:
+        _lib.call("mmgl_attn_decode_gqa_q8_fwd", dict(bytes=2.0 * B * S * (kd + Hkv) + 2.0 * B * (d + kd) * q.element_size()), ptr(q), q.stride(0),
+                  ptr(k_new), ptr(v_new), k_new.stride(0), ptr(kvq), ptr_off(kvq, kd), kvq.stride(1), kvq.stride(0), ptr(scale),
+                  ptr_off(scale, Hkv), scale.stride(1), scale.stride(0), capacity, ptr(key_valid), key_valid.stride(0), ptr(out), B, H, Hkv, S,
+                  D, code, stream_ptr())
     return out
 
 
