@@ -1,10 +1,10 @@
-"""The decode loop of generate(), once, for the three language models (MPTForCausalLM under CrossAttentionModel and SelfAttentionModel,
+"""The loops of generate(), once, for the three language models (MPTForCausalLM under CrossAttentionModel and SelfAttentionModel,
 LlamaNeighborLM): the prompt check, the two selection tails and the loop "logits -> (processors) -> (keep the step's logits) ->
 select -> write the ids column -> one cached decode step".  A model's generate() validates its keywords (sampling.py), checks the
 prompt (check_prompt), picks a tail, runs its prefill and hands decode_loop three things: its _last_logits, a callable for one cached
-decode step (tokens [rows, 1] -> hidden [rows, d]) and the prefill's last hidden row.  Beam search (MPTForCausalLM._generate_beam),
-prompt-lookup decoding (lookup_loop, below) and contrastive search (contrastive_loop, below) have loops of another shape; they share
-check_prompt, and contrastive search the processors' binding.
+decode step (tokens [rows, 1] -> hidden [rows, d]) and the prefill's last hidden row.  Beam search (beam_loop, below), prompt-lookup
+decoding (lookup_loop, below) and contrastive search (contrastive_loop, below) have loops of another shape; they share check_prompt,
+and contrastive search the processors' binding.
 
 Semantics, the same for every model:
   * Prompts are right-padded to the common width T; every new token is appended at the same column for all rows, and all
@@ -26,6 +26,7 @@ Semantics, the same for every model:
 import torch
 
 from .. import ops
+from .sampling import sampling_u
 
 
 def check_prompt(input_ids, inputs_embeds, attention_mask, max_new_tokens, eos_token_id, pad_token_id, config, max_positions):
@@ -84,6 +85,14 @@ class SampledTail:
         col = ids[:, c]
         ops.sample_tokens(logits, self.u[s].view(logits.shape[0], -1), *self.knobs, self.finished, self.eos, self.pad, out=col)
         return col
+
+
+def make_select(who, do_sample, n_new, B, R, device, seed, sample_u, temperature, top_k, top_p, eos_token_id, pad_token_id):
+    """The selection tail of a decode_loop over B prompts with R rows each: a SampledTail on the uniform numbers [n_new, B*R] of
+    sampling.sampling_u (`who` names the caller in its errors), or a GreedyTail."""
+    if do_sample:
+        return SampledTail(sampling_u(who, n_new, B * R, device, seed, sample_u), temperature, top_k, top_p, eos_token_id, pad_token_id)
+    return GreedyTail(B, device, eos_token_id, pad_token_id)
 
 
 def _bind_processors(proc, ids, prompt_mask, history_ids, history_mask, repeat=1):
@@ -171,6 +180,51 @@ def lookup_loop(last_logits, verify, hidden, lookup, input_ids, prompt_mask, n_n
         steps += 1
     ids = ids.to(input_ids.dtype)
     return (ids, dict(steps=steps, emitted=lookup.emitted[:steps + 1].clone())) if return_stats else ids
+
+
+def beam_loop(last_logits, step, hidden, book, input_ids, n_new, W, vocab_size, eos_token_id, pad_token_id, length_penalty, early_stopping,
+              return_scores=False, return_trace=False):
+    """Beam search behind a prefill of B rows whose last row is `hidden` [B, ...], W hypotheses per sample on the
+    beam-shared cache whose BeamState owns `book` (ops.BeamBook).  The prefill's logits seed the W beams (rows_in = 1 of ops.beam_topk,
+    in place of HF's -1e9 start scores); step(tokens [B*W, 1]) -> hidden [B*W, d] is one decode step of the B*W rows, last_logits as
+    in decode_loop.  Per step ops.beam_topk (two launches) picks each sample's 2W best continuations and ops.beam_advance (one
+    launch) turns them into the next tokens, parents, running scores, table and pool of finished hypotheses; nothing synchronises
+    with the host.
+    Semantics of transformers' beam search: the first W non-EOS candidates run on; an EOS candidate among the first W (every one
+    of them at the last step) enters the pool with score = log-prob sum / generated_length ** length_penalty; a sample is frozen
+    once its pool is full under early_stopping=True or the early-stop heuristic is met.  All n_new steps run.
+    Returns ids [B, T + n_new] -- the best pooled hypothesis, pad_token_id behind its last token -- then, as asked,
+    sequences_scores fp32 [B] and the trace: per step a dict of the running beams' parents / tokens / scores [B, W] and the 2W
+    candidates cand_index / cand_score [B, 2W]."""
+    B, dev = input_ids.shape[0], input_ids.device
+    start = torch.zeros(B, dtype=torch.float32, device=dev)
+    history = torch.empty(n_new, B, W, dtype=torch.int64, device=dev)       # history[s, b, w]: the token slot w took at step s
+    trace = []
+    for s in range(n_new):
+        logits = last_logits(hidden)
+        cs, ci = ops.beam_topk(logits, start if s == 0 else book.beam_score, W, rows_in=1 if s == 0 else W)
+        ops.beam_advance(cs, ci, book, s, vocab_size, eos_token_id, s == n_new - 1, early_stopping, float(s + 1) ** length_penalty)
+        history[s] = book.tokens.view(B, W)
+        if return_trace:
+            trace.append(dict(parents=book.parents.view(B, W).clone(), tokens=book.tokens.view(B, W).clone(),
+                              scores=book.beam_score.view(B, W).clone(), cand_index=ci, cand_score=cs))
+        if s + 1 < n_new:
+            hidden = step(history[s].reshape(B * W, 1))
+    # the best pooled hypothesis of each sample: tokens 0 .. len-2 through its ancestry row, its own last token, then padding
+    score, length, anc, last = (t.view(B, W, *t.shape[1:])[:, 0] for t in book.pool)
+    cols = torch.arange(n_new, device=dev)[None, :]
+    slot = torch.zeros(B, n_new, dtype=torch.int64, device=dev)
+    slot[:, :n_new - 1] = anc[:, :n_new - 1]
+    new = history.permute(1, 0, 2).gather(2, slot[:, :, None])[:, :, 0]                       # [B, n_new]
+    length = length.long()[:, None]
+    new = torch.where(cols < length - 1, new, torch.where(cols == length - 1, last[:, None], torch.full_like(new, pad_token_id)))
+    ids = torch.cat([input_ids, new.to(input_ids.dtype)], dim=1)
+    res = (ids,)
+    if return_scores:
+        res += (score.clone(),)
+    if return_trace:
+        res += (trace,)
+    return res[0] if len(res) == 1 else res
 
 
 def contrastive_loop(last_logits, step, prompt_hidden, src, input_ids, prompt_mask, n_new, k, penalty_alpha, vocab_size, eos_token_id=None,

@@ -37,9 +37,10 @@ from transformers.activations import ACT2FN
 from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutputWithPast
 
 from .. import ops
+from .decode_cache import BeamState, DecodeCache, LookupState      # noqa: F401 (re-exported: tests and tools import them from here)
 from .encoders import ClipTextEncoder, PackedTextEncoder, PackedVisionEncoder
-from .generation import GreedyTail, SampledTail, check_prompt, contrastive_loop, decode_loop, lookup_loop
-from .sampling import check_contrastive, check_kv_cache, check_lookup, check_processors, check_sampling, sampling_u
+from .generation import beam_loop, check_prompt, contrastive_loop, decode_loop, lookup_loop, make_select
+from .sampling import check_contrastive, check_kv_cache, check_lookup, check_processors, check_sampling
 
 CROSS_MODES = ("cross_attention", "embedding")
 
@@ -328,28 +329,10 @@ class MPTAttention(nn.Module):
         _plain(mod)
         return ops.decode_linear(x, mod.weight, mod.bias, out_scale=out_scale, out=out)
 
-    def decode_self(self, x, kv, key_mask, col, beam=None, tail=None, q8=None):
-        """x [B, d]: the new token's layer input.  Projects q and writes k|v into column `col` of the layer's cache rows kv
-        [B, capacity, 2d], then attends over columns 0..col (all at or before the query: no causal test).  q_proj and v_proj may be
-        LoRA-adapted (any other adapter type, and an adapted k_proj / out_proj, is refused).
-        beam (a BeamState) with the layer's tail buffer [B*W, n_cap, 2d]: x [B*W, d]; k|v go into column beam.n_tail of `tail`, and
-        the rows attend over the sample's `col` prompt columns of kv (shared, never copied) plus their own n_tail + 1 tail keys,
-        addressed through beam.book.src (ops.attn_decode_beam).  Plain nn.Linear projections only.
-        q8 = (scale, kv_new) of an FP8 cache (kv then holds e4m3fn codes): k|v go into the dense kv_new [B, 2d] instead of a cache
-        column, and ops.attn_decode_q8 attends over the `col` cached columns plus the new row and files it, quantised, at column
-        `col` -- the launches of the plain step.  Plain nn.Linear projections, no beams."""
+    def _decode_qkv(self, x, dst):
+        """q [rows, d], scaled, of the rows x of a decode step; their k|v go into dst [rows, 2d] (DecodeCache.new_kv).  One GEMM on the
+        fused frozen weight for q and one for k|v, or one per projection."""
         d = self.embed_dim
-        _plain(self.k_proj, self.out_proj)
-        if q8 is not None:
-            if beam is not None:
-                raise ValueError("the FP8 key/value cache has no beam step")
-            _plain(self.q_proj, self.v_proj)
-            scale, dst = q8
-        elif beam is None:
-            dst = kv[:, col]
-        else:
-            _plain(self.q_proj, self.v_proj)
-            dst = tail[:, beam.n_tail]
         fused = self._frozen_qkv()
         if fused is not None:
             w, b = fused
@@ -359,42 +342,22 @@ class MPTAttention(nn.Module):
             q = self._decode_proj(self.q_proj, x, out_scale=self.scaling)
             ops.decode_linear(x, self.k_proj.weight, self.k_proj.bias, out=dst[:, :d])
             self._decode_proj(self.v_proj, x, out=dst[:, d:])
-        if q8 is not None:
-            return ops.attn_decode_q8(q, dst[:, :d], dst[:, d:], kv, scale, key_mask[:, :col], self.num_heads)
-        if beam is None:
-            return ops.attn_decode(q, kv[:, :col + 1, :d], kv[:, :col + 1, d:], key_mask[:, :col + 1], self.num_heads)
-        n = beam.n_tail + 1
-        return ops.attn_decode_beam(q, kv[:, :col, :d], kv[:, :col, d:], key_mask[:, :col], self.num_heads, beam.W,
-                                    tail[:, :n, :d], tail[:, :n, d:], beam.book.src)
+        return q
 
-    def decode_block(self, x, kv, key_mask, lookup, scratch):
-        """x [B*m, d]: the layer input of the m = lookup.W new tokens per sample of a verify step (prompt-lookup decoding).  Projects
-        q, and k|v into the dense `scratch` [B*m, 2d]; ops.attn_decode_block then attends over the sample's lookup.len cache columns
-        of kv plus the new keys at or before each token, and files the new keys and values at columns lookup.len .. of kv -- the
-        launches of decode_self.  Plain nn.Linear projections only."""
-        d = self.embed_dim
-        _plain(self.q_proj, self.k_proj, self.v_proj, self.out_proj)
-        fused = self._frozen_qkv()
-        if fused is not None:
-            w, b = fused
-            q = ops.decode_linear(x, w[:d], b[:d])
-            ops.decode_linear(x, w[d:], b[d:], out=scratch)
-        else:
-            q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
-            ops.decode_linear(x, self.k_proj.weight, self.k_proj.bias, out=scratch[:, :d])
-            ops.decode_linear(x, self.v_proj.weight, self.v_proj.bias, out=scratch[:, d:])
-        return ops.attn_decode_block(q, scratch[:, :d], scratch[:, d:], kv[:, :, :d], kv[:, :, d:], key_mask, lookup.len, self.num_heads,
-                                     lookup.W)
+    def decode_self(self, x, cache, idx):
+        """x [rows, d]: the layer input of a step's rows.  Projects q, writes k|v where the cache's mode files them and attends over
+        layer idx's cache (decode_cache.DecodeCache: new_kv, attend_self).  q_proj and v_proj may be LoRA-adapted in the plain mode
+        only; any other adapter type, and an adapted k_proj / out_proj, is refused."""
+        _plain(self.k_proj, self.out_proj)
+        dst = cache.new_kv(idx)
+        if not cache.plain:
+            _plain(self.q_proj, self.v_proj)
+        return cache.attend_self(idx, self._decode_qkv(x, dst), dst, self.num_heads)
 
-    def decode_cross(self, x, k, v, key_valid, beam=None):
-        """beam: the cache's BeamState, or its LookupState -- beam.W rows per sample (beams, or the tokens of a verify step)."""
+    def decode_cross(self, x, cache, idx):
         _plain(self.q_proj, self.out_proj)
         q = ops.decode_linear(x, self.q_proj.weight, self.q_proj.bias, out_scale=self.scaling)
-        if beam is not None:                  # the W rows of a sample read its neighbor tokens once: k, v stay at B rows
-            return ops.attn_decode_beam(q, k, v, key_valid, self.num_heads, beam.W)
-        return ops.attn_decode(q, k, v, key_valid, self.num_heads)
-
-
+        return cache.attend_cross(idx, q, self.num_heads)
 
 
 class _Deferred:
@@ -536,12 +499,10 @@ class MPTDecoderLayer(nn.Module):
         return ops.activation_(ops.decode_linear(x, self.fc1.weight, self.fc1.bias), self.activation_name)
 
     def decode_step(self, h, cache, idx):
-        """The layer on the one new token of a decode step, h [B, d]: the existing LayerNorm / gated-residual kernels at M = B,
-        ops.decode_linear for every projection (residual adds in the GEMM epilogue of the frozen layers) and ops.attn_decode over
-        the cache -- layer idx's K|V rows (frozen layer) or neighbor layer idx's projected neighbor tokens (gated layer).
-        With cache.beam set h is [B*W, d]: the same kernels at M = B*W rows, the attention through ops.attn_decode_beam.
-        With cache.lookup set h is [B*m, d], m new tokens per sample (a verify step of prompt-lookup decoding): the same kernels at
-        M = B*m rows, ops.attn_decode_block in the frozen layers, ops.attn_decode_beam (m queries per sample) in the gated ones."""
+        """The layer on the rows of a decode or verify step, h [rows, d]: the existing LayerNorm / gated-residual kernels at M = rows,
+        ops.decode_linear for every projection (residual adds in the GEMM epilogue of the frozen layers) and the cache's attention
+        -- over layer idx's K|V rows (frozen layer) or neighbor layer idx's projected neighbor tokens (gated layer).  How many rows a
+        sample has, where its keys go and which attention op reads them is the cache's mode (decode_cache.DecodeCache)."""
         pre = self.do_layer_norm_before
         attn = self.self_attn
         ln1, ln2 = self.self_attn_layer_norm, self.final_layer_norm
@@ -550,19 +511,10 @@ class MPTDecoderLayer(nn.Module):
         gated = self.cross_attention
         if gated:                             # residual adds through ops.gated_residual (the gate is None outside flamingo)
             g1, g2 = (self.gating1, self.gating2) if self.peft_type == "flamingo" else (None, None)
-            k, v = cache.cross[idx]
-            a = attn.decode_cross(x, k, v, cache.cross_valid, cache.beam if cache.lookup is None else cache.lookup)
+            a = attn.decode_cross(x, cache, idx)
             h = ops.gated_residual(h, ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias), g1, 0.0, False)
         else:                                 # frozen layer: the residual adds ride in the GEMM epilogues
-            beam, lookup = cache.beam, cache.lookup
-            if lookup is not None:
-                if cache.kv_scale is not None:
-                    raise ValueError("the FP8 key/value cache has no verify step")
-                a = attn.decode_block(x, cache.kv[idx], cache.mask, lookup, lookup.scratch[idx])
-            else:
-                a = attn.decode_self(x, cache.kv[idx], cache.mask, cache.col, beam, None if beam is None else beam.tail[idx],
-                                     None if cache.kv_scale is None else (cache.kv_scale[idx], cache.kv_new))
-            h = ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias, residual=h)
+            h = ops.decode_linear(attn.decode_self(x, cache, idx), attn.out_proj.weight, attn.out_proj.bias, residual=h)
         if not pre:
             h = self._ln(ln1, h)
         x = self._decode_ffn(self._ln(ln2, h) if pre else h)
@@ -571,89 +523,6 @@ class MPTDecoderLayer(nn.Module):
         else:
             h = ops.decode_linear(x, self.fc2.weight, self.fc2.bias, residual=h)
         return h if pre else self._ln(ln2, h)
-
-
-class DecodeCache:
-    """State of greedy generation with a key/value cache (MPTDecoder.forward(use_cache=True) builds it, each decode step advances it):
-      kv          per frozen layer one preallocated [B, capacity, 2d] buffer: columns [0, d) of a row are that position's key, [d, 2d) its value
-                  (the project's [B, S, H*D] layout, never head-transposed; the kernels address the two slabs in place)
-      cross       per gated layer the neighbor tokens' (k_proj, v_proj) outputs [B, S, d], projected once at prefill; cross_valid their [B, S] mask
-      mask        the running [B, capacity] uint8 key mask: the prompt's attention mask (pad keys stay masked), then 1 per new token
-      col         the column the next token is written to -- the same for every sample (prompts are right-padded to a common width)
-      next_pos    [B] position id of the next token, counted from the mask as HF does (valid tokens so far + OPT's offset 2)
-      beam        None (greedy), or the BeamState of a beam search: then kv / mask / cross / cross_valid / next_pos stay at B rows --
-                  the prompt is prefilled once per sample and col stays at the prompt width -- and the decode steps run B*W rows
-      lookup      None, or the LookupState of prompt-lookup decoding: then col / next_pos stand still at the prompt's and the verify steps
-                  (MPTDecoder._verify_step) run B*(K+1) rows against per-sample cache lengths lookup.len
-      kv_dtype    None: kv in the model's dtype, as above.  ops.KV_FP8 (with num_heads = H): kv[l] holds e4m3fn codes [B, capacity, 2d],
-                  kv_scale[l] their int8 exponents [B, capacity, 2H] -- one power of two per (sample, column, key-or-value, head),
-                  key heads first -- and kv_new is the one dense [B, 2d] buffer, in the model's dtype, that takes every layer's k|v
-                  projection of a decode step (ops.attn_decode_q8 reads it and files it quantised).  cross stays in the model's dtype"""
-
-    def __init__(self, num_layers, batch_size, capacity, hidden_size, dtype, device, kv_dtype=None, num_heads=None):
-        self.capacity = int(capacity)
-        self.kv_dtype = kv_dtype
-        self.kv_scale = self.kv_new = None
-        if kv_dtype is not None:
-            if kv_dtype is not ops.KV_FP8 or not num_heads or hidden_size % int(num_heads):
-                raise ValueError(f"DecodeCache: kv_dtype = {kv_dtype!r} with num_heads = {num_heads} (None, or torch.float8_e4m3fn with the "
-                                 "number of heads)")
-            self.kv_scale = [torch.empty(batch_size, self.capacity, 2 * int(num_heads), dtype=torch.int8, device=device) for _ in range(num_layers)]
-            self.kv_new = torch.empty(batch_size, 2 * hidden_size, dtype=dtype, device=device)
-        self.kv = [torch.empty(batch_size, self.capacity, 2 * hidden_size, dtype=kv_dtype or dtype, device=device) for _ in range(num_layers)]
-        self.mask = torch.zeros(batch_size, self.capacity, dtype=torch.uint8, device=device)
-        self.cross = []
-        self.cross_valid = None
-        self.col = 0
-        self.next_pos = None
-        self.beam = None
-        self.lookup = None
-
-    def kv_out(self, idx):
-        """What layer idx's prefill files its keys and values into (MPTAttention._file_kv)."""
-        return self.kv[idx] if self.kv_scale is None else (self.kv[idx], self.kv_scale[idx])
-
-
-class LookupState:
-    """What prompt-lookup decoding adds to a prefilled DecodeCache (cache.lookup): per sample a cache length of its own and the block
-    of W = K + 1 tokens the next verify step feeds.  All of it lives on the device and is advanced by ops.lookup_accept.
-      len        int32 [B] cache columns filed (starts at the prompt width T: pad keys stay masked), gen int32 [B] tokens the row has,
-                 finished uint8 [B], n_draft int32 [B] drafts in the block
-      block      int64 [B, W] = [last token, drafts, filler], positions int64 [B, W] its position ids (clamped to the table)
-      scratch    per frozen layer the dense [B*W, 2d] output of the k|v projection; ops.attn_decode_block files it into the cache
-                 (scratch=False: None -- LlamaNeighborLM files the block's keys from its fused q|k|v rows, ops.rope_kv_append_block)
-      emitted    int32 [n_new, B]: row c holds the tokens call c of ops.lookup_accept appended (call 0: the prefill's row)"""
-
-    def __init__(self, cache, num_tokens, ngram_size, n_new, scratch=True):
-        B, _, two_d = cache.kv[0].shape
-        dev = cache.mask.device
-        self.K, self.N, self.W = int(num_tokens), int(ngram_size), int(num_tokens) + 1
-        self.len = torch.full((B,), cache.col, dtype=torch.int32, device=dev)
-        self.gen = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.finished = torch.zeros(B, dtype=torch.uint8, device=dev)
-        self.n_draft = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.block = torch.zeros(B, self.W, dtype=torch.int64, device=dev)
-        self.positions = torch.zeros(B, self.W, dtype=torch.int64, device=dev)
-        self.scratch = [torch.empty(B * self.W, two_d, dtype=kv.dtype, device=dev) for kv in cache.kv] if scratch else None
-        self.emitted = torch.zeros(max(int(n_new), 1), B, dtype=torch.int32, device=dev)
-        cache.mask[:, cache.col:] = 1                            # once: lookup.len bounds what a sample reads
-
-
-class BeamState:
-    """What a beam search adds to a prefilled DecodeCache (cache.beam): W hypotheses per sample that share the sample's cache rows.
-      tail    per frozen layer one [B*W, n_cap, 2d] buffer of the keys | values the hypotheses generated themselves: decode step j
-              writes column j of row b*W + w in place (the k|v projection's ldy), as a greedy step writes its cache column
-      book    ops.BeamBook: the running beams, the two parent tables that say which tail row holds a hypothesis' key of step j
-              (reordering the beams rewrites these few int32, never a cache row) and the pool of finished hypotheses
-      n_tail  tail columns filled so far = decode steps done"""
-
-    def __init__(self, cache, num_beams, n_cap):
-        B, _, two_d = cache.kv[0].shape
-        self.W = int(num_beams)
-        self.n_cap = max(int(n_cap), 1)
-        self.tail = [torch.empty(B * self.W, self.n_cap, two_d, dtype=kv.dtype, device=kv.device) for kv in cache.kv]
-        self.book = ops.BeamBook(B, self.W, self.n_cap, cache.mask.device)
-        self.n_tail = 0
 
 
 class MPTPreTrainedModel(nn.Module):
@@ -900,37 +769,42 @@ class MPTDecoder(MPTPreTrainedModel):
         ops.require_cuda(cache.mask, input_ids, inputs_embeds)
         with torch.no_grad():
             emb = self.embed_tokens(input_ids[:, 0]) if inputs_embeds is None else inputs_embeds[:, 0]
-            if self.project_in is not None:
-                emb = ops.decode_linear(emb.contiguous(), self.project_in.weight, self.project_in.bias)
             pos = cache.next_pos if beam is None else cache.next_pos.repeat_interleave(beam.W)      # the beams of a sample share it
-            h = emb + F.embedding(pos, self.embed_positions.weight)
             if beam is None:
                 cache.mask[:, cache.col] = 1
-            all_hidden_states = () if output_hidden_states else None
-            for idx, layer in enumerate(self.layers):
-                if output_hidden_states:
-                    all_hidden_states += (h[:, None],)
-                h = layer.decode_step(h, cache, idx)
-                if cache.cross and (idx + 1) % self.neighbor_layer_wise == 0:
-                    nb = (idx + 1) // self.neighbor_layer_wise - 1
-                    h = self.neighbor_layers[nb].decode_step(h, cache, nb)
-            if self.final_layer_norm is not None:
-                fln = self.final_layer_norm
-                h = ops.layer_norm(h, fln.weight, fln.bias, fln.eps)
-            if self.project_out is not None:
-                h = ops.decode_linear(h, self.project_out.weight, self.project_out.bias)
+            layer_inputs = [] if output_hidden_states else None
+            h = self._decode_rows(emb, pos, cache, layer_inputs)
             if beam is None:
                 cache.col += 1
             else:
                 beam.n_tail += 1
             cache.next_pos = cache.next_pos + 1
         h = h[:, None]
-        if output_hidden_states:
-            all_hidden_states += (h,)
+        all_hidden_states = tuple(x[:, None] for x in layer_inputs) + (h,) if output_hidden_states else None
         if not return_dict:
             return tuple(v for v in [h, cache, all_hidden_states] if v is not None)
         return BaseModelOutputWithPast(last_hidden_state=h, past_key_values=cache, hidden_states=all_hidden_states, attentions=None)
 
+    def _decode_rows(self, emb, positions, cache, layer_inputs=None):
+        """The walk of a decode or verify step over its rows: emb [rows, d_embed] the token embeddings, positions [rows] their position
+        ids -> the hidden rows [rows, d_embed] in front of lm_head.  project_in, the position rows, every layer's decode_step with the
+        gated layers interleaved, the final LayerNorm, project_out.  layer_inputs: a list that takes every frozen layer's input."""
+        if self.project_in is not None:
+            emb = ops.decode_linear(emb.contiguous(), self.project_in.weight, self.project_in.bias)
+        h = emb + F.embedding(positions, self.embed_positions.weight)
+        for idx, layer in enumerate(self.layers):
+            if layer_inputs is not None:
+                layer_inputs.append(h)
+            h = layer.decode_step(h, cache, idx)
+            if cache.cross and (idx + 1) % self.neighbor_layer_wise == 0:
+                nb = (idx + 1) // self.neighbor_layer_wise - 1
+                h = self.neighbor_layers[nb].decode_step(h, cache, nb)
+        if self.final_layer_norm is not None:
+            fln = self.final_layer_norm
+            h = ops.layer_norm(h, fln.weight, fln.bias, fln.eps)
+        if self.project_out is not None:
+            h = ops.decode_linear(h, self.project_out.weight, self.project_out.bias)
+        return h
 
     def _verify_step(self, cache):
         """A verify step of prompt-lookup decoding: the W = K + 1 tokens cache.lookup.block [B, W] of every sample -- its last token,
@@ -943,21 +817,7 @@ class MPTDecoder(MPTPreTrainedModel):
             raise ValueError("a verify step needs a prefilled DecodeCache with a LookupState (cache.lookup) and no BeamState")
         ops.require_cuda(cache.mask)
         with torch.no_grad():
-            emb = self.embed_tokens(lookup.block.view(-1))
-            if self.project_in is not None:
-                emb = ops.decode_linear(emb.contiguous(), self.project_in.weight, self.project_in.bias)
-            h = emb + F.embedding(lookup.positions.view(-1), self.embed_positions.weight)
-            for idx, layer in enumerate(self.layers):
-                h = layer.decode_step(h, cache, idx)
-                if cache.cross and (idx + 1) % self.neighbor_layer_wise == 0:
-                    nb = (idx + 1) // self.neighbor_layer_wise - 1
-                    h = self.neighbor_layers[nb].decode_step(h, cache, nb)
-            if self.final_layer_norm is not None:
-                fln = self.final_layer_norm
-                h = ops.layer_norm(h, fln.weight, fln.bias, fln.eps)
-            if self.project_out is not None:
-                h = ops.decode_linear(h, self.project_out.weight, self.project_out.bias)
-        return h
+            return self._decode_rows(self.embed_tokens(lookup.block.view(-1)), lookup.positions.view(-1), cache)
 
 
 class MPTModel(MPTPreTrainedModel):
@@ -1171,9 +1031,10 @@ class MPTForCausalLM(MPTPreTrainedModel):
         K, N = check_lookup("generate()", prompt_lookup_num_tokens, max_matching_ngram_size, return_lookup_stats, do_sample, W,
                             num_return_sequences, proc is not None, return_step_logits, inputs_embeds)
         if K > 0 or kc:                                        # with the other refusals, before any work: these steps have no adapter path
-            _plain(self.lm_head, *(m for layer in list(self.model.decoder.layers) + list(self.model.decoder.neighbor_layers)
-                                   for m in (layer.self_attn.q_proj, layer.self_attn.k_proj, layer.self_attn.v_proj,
-                                             layer.self_attn.out_proj, layer.fc1, layer.fc2)))
+            dec = self.model.decoder
+            _plain(self.lm_head, *self._self_attn_projections(), *(m for layer in dec.layers for m in (layer.fc1, layer.fc2)),
+                   *(m for layer in dec.neighbor_layers for m in (layer.self_attn.q_proj, layer.self_attn.k_proj, layer.self_attn.v_proj,
+                                                                  layer.self_attn.out_proj, layer.fc1, layer.fc2)))
         if W > 1:
             if inputs_embeds is not None:
                 raise ValueError("generate(): beam search (num_beams > 1) takes input_ids prompts, not inputs_embeds")
@@ -1195,11 +1056,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
                              f"{dec.max_target_positions}")
         if proc is not None:
             proc.upload(dev)                                   # in front of the prefill: see LogitsProcessors
-        if do_sample:
-            select = SampledTail(sampling_u("generate()", n_new, B * R, dev, seed, sample_u), temperature, top_k, top_p, eos_token_id,
-                                 pad_token_id)
-        else:
-            select = GreedyTail(B, dev, eos_token_id, pad_token_id)
+        select = make_select("generate()", do_sample, n_new, B, R, dev, seed, sample_u, temperature, top_k, top_p, eos_token_id, pad_token_id)
         out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
                   cache_capacity=T if R > 1 or kc else T + n_new - 1, kv_cache_dtype=kv_dtype)
@@ -1227,15 +1084,8 @@ class MPTForCausalLM(MPTPreTrainedModel):
         with B rows; its last-row logits seed the W beams (rows_in = 1 of ops.beam_topk, in place of HF's -1e9 start scores).  Every
         later step runs the decode kernels at M = B*W rows: the prompt keys and the neighbor tokens are read once per sample and
         scored against its W queries, the keys generated so far live in a [B*W, max_new_tokens - 1, 2d] tail per layer that a parent
-        table addresses (ops.attn_decode_beam) -- reordering hypotheses rewrites that table, no cache row moves.  Per step
-        ops.beam_topk (two launches) picks each sample's 2W best continuations and ops.beam_advance (one launch) turns them into the
-        next tokens, parents, running scores, table and pool of finished hypotheses; nothing synchronises with the host.
-        Semantics of transformers' beam search: the first W non-EOS candidates run on; an EOS candidate among the first W (every one
-        of them at the last step) enters the pool with score = log-prob sum / generated_length ** length_penalty; a sample is frozen
-        once its pool is full under early_stopping=True or the early-stop heuristic is met.  All max_new_tokens steps run.
-        Returns ids [B, T + max_new_tokens] -- the best pooled hypothesis, pad_token_id behind its last token -- then, as asked,
-        sequences_scores fp32 [B] and the trace: per step a dict of the running beams' parents / tokens / scores [B, W] and the 2W
-        candidates cand_index / cand_score [B, 2W]."""
+        table addresses (ops.attn_decode_beam) -- reordering hypotheses rewrites that table, no cache row moves.  The checks, the
+        prefill and the BeamState are here; the steps, the semantics and what is returned are generation.beam_loop's."""
         if input_ids is None or input_ids.dim() != 2:
             raise ValueError("generate(): beam search takes input_ids [B, T]")
         if W > ops.MAX_BEAMS:
@@ -1245,42 +1095,13 @@ class MPTForCausalLM(MPTPreTrainedModel):
                                                                  pad_token_id, self.config, dec.max_target_positions)
         if pad_token_id is None:                               # without EOS every hypothesis has all max_new_tokens tokens
             pad_token_id = 0 if self.config.pad_token_id is None else self.config.pad_token_id
-        dev = input_ids.device
         out = dec(input_ids=input_ids, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid, cache_capacity=T)
         cache = out.past_key_values
-        cache.beam = beam = BeamState(cache, W, n_new - 1)
-        book = beam.book
-        hidden = out.last_hidden_state[:, -1]
-        V = self.lm_head.weight.shape[0]
-        start = torch.zeros(B, dtype=torch.float32, device=dev)
-        history = torch.empty(n_new, B, W, dtype=torch.int64, device=dev)       # history[s, b, w]: the token slot w took at step s
-        trace = []
-        for s in range(n_new):
-            logits = self._last_logits(hidden)
-            cs, ci = ops.beam_topk(logits, start if s == 0 else book.beam_score, W, rows_in=1 if s == 0 else W)
-            ops.beam_advance(cs, ci, book, s, V, eos_token_id, s == n_new - 1, early_stopping, float(s + 1) ** length_penalty)
-            history[s] = book.tokens.view(B, W)
-            if return_trace:
-                trace.append(dict(parents=book.parents.view(B, W).clone(), tokens=book.tokens.view(B, W).clone(),
-                                  scores=book.beam_score.view(B, W).clone(), cand_index=ci, cand_score=cs))
-            if s + 1 < n_new:
-                hidden = dec(input_ids=history[s].reshape(B * W, 1), past_key_values=cache).last_hidden_state[:, 0]
-        # the best pooled hypothesis of each sample: tokens 0 .. len-2 through its ancestry row, its own last token, then padding
-        score, length, anc, last = (t.view(B, W, *t.shape[1:])[:, 0] for t in book.pool)
-        cols = torch.arange(n_new, device=dev)[None, :]
-        slot = torch.zeros(B, n_new, dtype=torch.int64, device=dev)
-        slot[:, :n_new - 1] = anc[:, :n_new - 1]
-        new = history.permute(1, 0, 2).gather(2, slot[:, :, None])[:, :, 0]                       # [B, n_new]
-        length = length.long()[:, None]
-        new = torch.where(cols < length - 1, new, torch.where(cols == length - 1, last[:, None], torch.full_like(new, pad_token_id)))
-        ids = torch.cat([input_ids, new.to(input_ids.dtype)], dim=1)
-        res = (ids,)
-        if return_scores:
-            res += (score.clone(),)
-        if return_trace:
-            res += (trace,)
-        return res[0] if len(res) == 1 else res
+        cache.beam = BeamState(cache, W, n_new - 1)
+        return beam_loop(self._last_logits, lambda tok: dec(input_ids=tok, past_key_values=cache).last_hidden_state[:, 0],
+                         out.last_hidden_state[:, -1], cache.beam.book, input_ids, n_new, W, self.lm_head.weight.shape[0], eos_token_id,
+                         pad_token_id, length_penalty, early_stopping, return_scores, return_trace)
 
 
 def copy_opt_weights(opt_model, mpt_model):

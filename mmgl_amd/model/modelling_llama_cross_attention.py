@@ -26,9 +26,9 @@ import torch.nn.functional as F
 from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from .. import ops
-from .modelling_cross_attention import DecodeCache, LookupState
-from .generation import GreedyTail, SampledTail, check_prompt, decode_loop, lookup_loop
-from .sampling import check_kv_cache, check_lookup, check_processors, check_sampling, sampling_u
+from .decode_cache import DecodeCache, LookupState
+from .generation import check_prompt, decode_loop, lookup_loop, make_select
+from .sampling import check_kv_cache, check_lookup, check_processors, check_sampling
 
 
 class LlamaGatedCrossAttentionLayer(nn.Module):
@@ -67,21 +67,16 @@ class LlamaGatedCrossAttentionLayer(nn.Module):
         m = ops.linear(ops.swiglu(gu), self.down_proj.weight, None)
         return ops.gated_residual(h, m, self.gating2, self.dropout, self.training)
 
-    def decode_step(self, h, k, v, key_valid, w_gu, rows=1):
-        """The layer on the one new token of a decode step, h [B, hidden], against the neighbor keys and values projected at the
-        prefill (k, v [B, S, hidden]); w_gu: the [gate | up] weight, concatenated once per generation.
-        rows = W > 1: h [B*W, hidden], the W tokens per sample of a verify step (prompt-lookup decoding) -- the W rows of a sample
-        read its neighbor tokens once (ops.attn_decode_beam without a tail, as MPTAttention.decode_cross): k, v stay at B rows."""
+    def decode_step(self, h, cache, k):
+        """The layer on the rows of a decode or verify step, h [rows, hidden], against the neighbor keys and values projected at the
+        prefill (cache.cross[k], at B rows in every mode: DecodeCache.attend_cross) with cache.cross_gu[k], the [gate | up] weight
+        concatenated once per generation."""
         x = ops.rms_norm(h, self.input_layernorm, self.eps)
         q = ops.decode_linear(x, self.q_proj.weight, None, out_scale=self.head_dim ** -0.5)
-        if rows > 1:
-            a = ops.attn_decode_beam(q, k, v, key_valid, self.num_heads, rows)
-        else:
-            a = ops.attn_decode(q, k, v, key_valid, self.num_heads)
-        a = ops.decode_linear(a, self.o_proj.weight, None)
+        a = ops.decode_linear(cache.attend_cross(k, q, self.num_heads), self.o_proj.weight, None)
         h = ops.gated_residual(h, a, self.gating1, 0.0, False)
         x = ops.rms_norm(h, self.post_attention_layernorm, self.eps)
-        m = ops.decode_linear(ops.swiglu(ops.decode_linear(x, w_gu, None)), self.down_proj.weight, None)
+        m = ops.decode_linear(ops.swiglu(ops.decode_linear(x, cache.cross_gu[k], None)), self.down_proj.weight, None)
         return ops.gated_residual(h, m, self.gating2, 0.0, False)
 
 
@@ -130,40 +125,17 @@ class _FrozenLlamaLayer:
         m = ops.frozen_linear(ops.swiglu(ops.frozen_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None)
         return h, m
 
-    def decode_step(self, h, kv, key_mask, col, cos_sin_row, q8=None):
-        """The layer on the one new token of a decode step, h [B, hidden] -> [B, hidden]: the token's q|k|v row from one skinny GEMM,
-        rotated and filed into column `col` of kv [B, capacity, 2*Hkv*D] by one kernel, single-query attention over columns 0..col
-        (all at or before the query: no causal test), both residual adds in GEMM epilogues.
-        q8 = (scale, kv_new) of an FP8 cache (kv then holds e4m3fn codes): the rotated k and the v go into the dense kv_new
-        [B, 2*Hkv*D] instead of a cache column, and ops.attn_decode_q8 attends over the `col` cached columns plus the new row and
-        files it, quantised, at column `col` -- the launches of the plain step."""
+    def decode_step(self, h, cache, l):
+        """The layer on the rows of a decode or verify step, h [rows, hidden] -> [rows, hidden]: the rows' q|k|v from one skinny GEMM
+        (per 64 rows) on w_qkv, rotated and filed by one kernel, the attention over layer l's Hkv-head cache, both residual adds in
+        GEMM epilogues.  Where the keys go, at which rotary positions, and which attention op reads them is the cache's mode
+        (decode_cache.DecodeCache: file_rotated, attend_self); every mode makes the launches of the plain step."""
         ly, eps = self.layer, self.cfg.rms_norm_eps
         w_qkv, w_gu = self._fused()
-        nq, nkv = self.H * self.D, self.Hkv * self.D
         x = ops.rms_norm(h, ly.input_layernorm.weight, eps)
-        if q8 is None:
-            qkv = ops.rope_kv_append(ops.decode_linear(x, w_qkv, None), cos_sin_row, kv[:, col], self.H, self.Hkv)
-            a = ops.attn_decode(qkv[:, :nq], kv[:, :col + 1, :nkv], kv[:, :col + 1, nkv:], key_mask[:, :col + 1], self.H, num_kv_heads=self.Hkv)
-        else:
-            scale, new = q8
-            qkv = ops.rope_kv_append(ops.decode_linear(x, w_qkv, None), cos_sin_row, new, self.H, self.Hkv)
-            a = ops.attn_decode_q8(qkv[:, :nq], new[:, :nkv], new[:, nkv:], kv, scale, key_mask[:, :col], self.H, num_kv_heads=self.Hkv)
-        h = ops.decode_linear(a, ly.self_attn.o_proj.weight, None, residual=h)
-        x = ops.rms_norm(h, ly.post_attention_layernorm.weight, eps)
-        return ops.decode_linear(ops.swiglu(ops.decode_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None, residual=h)
-
-    def decode_block(self, h, kv, key_mask, lookup, cos_sin):
-        """decode_step on the B*W rows of a verify step (prompt-lookup decoding), h [B*W, hidden] -> [B*W, hidden]: row b*W + i is
-        new token i of sample b, and its rotary position is its cache column lookup.len[b] + i -- per sample, on the device.  One
-        skinny GEMM per 64 rows on w_qkv; ops.rope_kv_append_block rotates at those positions (cos_sin: the cache's whole table)
-        and files the keys and values at columns lookup.len .. of kv (a column at or past the capacity is dropped);
-        ops.attn_decode_gqa_block then attends causally over the Hkv-head cache.  The launches of decode_step."""
-        ly, eps = self.layer, self.cfg.rms_norm_eps
-        w_qkv, w_gu = self._fused()
-        nq, nkv = self.H * self.D, self.Hkv * self.D
-        x = ops.rms_norm(h, ly.input_layernorm.weight, eps)
-        qkv = ops.rope_kv_append_block(ops.decode_linear(x, w_qkv, None), cos_sin, kv, lookup.len, self.H, self.Hkv, lookup.W)
-        a = ops.attn_decode_gqa_block(qkv[:, :nq], kv[:, :, :nkv], kv[:, :, nkv:], key_mask, lookup.len, self.H, self.Hkv, lookup.W)
+        qkv = ops.decode_linear(x, w_qkv, None)
+        new = cache.file_rotated(l, qkv, self.H, self.Hkv)
+        a = cache.attend_self(l, qkv[:, :self.H * self.D], new, self.H, self.Hkv)
         h = ops.decode_linear(a, ly.self_attn.o_proj.weight, None, residual=h)
         x = ops.rms_norm(h, ly.post_attention_layernorm.weight, eps)
         return ops.decode_linear(ops.swiglu(ops.decode_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None, residual=h)
@@ -321,48 +293,41 @@ class LlamaNeighborLM(nn.Module):
         if input_ids is None or input_ids.dim() != 2 or input_ids.shape[1] != 1 or input_ids.shape[0] != cache.mask.shape[0]:
             raise ValueError(f"a decode step takes one new token per cached sample ([{cache.mask.shape[0]}, 1]), "
                              f"got {None if input_ids is None else tuple(input_ids.shape)}")
-        if getattr(cache, "cos_sin", None) is None:
+        if cache.cos_sin is None:
             raise ValueError("the DecodeCache has not been filled: run the prompt with use_cache=True first")
         if cache.col >= cache.capacity:
             raise ValueError(f"decode cache is full: column {cache.col} of capacity {cache.capacity}")
         ops.require_cuda(cache.mask, input_ids)
-        col, eps = cache.col, self.config.rms_norm_eps
         with torch.no_grad():
-            h = self.llama.get_input_embeddings()(input_ids[:, 0])
-            cache.mask[:, col] = 1
-            row = cache.cos_sin[col]
-            k = 0
-            for l, layer in enumerate(self._frozen):
-                h = layer.decode_step(h, cache.kv[l], cache.mask, col, row, None if cache.kv_scale is None else (cache.kv_scale[l], cache.kv_new))
-                if (l + 1) % self.neighbor_layer_wise == 0:
-                    if cache.cross:
-                        h = self.neighbor_layers[k].decode_step(h, *cache.cross[k], cache.cross_valid, cache.cross_gu[k])
-                    k += 1
-            h = ops.rms_norm(h, self.llama.model.norm.weight, eps)
+            cache.mask[:, cache.col] = 1
+            h = self._decode_rows(input_ids[:, 0], cache)
             cache.col += 1
         return h
 
     def _verify_step(self, cache):
         """A verify step of prompt-lookup decoding: the W = K + 1 tokens cache.lookup.block [B, W] of every sample -- its last token,
-        then the drafts -- causally against the sample's lookup.len cache columns.  The layers run at B*W rows
-        (_FrozenLlamaLayer.decode_block, the gated layers' decode_step with W rows per sample) and file the block's keys and values at
-        columns lookup.len .. lookup.len + W - 1 (below the capacity); which of them count is decided afterwards by
-        ops.lookup_accept, which advances lookup.len.  A token's position is its column, so lookup.positions is not read, and
+        then the drafts -- causally against the sample's lookup.len cache columns.  The layers run at B*W rows and file the block's
+        keys and values at columns lookup.len .. lookup.len + W - 1 (below the capacity); which of them count is decided afterwards
+        by ops.lookup_accept, which advances lookup.len.  A token's position is its column, so lookup.positions is not read, and
         cache.col stands still at the prompt's width.  Returns the final-norm hidden rows [B*W, hidden]."""
-        lookup = cache.lookup
-        if lookup is None or getattr(cache, "cos_sin", None) is None:
+        if cache.lookup is None or cache.cos_sin is None:
             raise ValueError("a verify step needs a prefilled DecodeCache with a LookupState (cache.lookup)")
         ops.require_cuda(cache.mask)
         with torch.no_grad():
-            h = self.llama.get_input_embeddings()(lookup.block.view(-1))
-            k = 0
-            for l, layer in enumerate(self._frozen):
-                h = layer.decode_block(h, cache.kv[l], cache.mask, lookup, cache.cos_sin)
-                if (l + 1) % self.neighbor_layer_wise == 0:
-                    if cache.cross:
-                        h = self.neighbor_layers[k].decode_step(h, *cache.cross[k], cache.cross_valid, cache.cross_gu[k], lookup.W)
-                    k += 1
-            return ops.rms_norm(h, self.llama.model.norm.weight, self.config.rms_norm_eps)
+            return self._decode_rows(cache.lookup.block.view(-1), cache)
+
+    def _decode_rows(self, tokens, cache):
+        """The walk of a decode or verify step: tokens [rows] -> final-norm hidden [rows, hidden] through every frozen layer's
+        decode_step, the gated layers interleaved."""
+        h = self.llama.get_input_embeddings()(tokens)
+        k = 0
+        for l, layer in enumerate(self._frozen):
+            h = layer.decode_step(h, cache, l)
+            if (l + 1) % self.neighbor_layer_wise == 0:
+                if cache.cross:
+                    h = self.neighbor_layers[k].decode_step(h, cache, k)
+                k += 1
+        return ops.rms_norm(h, self.llama.model.norm.weight, self.config.rms_norm_eps)
 
     def _last_logits(self, hidden):
         """lm_head on one row per sample, hidden [B, hidden] (any row stride): the [V, hidden] head is read once for the B rows."""
@@ -423,11 +388,7 @@ class LlamaNeighborLM(nn.Module):
         dev = input_ids.device
         if proc is not None:
             proc.upload(dev)                                   # in front of the prefill: see LogitsProcessors
-        if do_sample:
-            select = SampledTail(sampling_u("LlamaNeighborLM.generate()", n_new, B, dev, seed, sample_u), temperature, top_k, top_p,
-                                 eos_token_id, pad_token_id)
-        else:
-            select = GreedyTail(B, dev, eos_token_id, pad_token_id)
+        select = make_select(who, do_sample, n_new, B, 1, dev, seed, sample_u, temperature, top_k, top_p, eos_token_id, pad_token_id)
         hidden, cache = self._hidden(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid, True,
                                      T + n_new - 1, kv_dtype)
         if K > 0:

@@ -4,9 +4,9 @@ and mmgl_kv_quantize against the copy it replaces at the prefill.
     python tools/bench_attn_decode_q8.py [--batches 2,16,64] [--keys 512,2048] [--iters 200] [--rounds 5] [--out FILE]
 
 Both attention arms answer one decode step's call for q [B, H*D] bf16, H = 32, D = 64, over S cached columns plus the new token: the
-bf16 arm reads cache rows [B, S + 1, 2 H D] bf16 whose last column holds the new token (as MPTAttention.decode_self leaves it), the
-FP8 arm reads S columns of e4m3fn codes [B, S + 1, 2 H D] with their int8 exponents [B, S + 1, 2 H], takes the new token dense and
-files it at column S.  A decode step streams gigabytes of weights between two attention calls, so no cache row is in a cache when its
+bf16 arm reads cache rows [B, S + 1, 2 H D] bf16 whose last column holds the new token (as MPTAttention.decode_self leaves it in the
+plain mode of DecodeCache), the FP8 arm reads S columns of e4m3fn codes [B, S + 1, 2 H D] with their int8 exponents [B, S + 1, 2 H],
+takes the new token dense and files it at column S.  A decode step streams gigabytes of weights between two attention calls, so no cache row is in a cache when its
 call starts: each timed loop walks a ring of caches larger than the 256 MB Infinity Cache, as tools/bench_attn_decode_gqa.py does.
 Rounds alternate fp8 / bf16 / fp8 / ...; the table gives the median microseconds per call of each arm (min..max over the rounds), the
 bytes each arm reads over its time, and the ratio.  The prefill table times one ops.kv_quantize launch against the one strided copy of
