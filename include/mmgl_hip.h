@@ -597,6 +597,24 @@ int mmgl_logits_process(void* logits, size_t ld_logits, const int64_t* history, 
                         size_t ld_valid, int n_masked, int hist_len, const int* ban, int n_ban, int rows, int V,
                         float repetition_penalty, int no_repeat_ngram_size, int dtype, void* stream);
 
+/* ---- neighbor guidance (generate(guidance_scale = g); csrc/guidance.hip), one launch -----------------------------------------------
+ * replaces: transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor arithmetic -- log_softmax of the conditional and of the
+ *           unconditional logits and their combination, three aten launches and two [rows, V] fp32 intermediates.
+ *
+ * mmgl_guidance_logits: logits [2 * batch, V] (bf16 / fp32, row stride ld_logits >= V elements, any alignment).  Rows b and batch + b
+ * are a pair: row b the logits with neighbors, row batch + b those of the same tokens without the gated layers.  With
+ * lc = log_softmax(row b), lu = log_softmax(row batch + b) in fp32 (a NaN logit counts as -inf), row b is rewritten in place with
+ *   lu + guidance_scale * (lc - lu)
+ * evaluated in fp32 and rounded once to the logits' dtype.  Where the conditional logit is -inf the result is -inf; where only the
+ * unconditional one is, the result is lc.  A row without any finite logit is outside the contract: nothing faults, what is stored is
+ * unspecified.  Rows batch .. 2 batch - 1, the columns between V and ld_logits and everything else keep their bits.
+ * Both log-sum-exps are reduced in a fixed order (a thread's elements in index order, a wave butterfly, the waves in order): two
+ * runs are bitwise equal.
+ *   V <= 131072, else MMGL_ERR_UNSUPPORTED.  MMGL_ERR_INVALID: a null pointer, batch <= 0, V <= 0, ld_logits < V, a bad dtype, a
+ *   guidance_scale that is negative or not finite.  A refused call writes nothing.
+ *   One workgroup per pair, no workspace, no atomics, no host synchronisation.  Plain vector stores only. */
+int mmgl_guidance_logits(void* logits, size_t ld_logits, int batch, int V, float guidance_scale, int dtype, void* stream);
+
 /* ---- prompt-lookup decoding (generate(prompt_lookup_num_tokens = K), 1 <= K <= 7; csrc/decode.hip, csrc/lookup.hip) ---------------
  * replaces: transformers' PromptLookupCandidateGenerator + the assisted-decoding verification behind generate(
  *           prompt_lookup_num_tokens=K), which re-runs a [B = 1, K + 1] forward through the dynamic cache and crops it afterwards.

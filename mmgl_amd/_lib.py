@@ -100,6 +100,7 @@ SIGNATURES = {
     "mmgl_beam_advance": (I, [P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, P]),
     "mmgl_sample_tokens": (I, [P, Z, P, P, L, P, P, I, I, I, F, I, F, I, L, I, P]),
     "mmgl_logits_process": (I, [P, Z, P, Z, P, Z, I, I, P, I, I, I, F, I, I, P]),
+    "mmgl_guidance_logits": (I, [P, Z, I, I, F, I, P]),
     "mmgl_attn_decode_block_fwd": (I, [P, I, P, P, I, P, P, I, Z, I, P, I, P, P, I, I, I, I, I, P]),
     "mmgl_lookup_accept": (I, [P, Z, I, P, P, P, P, Z, P, Z, P, P, P, P, I, I, I, I, I, I, L, L, I, I, I, P]),
     "mmgl_rope_kv_append_block": (I, [P, I, P, I, P, I, Z, I, P, I, I, I, I, I, I, P]),

@@ -42,7 +42,7 @@ class Arguments:
     """Same field names and defaults as the reference's Arguments (:66-229) + `neighbor_layer_wise` + `num_beams` + the sampling knobs
     `do_sample` / `temperature` / `top_k` / `top_p` + the logits processors `repetition_penalty` / `no_repeat_ngram_size` /
     `min_new_tokens` + prompt-lookup decoding's `prompt_lookup_num_tokens` / `max_matching_ngram_size` + contrastive search's
-    `penalty_alpha` (with `top_k` as its k) + the FP8 key/value cache's `kv_cache_dtype`."""
+    `penalty_alpha` (with `top_k` as its k) + the FP8 key/value cache's `kv_cache_dtype` + neighbor guidance's `guidance_scale`."""
     overwrite_cache: Optional[bool] = _f(False, "Overwrite the cached preprocessed datasets or not.")
     dataset: Optional[str] = _f("wikiweb2m", "The name of the dataset to use.")
     task: Optional[str] = _f("section", "One of three generation tasks in WikiWeb2M")
@@ -107,6 +107,8 @@ class Arguments:
     penalty_alpha: float = _f(0.0, "contrastive search in the test protocol's generate(): the weight of the degeneration penalty, in "
                                    "(0, 1), with top_k candidates per step (OPT fork, plain projections; not with do_sample); 0 = off")
     repetition_penalty: float = _f(1.0, "repetition penalty of the test protocol's generate(); 1 = off")
+    guidance_scale: float = _f(1.0, "neighbor guidance of the test protocol's generate(): each step scores lu + g (lc - lu) on the "
+                                    "log-probabilities with (lc) and without (lu) neighbors; > 1 pushes towards the neighbors; 1 = off")
     no_repeat_ngram_size: int = _f(0, "no n-gram of this size occurs twice in the test protocol's generations; 0 = off")
     min_new_tokens: int = _f(0, "the end-of-sequence token is banned for this many new tokens in the test protocol's generate()")
     prompt_lookup_num_tokens: int = _f(0, "tokens drafted from the prompt and verified per step of the test protocol's greedy generate() "
@@ -645,6 +647,8 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                                   seed=getattr(args, "seed", None))
                 if float(getattr(args, "repetition_penalty", 1.0)) != 1.0:      # logits processors; the default protocol has none
                     fields["repetition_penalty"] = float(args.repetition_penalty)
+                if float(getattr(args, "guidance_scale", 1.0)) != 1.0 and "guidance_scale" in named:     # neighbor guidance; off by default
+                    fields["guidance_scale"] = float(args.guidance_scale)
                 if int(getattr(args, "no_repeat_ngram_size", 0)) != 0:
                     fields["no_repeat_ngram_size"] = int(args.no_repeat_ngram_size)
                 if int(getattr(args, "min_new_tokens", 0)) != 0:

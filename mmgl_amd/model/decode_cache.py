@@ -21,6 +21,7 @@ class DecodeCache:
       cos_sin     None, or the Llama LM's fp32 rotary table [capacity, D/2, 2]; cross_gu its gated layers' [gate | up] weights, concatenated
                   once per generation
       beam, lookup, kv_dtype    what selects the mode of a step, below
+      pairs       None, or the pair count B of a guided generation: batch_size is then 2B (the mode `guided`, below)
 
     The modes.  x is the layer input of a step's rows, q|k|v its projection, n the key width as above:
       plain       beam, lookup and kv_dtype None; rows = B.  k|v go into kv[l][:, col] -- the GEMM (OPT fork) or ops.rope_kv_append (Llama)
@@ -40,6 +41,10 @@ class DecodeCache:
                   first.  k|v of every layer go into the one dense kv_new [B, 2n] in the model's dtype, and ops.attn_decode_q8 attends
                   over the `col` cached columns plus the new row and files it, quantised, at column `col` -- the launches of the plain
                   step.  cross stays in the model's dtype.  No beams and no verify step.
+      guided      pairs = B (neighbor guidance, generate(guidance_scale)): the plain mode over 2B rows.  kv / mask / next_pos have 2B rows
+                  -- rows [0, B) are the prompts with neighbors, rows [B, 2B) the same prompts prefilled without the gated layers --
+                  and every frozen layer runs the plain step on all of them; cross / cross_valid keep B rows and the gated layers run
+                  on the leading B rows only (MPTDecoder._decode_rows).  No new branch below: pairs selects no kernel.  OPT fork only.
     The gated layers attend over cross[k] in every mode: ops.attn_decode, or with a BeamState / LookupState ops.attn_decode_beam without a
     tail -- the W rows of a sample read its neighbor tokens once."""
 
@@ -63,6 +68,7 @@ class DecodeCache:
         self.next_pos = None
         self.beam = None
         self.lookup = None
+        self.pairs = None
 
     def kv_out(self, idx):
         """What layer idx's prefill files its keys and values into (MPTAttention._file_kv)."""

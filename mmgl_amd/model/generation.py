@@ -22,7 +22,12 @@ Semantics, the same for every model:
     in front of the selection, with the returned row so far -- the prompt without its masked columns, then the new
     tokens -- as history; on step 0 of R > 1 the R draws of a prompt share its logits row and the prompt as history.  An embeddings
     prompt may name the ids it stands for (history_ids / history_mask [B, Th]); without them its history is the new tokens.
-  * return_step_logits: also the [rows, max_new_tokens, V] logits the tokens were picked from (the processed ones with proc)."""
+  * guidance (guidance_scale = g, sampling.check_guidance; None: off): every prompt has a row with neighbors and a row without, in
+    lockstep on the same tokens.  Each step's [2B, V] logits become B rows of lu + g (lc - lu) on log-probabilities
+    in one ops.guidance_logits call; then, in transformers' order, the processors, return_step_logits and the selection run on
+    those B rows, and the chosen token is fed to both rows of its pair.  The result has B rows.
+  * return_step_logits: also the [rows, max_new_tokens, V] logits the tokens were picked from (the processed ones with proc, the
+    guided scores with guidance)."""
 import torch
 
 from .. import ops
@@ -118,12 +123,13 @@ def _bind_processors(proc, ids, prompt_mask, history_ids, history_mask, repeat=1
 
 
 def decode_loop(last_logits, step, hidden, select, n_new, input_ids=None, prompt_mask=None, R=1, proc=None, history_ids=None,
-                history_mask=None, return_step_logits=False):
+                history_mask=None, return_step_logits=False, guidance=None):
     """The n_new steps behind a prefill whose last row is `hidden` [B, ...]: see the module docstring.  last_logits(hidden) ->
     [rows, V]; step(tokens [rows, 1]) -> the next hidden, called n_new - 1 times; select: a GreedyTail or a SampledTail over B*R
     rows; input_ids [B, T]: the prompt to return in front of the new tokens (None: an embeddings prompt); prompt_mask [B, T]: its
-    valid columns, read by proc only.  Returns ids, or (ids, step logits)."""
-    rows = hidden.shape[0] * R
+    valid columns, read by proc only.  guidance (a float g, None: off -- then nothing is added): `hidden` and every step have 2B rows,
+    the B rows with neighbors and then the B rows without; R is 1.  Returns ids, or (ids, step logits)."""
+    rows = hidden.shape[0] * R if guidance is None else hidden.shape[0] // 2
     T = 0 if input_ids is None else input_ids.shape[1]       # columns of the result in front of the new tokens
     ids = torch.empty(rows, T + n_new, dtype=select.ids_dtype or (torch.int64 if input_ids is None else input_ids.dtype),
                       device=hidden.device)
@@ -135,6 +141,8 @@ def decode_loop(last_logits, step, hidden, select, n_new, input_ids=None, prompt
     steps = []
     for s in range(n_new):
         logits = last_logits(hidden)
+        if guidance is not None:
+            logits = ops.guidance_logits(logits, rows, guidance)        # [2B, V] -> the B guided rows, in place
         shared = rows // logits.shape[0]                       # R on step 0 of R > 1 (the prefill's B rows, R draws each), else 1
         if proc is not None:
             proc(logits, hist[::shared, :Th + s], s, shared)
@@ -142,7 +150,7 @@ def decode_loop(last_logits, step, hidden, select, n_new, input_ids=None, prompt
             steps.append(logits if shared == 1 else logits.repeat_interleave(shared, dim=0))
         tok = select(logits, ids, T + s, s)
         if s + 1 < n_new:
-            hidden = step(tok[:, None])
+            hidden = step(tok[:, None] if guidance is None else tok.repeat(2)[:, None])
     if input_ids is not None:
         ids = ids.to(input_ids.dtype)
     elif not ids.is_contiguous():

@@ -40,7 +40,7 @@ from .. import ops
 from .decode_cache import BeamState, DecodeCache, LookupState      # noqa: F401 (re-exported: tests and tools import them from here)
 from .encoders import ClipTextEncoder, PackedTextEncoder, PackedVisionEncoder
 from .generation import beam_loop, check_prompt, contrastive_loop, decode_loop, lookup_loop, make_select
-from .sampling import check_contrastive, check_kv_cache, check_lookup, check_processors, check_sampling
+from .sampling import check_contrastive, check_guidance, check_kv_cache, check_lookup, check_processors, check_sampling
 
 CROSS_MODES = ("cross_attention", "embedding")
 
@@ -598,13 +598,15 @@ class MPTDecoder(MPTPreTrainedModel):
     def forward(self, input_ids=None, attention_mask=None, head_mask=None, past_key_values=None, inputs_embeds=None,
                 neighbor_embeds=None, neighbor_attention_mask=None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, first_key_valid=False, cache_capacity=None, key_tiles=None,
-                kv_cache_dtype=None):
+                kv_cache_dtype=None, cache_rows=None):
         """key_tiles (an ops.KeyTiles of attention_mask, optional): the frozen layers project keys and values for the 64-key tiles that
         hold a valid key only (MPTAttention.key_tiles_route says where); the result is that of the dense path.
         use_cache=True: the prefill of greedy generation -- the same kernels as any forward, plus a copy of every layer's keys and
         values into a DecodeCache (capacity `cache_capacity` columns, default max_position_embeddings) returned as past_key_values.
         kv_cache_dtype ("fp8" / torch.float8_e4m3fn, with use_cache=True): that cache keeps the frozen layers' keys and values as
         e4m3fn codes (sampling.check_kv_cache); the prefill's own attention still runs on the unquantised prompt.
+        cache_rows = (cache, r0) with use_cache=True: the prefill files into rows [r0, r0 + B) of that DecodeCache instead of a new one
+        (prefill_guided: the two halves of a guided generation's cache).
         past_key_values=DecodeCache with input_ids [B, 1]: one decode step (see _decode_step).  Any other past_key_values keeps its
         meaning: a fixed key/value prefix (prefix tuning)."""
         output_attentions = bool(output_attentions)
@@ -658,7 +660,14 @@ class MPTDecoder(MPTPreTrainedModel):
         if inputs_embeds is None:
             inputs_embeds = self.embed_tokens(input_ids)
         batch_size, seq_length = input_shape
-        if use_cache:
+        rows = slice(None)                                   # the cache rows this prefill files into
+        if use_cache and cache_rows is not None:
+            cache, r0 = cache_rows
+            rows = slice(r0, r0 + batch_size)
+            if kv_dtype is not None or cache.kv_scale is not None or seq_length > cache.capacity or rows.stop > cache.mask.shape[0]:
+                raise ValueError(f"decode cache: rows [{r0}, {rows.stop}) x {seq_length} columns do not fit a cache of "
+                                 f"{cache.mask.shape[0]} rows x {cache.capacity} columns in the model's dtype")
+        elif use_cache:
             capacity = self.max_target_positions if cache_capacity is None else int(cache_capacity)
             if seq_length > capacity or capacity > self.max_target_positions:
                 raise ValueError(f"decode cache: a prompt of {seq_length} columns, capacity {capacity}, max_position_embeddings "
@@ -710,7 +719,8 @@ class MPTDecoder(MPTPreTrainedModel):
             layer_outputs = decoder_layer(hidden_states, attention_mask=causal_attention_mask, layer_head_mask=lhm,
                                           output_attentions=output_attentions, defer_residual=defer,
                                           past_key_value=None if past_key_values is None else past_key_values[idx],
-                                          kv_out=None if cache is None else cache.kv_out(idx), key_tiles=key_tiles)
+                                          kv_out=None if cache is None else cache.kv_out(idx) if cache_rows is None else cache.kv[idx][rows],
+                                          key_tiles=key_tiles)
             if self.cross_attention and neighbor_embeds is not None and (idx + 1) % self.neighbor_layer_wise == 0:
                 hidden_states = _materialize(layer_outputs[0])
                 neighbor_idx = (idx + 1) // self.neighbor_layer_wise - 1
@@ -735,16 +745,43 @@ class MPTDecoder(MPTPreTrainedModel):
         if output_hidden_states:
             all_hidden_states += (hidden_states,)
         if cache is not None:
-            cache.mask[:, :seq_length] = causal_attention_mask
+            cache.mask[rows, :seq_length] = causal_attention_mask
             cache.col = seq_length
-            cache.next_pos = causal_attention_mask.sum(dim=1, dtype=torch.int64) + self.embed_positions.offset
-            if cache.cross:
+            next_pos = causal_attention_mask.sum(dim=1, dtype=torch.int64) + self.embed_positions.offset
+            if cache_rows is None:
+                cache.next_pos = next_pos
+            else:
+                cache.next_pos[rows] = next_pos
+            if cache.cross and (cache_rows is None or neighbor_embeds is not None):
                 cache.cross_valid = key_valid if key_valid is not None else torch.ones(cache.cross[0][0].shape[:2], dtype=torch.uint8,
                                                                                        device=hidden_states.device)
         if not return_dict:
             return tuple(v for v in [hidden_states, cache, all_hidden_states, all_self_attns] if v is not None)
         return BaseModelOutputWithPast(last_hidden_state=hidden_states, past_key_values=cache,
                                        hidden_states=all_hidden_states, attentions=all_self_attns)
+
+    def prefill_guided(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid=False,
+                       cache_capacity=None):
+        """The prefill of a guided generation (generate(guidance_scale)): the prompt twice through the existing
+        kernels into the two halves of ONE DecodeCache of 2B rows -- rows [0, B) with the neighbors, rows [B, 2B) with
+        neighbor_embeds=None, the LM without its gated layers.  cross / cross_valid keep B rows; cache.pairs = B.  Returns
+        (the last hidden rows [2B, d_embed], cache)."""
+        B, T = input_ids.shape
+        capacity = self.max_target_positions if cache_capacity is None else int(cache_capacity)
+        if T > capacity or capacity > self.max_target_positions:
+            raise ValueError(f"decode cache: a prompt of {T} columns, capacity {capacity}, max_position_embeddings {self.max_target_positions}")
+        w = self.embed_tokens.weight
+        cache = DecodeCache(len(self.layers), 2 * B, capacity, self.config.hidden_size, w.dtype, w.device)
+        cache.pairs = B
+        cache.next_pos = torch.empty(2 * B, dtype=torch.int64, device=w.device)
+        last = []
+        for r0, ne, nm in ((0, neighbor_embeds, neighbor_attention_mask), (B, None, None)):
+            out = self(input_ids=input_ids, attention_mask=attention_mask, neighbor_embeds=ne, neighbor_attention_mask=nm, use_cache=True,
+                       first_key_valid=first_key_valid, cache_rows=(cache, r0))
+            last.append(out.last_hidden_state[:, -1])
+        if len(cache.cross) != len(self.neighbor_layers) or not cache.cross:
+            raise ValueError("guidance_scale: the decoder ran no gated layer on the neighbors: there is nothing to contrast")
+        return torch.cat(last, dim=0), cache
 
     def _decode_step(self, input_ids, inputs_embeds, cache, output_hidden_states, return_dict):
         """One new token per sample against the cache: input_ids [B, 1] (or inputs_embeds [B, 1, d_embed]).  The token is appended
@@ -788,7 +825,9 @@ class MPTDecoder(MPTPreTrainedModel):
     def _decode_rows(self, emb, positions, cache, layer_inputs=None):
         """The walk of a decode or verify step over its rows: emb [rows, d_embed] the token embeddings, positions [rows] their position
         ids -> the hidden rows [rows, d_embed] in front of lm_head.  project_in, the position rows, every layer's decode_step with the
-        gated layers interleaved, the final LayerNorm, project_out.  layer_inputs: a list that takes every frozen layer's input."""
+        gated layers interleaved, the final LayerNorm, project_out.  layer_inputs: a list that takes every frozen layer's input.
+        A guided step (cache.pairs = B, rows = 2B: DecodeCache's mode `guided`) runs the gated layers on the leading B rows only and
+        copies their output back into those rows."""
         if self.project_in is not None:
             emb = ops.decode_linear(emb.contiguous(), self.project_in.weight, self.project_in.bias)
         h = emb + F.embedding(positions, self.embed_positions.weight)
@@ -798,7 +837,10 @@ class MPTDecoder(MPTPreTrainedModel):
             h = layer.decode_step(h, cache, idx)
             if cache.cross and (idx + 1) % self.neighbor_layer_wise == 0:
                 nb = (idx + 1) // self.neighbor_layer_wise - 1
-                h = self.neighbor_layers[nb].decode_step(h, cache, nb)
+                if cache.pairs is None:
+                    h = self.neighbor_layers[nb].decode_step(h, cache, nb)
+                else:                         # a guided step: the rows with neighbors lead; the rows without skip the gated layer
+                    h[:cache.pairs] = self.neighbor_layers[nb].decode_step(h[:cache.pairs], cache, nb)
         if self.final_layer_norm is not None:
             fln = self.final_layer_norm
             h = ops.layer_norm(h, fln.weight, fln.bias, fln.eps)
@@ -977,7 +1019,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
                  num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, history_ids=None,
                  history_mask=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False, penalty_alpha=0.0,
-                 return_contrastive_trace=False, kv_cache_dtype=None):
+                 return_contrastive_trace=False, kv_cache_dtype=None, guidance_scale=None):
         """Generation with a key/value cache: what the reference's test protocol asks of its wrappers
         (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of every
         layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
@@ -1008,7 +1050,19 @@ class MPTForCausalLM(MPTPreTrainedModel):
         projected and are filed quantised; the prefill's attention runs on the unquantised prompt; the neighbor tokens of the gated
         layers stay in the model's dtype.  For the greedy and sampled loop of one row per prompt, with the processors and
         return_step_logits; refused with beams, num_return_sequences > 1, prompt-lookup decoding, contrastive search and adapted
-        projections (sampling.check_kv_cache)."""
+        projections (sampling.check_kv_cache).
+        guidance_scale = g (None or 1: off, every path as without it; else a finite g >= 0): neighbor guidance, transformers'
+        guidance_scale with the LM without its gated layers -- forward(neighbor_embeds=None) -- as the unconditional model (DESIGN.md
+        4.20).  Every prompt has a row with neighbors and a row without, prefilled in two passes into one cache of 2B rows
+        (MPTDecoder.prefill_guided) and stepped in lockstep on the same tokens; each step's [2B, V] logits become B rows of
+        lu + g (lc - lu) on log-probabilities (ops.guidance_logits), which the processors, return_step_logits and the greedy or
+        sampled selection then take.  g > 1 pushes towards what the neighbors contribute, g = 0 follows the LM without them.  For the
+        loop of one row per prompt with input_ids prompts and neighbor tokens; refused with the other decoding modes
+        (sampling.check_guidance)."""
+        dec = self.model.decoder
+        guidance = check_guidance("generate()", guidance_scale, num_beams, num_return_sequences, prompt_lookup_num_tokens, penalty_alpha,
+                                  kv_cache_dtype, inputs_embeds, neighbor_embeds is not None,
+                                  dec.cross_attention and len(dec.neighbor_layers) > 0)
         kv_dtype = check_kv_cache("generate()", kv_cache_dtype, num_beams, num_return_sequences, prompt_lookup_num_tokens, penalty_alpha,
                                   self._self_attn_projections() if kv_cache_dtype is not None else ())
         kc = check_contrastive("generate()", penalty_alpha, top_k, return_contrastive_trace, do_sample, num_beams, num_return_sequences,
@@ -1057,6 +1111,11 @@ class MPTForCausalLM(MPTPreTrainedModel):
         if proc is not None:
             proc.upload(dev)                                   # in front of the prefill: see LogitsProcessors
         select = make_select("generate()", do_sample, n_new, B, R, dev, seed, sample_u, temperature, top_k, top_p, eos_token_id, pad_token_id)
+        if guidance is not None:
+            hidden, cache = dec.prefill_guided(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid,
+                                               T + n_new - 1)
+            return decode_loop(self._last_logits, lambda tok: dec(input_ids=tok, past_key_values=cache).last_hidden_state[:, 0], hidden,
+                               select, n_new, input_ids, attention_mask, 1, proc, None, None, return_step_logits, guidance)
         out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
                   cache_capacity=T if R > 1 or kc else T + n_new - 1, kv_cache_dtype=kv_dtype)
@@ -1415,7 +1474,7 @@ class CrossAttentionModel(nn.Module):
                  return_sequences_scores=False, return_beam_trace=False, num_return_sequences=1, do_sample=False, temperature=1.0,
                  top_k=0, top_p=1.0, seed=None, sample_u=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
                  suppress_tokens=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False, penalty_alpha=0.0,
-                 return_contrastive_trace=False, kv_cache_dtype=None):
+                 return_contrastive_trace=False, kv_cache_dtype=None, guidance_scale=None):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded): the neighbors are encoded and interleaved once, exactly
         as forward does, then MPTForCausalLM.generate runs the prefill and the cached decode steps.  Returns [B, T + max_new_tokens]
         ids (and the step logits with return_step_logits=True).  num_beams, length_penalty, early_stopping, return_sequences_scores and
@@ -1427,9 +1486,14 @@ class CrossAttentionModel(nn.Module):
         return_lookup_stats (drafts come from input_ids and the new tokens, never from the neighbors), and its contrastive-search
         keywords penalty_alpha (with top_k as its k) and return_contrastive_trace (the k candidates of a sample read its neighbor
         tokens once: they stay at B rows), and its kv_cache_dtype ("fp8": the frozen layers' cache as e4m3fn codes; the projected
-        neighbor tokens stay in the model's dtype)."""
+        neighbor tokens stay in the model's dtype), and its guidance_scale (neighbor guidance: the neighbors are encoded once and feed
+        the B rows with neighbors; the B rows without run the LM alone)."""
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the OPT fork only, not for {type(self.lm).__name__}")
+        dec = self.lm.model.decoder
+        check_guidance("generate()", guidance_scale, num_beams, num_return_sequences, prompt_lookup_num_tokens, penalty_alpha, kv_cache_dtype,
+                       None, not (self.neighbor_mode == "raw" or self.context == "section_only") and neighbor_input_ids is not None,
+                       dec.cross_attention and len(dec.neighbor_layers) > 0)
         check_kv_cache("generate()", kv_cache_dtype, num_beams, num_return_sequences, prompt_lookup_num_tokens, penalty_alpha,
                        self.lm._self_attn_projections() if kv_cache_dtype is not None else ())
         kc = check_contrastive("generate()", penalty_alpha, top_k, return_contrastive_trace, do_sample, num_beams, num_return_sequences,
@@ -1455,4 +1519,5 @@ class CrossAttentionModel(nn.Module):
                                 no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
                                 prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
                                 return_lookup_stats=return_lookup_stats, penalty_alpha=penalty_alpha,
-                                return_contrastive_trace=return_contrastive_trace, kv_cache_dtype=kv_cache_dtype)
+                                return_contrastive_trace=return_contrastive_trace, kv_cache_dtype=kv_cache_dtype,
+                                guidance_scale=guidance_scale)

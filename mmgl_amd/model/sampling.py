@@ -1,4 +1,4 @@
-"""The sampling, logits-processor, prompt-lookup, contrastive-search and key/value-cache arguments shared by the three generate()
+"""The sampling, logits-processor, prompt-lookup, contrastive-search, key/value-cache and neighbor-guidance arguments shared by the three generate()
 methods (MPTForCausalLM / CrossAttentionModel, SelfAttentionModel, LlamaNeighborLM): their checks, which need no device, the uniform numbers a sampled generation consumes and the
 per-generation state of the processors.  The selection itself is ops.sample_tokens, the processors are ops.process_logits, one launch
 per decode step each; the loop that makes those calls is generation.decode_loop."""
@@ -148,7 +148,45 @@ def check_kv_cache(who, kv_cache_dtype, num_beams=1, num_return_sequences=1, pro
     return ops.KV_FP8
 
 
-MAX_SUPPRESS = ops.MAX_BAN - 1         # the ban array of a generation is suppress_tokens followed by the EOS entry
+def check_guidance(who, guidance_scale, num_beams=1, num_return_sequences=1, prompt_lookup_num_tokens=0, penalty_alpha=0.0,
+                   kv_cache_dtype=None, inputs_embeds=None, neighbors=True, gated_layers=True):
+    """Validates generate()'s guidance_scale; returns None (off: None or 1.0 -- every path runs exactly as without the
+    keyword) or g as a float.  Any other finite g >= 0 contrasts each step's next-token distribution with neighbors against the one
+    of the LM without its gated layers: score = lu + g (lc - lu) on log-probabilities.  It belongs to the greedy and sampled loop of
+    one row per prompt (generation.decode_loop: the processors and return_step_logits combine with it) on a cache of 2B rows.
+    `neighbors`: whether the call has neighbor tokens; `gated_layers`: whether the decoder has layers that read them."""
+    if guidance_scale is None:
+        return None
+    if isinstance(guidance_scale, bool) or not isinstance(guidance_scale, (int, float)):
+        raise ValueError(f"{who}: guidance_scale = {guidance_scale!r} must be a finite number >= 0 (None or 1: off)")
+    g = float(guidance_scale)
+    if not (0.0 <= g < math.inf):
+        raise ValueError(f"{who}: guidance_scale = {guidance_scale} must be a finite number >= 0 (None or 1: off)")
+    if g == 1.0:
+        return None
+    on = f"{who}: guidance_scale = {guidance_scale} (neighbor guidance)"
+    if int(num_beams) != 1:
+        raise ValueError(f"{on} with num_beams = {num_beams} is not implemented (beam search scores hypotheses on the beam-shared cache)")
+    if int(num_return_sequences) != 1:
+        raise ValueError(f"{on} with num_return_sequences = {num_return_sequences} is not implemented (the continuations share the "
+                         "prompt's cache rows through the beam kernel)")
+    if int(prompt_lookup_num_tokens) != 0:
+        raise ValueError(f"{on} with prompt_lookup_num_tokens = {prompt_lookup_num_tokens} is not implemented (the drafts are verified "
+                         "against the unguided greedy choice)")
+    if float(penalty_alpha) != 0.0:
+        raise ValueError(f"{on} with penalty_alpha = {penalty_alpha} is not implemented (contrastive search ranks its candidates on the "
+                         "beam-shared cache)")
+    if kv_cache_dtype is not None:
+        raise ValueError(f"{on} with kv_cache_dtype = {kv_cache_dtype!r} is not implemented (the FP8 cache has no step of paired rows)")
+    if inputs_embeds is not None:
+        raise ValueError(f"{on} with inputs_embeds is not implemented (it takes input_ids prompts)")
+    if not neighbors or not gated_layers:
+        raise ValueError(f"{on} without neighbor tokens, or on a decoder without gated layers, is not implemented: there is nothing to "
+                         "contrast")
+    return g
+
+
+MAX_SUPPRESS = ops.MAX_BAN - 1        # the ban array of a generation is suppress_tokens followed by the EOS entry
 
 
 def check_processors(who, repetition_penalty, no_repeat_ngram_size, min_new_tokens, suppress_tokens, eos_token_id, max_new_tokens,

@@ -2295,6 +2295,29 @@ def process_logits(logits, history, history_valid=None, n_masked=None, repetitio
     return logits
 
 
+def guidance_logits(logits, batch, guidance_scale):
+    """Neighbor guidance of generate(guidance_scale=g) in one launch (mmgl_guidance_logits), in place on logits [2 * batch, V] (bf16 /
+    fp32, unit column stride, any row stride; V <= 131072).  Rows b and batch + b are a pair: the logits with neighbors and those of
+    the same tokens without the gated layers.  With lc / lu their log_softmax in fp32 (NaN counts as -inf), row b becomes
+    lu + g * (lc - lu), rounded once -- transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor.  A conditional -inf stays -inf,
+    an unconditional -inf under a finite conditional gives lc; a row without any finite logit is outside the contract.  Rows
+    batch .. 2 batch - 1 and every other byte keep their bits.  Returns the guided rows, the view logits[:batch].  No [rows, V]
+    intermediate, no host synchronisation, bitwise reproducible.  Forward only; GPU only."""
+    require_cuda(logits)
+    rows, V, code = _logits_operand("guidance_logits", logits)
+    batch, g = int(batch), float(guidance_scale)
+    if batch < 1 or rows != 2 * batch:
+        raise ValueError(f"guidance_logits: logits of {rows} rows for batch = {batch} (the conditional rows, then the unconditional ones: "
+                         f"{2 * batch} rows)")
+    if not (0.0 <= g < float("inf")):
+        raise ValueError(f"guidance_logits: guidance_scale = {guidance_scale} must be finite and not negative")
+    if logits.stride(0) < V:
+        raise ValueError(f"guidance_logits: logits{tuple(logits.shape)}/{logits.stride()}: the row stride must be at least V")
+    _lib.call("mmgl_guidance_logits", dict(bytes=float(batch) * V * logits.element_size() * 7), ptr(logits), logits.stride(0), batch, V, g,
+              code, stream_ptr())
+    return logits[:batch]
+
+
 class BeamBook:
     """The bookkeeping state of a beam search over B samples x W beams, all on the device (ops.beam_advance moves it one step):
       tokens int64 / parents int32 / beam_score fp32 [B*W]   the running beams of the last step (slot order = candidate order)
