@@ -778,7 +778,8 @@ int launch_gemm8p(const bf16* X, int ldx, const bf16* W, int ldw, bf16* Y, int l
             case 1: if (zr) P8_LAUNCH(1, true); else P8_LAUNCH(1, false); break;
             case 2: if (zr) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "gemm8p: gelu(erf) with residual / zmask is not instantiated"); P8_LAUNCH(2, false); break;
             case 3: if (zr) P8_LAUNCH(3, true); else P8_LAUNCH(3, false); break;
-            case 4: P8_LAUNCH(4, true); break;
+            // (the ZR kernels read a residual tile when they are given neither zmask nor mask bits: never launch one without any of the three)
+            case 4: if (zr) P8_LAUNCH(4, true); else P8_LAUNCH(4, false); break;
             default: MMGL_FAIL(MMGL_ERR_INVALID, "gemm8p: unknown activation %d", act);
         }
 #undef P8_LAUNCH
