@@ -791,6 +791,35 @@ int mmgl_attn_decode_gqa_q8_fwd(const void* q, int ldq, const void* k_new, const
                                 size_t batch_stride_scale, int capacity, const uint8_t* key_valid, int ld_valid, void* out, int B, int H,
                                 int Hkv, int S, int D, int dtype, void* stream);
 
+/* ---- FP8 frozen weights (generate(weight_dtype="fp8"); csrc/decode.hip) ---------------------------------------------------------------
+ * replaces: nothing in the reference (its decode step multiplies weights in the model's dtype).  Forward only; deterministic (no atomics).
+ *
+ * Format.  The FP8 key/value cache's, per weight row: a weight W [N, K] is `codes` [N, K] OCP e4m3fn bytes (unit column stride, row
+ * stride ld_codes bytes) and `exps` [N] int8; W[n, k] = codes[n, k] * 2^exps[n].  exps[n] is the exponent rule above applied to
+ * a = max_k |W[n, k]| (one function in the library, q8_exponent), the codes are e4m3fn(W[n, k] * 2^-exps[n]), round to nearest even:
+ * nothing saturates, and every value is exact in bf16.  Weights are finite: a NaN or an infinity is outside the contract (the row's
+ * exponent and codes are then unspecified); magnitudes outside [2^-100, 2^100] meet the exponent clamp.
+ *
+ * mmgl_weight_quantize: W [N, K] of T (bf16 or fp32, row stride ldw elements) -> codes, exps.  One launch, run once per weight: one
+ * wave per row, a first pass for the row's maximum, a second that encodes; 16 elements per lane and 16-byte stores where K % 16 == 0
+ * and the rows are 16-byte aligned, element by element otherwise.  Bitwise reproducible.  N, K < 1, a bad dtype, a null pointer,
+ * ldw < K or ld_codes < K: MMGL_ERR_INVALID, nothing written.
+ *
+ * mmgl_gemm_skinny_w8: y[M,N] = act((x[M,K] . (codes * 2^exps)^T + bias) * scale) + residual for 1 <= M <= 64 rows: mmgl_gemm_skinny
+ * on a quantised weight.  dtype is the type of x, bias, residual and y; ldx, ldy (elements) and ld_codes (bytes) are free.
+ *   bf16, K % 128 == 0, N % 8 == 0, ldx % 8 == 0, ld_codes % 16 == 0, x and codes 16-byte aligned: the MFMA kernel of
+ *   mmgl_gemm_skinny on code loads -- a K unit of 128 codes (one 128-byte line per weight row, two 16-byte loads per lane, non-temporal,
+ *   no LDS round trip, a ring of 4 units per lane in flight), codes -> bf16 A fragments in registers (v_cvt_scalef32_pk_bf16_fp8),
+ *   bf16 MFMA, fp32 accumulation, 16 or 8 weight rows per workgroup by mmgl_gemm_skinny's rule, the K slots folded in slot order; 2^exps[n]
+ *   multiplies the folded fp32 sum (exact) in front of bias, scale, activation and residual.
+ *   Anything else (fp32, other K / N, unaligned rows): one wave per output column, fp32 accumulation, the same epilogue.
+ * Two runs are bitwise equal.  Refusals as mmgl_gemm_skinny, under this name: sizes < 1, a bad dtype, a null x / codes / exps / y, an
+ * unknown activation, ldx < K, ld_codes < K or ldy < N: MMGL_ERR_INVALID; M > 64: MMGL_ERR_UNSUPPORTED.  A refused call writes
+ * nothing.  Plain vector stores only. */
+int mmgl_weight_quantize(const void* w, int ldw, void* codes, int ld_codes, void* exps, int N, int K, int dtype, void* stream);
+int mmgl_gemm_skinny_w8(const void* x, int ldx, const void* codes, int ld_codes, const void* exps, const void* bias, const void* residual,
+                        void* y, int ldy, int M, int N, int K, int act, float scale, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

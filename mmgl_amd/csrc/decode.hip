@@ -56,6 +56,11 @@
 // of its group): a 16-byte load of codes is issued and dequantised once and scored against the block's query heads from registers.
 // Every block folds the new token unquantised; block 0 of a group alone files it as codes.
 //
+// mmgl_weight_quantize / mmgl_gemm_skinny_w8 (weight_quantize_kernel, skinny_w8_mfma_kernel, skinny_w8_generic_kernel).  FP8 frozen
+// weights: a weight [N, K] as e4m3fn codes with one power-of-two scale per row, quantised once, and the skinny GEMM on the codes --
+// skinny_mfma_kernel's structure over a K unit of 128 codes (one 128-byte line per weight row), the codes converted to bf16 fragments
+// in registers, the row's scale applied to the folded fp32 sum.
+//
 // mmgl_rope_kv_append (rope_kv_append_kernel).  The new token's q | k | v row: q rotated in place, k rotated into the token's cache column,
 // v copied there -- one launch where separate projections and rotations would take four (the step is launch-bound).
 #include "common.h"
@@ -1333,6 +1338,254 @@ __global__ __launch_bounds__(256) void kv_quantize_kernel(const T* __restrict__ 
     if (c == 0) scale[b * bs_scale + (size_t)row * ld_scale + hh] = (int8_t)e;
 }
 
+// ------------------------------------------------------------------------------------------------ FP8 frozen weights
+// A frozen weight [N, K] in the cache's format, per weight row: e4m3fn codes [N, K] (row stride ldc bytes) and one int8 exponent per
+// row, value = code * 2^exps[n], exps[n] = q8_exponent(max |w[n, :]|).  Every e4m3 value is exact in bf16, so the decode GEMM keeps
+// its bf16 MFMA and its fp32 accumulation and reads half the bytes; the power of two multiplies the folded sum (exact).
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// mmgl_weight_quantize: one wave per weight row, two passes over it (the second re-reads the row from L2): the row's largest magnitude
+// by a butterfly (a maximum does not depend on the order), then the codes.  VEC: 16 elements per lane and trip, 16-byte code stores
+// (K % 16 == 0 and aligned rows); else element by element.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void weight_quantize_kernel(const T* __restrict__ w, long long ldw, uint8_t* __restrict__ codes, long long ldc,
+                                                             int8_t* __restrict__ exps, int N, int K) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;                             // whole waves leave; the kernel has no barrier
+    const T* src = w + (size_t)n * ldw;
+    uint8_t* dst = codes + (size_t)n * ldc;
+    float a = 0.f;
+    if (VEC) {
+        for (int k = lane * Q8_VEC; k < K; k += WAVE * Q8_VEC) {
+            float f[Q8_VEC];
+            load16<T>(src + k, f);
+#pragma unroll
+            for (int i = 0; i < Q8_VEC; ++i) a = fmaxf(a, fabsf(f[i]));
+        }
+    } else {
+        for (int k = lane; k < K; k += WAVE) a = fmaxf(a, fabsf(Elem<T>::to_f(src[k])));
+    }
+    const int e = q8_exponent(wave_max(a));
+    const float inv = q8_pow2(-e);
+    if (VEC) {
+        for (int k = lane * Q8_VEC; k < K; k += WAVE * Q8_VEC) {
+            float f[Q8_VEC];
+            load16<T>(src + k, f);
+            *(u32x4*)(dst + k) = q8_encode(f, inv);
+        }
+    } else {
+        for (int k = lane; k < K; k += WAVE)
+            dst[k] = (uint8_t)__builtin_amdgcn_cvt_pk_fp8_f32(Elem<T>::to_f(src[k]) * inv, 0.f, 0, false);
+    }
+    if (lane == 0) exps[n] = (int8_t)e;
+}
+
+template <typename T> struct SkW8Args {
+    SkArgs<T> a;                                    // x, bias, residual, y and the sizes; a.W and a.ldw are unused
+    const uint8_t* C; const int8_t* E;
+    int ldc;
+};
+
+// 8 codes (two 32-bit words, k ascending from the low byte) as a bf16 A fragment: v_cvt_scalef32_pk_bf16_fp8, scale 1
+__device__ __forceinline__ bf16x8 w8_frag(uint32_t lo, uint32_t hi) {
+    const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
+    const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true);
+    const bf16x4 ab = __builtin_shufflevector(a, b, 0, 1, 2, 3), cd = __builtin_shufflevector(c, d, 0, 1, 2, 3);
+    return __builtin_shufflevector(ab, cd, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// mmgl_gemm_skinny_w8, bf16: skinny_mfma_kernel on code loads.  The K unit is 128 codes = one 128-byte line of a weight row: lane
+// (i, g) reads codes[n0 + i][128 p + 64 h + 16 g .. + 15] for h = 0, 1, so each of the two 16-byte loads of a unit covers a 64-byte
+// half line over the four lane groups and the pair the whole line.  Half h of unit p is "pair" 2 p + h of skinny_mfma_kernel: the
+// same 64 x columns, staged and read the same way, and MFMA t of it contracts k = 128 p + 64 h + 16 g + 8 t + (0..7).  The K slots
+// are dealt unit by unit (slot s takes units s, s + NS, ...); a ring of DW units = DW x 32 bytes per lane is in flight, the bytes
+// skinny_mfma_kernel keeps in flight over twice the K.  Codes become bf16 fragments in registers (w8_frag); the row's power of two
+// multiplies the folded fp32 sum in front of the epilogue.
+template <int MT, bool HALF>
+__global__ __launch_bounds__(SK_THREADS) void skinny_w8_mfma_kernel(const SkW8Args<bf16> q) {
+    constexpr int SL = HALF ? 2 : 1;               // K slots per wave
+    constexpr int ROWS = HALF ? 8 : 16;            // weight rows per workgroup
+    constexpr int NS = SK_WAVES * SL;              // K slots per workgroup
+    constexpr int MR = MT * 16;                    // x rows held (rows >= M are zeros)
+    constexpr int XL = MR / 8;                     // x loads per lane, slot and half unit
+    constexpr int DW = 4;                          // W units in flight per lane
+    constexpr int DX = MT == 1 ? 4 : MT == 2 ? 2 : 1;      // x half units in flight per lane
+    __shared__ __attribute__((aligned(16))) unsigned char smem[NS * MR * 128];      // x staging of one half unit; the fold reuses it
+
+    const SkArgs<bf16>& a = q.a;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int i = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * ROWS;
+    const int P = a.K >> 7;
+    const int iters = (P + NS - 1) / NS;
+    const int wslot = HALF ? w * 2 + (i >> 3) : w;
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(q.C + (size_t)n0 * q.ldc, (uint32_t)((size_t)(ROWS - 1) * q.ldc + a.K));
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.X, (uint32_t)(((size_t)(a.M - 1) * a.ldx + a.K) * 2));
+    const uint32_t woff = (uint32_t)((HALF ? (i & 7) : i) * q.ldc + 16 * g);
+    const int xr_row = lane >> 3, xr_c = lane & 7;
+
+    u32x4 wr[DW][2];
+    bf16x8 xr[DX][SL * XL];
+    auto load_w = [&](int it, u32x4 (&dst)[2]) {
+        const int p = it * NS + wslot;
+        const uint32_t off = p < P ? woff + (uint32_t)p * 128u : OOB;
+        dst[0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, off, 0, 2));              // aux 2: non-temporal
+        dst[1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, off + 64u, 0, 2));
+    };
+    auto load_x = [&](int j, bf16x8 (&dst)[SL * XL]) {          // j: half unit 2 it + h of the slots' sequence
+#pragma unroll
+        for (int sl = 0; sl < SL; ++sl) {
+            const int p = (j >> 1) * NS + w * SL + sl;
+#pragma unroll
+            for (int r8 = 0; r8 < XL; ++r8) {
+                const int r = r8 * 8 + xr_row;
+                const uint32_t off = (p < P && r < a.M)
+                                         ? ((uint32_t)r * (uint32_t)a.ldx + (uint32_t)p * 128u + (uint32_t)(j & 1) * 64u + (uint32_t)xr_c * 8u) * 2u
+                                         : OOB;
+                dst[sl * XL + r8] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
+            }
+        }
+    };
+#pragma unroll
+    for (int u = 0; u < DW; ++u) load_w(u, wr[u]);
+#pragma unroll
+    for (int u = 0; u < DX; ++u) load_x(u, xr[u]);
+
+    f32x4 acc0[MT], acc1[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) { acc0[mt] = vzero<f32x4>(); acc1[mt] = vzero<f32x4>(); }
+
+    unsigned char* xs = smem + (size_t)w * SL * MR * 128;          // this wave's staging image
+    for (int it0 = 0; it0 < iters; it0 += DW) {
+#pragma unroll
+        for (int u = 0; u < DW; ++u) {
+            const int it = it0 + u;
+            if (it < iters) {                                       // uniform over the workgroup
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int xi = (2 * u + h) % DX;                // = (2 it + h) % DX: DX divides 2 DW
+#pragma unroll
+                    for (int sl = 0; sl < SL; ++sl)
+#pragma unroll
+                        for (int r8 = 0; r8 < XL; ++r8) {
+                            const int r = r8 * 8 + xr_row;
+                            *(bf16x8*)(xs + ((sl * MR + r) * 128) + ((xr_c ^ (r & 7)) << 4)) = xr[xi][sl * XL + r8];
+                        }
+                    __syncthreads();
+                    load_x(2 * it + h + DX, xr[xi]);
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        const bf16x8 af = w8_frag(wr[u][h][2 * t], wr[u][h][2 * t + 1]);
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) {
+                            const int row = mt * 16 + i;
+                            const int off = row * 128 + (((2 * g + t) ^ (i & 7)) << 4);
+                            const bf16x8 b0 = *(const bf16x8*)(xs + off);
+                            mma16(acc0[mt], af, b0);
+                            if (HALF) {
+                                const bf16x8 b1 = *(const bf16x8*)(xs + MR * 128 + off);
+                                mma16(acc1[mt], af, b1);
+                            }
+                        }
+                    }
+                    if (h == 1) load_w(it + DW, wr[u]);
+                    __syncthreads();
+                }
+            }
+        }
+    }
+
+    // fold: part[slot][m][ROWS] fp32, summed in slot order, then the row's power of two
+    float* part = (float*)smem;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        if (HALF) {
+            const int slot = 2 * w + (g >> 1);
+            *(f32x4*)&part[((size_t)slot * MR + mt * 16 + i) * 8 + 4 * (g & 1)] = g < 2 ? acc0[mt] : acc1[mt];
+        } else {
+            *(f32x4*)&part[((size_t)w * MR + mt * 16 + i) * 16 + 4 * g] = acc0[mt];
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < ROWS * a.M; idx += SK_THREADS) {
+        const int n = idx % ROWS, m = idx / ROWS;
+        float s = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) s += part[((size_t)sl * MR + m) * ROWS + n];
+        sk_store(a, m, n0 + n, s * q8_pow2(q.E[n0 + n]));
+    }
+}
+
+// skinny_generic_kernel on codes: one wave per output column, 8 rows of x per wave, fp32 accumulation, any K, N, stride and alignment
+template <typename T>
+__global__ __launch_bounds__(256) void skinny_w8_generic_kernel(const SkW8Args<T> q) {
+    const SkArgs<T>& a = q.a;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int n = blockIdx.x * 4 + w, m0 = blockIdx.y * 8;
+    if (n >= a.N) return;                           // whole waves leave; the kernel has no barrier
+    float acc[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[r] = 0.f;
+    const uint8_t* crow = q.C + (size_t)n * q.ldc;
+    for (int k = lane; k < a.K; k += WAVE) {
+        const float wv = __builtin_amdgcn_cvt_f32_fp8((int)crow[k], 0);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int m = min(m0 + r, a.M - 1);
+            acc[r] += wv * Elem<T>::to_f(a.X[(size_t)m * a.ldx + k]);
+        }
+    }
+    float mine = 0.f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const float s = wave_sum(acc[r]);
+        if (lane == r) mine = s;
+    }
+    if (lane < 8 && m0 + lane < a.M) sk_store(a, m0 + lane, n, mine * q8_pow2(q.E[n]));
+}
+
+template <int MT, bool HALF> int launch_skinny_w8_mfma(const SkW8Args<bf16>& q, hipStream_t st) {
+    hipLaunchKernelGGL((skinny_w8_mfma_kernel<MT, HALF>), dim3(q.a.N / (HALF ? 8 : 16)), dim3(SK_THREADS), 0, st, q);
+    MMGL_CHECK_LAUNCH("mmgl_gemm_skinny_w8");
+    return MMGL_OK;
+}
+
+template <bool HALF> int launch_skinny_w8_mt(const SkW8Args<bf16>& q, hipStream_t st) {
+    if (q.a.M <= 16) return launch_skinny_w8_mfma<1, HALF>(q, st);
+    if (q.a.M <= 32) return launch_skinny_w8_mfma<2, HALF>(q, st);
+    return launch_skinny_w8_mfma<4, HALF>(q, st);
+}
+
+template <typename T> int launch_skinny_w8_generic(const SkW8Args<T>& q, hipStream_t st) {
+    hipLaunchKernelGGL((skinny_w8_generic_kernel<T>), dim3(cdiv(q.a.N, 4), cdiv(q.a.M, 8)), dim3(256), 0, st, q);
+    MMGL_CHECK_LAUNCH("mmgl_gemm_skinny_w8");
+    return MMGL_OK;
+}
+
+// the route of a bf16 call on codes: skinny_bf16's rule with the 128-code unit and 16-byte code rows
+int skinny_w8_bf16(const SkW8Args<bf16>& q, hipStream_t st) {
+    const SkArgs<bf16>& a = q.a;
+    const bool mfma = a.K % 128 == 0 && a.N % 8 == 0 && a.ldx % 8 == 0 && q.ldc % 16 == 0 && aligned16(a.X) && aligned16(q.C) &&
+                      ((size_t)(a.M - 1) * a.ldx + a.K) * 2 < (1ull << 31) && (size_t)16 * q.ldc < (1ull << 31);
+    if (!mfma) return launch_skinny_w8_generic<bf16>(q, st);
+    if (a.N % 16 == 0 && a.N / 16 >= mmgl_num_cu()) return launch_skinny_w8_mt<false>(q, st);
+    return launch_skinny_w8_mt<true>(q, st);
+}
+
+template <typename T> int launch_weight_quantize(const void* w, int ldw, void* codes, int ldc, void* exps, int N, int K, hipStream_t st) {
+    const bool vec = K % Q8_VEC == 0 && ((size_t)ldw * sizeof(T)) % 16 == 0 && ldc % 16 == 0 && aligned16(w) && aligned16(codes);
+    const dim3 grid(cdiv(N, 4)), block(256);
+    if (vec) hipLaunchKernelGGL((weight_quantize_kernel<T, true>), grid, block, 0, st, (const T*)w, (long long)ldw, (uint8_t*)codes, (long long)ldc, (int8_t*)exps, N, K);
+    else hipLaunchKernelGGL((weight_quantize_kernel<T, false>), grid, block, 0, st, (const T*)w, (long long)ldw, (uint8_t*)codes, (long long)ldc, (int8_t*)exps, N, K);
+    MMGL_CHECK_LAUNCH("mmgl_weight_quantize");
+    return MMGL_OK;
+}
+
 // mmgl_attn_decode_q8_fwd: attn_decode_kernel over a cache of codes.  D / 16 lanes share a key (one 16-byte load of K codes and one
 // of V codes per lane: 16 codes), a wave covers 1024 / D keys per instruction, the 4 waves interleave key blocks and AD_UNROLL blocks
 // are in flight; keys past S fall outside the descriptors.  The key's scale multiplies the dot product, the value's scale multiplies
@@ -2018,4 +2271,32 @@ extern "C" int mmgl_attn_decode_gqa_q8_fwd(const void* q, int ldq, const void* k
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(attn_decode_gqa_q8_nq, bf16, D, a, Hkv, st);
     RETURN_BY_HEAD_DIM(attn_decode_gqa_q8_nq, float, D, a, Hkv, st);
+}
+
+extern "C" int mmgl_weight_quantize(const void* w, int ldw, void* codes, int ld_codes, void* exps, int N, int K, int dtype, void* stream) {
+    MMGL_CHECK_ARG(N >= 1 && K >= 1, "mmgl_weight_quantize: bad sizes N=%d K=%d", N, K);
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_weight_quantize: bad dtype %d", dtype);
+    MMGL_CHECK_ARG(w && codes && exps, "mmgl_weight_quantize: null pointer");
+    MMGL_CHECK_ARG(ldw >= K && ld_codes >= K, "mmgl_weight_quantize: leading dimensions (%d, %d) smaller than the rows (K=%d)", ldw, ld_codes, K);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_BF16) return launch_weight_quantize<bf16>(w, ldw, codes, ld_codes, exps, N, K, st);
+    return launch_weight_quantize<float>(w, ldw, codes, ld_codes, exps, N, K, st);
+}
+
+extern "C" int mmgl_gemm_skinny_w8(const void* x, int ldx, const void* codes, int ld_codes, const void* exps, const void* bias,
+                                   const void* residual, void* y, int ldy, int M, int N, int K, int act, float scale, int dtype, void* stream) {
+    MMGL_CHECK_ARG(M >= 1 && N >= 1 && K >= 1, "mmgl_gemm_skinny_w8: bad sizes M=%d N=%d K=%d", M, N, K);
+    const int bad = check_skinny(__func__, "chunk the rows", x && codes && exps && y, M, act, dtype);
+    if (bad) return bad;
+    MMGL_CHECK_ARG(ldx >= K && ld_codes >= K && ldy >= N, "mmgl_gemm_skinny_w8: leading dimensions (%d, %d, %d) smaller than the rows (K=%d, N=%d)",
+                   ldx, ld_codes, ldy, K, N);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_F32) {
+        const SkW8Args<float> q{{(const float*)x, nullptr, (const float*)bias, (const float*)residual, (float*)y, ldx, 0, ldy, M, N, K, act, scale},
+                                (const uint8_t*)codes, (const int8_t*)exps, ld_codes};
+        return launch_skinny_w8_generic<float>(q, st);
+    }
+    const SkW8Args<bf16> q{{(const bf16*)x, nullptr, (const bf16*)bias, (const bf16*)residual, (bf16*)y, ldx, 0, ldy, M, N, K, act, scale},
+                           (const uint8_t*)codes, (const int8_t*)exps, ld_codes};
+    return skinny_w8_bf16(q, st);
 }

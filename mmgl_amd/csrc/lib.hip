@@ -84,4 +84,5 @@ int mmgl_num_cu() {
 // mmgl_contrastive_chunk / mmgl_contrastive_workspace / mmgl_contrastive_select (contrastive search for generate()) were added at 110 the same way.
 // mmgl_kv_quantize / mmgl_attn_decode_q8_fwd (FP8 key/value cache for generate()) were added at 110 the same way.
 // mmgl_attn_decode_gqa_q8_fwd (FP8 key/value cache on the Llama-family LM) was added at 110 the same way.
+// mmgl_weight_quantize / mmgl_gemm_skinny_w8 (FP8 frozen weights for generate()) were added at 110 the same way.
 extern "C" int mmgl_version(void) { return 110; }

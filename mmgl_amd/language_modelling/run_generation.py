@@ -42,7 +42,8 @@ class Arguments:
     """Same field names and defaults as the reference's Arguments (:66-229) + `neighbor_layer_wise` + `num_beams` + the sampling knobs
     `do_sample` / `temperature` / `top_k` / `top_p` + the logits processors `repetition_penalty` / `no_repeat_ngram_size` /
     `min_new_tokens` + prompt-lookup decoding's `prompt_lookup_num_tokens` / `max_matching_ngram_size` + contrastive search's
-    `penalty_alpha` (with `top_k` as its k) + the FP8 key/value cache's `kv_cache_dtype` + neighbor guidance's `guidance_scale`."""
+    `penalty_alpha` (with `top_k` as its k) + the FP8 key/value cache's `kv_cache_dtype` + neighbor guidance's `guidance_scale` +
+    the FP8 frozen weights' `weight_dtype`."""
     overwrite_cache: Optional[bool] = _f(False, "Overwrite the cached preprocessed datasets or not.")
     dataset: Optional[str] = _f("wikiweb2m", "The name of the dataset to use.")
     task: Optional[str] = _f("section", "One of three generation tasks in WikiWeb2M")
@@ -117,6 +118,9 @@ class Arguments:
     kv_cache_dtype: Optional[str] = _f(None, "key/value cache of the test protocol's generate(): fp8 keeps the frozen layers' cached keys "
                                              "and values as e4m3fn codes (OPT fork, greedy or sampled, plain projections); default: the "
                                              "model's dtype")
+    weight_dtype: Optional[str] = _f(None, "weights of the frozen layers in the decode steps of the test protocol's generate(): fp8 "
+                                           "multiplies e4m3fn codes with one power-of-two scale per weight row (plain projections; the "
+                                           "prefill, the gated layers and lm_head keep the model's dtype); default: the model's dtype")
     peft_type: str = _f("none", "peft type: none, prefix, prompt, lora, flamingo")
     lora_r: int = _f(64, "lora row rank")
     lora_alpha: float = _f(1, "lora scaling factor")
@@ -662,6 +666,8 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                                   max_matching_ngram_size=int(getattr(args, "max_matching_ngram_size", 2)))
                 if getattr(args, "kv_cache_dtype", None) is not None and "kv_cache_dtype" in named:
                     fields["kv_cache_dtype"] = args.kv_cache_dtype                                   # generate() says what it combines with
+                if getattr(args, "weight_dtype", None) is not None and "weight_dtype" in named:
+                    fields["weight_dtype"] = args.weight_dtype
                 generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),
                                                attention_mask=batch["attention_mask"][:, :L_in].contiguous(), **fields,
                                                host_meta=extra.get("host_meta"), max_new_tokens=32,

@@ -22,6 +22,9 @@ class DecodeCache:
                   once per generation
       beam, lookup, kv_dtype    what selects the mode of a step, below
       pairs       None, or the pair count B of a guided generation: batch_size is then 2B (the mode `guided`, below)
+      w8          None, or a StepCodes (generate(weight_dtype="fp8")): the frozen layers' decode_step then multiplies e4m3fn codes of its
+                  weights (ops.decode_linear_w8 on what w8.get returns) instead of the weights.  It is only another GEMM: it selects
+                  no attention kernel and is no mode below
 
     The modes.  x is the layer input of a step's rows, q|k|v its projection, n the key width as above:
       plain       beam, lookup and kv_dtype None; rows = B.  k|v go into kv[l][:, col] -- the GEMM (OPT fork) or ops.rope_kv_append (Llama)
@@ -69,6 +72,7 @@ class DecodeCache:
         self.beam = None
         self.lookup = None
         self.pairs = None
+        self.w8 = None
 
     def kv_out(self, idx):
         """What layer idx's prefill files its keys and values into (MPTAttention._file_kv)."""
@@ -144,6 +148,54 @@ class DecodeCache:
         if rows is None:
             return ops.attn_decode(q, k, v, self.cross_valid, num_heads)
         return ops.attn_decode_beam(q, k, v, self.cross_valid, num_heads, rows.W)
+
+
+class WeightCodes:
+    """A frozen layer's weights as FP8 codes (ops.quantize_weight_fp8: e4m3fn codes [N, K] and int8 exponents [N]), quantised on first
+    use and kept beside the layer's fused-weight cache: get(name, w) returns the pair for the weight the decode step would multiply and
+    quantises again when `key` changed -- by default the weight's (data pointer, _version, dtype, device), for a derived fused weight
+    the key of the cache it came from (a rebuilt copy may land on the old address).  The weights themselves stay resident: the prefill
+    multiplies them."""
+
+    def __init__(self):
+        self._codes = {}
+
+    def get(self, name, w, key=None):
+        key = (w.data_ptr(), w._version, w.dtype, w.device) if key is None else key
+        hit = self._codes.get(name)
+        if hit is None or hit[0] != key:
+            hit = (key, ops.quantize_weight_fp8(w))
+            self._codes[name] = hit
+        return hit[1]
+
+    def tensors(self):
+        """Every (codes, exps) pair held, by name."""
+        return {name: hit[1] for name, hit in self._codes.items()}
+
+    @staticmethod
+    def of(holder):
+        """The WeightCodes of a frozen layer (or of its attention), kept in the holder's __dict__ beside its fused-weight cache: no
+        parameter, no buffer, nothing in a state_dict."""
+        codes = holder.__dict__.get("_w8_codes")
+        if codes is None:
+            codes = holder.__dict__["_w8_codes"] = WeightCodes()
+        return codes
+
+
+class StepCodes:
+    """What DecodeCache.w8 holds during one generation with FP8 frozen weights: the (codes, exps) pairs its steps multiply, looked up
+    once.  get(holder, name, w) asks the holder's WeightCodes on the first step -- which quantises, or finds the weight unchanged --
+    and answers every later step of the generation from a dict: the weights are frozen, so a step does not look at them again."""
+
+    def __init__(self):
+        self._pairs = {}
+
+    def get(self, holder, name, w, key=None):
+        k = (id(holder), name)
+        pair = self._pairs.get(k)
+        if pair is None:
+            pair = self._pairs[k] = WeightCodes.of(holder).get(name, w, key)
+        return pair
 
 
 class LookupState:

@@ -37,10 +37,11 @@ from transformers.activations import ACT2FN
 from transformers.modeling_outputs import BaseModelOutputWithPast, CausalLMOutputWithPast
 
 from .. import ops
-from .decode_cache import BeamState, DecodeCache, LookupState      # noqa: F401 (re-exported: tests and tools import them from here)
+from .decode_cache import BeamState, DecodeCache, LookupState, StepCodes      # noqa: F401 (re-exported: tests and tools import them from here)
 from .encoders import ClipTextEncoder, PackedTextEncoder, PackedVisionEncoder
 from .generation import beam_loop, check_prompt, contrastive_loop, decode_loop, lookup_loop, make_select
-from .sampling import check_contrastive, check_guidance, check_kv_cache, check_lookup, check_processors, check_sampling
+from .sampling import (check_contrastive, check_guidance, check_kv_cache, check_lookup, check_processors, check_sampling,
+                       check_weight_dtype)
 
 CROSS_MODES = ("cross_attention", "embedding")
 
@@ -131,6 +132,16 @@ def _lin(module: nn.Module, x):
 def _plain(*mods):
     if any(type(m) is not nn.Linear for m in mods):
         raise ValueError("the decode step runs plain nn.Linear projections only (adapted projections, e.g. LoRA, have no decode path)")
+
+
+def _decode_linear(layer, name, x, w8=None, act="none", residual=None):
+    """A frozen layer's plain linear `name` (of the layer or of its self_attn; decode_step has checked that it is plain) on the rows of
+    a decode step: ops.decode_linear, or with w8 = the cache's StepCodes (generate(weight_dtype="fp8")) ops.decode_linear_w8 -- the same
+    epilogue on e4m3fn codes of its weight."""
+    mod = getattr(layer.self_attn if name == "out_proj" else layer, name)
+    if w8 is None:
+        return ops.decode_linear(x, mod.weight, mod.bias, act=act, residual=residual)
+    return ops.decode_linear_w8(x, *w8.get(layer, name, mod.weight), mod.bias, act=act, residual=residual)
 
 
 class MPTAttention(nn.Module):
@@ -329,11 +340,24 @@ class MPTAttention(nn.Module):
         _plain(mod)
         return ops.decode_linear(x, mod.weight, mod.bias, out_scale=out_scale, out=out)
 
-    def _decode_qkv(self, x, dst):
+    def _decode_qkv(self, x, dst, w8=None):
         """q [rows, d], scaled, of the rows x of a decode step; their k|v go into dst [rows, 2d] (DecodeCache.new_kv).  One GEMM on the
-        fused frozen weight for q and one for k|v, or one per projection."""
+        fused frozen weight for q and one for k|v, or one per projection.  w8 = the cache's StepCodes (generate(weight_dtype="fp8")): the
+        same GEMMs on e4m3fn codes of those weights, kept in this module's WeightCodes; the q rows of the fused weight carry the
+        scaling, else it rides in the epilogue as before."""
         d = self.embed_dim
         fused = self._frozen_qkv()
+        if w8 is not None:
+            if fused is not None:
+                w, b = fused
+                key = self.__dict__["_qkv_cache"][0]          # the fused copy follows its sources: so do its codes
+                q = ops.decode_linear_w8(x, *w8.get(self, "q", w[:d], key), b[:d])
+                ops.decode_linear_w8(x, *w8.get(self, "kv", w[d:], key), b[d:], out=dst)
+            else:                                             # decode_self has checked that q, k and v are plain
+                q = ops.decode_linear_w8(x, *w8.get(self, "q", self.q_proj.weight), self.q_proj.bias, out_scale=self.scaling)
+                ops.decode_linear_w8(x, *w8.get(self, "k", self.k_proj.weight), self.k_proj.bias, out=dst[:, :d])
+                ops.decode_linear_w8(x, *w8.get(self, "v", self.v_proj.weight), self.v_proj.bias, out=dst[:, d:])
+            return q
         if fused is not None:
             w, b = fused
             q = ops.decode_linear(x, w[:d], b[:d])
@@ -350,9 +374,9 @@ class MPTAttention(nn.Module):
         only; any other adapter type, and an adapted k_proj / out_proj, is refused."""
         _plain(self.k_proj, self.out_proj)
         dst = cache.new_kv(idx)
-        if not cache.plain:
+        if not cache.plain or cache.w8 is not None:
             _plain(self.q_proj, self.v_proj)
-        return cache.attend_self(idx, self._decode_qkv(x, dst), dst, self.num_heads)
+        return cache.attend_self(idx, self._decode_qkv(x, dst, cache.w8), dst, self.num_heads)
 
     def decode_cross(self, x, cache, idx):
         _plain(self.q_proj, self.out_proj)
@@ -493,35 +517,38 @@ class MPTDecoderLayer(nn.Module):
         return outputs
 
 
-    def _decode_ffn(self, x):
+    def _decode_ffn(self, x, w8=None):
         if self.activation_name == "relu":
-            return ops.decode_linear(x, self.fc1.weight, self.fc1.bias, act="relu")
-        return ops.activation_(ops.decode_linear(x, self.fc1.weight, self.fc1.bias), self.activation_name)
+            return _decode_linear(self, "fc1", x, w8, act="relu")
+        return ops.activation_(_decode_linear(self, "fc1", x, w8), self.activation_name)
 
     def decode_step(self, h, cache, idx):
         """The layer on the rows of a decode or verify step, h [rows, d]: the existing LayerNorm / gated-residual kernels at M = rows,
         ops.decode_linear for every projection (residual adds in the GEMM epilogue of the frozen layers) and the cache's attention
         -- over layer idx's K|V rows (frozen layer) or neighbor layer idx's projected neighbor tokens (gated layer).  How many rows a
-        sample has, where its keys go and which attention op reads them is the cache's mode (decode_cache.DecodeCache)."""
+        sample has, where its keys go and which attention op reads them is the cache's mode (decode_cache.DecodeCache).  With cache.w8
+        set (generate(weight_dtype="fp8")) a frozen layer's GEMMs -- q, k|v, out_proj, fc1, fc2: five with the fused q|k|v weight, six
+        without -- run on e4m3fn codes of their weights (ops.decode_linear_w8); a gated layer never does."""
         pre = self.do_layer_norm_before
         attn = self.self_attn
         ln1, ln2 = self.self_attn_layer_norm, self.final_layer_norm
         _plain(self.fc1, self.fc2, attn.out_proj)
         x = self._ln(ln1, h) if pre else h
         gated = self.cross_attention
+        w8 = None if gated else cache.w8
         if gated:                             # residual adds through ops.gated_residual (the gate is None outside flamingo)
             g1, g2 = (self.gating1, self.gating2) if self.peft_type == "flamingo" else (None, None)
             a = attn.decode_cross(x, cache, idx)
             h = ops.gated_residual(h, ops.decode_linear(a, attn.out_proj.weight, attn.out_proj.bias), g1, 0.0, False)
         else:                                 # frozen layer: the residual adds ride in the GEMM epilogues
-            h = ops.decode_linear(attn.decode_self(x, cache, idx), attn.out_proj.weight, attn.out_proj.bias, residual=h)
+            h = _decode_linear(self, "out_proj", attn.decode_self(x, cache, idx), w8, residual=h)
         if not pre:
             h = self._ln(ln1, h)
-        x = self._decode_ffn(self._ln(ln2, h) if pre else h)
+        x = self._decode_ffn(self._ln(ln2, h) if pre else h, w8)
         if gated:
             h = ops.gated_residual(h, ops.decode_linear(x, self.fc2.weight, self.fc2.bias), g2, 0.0, False)
         else:
-            h = ops.decode_linear(x, self.fc2.weight, self.fc2.bias, residual=h)
+            h = _decode_linear(self, "fc2", x, w8, residual=h)
         return h if pre else self._ln(ln2, h)
 
 
@@ -1012,6 +1039,10 @@ class MPTForCausalLM(MPTPreTrainedModel):
         return [m for layer in self.model.decoder.layers
                 for m in (layer.self_attn.q_proj, layer.self_attn.k_proj, layer.self_attn.v_proj, layer.self_attn.out_proj)]
 
+    def _frozen_linears(self):
+        """What check_weight_dtype looks at: every linear a frozen layer's decode step multiplies."""
+        return self._self_attn_projections() + [m for layer in self.model.decoder.layers for m in (layer.fc1, layer.fc2)]
+
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, neighbor_embeds=None, neighbor_attention_mask=None, max_new_tokens=32,
                  eos_token_id=None, pad_token_id=None, return_step_logits=False, first_key_valid=False, inputs_embeds=None,
@@ -1019,7 +1050,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
                  num_return_sequences=1, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, sample_u=None,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, suppress_tokens=None, history_ids=None,
                  history_mask=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False, penalty_alpha=0.0,
-                 return_contrastive_trace=False, kv_cache_dtype=None, guidance_scale=None):
+                 return_contrastive_trace=False, kv_cache_dtype=None, guidance_scale=None, weight_dtype=None):
         """Generation with a key/value cache: what the reference's test protocol asks of its wrappers
         (language_modelling/run_generation.py:597-603).  One prefill over the prompt -- the existing kernels, plus the copy of every
         layer's K and V into a DecodeCache -- then max_new_tokens - 1 decode steps on the HIP decode path (ops.decode_linear,
@@ -1058,8 +1089,17 @@ class MPTForCausalLM(MPTPreTrainedModel):
         lu + g (lc - lu) on log-probabilities (ops.guidance_logits), which the processors, return_step_logits and the greedy or
         sampled selection then take.  g > 1 pushes towards what the neighbors contribute, g = 0 follows the LM without them.  For the
         loop of one row per prompt with input_ids prompts and neighbor tokens; refused with the other decoding modes
-        (sampling.check_guidance)."""
+        (sampling.check_guidance).
+        weight_dtype = "fp8" (or torch.float8_e4m3fn; None: off, every path as without it): the decode steps multiply e4m3fn codes of
+        the frozen layers' weights -- the q|k|v weight(s), out_proj, fc1 and fc2, one power-of-two scale per weight row, quantised
+        once on the first such call and kept on the layer until a weight changes -- through ops.decode_linear_w8: half the bytes a
+        step streams.  The gated layers, project_in / project_out, lm_head and the whole prefill keep the model's
+        dtype: the prompt's keys come from the exact weights, only the steps run on codes, and the weights stay resident beside their
+        codes (N K + N more bytes per weight: this saves bandwidth, not memory).  It is only another GEMM and combines with every
+        decoding mode above (inputs_embeds too: the prefill alone reads them); adapted (non-nn.Linear) projections or FFN layers of
+        the frozen layers are refused (sampling.check_weight_dtype)."""
         dec = self.model.decoder
+        w8 = check_weight_dtype("generate()", weight_dtype, () if weight_dtype is None else self._frozen_linears())
         guidance = check_guidance("generate()", guidance_scale, num_beams, num_return_sequences, prompt_lookup_num_tokens, penalty_alpha,
                                   kv_cache_dtype, inputs_embeds, neighbor_embeds is not None,
                                   dec.cross_attention and len(dec.neighbor_layers) > 0)
@@ -1096,7 +1136,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
                 raise ValueError("generate(): return_step_logits belongs to the greedy path; beam search has return_beam_trace")
             return self._generate_beam(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
                                        pad_token_id, first_key_valid, W, float(length_penalty), bool(early_stopping),
-                                       return_sequences_scores, return_beam_trace)
+                                       return_sequences_scores, return_beam_trace, w8)
         if return_sequences_scores or return_beam_trace:
             raise ValueError("generate(): return_sequences_scores / return_beam_trace belong to beam search (num_beams > 1)")
         if R > 1 and inputs_embeds is not None:
@@ -1114,12 +1154,14 @@ class MPTForCausalLM(MPTPreTrainedModel):
         if guidance is not None:
             hidden, cache = dec.prefill_guided(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid,
                                                T + n_new - 1)
+            cache.w8 = None if w8 is None else StepCodes()
             return decode_loop(self._last_logits, lambda tok: dec(input_ids=tok, past_key_values=cache).last_hidden_state[:, 0], hidden,
                                select, n_new, input_ids, attention_mask, 1, proc, None, None, return_step_logits, guidance)
         out = dec(input_ids=input_ids, inputs_embeds=inputs_embeds, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid,
                   cache_capacity=T if R > 1 or kc else T + n_new - 1, kv_cache_dtype=kv_dtype)
         cache = out.past_key_values
+        cache.w8 = None if w8 is None else StepCodes()
         if kc:
             cache.beam = BeamState(cache, kc, n_new)           # beam_advance is never called: book.src is the table the select call writes
             return contrastive_loop(self._last_logits, lambda tok: dec(input_ids=tok, past_key_values=cache).last_hidden_state[:, 0],
@@ -1138,7 +1180,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
                            return_step_logits)
 
     def _generate_beam(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, max_new_tokens, eos_token_id,
-                       pad_token_id, first_key_valid, W, length_penalty, early_stopping, return_scores, return_trace):
+                       pad_token_id, first_key_valid, W, length_penalty, early_stopping, return_scores, return_trace, w8=None):
         """Beam search, W hypotheses per sample on ONE copy of the sample's cache.  The unchanged prefill runs once
         with B rows; its last-row logits seed the W beams (rows_in = 1 of ops.beam_topk, in place of HF's -1e9 start scores).  Every
         later step runs the decode kernels at M = B*W rows: the prompt keys and the neighbor tokens are read once per sample and
@@ -1157,6 +1199,7 @@ class MPTForCausalLM(MPTPreTrainedModel):
         out = dec(input_ids=input_ids, attention_mask=attention_mask, neighbor_embeds=neighbor_embeds,
                   neighbor_attention_mask=neighbor_attention_mask, use_cache=True, first_key_valid=first_key_valid, cache_capacity=T)
         cache = out.past_key_values
+        cache.w8 = None if w8 is None else StepCodes()
         cache.beam = BeamState(cache, W, n_new - 1)
         return beam_loop(self._last_logits, lambda tok: dec(input_ids=tok, past_key_values=cache).last_hidden_state[:, 0],
                          out.last_hidden_state[:, -1], cache.beam.book, input_ids, n_new, W, self.lm_head.weight.shape[0], eos_token_id,
@@ -1474,7 +1517,7 @@ class CrossAttentionModel(nn.Module):
                  return_sequences_scores=False, return_beam_trace=False, num_return_sequences=1, do_sample=False, temperature=1.0,
                  top_k=0, top_p=1.0, seed=None, sample_u=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
                  suppress_tokens=None, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False, penalty_alpha=0.0,
-                 return_contrastive_trace=False, kv_cache_dtype=None, guidance_scale=None):
+                 return_contrastive_trace=False, kv_cache_dtype=None, guidance_scale=None, weight_dtype=None):
         """Greedy generation from the prompt `input_ids` [B, T] (right-padded): the neighbors are encoded and interleaved once, exactly
         as forward does, then MPTForCausalLM.generate runs the prefill and the cached decode steps.  Returns [B, T + max_new_tokens]
         ids (and the step logits with return_step_logits=True).  num_beams, length_penalty, early_stopping, return_sequences_scores and
@@ -1487,7 +1530,8 @@ class CrossAttentionModel(nn.Module):
         keywords penalty_alpha (with top_k as its k) and return_contrastive_trace (the k candidates of a sample read its neighbor
         tokens once: they stay at B rows), and its kv_cache_dtype ("fp8": the frozen layers' cache as e4m3fn codes; the projected
         neighbor tokens stay in the model's dtype), and its guidance_scale (neighbor guidance: the neighbors are encoded once and feed
-        the B rows with neighbors; the B rows without run the LM alone)."""
+        the B rows with neighbors; the B rows without run the LM alone), and its weight_dtype ("fp8": the decode steps of the frozen
+        layers on e4m3fn codes of their weights; the encoders, the prefill, the gated layers and lm_head keep the model's dtype)."""
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the OPT fork only, not for {type(self.lm).__name__}")
         dec = self.lm.model.decoder
@@ -1496,6 +1540,7 @@ class CrossAttentionModel(nn.Module):
                        dec.cross_attention and len(dec.neighbor_layers) > 0)
         check_kv_cache("generate()", kv_cache_dtype, num_beams, num_return_sequences, prompt_lookup_num_tokens, penalty_alpha,
                        self.lm._self_attn_projections() if kv_cache_dtype is not None else ())
+        check_weight_dtype("generate()", weight_dtype, () if weight_dtype is None else self.lm._frozen_linears())
         kc = check_contrastive("generate()", penalty_alpha, top_k, return_contrastive_trace, do_sample, num_beams, num_return_sequences,
                                prompt_lookup_num_tokens, None, return_beam_trace, return_sequences_scores)
         check_sampling("generate()", do_sample, temperature, 0 if kc else top_k, top_p, seed, sample_u, num_beams, num_return_sequences,
@@ -1520,4 +1565,4 @@ class CrossAttentionModel(nn.Module):
                                 prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
                                 return_lookup_stats=return_lookup_stats, penalty_alpha=penalty_alpha,
                                 return_contrastive_trace=return_contrastive_trace, kv_cache_dtype=kv_cache_dtype,
-                                guidance_scale=guidance_scale)
+                                guidance_scale=guidance_scale, weight_dtype=weight_dtype)

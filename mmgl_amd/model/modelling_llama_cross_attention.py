@@ -26,9 +26,9 @@ import torch.nn.functional as F
 from transformers.modeling_outputs import CausalLMOutputWithPast
 
 from .. import ops
-from .decode_cache import DecodeCache, LookupState
+from .decode_cache import DecodeCache, LookupState, StepCodes
 from .generation import check_prompt, decode_loop, lookup_loop, make_select
-from .sampling import check_kv_cache, check_lookup, check_processors, check_sampling
+from .sampling import check_kv_cache, check_lookup, check_processors, check_sampling, check_weight_dtype
 
 
 class LlamaGatedCrossAttentionLayer(nn.Module):
@@ -132,13 +132,19 @@ class _FrozenLlamaLayer:
         (decode_cache.DecodeCache: file_rotated, attend_self); every mode makes the launches of the plain step."""
         ly, eps = self.layer, self.cfg.rms_norm_eps
         w_qkv, w_gu = self._fused()
+        if cache.w8 is None:
+            mm = lambda name, w, x, residual=None: ops.decode_linear(x, w, None, residual=residual)
+        else:                                 # the four GEMMs on codes: only the kernel differs
+            fused = self._cache[0]            # the fused copies follow their sources: so do their codes
+            mm = lambda name, w, x, residual=None: ops.decode_linear_w8(
+                x, *cache.w8.get(self, name, w, fused if name in ("w_qkv", "w_gu") else None), residual=residual)
         x = ops.rms_norm(h, ly.input_layernorm.weight, eps)
-        qkv = ops.decode_linear(x, w_qkv, None)
+        qkv = mm("w_qkv", w_qkv, x)
         new = cache.file_rotated(l, qkv, self.H, self.Hkv)
         a = cache.attend_self(l, qkv[:, :self.H * self.D], new, self.H, self.Hkv)
-        h = ops.decode_linear(a, ly.self_attn.o_proj.weight, None, residual=h)
+        h = mm("o_proj", ly.self_attn.o_proj.weight, a, h)
         x = ops.rms_norm(h, ly.post_attention_layernorm.weight, eps)
-        return ops.decode_linear(ops.swiglu(ops.decode_linear(x, w_gu, None)), ly.mlp.down_proj.weight, None, residual=h)
+        return mm("down_proj", ly.mlp.down_proj.weight, ops.swiglu(mm("w_gu", w_gu, x)), h)
 
 
 class LlamaNeighborLM(nn.Module):
@@ -229,6 +235,11 @@ class LlamaNeighborLM(nn.Module):
     def _self_attn_projections(self):
         """What check_kv_cache looks at: the q / k / v / o projections of the frozen layers."""
         return [getattr(ly.self_attn, n) for ly in self.llama.model.layers for n in ("q_proj", "k_proj", "v_proj", "o_proj")]
+
+    def _frozen_linears(self):
+        """What check_weight_dtype looks at: every linear of the frozen layers."""
+        return self._self_attn_projections() + [getattr(ly.mlp, n) for ly in self.llama.model.layers
+                                                for n in ("gate_proj", "up_proj", "down_proj")]
 
     def _hidden(self, input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid=False, use_cache=False,
                 cache_capacity=None, kv_dtype=None):
@@ -351,9 +362,10 @@ class LlamaNeighborLM(nn.Module):
         the logits processors and return_step_logits are generation.decode_loop's: see that module.  Refused here: num_beams > 1
         (beam search is implemented for the OPT fork only), num_return_sequences > 1 (it needs the beam-shared cache of the OPT
         fork) and do_sample=True on prompts that are not int64.
-        **lookup takes exactly four keywords, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False and
-        kv_cache_dtype=None (any other name is the TypeError of an unknown keyword).  They are not named parameters: the parameter
-        list above is the greedy and sampled contract, which tests/test_lookup_accept_cpu.py pins by inspecting this signature.
+        **lookup takes exactly five keywords, prompt_lookup_num_tokens=0, max_matching_ngram_size=2, return_lookup_stats=False,
+        kv_cache_dtype=None and weight_dtype=None (any other name is the TypeError of an unknown keyword).  They are not named
+        parameters: the parameter list above is the greedy and sampled contract, which tests/test_lookup_accept_cpu.py pins by
+        inspecting this signature.
         prompt_lookup_num_tokens = K (1..7; 0: off, today's loop) with max_matching_ngram_size = N (1..4): prompt-lookup decoding
         with the keywords, semantics and refusals of MPTForCausalLM.generate -- each step drafts up to K tokens from the row's own
         text and verifies them in one step of B*(K+1) rows (_verify_step, generation.lookup_loop).  The result is the
@@ -361,12 +373,21 @@ class LlamaNeighborLM(nn.Module):
         kv_cache_dtype = "fp8" (or torch.float8_e4m3fn; None: off, every call as without it): the frozen layers keep the Hkv cached
         key/value heads as e4m3fn codes with power-of-two scales, (D + 1) / 2D of the bf16 cache's bytes; the steps read them through
         ops.attn_decode_q8 with num_kv_heads.  Greedy, do_sample, the processors, return_step_logits and EOS handling
-        combine with it; prompt_lookup_num_tokens > 0 is refused (the verify kernel has no FP8 form), adapted projections too."""
+        combine with it; prompt_lookup_num_tokens > 0 is refused (the verify kernel has no FP8 form), adapted projections too.
+        weight_dtype = "fp8" (or torch.float8_e4m3fn; None: off, every call as without it): the decode and verify steps multiply
+        e4m3fn codes of the frozen layers' weights -- the fused q|k|v and gate|up weights, o_proj and down_proj, one power-of-two scale
+        per weight row, quantised once on the first such call and kept on the layer until a weight changes -- through
+        ops.decode_linear_w8: half the bytes a step streams.  The gated layers, lm_head and the whole prefill keep the
+        model's dtype: the prompt's keys come from the exact weights, only the steps run on codes, and the weights stay resident
+        beside their codes (N K + N more bytes per weight: this saves bandwidth, not memory).  It is only another GEMM: greedy,
+        do_sample, the processors, return_step_logits, EOS handling, kv_cache_dtype and prompt_lookup_num_tokens combine with it;
+        adapted (non-nn.Linear) projections are refused."""
         who = "LlamaNeighborLM.generate()"
         prompt_lookup_num_tokens = lookup.pop("prompt_lookup_num_tokens", 0)
         max_matching_ngram_size = lookup.pop("max_matching_ngram_size", 2)
         return_lookup_stats = lookup.pop("return_lookup_stats", False)
         kv_cache_dtype = lookup.pop("kv_cache_dtype", None)
+        weight_dtype = lookup.pop("weight_dtype", None)
         if lookup:
             raise TypeError(f"{who} got an unexpected keyword argument '{next(iter(lookup))}'")
         if int(num_beams) != 1:
@@ -374,6 +395,7 @@ class LlamaNeighborLM(nn.Module):
         # num_beams and num_return_sequences keep this model's own refusals (above, and check_sampling's)
         kv_dtype = check_kv_cache(who, kv_cache_dtype, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
                                   projections=() if kv_cache_dtype is None else self._self_attn_projections())
+        w8 = check_weight_dtype(who, weight_dtype, () if weight_dtype is None else self._frozen_linears())
         if int(prompt_lookup_num_tokens) != 0:                 # its refusals of do_sample / num_return_sequences come before check_sampling's
             check_lookup(who, prompt_lookup_num_tokens, max_matching_ngram_size, return_lookup_stats, do_sample, 1, num_return_sequences)
         check_sampling(who, do_sample, temperature, top_k, top_p, seed, sample_u, 1, num_return_sequences)
@@ -391,6 +413,7 @@ class LlamaNeighborLM(nn.Module):
         select = make_select(who, do_sample, n_new, B, 1, dev, seed, sample_u, temperature, top_k, top_p, eos_token_id, pad_token_id)
         hidden, cache = self._hidden(input_ids, attention_mask, neighbor_embeds, neighbor_attention_mask, first_key_valid, True,
                                      T + n_new - 1, kv_dtype)
+        cache.w8 = None if w8 is None else StepCodes()
         if K > 0:
             cache.lookup = LookupState(cache, K, N, n_new, scratch=False)
             return lookup_loop(self._last_logits, lambda: self._verify_step(cache), hidden[:, -1], cache.lookup, input_ids, attention_mask,

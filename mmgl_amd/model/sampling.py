@@ -148,6 +148,23 @@ def check_kv_cache(who, kv_cache_dtype, num_beams=1, num_return_sequences=1, pro
     return ops.KV_FP8
 
 
+def check_weight_dtype(who, weight_dtype, linears=()):
+    """Validates generate()'s weight_dtype; returns None (off: every path runs exactly as without the keyword) or
+    ops.KV_FP8.  "fp8" / torch.float8_e4m3fn runs the decode steps' GEMMs of the frozen layers on e4m3fn codes of their weights with
+    one power-of-two scale per weight row (ops.decode_linear_w8).  It is only another GEMM, so it selects no decoding mode and
+    combines with all of them.  `linears`: the modules whose weights the frozen layers' steps multiply, which must be plain nn.Linear
+    (a LoRA-adapted projection runs the skinny GEMM with the rank-r term, which has no form on codes)."""
+    if weight_dtype is None:
+        return None
+    if not (weight_dtype == "fp8" or weight_dtype is ops.KV_FP8):
+        raise ValueError(f"{who}: weight_dtype = {weight_dtype!r} is unknown: None (the model's dtype), 'fp8' or torch.float8_e4m3fn "
+                         "(FP8 frozen weights for the decode steps)")
+    if any(type(m) is not torch.nn.Linear for m in linears):
+        raise ValueError(f"{who}: weight_dtype = 'fp8' (FP8 frozen weights) runs plain nn.Linear projections and FFN layers only (adapted "
+                         "projections, e.g. LoRA, are not implemented)")
+    return ops.KV_FP8
+
+
 def check_guidance(who, guidance_scale, num_beams=1, num_return_sequences=1, prompt_lookup_num_tokens=0, penalty_alpha=0.0,
                    kv_cache_dtype=None, inputs_embeds=None, neighbors=True, gated_layers=True):
     """Validates generate()'s guidance_scale; returns None (off: None or 1.0 -- every path runs exactly as without the

@@ -1678,6 +1678,78 @@ def decode_lora_linear(x, weight, bias, lora_A, lora_B, scaling, out_scale=1.0, 
     return y
 
 
+# -- FP8 frozen weights: a weight as e4m3fn codes with one power-of-two scale per row (include/mmgl_hip.h), and the decode GEMM on them
+def quantize_weight_fp8(weight, out=None):
+    """weight [N, K] (bf16 or fp32, unit column stride, any row stride) -> (codes [N, K] torch.float8_e4m3fn, exps [N] int8) with
+    weight ~ codes * 2^exps[:, None]: the FP8 key/value cache's format per weight row (mmgl_weight_quantize, one launch).  Run once per
+    frozen weight; non-finite weights are outside the contract.  out: a (codes, exps) pair to fill -- codes [N, K] e4m3fn or uint8 with
+    unit column stride and any row stride, exps [N] int8 contiguous.  Forward only; GPU only."""
+    require_cuda(weight)
+    if weight.dim() != 2 or weight.dtype not in (torch.bfloat16, torch.float32) or weight.shape[0] == 0 or weight.shape[1] == 0:
+        raise ValueError(f"quantize_weight_fp8: weight{tuple(weight.shape)} {weight.dtype} must be a non-empty [N, K] bf16 or fp32 matrix")
+    w = weight.detach()
+    w = w if w.stride(1) == 1 else w.contiguous()
+    N, K = w.shape
+    if out is None:
+        codes = torch.empty(N, K, dtype=KV_FP8, device=w.device)
+        exps = torch.empty(N, dtype=torch.int8, device=w.device)
+    else:
+        codes, exps = out
+        require_cuda(codes, exps)
+        if (tuple(codes.shape) != (N, K) or codes.dtype not in (KV_FP8, torch.uint8) or codes.stride(1) != 1 or tuple(exps.shape) != (N,)
+                or exps.dtype != torch.int8 or not exps.is_contiguous() or codes.device != w.device or exps.device != w.device):
+            raise ValueError(f"quantize_weight_fp8: out = (codes{tuple(codes.shape)}/{codes.stride()} {codes.dtype}, exps{tuple(exps.shape)} "
+                             f"{exps.dtype}) for weight{tuple(w.shape)}: codes [N, K] {KV_FP8} with unit column stride, exps [N] int8")
+    _lib.call("mmgl_weight_quantize", dict(bytes=float(N * K) * (2 * w.element_size() + 1)), ptr(w), w.stride(0), ptr(codes), codes.stride(0),
+              ptr(exps), N, K, dtype_code(w), stream_ptr())
+    return codes, exps
+
+
+def _w8_operands(op, x, codes, exps):
+    if (x.dim() != 2 or codes.dim() != 2 or x.shape[1] != codes.shape[1] or codes.dtype not in (KV_FP8, torch.uint8) or codes.stride(1) != 1
+            or exps.dtype != torch.int8 or tuple(exps.shape) != (codes.shape[0],) or not exps.is_contiguous()
+            or codes.device != x.device or exps.device != x.device):
+        raise ValueError(f"{op}: shapes x{tuple(x.shape)} codes{tuple(codes.shape)}/{codes.stride()} {codes.dtype} exps{tuple(exps.shape)} "
+                         f"{exps.dtype}: codes [N, K] {KV_FP8} with unit column stride and exps [N] int8 on {x.device}")
+
+
+def gemm_skinny_w8(x, codes, exps, bias=None, residual=None, act=0, out_scale=1.0, out=None):
+    """Raw mmgl_gemm_skinny_w8 call: x [M <= 64, K], codes [N, K] e4m3fn (or uint8), exps [N] int8, out [M, N]; row strides are free,
+    column strides 1.  No autograd; the operands are the caller's to check (decode_linear_w8 does)."""
+    require_cuda(x, codes, exps)
+    M, K = x.shape
+    N = codes.shape[0]
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+    _lib.call("mmgl_gemm_skinny_w8", dict(flops=2.0 * M * N * K, bytes=float(M * K + M * N) * x.element_size() + float(N * K + N), tag=f"{M}x{N}x{K}"),
+              ptr(x), x.stride(0), ptr(codes), codes.stride(0), ptr(exps), ptr(bias), ptr(residual), ptr(y), y.stride(0), M, N, K, act,
+              float(out_scale), dtype_code(x), stream_ptr())
+    return y
+
+
+def decode_linear_w8(x, codes, exps, bias=None, act="none", out_scale=1.0, residual=None, out=None):
+    """ops.decode_linear on a quantised weight: act((x @ (codes * 2^exps)^T + bias) * out_scale) + residual for the few rows of a decode
+    step, x [M, K], (codes [N, K], exps [N]) as quantize_weight_fp8 returned them.  `out` [M, N] may be a strided view with unit column
+    stride -- a column of the key/value cache -- and `residual` shares its row stride.  Rows go to mmgl_gemm_skinny_w8 in chunks of 64;
+    there is no other route (mmgl_gemm_nt has no form on codes).  Forward only; GPU only."""
+    require_cuda(x, codes, exps)
+    _no_grad_inputs("decode_linear_w8", x, bias, residual)
+    _w8_operands("decode_linear_w8", x, codes, exps)
+    M, N = x.shape[0], codes.shape[0]
+    code = _act_code("decode_linear_w8", act)
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    y = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+    if tuple(y.shape) != (M, N) or y.stride(1) != 1 or y.dtype != x.dtype or x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"decode_linear_w8: out{tuple(y.shape)} {y.dtype} for x{tuple(x.shape)} {x.dtype} codes{tuple(codes.shape)}")
+    if bias is not None and bias.dtype != x.dtype:
+        bias = bias.to(x.dtype)
+    if residual is not None and (tuple(residual.shape) != (M, N) or residual.stride(1) != 1 or residual.stride(0) != y.stride(0)):
+        raise ValueError("decode_linear_w8: residual must have the output's shape and row stride")
+    for rows in _row_chunks(M):
+        gemm_skinny_w8(x[rows], codes, exps, bias, None if residual is None else residual[rows], code, out_scale, y[rows])
+    return y
+
+
 def _decode_attn_operands(op, q, k, v, key_valid, num_heads, out, q_rows=1, key_cols=None, names=("k", "v", "keys"), tail=""):
     """The operands of single-query attention: q [B * q_rows, d] against the per-sample views k, v [B, S, key_cols] (None: d columns)
     with unit column stride and common strides, and key_valid [B, S].  Returns (B, S, d, the mask as uint8 with unit column stride
