@@ -264,6 +264,13 @@ int mmgl_neighbor_interleave_bwd(const void* d_out_emb, const int64_t* text_loc,
  * pointer arithmetic: row r of `logits` is scored against labels[r]).
  *   loss_sum, count: fp32 device scalars (OVERWRITTEN); row_lse, row_loss [rows] fp32 (row_lse saved for backward).
  *   bwd writes dlogits = (softmax - onehot) * (*dloss_scale) / count, zero on ignored rows.
+ *   A label < 0 or >= V counts as ignored.  V may be any positive size (a row that is no whole number of 16-byte chunks takes the
+ *   element-wise path).
+ *   -inf logits (a logits processor's banned tokens) are allowed where the row keeps at least one finite logit and the label's
+ *   logit is finite: they carry no mass, row_lse is that of the finite logits, dlogits is exactly 0 at them.  +inf and NaN are not.
+ *   In place: dlogits == logits (the same pointer, the same layout) is allowed -- every element is read and then written by the
+ *   same thread and by no other, so no thread sees a gradient where it expects a logit (the LM head scores each chunk of logits
+ *   this way).  A partial overlap of the two buffers is not allowed.
  */
 int mmgl_cross_entropy_fwd(const void* logits, const int64_t* labels, float* row_lse, float* row_loss,
                            float* loss_sum, float* count, int rows, int V, int64_t ignore_index, int dtype,

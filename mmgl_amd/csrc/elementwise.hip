@@ -217,10 +217,11 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
 #pragma unroll
         for (int j = 1; j < VN; ++j) lm = fmaxf(lm, (float)v[j]);
         const float nm = fmaxf(m, lm);
+        const float sh = nm == -INFINITY ? 0.f : nm;      // nothing but -inf so far (banned tokens): exp(-inf - -inf) would be NaN, exp(-inf - 0) adds 0
         float acc = 0.f;
 #pragma unroll
-        for (int j = 0; j < VN; ++j) acc += __expf((float)v[j] - nm);
-        s = s * __expf(m - nm) + acc;
+        for (int j = 0; j < VN; ++j) acc += __expf((float)v[j] - sh);
+        s = s * __expf(m - sh) + acc;
         m = nm;
     };
     // four independent 16-byte loads in flight per thread (one load, one wait, nine exps per trip ran at 45 % of the HBM rate)
@@ -236,7 +237,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
     for (int i = nvec * VN + threadIdx.x; i < V_; i += 256) {
         const float a = (float)x[i];
         const float nm = fmaxf(m, a);
-        s = s * __expf(m - nm) + __expf(a - nm);
+        const float sh = nm == -INFINITY ? 0.f : nm;      // as in fold
+        s = s * __expf(m - sh) + __expf(a - sh);
         m = nm;
     }
     const float gm = block_max(m, red);
@@ -263,6 +265,9 @@ __global__ __launch_bounds__(256) void ce_finish_kernel(const float* __restrict_
     if (threadIdx.x == 0) { *loss_sum = sa; *count = sc; }
 }
 
+// dlogits == logits is allowed (the LM head scores a chunk in place; the contract is in the header): element e is loaded and stored
+// by the same thread and by no other, and its store takes the loaded value as an operand, so the load comes first whatever
+// __restrict__ lets the compiler assume about the two pointers.  A partial overlap is not allowed.
 template <typename T>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
                                                      const float* __restrict__ row_lse, const float* __restrict__ count,
