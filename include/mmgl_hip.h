@@ -137,6 +137,17 @@ int mmgl_selfattn_tiles_bwd(const void* dout, const void* q, const void* k, cons
                             const uint8_t* key_valid, const int32_t* key_tiles, void* dq, void* dk, void* dv, void* workspace,
                             size_t workspace_bytes, int B, int H, int T, int D, int m_live, int ld_q, int ld_kv, int ld_dq,
                             int ld_dkv, int dtype, void* stream);
+/* mmgl_selfattn_tiles_rows_bwd: mmgl_selfattn_tiles_bwd with live-first gradient rows.  dq, dk, dv are [B * T, ld] buffers and
+ * dest_tiles [B, T / 64] int32 is a permutation of the batch's 64-row tiles: the rows of tile j of sample b go to rows
+ * 64 dest_tiles[b][j] .. + 63.  The caller sends a live tile to its compact index (key_tiles) and the dead ones behind them, so
+ * that the rows from m_live on have dk = dv = 0 and a GEMM over [dq | dk | dv] may skip those columns there (mmgl_gemm_nt_rowk).
+ * Every value is bitwise that of mmgl_selfattn_tiles_bwd; only the store addresses differ.  dk / dv rows from dkv_rows on (a
+ * multiple of 64, >= m_live) are not stored at all; the zeros of the dead tiles below it are.  An entry of dest_tiles outside
+ * [0, B * T / 64) drops that tile's stores.  The gradient buffers must stay below 2 GiB. */
+int mmgl_selfattn_tiles_rows_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                 const uint8_t* key_valid, const int32_t* key_tiles, const int32_t* dest_tiles, void* dq, void* dk,
+                                 void* dv, void* workspace, size_t workspace_bytes, int B, int H, int T, int D, int m_live,
+                                 int dkv_rows, int ld_q, int ld_kv, int ld_dq, int ld_dkv, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * General attention core: the options of MPTAttention.forward the fused kernels above leave out -- attention-probability dropout,
@@ -337,6 +348,18 @@ int mmgl_gemm_nt(const void* x, int ldx, const void* W, int ldw, const void* bia
                  void* y, int ldy, int M, int N, int K, int act, float out_scale, void* workspace, size_t workspace_bytes,
                  int dtype, void* stream);
 int mmgl_relu_bwd(const void* dy, const void* y, void* out, size_t n, int dtype, void* stream);
+/* mmgl_gemm_nt_rowk: y[M,N] = x[M,K] W[N,K]^T (bf16, no epilogue) on the persistent 256x256 kernel, where only the 256-row tiles
+ * that hold a row below m_full contract over all of K; the tiles behind them contract over the first K_short columns and never
+ * read x[.., K_short..K) -- which the caller knows to be zero there (it may be uninitialised from row ceil(m_full / 256) * 256 on).
+ * One launch, no K splits, no scratch, at any tile count; every output element is the sum mmgl_gemm_nt without K-split workspace
+ * forms, minus a tail of exact zeros.  K, K_short multiples of 128, 256 <= K_short <= K, N a multiple of 16, 0 <= m_full <= M;
+ * anything else returns MMGL_ERR_UNSUPPORTED / MMGL_ERR_INVALID.  Tiles are handed out so that no workgroup's K steps exceed the
+ * mean by more than one long tile; under the dynamic tile schedule (below) long tiles first.
+ * mmgl_gemm_nt_rowk_item: that static schedule for tests -- the it-th work item of workgroup wg of G for n_long + n_short tiles,
+ * q = K / K_short: a long tile's index, n_long + a short tile's index, or -1. */
+int mmgl_gemm_nt_rowk(const void* x, int ldx, const void* W, int ldw, void* y, int ldy, int M, int N, int K, int K_short,
+                      int m_full, int dtype, void* stream);
+int mmgl_gemm_nt_rowk_item(int G, int n_long, int n_short, int q, int wg, int it);
 /* Dynamic tile schedule of the persistent bf16 GEMM kernel behind mmgl_gemm_nt / _relu_bits / _masked / mmgl_linear_*.
  * replaces: nothing in the reference -- it is what lets those GEMMs share the GPU with the gradient all-reduce that
  *   DistributedDataParallel overlaps with the backward pass (language_modelling/run_generation.py:317-319, 485): with the default
@@ -403,6 +426,14 @@ int mmgl_layernorm_tiles_fwd(const void* x, const void* gamma, const void* beta,
 int mmgl_add_layernorm_tiles_fwd(const void* x, const void* res, const void* gamma, const void* beta, void* sum_out, void* y,
                                  void* yc, const int32_t* rowmap, float* mean, float* rstd, int rows, int cols, int crows,
                                  float eps, float p_drop, uint64_t seed, int dtype, void* stream);
+/* mmgl_add_layernorm_rows_bwd: mmgl_add_layernorm_bwd with dy read through a row map: the gradient of row r of y is row dy_rows[r]
+ * of dy (dy_rows [rows] int32, every entry in [0, rows)) -- the live-first row order in which mmgl_selfattn_tiles_rows_bwd and
+ * mmgl_gemm_nt_rowk leave the gradient of a frozen layer's normed input.  Everything else -- sum, mean, rstd, dsum, dres, dx, the
+ * dropout counters -- keeps the dense row, and every output is bitwise that of mmgl_add_layernorm_bwd on the un-permuted dy. */
+int mmgl_add_layernorm_rows_bwd(const void* dy, const int32_t* dy_rows, const void* dsum, const void* sum, const void* gamma,
+                                const float* mean, const float* rstd, void* dres, void* dx, float* dgamma, float* dbeta,
+                                void* workspace, size_t workspace_bytes, int rows, int cols, float p_drop, uint64_t seed,
+                                int dtype, void* stream);
 int mmgl_activation_fwd(const void* x, void* y, size_t n, int act, int dtype, void* stream);
 /* y[i] = x[i] * (*scale), product in fp32, scale read from device memory (x == y allowed).  The upstream gradient of a scalar
  * loss -- `loss / args.grad_accumulation_steps` at reference language_modelling/run_generation.py:483 -- applied to a saved

@@ -34,6 +34,7 @@ SIGNATURES = {
     "mmgl_selfattn_prefix_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, I, I, I, P]),
     "mmgl_selfattn_tiles_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "mmgl_selfattn_tiles_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, I, I, I, P]),
+    "mmgl_selfattn_tiles_rows_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, I, I, I, I, P]),
     "mmgl_selfattn_gqa_fwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "mmgl_selfattn_gqa_bwd_workspace": (Z, [I, I, I, I, I, I]),
     "mmgl_selfattn_gqa_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, I, I, I, P]),
@@ -76,6 +77,9 @@ SIGNATURES = {
     "mmgl_gemm_nt_relu_bits": (I, [P, I, P, I, P, P, I, P, I, I, I, F, I, P]),
     "mmgl_gemm_nt_masked": (I, [P, I, P, I, P, P, I, I, I, I, F, I, P]),
     "mmgl_gemm_nt": (I, [P, I, P, I, P, P, P, P, I, I, I, I, I, F, P, Z, I, P]),
+    "mmgl_gemm_nt_rowk": (I, [P, I, P, I, P, I, I, I, I, I, I, I, P]),
+    "mmgl_gemm_nt_rowk_item": (I, [I, I, I, I, I, I]),
+    "mmgl_add_layernorm_rows_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, Z, I, I, F, U, I, P]),
     "mmgl_relu_bwd": (I, [P, P, P, Z, I, P]),
     "mmgl_gemm_set_tile_counter": (I, [P]),
     "mmgl_gemm_get_tile_counter": (P, []),

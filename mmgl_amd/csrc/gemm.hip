@@ -987,6 +987,16 @@ extern "C" int mmgl_gemm_nt(const void* x, int ldx, const void* W, int ldw, cons
                                (const float*)zmask, M, N, K, act, out_scale, (float*)workspace, workspace_bytes, st));
 }
 
+// y = x W^T with a K extent per 256-row tile (launch_gemm8p_rowk): the fused QKV dgrad of a frozen layer whose gradient rows are
+// sorted live key tiles first -- the dK | dV columns of the rows behind them are zero, their row tiles contract over dQ only.
+extern "C" int mmgl_gemm_nt_rowk(const void* x, int ldx, const void* W, int ldw, void* y, int ldy, int M, int N, int K, int K_short,
+                                 int m_full, int dtype, void* stream) {
+    MMGL_CHECK_ARG(x && W && y, "mmgl_gemm_nt_rowk: null pointer");
+    if (dtype != MMGL_BF16) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_gemm_nt_rowk: bf16 only (dtype %d)", dtype);
+    MMGL_CHECK_ARG(ldx >= K && ldw >= K && ldy >= N, "mmgl_gemm_nt_rowk: leading dimensions (%d, %d, %d) smaller than the rows (K=%d, N=%d)", ldx, ldw, ldy, K, N);
+    return launch_gemm8p_rowk((const bf16*)x, ldx, (const bf16*)W, ldw, (bf16*)y, ldy, M, N, K, K_short, m_full, (hipStream_t)stream);
+}
+
 // ReLU mask as bits.  fc1 of a frozen FFN writes one bit per element of relu(x W1^T + b1) beside the activation; fc2's dgrad
 // (dh = (dy W2) where h > 0) applies them in its epilogue instead of re-reading the [M, ffn] activation: 16 bytes per lane and
 // tile instead of 256, and the activation need not be kept for the backward pass.  Only for shapes that run as whole 256x256

@@ -13,6 +13,28 @@ size_t gemm8p_split_bytes(int M, int N, int K);   // fp32 partial tiles of the K
 int launch_gemm8p(const bf16* X, int ldx, const bf16* W, int ldw, bf16* Y, int ldy, const bf16* bias, const bf16* resid,
                   const bf16* zmask, int M, int N, int K, int act, float scale, hipStream_t st, float* part = nullptr,
                   size_t part_bytes = 0, unsigned* bits_out = nullptr, const unsigned* bits_in = nullptr);
+// Per-row-tile K extent (mmgl_gemm_nt_rowk): row tiles tm < cdiv(m_full, 256) contract over K ("long" tiles), the others over the
+// first K_short columns only -- the caller knows that X[m_full.., K_short..K) is zero (or never written).  ONE launch, no K splits,
+// every element's K walk starts at 0 and ascends: dropping a zero tail leaves the fp32 accumulator where the full walk leaves it.
+// Plain epilogue (no bias / activation / mask / residual), no scratch, the persistent kernel at any tile count.
+int launch_gemm8p_rowk(const bf16* X, int ldx, const bf16* W, int ldw, bf16* Y, int ldy, int M, int N, int K, int K_short, int m_full,
+                       hipStream_t st);
+// Static schedule of that launch: the it-th work item of workgroup wg of G, as a virtual id -- v < L: long tile v, else short tile
+// v - L -- or -1 when the workgroup has no it-th item.  q = K / K_short short tiles weigh one long one.  Long tiles go round-robin
+// first (round `it`, slot wg); the r = L % G workgroups of the last, partial long round are then one long tile ahead, so the other
+// G - r take up to q short tiles each (round-robin among themselves) before the rest of the short tiles goes round-robin over all G:
+// no workgroup's K steps exceed the mean by more than one long tile.  (Plain round-robin over "long first" hands the first short
+// tiles to the workgroups that already hold the extra long one: 14 against 11 units for 8 workgroups at 776 + 504 tiles on 256.)
+__host__ __device__ inline int gemm8p_rowk_item(int G, int L, int S, int q, int wg, int it) {
+    const int r = L % G, nl = L / G + (wg < r ? 1 : 0);
+    if (it < nl) return it * G + wg;
+    const int j = it - nl;
+    long long s;
+    if (r > 0 && wg >= r) s = j < q ? (long long)j * (G - r) + (wg - r) : (long long)q * (G - r) + (long long)(j - q) * G + wg;
+    else s = (r > 0 ? (long long)q * (G - r) : 0) + (long long)j * G + wg;
+    return s < S ? L + (int)s : -1;
+}
+
 // ReLU mask as bits: 8 KiB per 256x256 output tile ([tile][8 waves][64 lanes][4 dwords], lane-private: the kernel that applies
 // them has the same tile -> lane mapping as the one that wrote them); written by the act = 1 epilogue, applied by the plain one
 inline size_t gemm8p_bits_bytes(int M, int N) { return (size_t)cdiv(M, 256) * cdiv(N, 256) * 8192; }

@@ -63,6 +63,7 @@ struct P8Args {
     int trace_wg;
     unsigned* sched;       // dynamic tile schedule (mmgl_gemm_set_tile_counter): [0..7] per-XCD item counters, [8] finished workgroups;
                            // all zero between launches.  NULL: static schedule (work item it * gridDim + wg)
+    int k_short, tiles_m_full;   // ROWK kernels: row tiles tm >= tiles_m_full contract over the first k_short columns only
 };
 
 // Work items of a launch in the order XCD j takes them (j = blockIdx & 7 when the grid is a multiple of 8, else one list): item k
@@ -138,7 +139,12 @@ __device__ __forceinline__ int p8_lane() {
 #define P8_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #define P8_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
-template <int ACT, bool ZR> __global__ __launch_bounds__(512) void gemm8p_kernel(P8Args a) {
+// ROWK (mmgl_gemm_nt_rowk): a work item is a whole tile with its own K extent -- "long" tiles (tm < a.tiles_m_full, K) take the
+// virtual ids [0, L), "short" ones (a.k_short) the ids from L up, each class in its own grouped_tile order; k0 = 0 and one split
+// for every item, so an output element is the same sum whichever workgroup forms it.  The unit stream already crosses items of
+// different lengths (the K-split items): a phase issues one unit and waits for one, whatever nk is.  The static schedule follows
+// gemm8p_rowk_item, the dynamic one hands the ids out in order (long tiles first).
+template <int ACT, bool ZR, bool ROWK = false> __global__ __launch_bounds__(512) void gemm8p_kernel(P8Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -158,6 +164,20 @@ template <int ACT, bool ZR> __global__ __launch_bounds__(512) void gemm8p_kernel
     auto item_origin = [&](int v, int& m0, int& n0, int& k0, int& nki, int& sp) -> bool {
         if (v < 0 || v >= a.total * a.nsplit) return false;
         int tm, tn;
+        if constexpr (ROWK) {
+            const int L = a.tiles_m_full * a.tiles_n;
+            if (v < L) grouped_tile(v, a.tiles_m_full, a.tiles_n, tm, tn);
+            else {
+                grouped_tile(v - L, a.tiles_m - a.tiles_m_full, a.tiles_n, tm, tn);
+                tm += a.tiles_m_full;
+            }
+            m0 = tm * 256;
+            n0 = tn * 256;
+            k0 = 0;
+            sp = 0;
+            nki = (v < L ? a.K : a.k_short) >> 6;
+            return true;
+        }
         sp = v % a.nsplit;
         grouped_tile(a.tile0 + v / a.nsplit, a.tiles_m, a.tiles_n, tm, tn);
         m0 = tm * 256;
@@ -167,7 +187,14 @@ template <int ACT, bool ZR> __global__ __launch_bounds__(512) void gemm8p_kernel
         nki = (base + (sp < rem ? 1 : 0)) * 2;
         return true;
     };
-    auto tile_origin = [&](int it, int& m0, int& n0, int& k0, int& nki, int& sp) -> bool { return item_origin(it * G + wg, m0, n0, k0, nki, sp); };
+    // static schedule: virtual id of this workgroup's it-th work item
+    auto static_item = [&](int it) -> int {
+        if constexpr (ROWK) {
+            const int L = a.tiles_m_full * a.tiles_n;
+            return gemm8p_rowk_item(G, L, a.total - L, a.K / a.k_short, wg, it);
+        } else return it * G + wg;
+    };
+    auto tile_origin = [&](int it, int& m0, int& n0, int& k0, int& nki, int& sp) -> bool { return item_origin(static_item(it), m0, n0, k0, nki, sp); };
     // rows [row0, rows) of an operand with row stride ld: everything past the last row reads as zero.  (A K tile may run past
     // the end of a ROW when the caller pads K -- lm_head's dgrad contracts over V = 50272 -- and then reads the start of the next
     // row: finite values that meet the zero padding of the other operand.)
@@ -253,7 +280,7 @@ template <int ACT, bool ZR> __global__ __launch_bounds__(512) void gemm8p_kernel
 
     int m0 = 0, n0 = 0, m1 = 0, n1 = 0, k0 = 0, k1 = 0, nk1 = 0, sp0 = 0, sp1 = 0;
     int it = 0;
-    int vcur = wg, vnext = G + wg;                        // virtual ids of the current / next work item (static schedule: it * G + wg)
+    int vcur = static_item(0), vnext = static_item(1);    // virtual ids of the current / next work item (static schedule: it * G + wg)
     if (dyn) {                                            // the first item: one lane asks, everybody waits (~1 us, once per launch)
         if (tid == 0) mailbox[2] = p8_fetch_item(a.sched, xcd, nlists, G, Gx, a.total * a.nsplit);
         __syncthreads();
@@ -571,7 +598,7 @@ template <int ACT, bool ZR> __global__ __launch_bounds__(512) void gemm8p_kernel
         dXc = dXn;
         dWc = dWn;
         vcur = vnext;
-        vnext = dyn ? mailbox[it & 1] : (it + 1) * G + wg;       // the slot written at the PREVIOUS switch (or by the prologue)
+        vnext = dyn ? mailbox[it & 1] : static_item(it + 1);     // the slot written at the PREVIOUS switch (or by the prologue)
         have_next = item_origin(vnext, m1, n1, k1, nk1, sp1);
         dXn = mk_desc(a.X, m1, a.M, a.ldx, k1, have_next);
         dWn = mk_desc(a.W, n1, a.N, a.ldw, k1, have_next);
@@ -804,6 +831,39 @@ int launch_gemm8p(const bf16* X, int ldx, const bf16* W, int ldw, bf16* Y, int l
         MMGL_CHECK_LAUNCH("gemm8p split-K finish");
     }
     return MMGL_OK;
+}
+
+int launch_gemm8p_rowk(const bf16* X, int ldx, const bf16* W, int ldw, bf16* Y, int ldy, int M, int N, int K, int K_short, int m_full,
+                       hipStream_t st) {
+    if (!gemm8p_supported(M, N, K, ldx, ldw, ldy))
+        MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "gemm8p (row K): shape M=%d N=%d K=%d (ld %d %d %d) not supported", M, N, K, ldx, ldw, ldy);
+    MMGL_CHECK_ARG(K_short >= 256 && K_short % 128 == 0 && K_short <= K, "gemm8p (row K): K_short = %d must be a multiple of 128 in [256, K = %d]", K_short, K);
+    MMGL_CHECK_ARG(m_full >= 0 && m_full <= M, "gemm8p (row K): m_full = %d outside [0, M = %d]", m_full, M);
+    P8Args a;
+    a.X = X; a.W = W; a.Y = Y; a.bias = nullptr; a.resid = nullptr; a.zmask = nullptr;
+    a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.scale = 1.f; a.act = 0;
+    a.tiles_m = cdiv(M, 256); a.tiles_n = cdiv(N, 256); a.total = a.tiles_m * a.tiles_n;
+    a.nsplit = 1;
+    a.part = nullptr;
+    a.bits_out = nullptr;
+    a.bits_in = nullptr;
+    a.tile0 = 0;
+    a.trace = nullptr;
+    a.trace_wg = 0;
+    a.k_short = K_short;
+    a.tiles_m_full = cdiv(m_full, 256);
+    if (!p8_tile_counter_for(st, &a.sched)) a.sched = nullptr;       // (another stream owns the counters: static schedule, as launch_gemm8p)
+    const int n_cu = mmgl_num_cu(), grid = a.total < n_cu ? a.total : n_cu;
+    if (int rc = mmgl_set_lds(gemm8p_kernel<0, false, true>, P8_LDS_ALLOC, "gemm8p (row K)")) return rc;
+    hipLaunchKernelGGL((gemm8p_kernel<0, false, true>), dim3(grid), dim3(512), P8_LDS_ALLOC, st, a);
+    MMGL_CHECK_LAUNCH("gemm8p (row K)");
+    return MMGL_OK;
+}
+
+// the schedule as the host sees it (tests): gemm8p_rowk_item
+extern "C" int mmgl_gemm_nt_rowk_item(int G, int n_long, int n_short, int q, int wg, int it) {
+    if (G <= 0 || n_long < 0 || n_short < 0 || q < 1 || wg < 0 || wg >= G || it < 0) return -1;
+    return gemm8p_rowk_item(G, n_long, n_short, q, wg, it);
 }
 
 extern "C" int mmgl_gemm_set_tile_counter(void* counter) {

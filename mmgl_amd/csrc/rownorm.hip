@@ -123,20 +123,30 @@ __global__ __launch_bounds__(256) void norm_fwd_kernel(const T* __restrict__ x, 
     }
 }
 
-// MODE bit 0: RMSNorm (no mean); bit 1: accumulate the dgamma / dbeta column partials (skipped for frozen affines)
+// MODE bit 0: RMSNorm (no mean); bit 1: accumulate the dgamma / dbeta column partials (skipped for frozen affines); bit 3: dy is
+// read through a row map -- the gradient of dense row r lies in row dy_rows[r] of dy (the live-first gradient rows of a frozen layer's
+// fused dgrad); statistics, x, dres, dx, dx_drop and the dropout counters keep the dense row
 template <typename T, int TPR, int NV, int MODE>
 __global__ __launch_bounds__(256) void norm_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                        const T* __restrict__ gamma, const float* __restrict__ mean,
                                                        const float* __restrict__ rstd, const T* __restrict__ dres,
                                                        T* __restrict__ dx, T* __restrict__ dx_drop, float* __restrict__ part,
-                                                       int rows, int cols, float p, uint64_t seed) {
-    constexpr bool RMS = (MODE & 1) != 0, PARAMS = (MODE & 2) != 0;
+                                                       int rows, int cols, float p, uint64_t seed,
+                                                       const int* __restrict__ dy_rows) {
+    constexpr bool RMS = (MODE & 1) != 0, PARAMS = (MODE & 2) != 0, DYMAP = (MODE & 8) != 0;
     typedef typename Vec<T>::type V;
     constexpr int VN = Vec<T>::N;
     __shared__ float red[4];
     const int rpb = 256 / TPR;
     const int tr = threadIdx.x % TPR, rib = threadIdx.x / TPR;
     const int nchunks = cols / VN;
+    // the dy loads wait for their row's map entry: a row's entry is requested one trip ahead -- the first one here, in front of the
+    // gamma loads -- so that its latency is not added to the row's own (a block makes one or two trips)
+    int drow_next = 0;
+    if constexpr (DYMAP) {
+        const int r0 = blockIdx.x * rpb + rib;
+        drow_next = r0 < rows ? dy_rows[r0] : 0;
+    }
     float dg[NV][VN], dbt[NV][VN], gm[NV][VN];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -152,6 +162,12 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(const T* __restrict__ dy,
         const bool live = row < rows;
         const float mu = (!RMS && live) ? mean[row] : 0.f;
         const float rs = live ? rstd[row] : 0.f;
+        int drow = row;
+        if constexpr (DYMAP) {
+            drow = drow_next;
+            const long long rn = (long long)row + (long long)gridDim.x * rpb;
+            drow_next = rn < rows ? dy_rows[rn] : 0;
+        }
         float xh[NV][VN], gy[NV][VN];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -159,7 +175,7 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(const T* __restrict__ dy,
             const int c = tr + i * TPR;
             if (live && c < nchunks) {
                 const V xv = *(const V*)(x + (size_t)row * cols + c * VN);
-                const V dv = *(const V*)(dy + (size_t)row * cols + c * VN);
+                const V dv = *(const V*)(dy + (size_t)drow * cols + c * VN);
 #pragma unroll
                 for (int j = 0; j < VN; ++j) {
                     const float h = ((float)xv[j] - mu) * rs;
@@ -305,7 +321,7 @@ int norm_fwd(const char* who, const void* x, const void* res, const void* gamma,
 template <typename T, bool RMS>
 int norm_bwd(const char* who, const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
              const void* dres, void* dx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, int rows, int cols, hipStream_t st,
-             void* dx_drop = nullptr, float p = 0.f, uint64_t seed = 0) {
+             void* dx_drop = nullptr, float p = 0.f, uint64_t seed = 0, const int* dy_rows = nullptr) {
     Geo g;
     int rc = geometry<T>(who, rows, cols, g);
     if (rc) return rc;
@@ -318,12 +334,19 @@ int norm_bwd(const char* who, const void* dy, const void* x, const void* gamma, 
                        "%s: workspace too small (%zu B)", who, ws_bytes);
         part = (float*)ws;
     }
-    if (want)
+    if (!RMS && dy_rows) {                             // (the row map exists for LayerNorm only)
+        if (want)
+            NORM_DISPATCH(norm_bwd_kernel, T, (RMS ? 3 : 10), g, dim3(blocks), dim3(256), 0, st, (const T*)dy, (const T*)x,
+                          (const T*)gamma, mean, rstd, (const T*)dres, (T*)dx, (T*)dx_drop, part, rows, cols, p, seed, dy_rows);
+        else
+            NORM_DISPATCH(norm_bwd_kernel, T, (RMS ? 1 : 8), g, dim3(blocks), dim3(256), 0, st, (const T*)dy, (const T*)x,
+                          (const T*)gamma, mean, rstd, (const T*)dres, (T*)dx, (T*)dx_drop, part, rows, cols, p, seed, dy_rows);
+    } else if (want)
         NORM_DISPATCH(norm_bwd_kernel, T, (RMS ? 3 : 2), g, dim3(blocks), dim3(256), 0, st, (const T*)dy, (const T*)x,
-                      (const T*)gamma, mean, rstd, (const T*)dres, (T*)dx, (T*)dx_drop, part, rows, cols, p, seed);
+                      (const T*)gamma, mean, rstd, (const T*)dres, (T*)dx, (T*)dx_drop, part, rows, cols, p, seed, (const int*)nullptr);
     else
         NORM_DISPATCH(norm_bwd_kernel, T, (RMS ? 1 : 0), g, dim3(blocks), dim3(256), 0, st, (const T*)dy, (const T*)x,
-                      (const T*)gamma, mean, rstd, (const T*)dres, (T*)dx, (T*)dx_drop, part, rows, cols, p, seed);
+                      (const T*)gamma, mean, rstd, (const T*)dres, (T*)dx, (T*)dx_drop, part, rows, cols, p, seed, (const int*)nullptr);
     MMGL_CHECK_LAUNCH(who);
     if (want) {
         hipLaunchKernelGGL(norm_param_reduce_kernel, dim3((2 * cols + 31) / 32), dim3(256), 0, st, part, dgamma, dbeta,
@@ -399,6 +422,18 @@ extern "C" int mmgl_add_layernorm_bwd(const void* dy, const void* dsum, const vo
     MMGL_CHECK_ARG(p_drop == 0.f || dx, "mmgl_add_layernorm_bwd: dx is required when p_drop > 0");
     NORM_BY_DTYPE(norm_bwd, false, dy, sum, gamma, mean, rstd, dsum, dres, dgamma, dbeta, workspace, workspace_bytes, rows, cols,
                   (hipStream_t)stream, p_drop > 0.f ? dx : nullptr, p_drop, seed);
+}
+
+// ---- the backward of that LayerNorm when the fused dgrad left its result in live-first row order: dy row dy_rows[r] belongs to row r
+extern "C" int mmgl_add_layernorm_rows_bwd(const void* dy, const int32_t* dy_rows, const void* dsum, const void* sum, const void* gamma,
+                                           const float* mean, const float* rstd, void* dres, void* dx, float* dgamma, float* dbeta,
+                                           void* workspace, size_t workspace_bytes, int rows, int cols, float p_drop, uint64_t seed,
+                                           int dtype, void* stream) {
+    MMGL_CHECK_ARG(dy && dy_rows && sum && mean && rstd && dres, "mmgl_add_layernorm_rows_bwd: null pointer");
+    MMGL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "mmgl_add_layernorm_rows_bwd: dropout p=%g outside [0,1)", p_drop);
+    MMGL_CHECK_ARG(p_drop == 0.f || dx, "mmgl_add_layernorm_rows_bwd: dx is required when p_drop > 0");
+    NORM_BY_DTYPE(norm_bwd, false, dy, sum, gamma, mean, rstd, dsum, dres, dgamma, dbeta, workspace, workspace_bytes, rows, cols,
+                  (hipStream_t)stream, p_drop > 0.f ? dx : nullptr, p_drop, seed, dy_rows);
 }
 
 extern "C" int mmgl_layernorm_bwd(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,

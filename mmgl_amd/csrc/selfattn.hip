@@ -984,6 +984,27 @@ extern "C" int mmgl_selfattn_tiles_bwd(const void* dout, const void* q, const vo
                           ld_dq, ld_dkv, (hipStream_t)stream);
 }
 
+// live-first gradient rows: dq, dk, dv are [B * T, ld] buffers, tile (b, j) goes to rows 64 dest_tiles[b][j] .. + 63 (see the header)
+extern "C" int mmgl_selfattn_tiles_rows_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
+                                            const uint8_t* key_valid, const int32_t* key_tiles, const int32_t* dest_tiles, void* dq, void* dk,
+                                            void* dv, void* workspace, size_t workspace_bytes, int B, int H, int T, int D, int m_live,
+                                            int dkv_rows, int ld_q, int ld_kv, int ld_dq, int ld_dkv, int dtype, void* stream) {
+    int rc = tiles_check("mmgl_selfattn_tiles_rows_bwd", B, H, T, D, m_live, ld_kv, dtype);
+    if (rc) return rc;
+    if ((rc = sa_ld("mmgl_selfattn_tiles_rows_bwd", ld_q, H, D)) || (rc = sa_ld("mmgl_selfattn_tiles_rows_bwd", ld_kv, H, D)) ||
+        (rc = sa_ld("mmgl_selfattn_tiles_rows_bwd", ld_dq, H, D)) || (rc = sa_ld("mmgl_selfattn_tiles_rows_bwd", ld_dkv, H, D))) return rc;
+    MMGL_CHECK_ARG(dout && q && k && v && out && lse && key_valid && key_tiles && dest_tiles && dq && dk && dv && workspace,
+                   "mmgl_selfattn_tiles_rows_bwd: null pointer");
+    MMGL_CHECK_ARG(workspace_bytes >= mmgl_selfattn_bwd_workspace(B, H, T), "mmgl_selfattn_tiles_rows_bwd: workspace too small");
+    MMGL_CHECK_ARG(dkv_rows >= m_live && dkv_rows % 64 == 0, "mmgl_selfattn_tiles_rows_bwd: dkv_rows = %d must be a multiple of 64, at least m_live = %d",
+                   dkv_rows, m_live);
+    // one descriptor spans a whole gradient buffer: it has to stay inside the 2 GiB the kernels' out-of-range offset is sized for
+    const long long ldmax = ld_dq > ld_dkv ? ld_dq : ld_dkv;
+    MMGL_CHECK_ARG((long long)B * T * ldmax * 2 < (1ll << 31), "mmgl_selfattn_tiles_rows_bwd: the gradient buffers must stay below 2 GiB");
+    return sa32_tiles_bwd(dout, q, k, v, out, lse, key_valid, key_tiles, dq, dk, dv, (float*)workspace, B, H, T, m_live / 64, ld_q, ld_kv,
+                          ld_dq, ld_dkv, (hipStream_t)stream, dest_tiles, dkv_rows);
+}
+
 // ---- grouped-query attention: k, v, dk, dv [B, T, Hkv*D]; query head h reads key / value head h / (H / Hkv)
 static int gqa_check(const char* who, int B, int H, int Hkv, int T, int D, int dtype) {
     MMGL_CHECK_ARG(Hkv >= 1 && H >= Hkv && H % Hkv == 0, "%s: H = %d must be a positive multiple of Hkv = %d", who, H, Hkv);

@@ -500,6 +500,11 @@ struct SA32BwdArgs {
     int G;                     // GQA instantiations only: query head h reads key / value head h / G (dk, dv stay per QUERY head)
     const int* tiles;          // TILES instantiations only (see SA32Args): k, v are compact [64 ntc, ldk]; dq, dk, dv stay dense
     int ntc;
+    // TILES instantiations, optional (null: the dense layout above).  Live-first gradient rows: dest [B, T / 64] is a permutation of
+    // the batch's 64-row tiles, and the rows of tile j of sample b are stored at rows 64 dest[b][j] .. + 63 of dq, dk, dv taken as
+    // [B * T, ld] buffers.  Only the store addresses change.  dk / dv rows from dkv_rows on are not stored (nobody reads them).
+    const int* dest;
+    int dkv_rows;
 };
 
 // 16 transposed fragments' worth of reads for ONE 32-channel block: f[blk][jj][half]; rows 32 blk + 16 jj (+ 8) of the tile at `ad`
@@ -718,7 +723,15 @@ __global__ __launch_bounds__(256, SA32_DQ_OCC) void sa32_bwd_dq_kernel(SA32BwdAr
     }
 
     if (EARLY) SA32_VMCNT(0);
-    const uint32_t orow = wave_active ? (uint32_t)trow * ldgB : OOB;
+    uint32_t orow = wave_active ? (uint32_t)trow * ldgB : OOB;
+    __amdgpu_buffer_rsrc_t rdst = rd;
+    if constexpr (TILES) {
+        if (a.dest) {                        // live-first rows: the wave's 32 rows lie in one 64-row tile (T is a multiple of 64)
+            const int dt = wave_active ? a.dest[(size_t)b * (Tq / G::KT) + (t0 >> 6)] : -1;
+            rdst = make_rsrc(a.dq + h * D, (uint32_t)(a.B * Tq - 1) * ldgB + D * 2);
+            orow = (dt >= 0 && dt < a.B * (Tq / G::KT)) ? (uint32_t)(dt * G::KT + (trow & 63)) * ldgB : OOB;
+        }
+    }
 #pragma unroll
     for (int db = 0; db < G::NDB; ++db)
 #pragma unroll
@@ -734,7 +747,7 @@ __global__ __launch_bounds__(256, SA32_DQ_OCC) void sa32_bwd_dq_kernel(SA32BwdAr
             swap32_u32(a0, b0);
             swap32_u32(a1, b1);
             const u32x4 val = {a0, a1, b0, b1};
-            __builtin_amdgcn_raw_buffer_store_b128(val, rd, orow + (uint32_t)(32 * db + 8 * (c + hi)) * 2u, 0, ATTN_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(val, TILES ? rdst : rd, orow + (uint32_t)(32 * db + 8 * (c + hi)) * 2u, 0, ATTN_STORE_AUX);
         }
 }
 
@@ -960,7 +973,19 @@ __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dk
 
     if (EARLY || wg_dead) SA32_VMCNT(0);                                 // (the prologue's requests must not outlive the workgroup's LDS)
     // ---- epilogue: dK = -acc, dV rows (lane = key row: the forward kernel's output store)
-    const uint32_t orow = (krow < Tk) ? (uint32_t)krow * ldgB : OOB;
+    uint32_t orow = (krow < Tk) ? (uint32_t)krow * ldgB : OOB;
+    __amdgpu_buffer_rsrc_t rdkd = rdk, rdvd = rdv;
+    if constexpr (TILES) {
+        if (a.dest) {                        // live-first rows (see SA32BwdArgs): the wave's 32 keys lie in one tile
+            const int ntl = Tk / G::KT, jt = k0 >> 6;
+            const int dt = jt < ntl ? a.dest[(size_t)b * ntl + jt] : -1;
+            const uint32_t span = (uint32_t)(a.B * Tk - 1) * ldgB + D * 2;
+            rdkd = make_rsrc(a.dk + h * D, span);
+            rdvd = make_rsrc(a.dv + h * D, span);
+            const int drow0 = dt * G::KT;
+            orow = (dt >= 0 && dt < a.B * ntl && drow0 < a.dkv_rows) ? (uint32_t)(drow0 + (krow & 63)) * ldgB : OOB;
+        }
+    }
 #pragma unroll
     for (int which = 0; which < 2; ++which)
 #pragma unroll
@@ -978,7 +1003,8 @@ __global__ __launch_bounds__(256, D == 64 ? SA32_DKV_OCC64 : 1) void sa32_bwd_dk
                 swap32_u32(a0, b0);
                 swap32_u32(a1, b1);
                 const u32x4 val = {a0, a1, b0, b1};
-                __builtin_amdgcn_raw_buffer_store_b128(val, which ? rdv : rdk, orow + (uint32_t)(32 * db + 8 * (c + hi)) * 2u, 0, ATTN_STORE_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(val, TILES ? (which ? rdvd : rdkd) : (which ? rdv : rdk), orow + (uint32_t)(32 * db + 8 * (c + hi)) * 2u, 0,
+                                                       ATTN_STORE_AUX);
             }
 }
 
@@ -1065,8 +1091,9 @@ int sa32_bwd(const void* dout, const void* q, const void* k, const void* v, cons
 
 int sa32_tiles_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse, const uint8_t* valid,
                    const int* tiles, void* dq, void* dk, void* dv, float* delta, int B, int H, int T, int ntc, int ldq, int ldk, int ldg,
-                   int ldgk, hipStream_t st) {
+                   int ldgk, hipStream_t st, const int* dest, int dkv_rows) {
     SA32BwdArgs a{};
+    a.dest = dest; a.dkv_rows = dkv_rows;
     a.dout = (const bf16*)dout; a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (const bf16*)out; a.lse = lse;
     a.valid = valid; a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.delta = delta;
     a.B = B; a.H = H; a.T = T; a.P = 0; a.nqb = cdiv(T, 128); a.nkb = cdiv(T, 128); a.ldq = ldq; a.ldk = ldk; a.ldg = ldg; a.ldgk = ldgk;

@@ -221,6 +221,22 @@ class MPTAttention(nn.Module):
             return False
         return ops.selfattn_tiles_supported(x, self.num_heads, key_tiles) and self._frozen_qkv() is not None
 
+    def block_tiles_route(self, x, key_tiles, ln, attention_mask):
+        """Whether a pre-LN layer that takes key_tiles_route runs LayerNorm -> projections -> attention as ONE autograd node
+        (ops.frozen_attn_block_tiles), whose backward sorts the gradient rows live key tiles first and skips the zero dK | dV of the
+        dead ones in the fused dgrad: gradients flow, the LayerNorm's parameters are frozen, and the dense dgrad of this batch is
+        one sum per element on the persistent GEMM kernel (ops.frozen_attn_block_supported).  Anything else keeps the three nodes."""
+        if not torch.is_grad_enabled() or attention_mask is None or attention_mask.dim() != 2:
+            return False
+        return ops.frozen_attn_block_supported(x, self.num_heads, key_tiles, ln.weight, ln.bias, self._frozen_qkv()[0])
+
+    def block_tiles(self, x, res, ln, attention_mask, key_tiles, p_drop=0.0, training=False):
+        """(s, attention output after out_proj) with s = x, or res + dropout(x): the caller checked key_tiles_route and
+        block_tiles_route."""
+        s, o = ops.frozen_attn_block_tiles(x, res, ln.weight, ln.bias, ln.eps, *self._frozen_qkv(), attention_mask, key_tiles, self.num_heads,
+                                           p_drop, training)
+        return s, _lin(self.out_proj, o)
+
     def _frozen_qkv(self):
         """The fused weight / bias (_fused_qkv) when the three projections are frozen (the reference freezes the whole LM outside
         the cross-attention layers, :731-737), else None."""
@@ -467,13 +483,21 @@ class MPTDecoderLayer(nn.Module):
         ln1, ln2 = self.self_attn_layer_norm, self.final_layer_norm
         pair = lambda x, r, ln: ops.add_layer_norm_pair(x, r, ln.weight, ln.bias, ln.eps, self.dropout, self.training)
         like = h.residual if isinstance(h, _Deferred) else h
-        live = None
+        live = a = None
         if pre and self.self_attn.key_tiles_route(like, key_tiles, layer_head_mask, output_attentions, past_key_value, kv_out):
-            if isinstance(h, _Deferred):
+            needs_grad = like.requires_grad or (isinstance(h, _Deferred) and h.branch.requires_grad)
+            if needs_grad and self.self_attn.block_tiles_route(like, key_tiles, ln1, attention_mask):
+                # LayerNorm, projections and attention as one node: its backward skips the zero dK | dV of the dead key tiles
+                if isinstance(h, _Deferred):
+                    h, a = self.self_attn.block_tiles(h.branch, h.residual, ln1, attention_mask, key_tiles, h.p_drop, h.training)
+                else:
+                    h, a = self.self_attn.block_tiles(h, None, ln1, attention_mask, key_tiles)
+            elif isinstance(h, _Deferred):
                 h, x, yc = ops.add_layer_norm_tiles(h.branch, h.residual, ln1.weight, ln1.bias, ln1.eps, key_tiles, h.p_drop, h.training)
+                live = (yc, key_tiles)
             else:
                 h, x, yc = ops.layer_norm_tiles(h, ln1.weight, ln1.bias, ln1.eps, key_tiles)
-            live = (yc, key_tiles)
+                live = (yc, key_tiles)
         elif isinstance(h, _Deferred):
             if pre:
                 h, x = ops.add_layer_norm_pair(h.branch, h.residual, ln1.weight, ln1.bias, ln1.eps, h.p_drop, h.training)
@@ -484,8 +508,10 @@ class MPTDecoderLayer(nn.Module):
         else:
             x = h
         residual = h
-        a, attn_w, _ = self.self_attn(x, attention_mask=attention_mask, layer_head_mask=layer_head_mask,
-                                      output_attentions=output_attentions, past_key_value=past_key_value, kv_out=kv_out, live=live)
+        attn_w = None
+        if a is None:
+            a, attn_w, _ = self.self_attn(x, attention_mask=attention_mask, layer_head_mask=layer_head_mask,
+                                          output_attentions=output_attentions, past_key_value=past_key_value, kv_out=kv_out, live=live)
         if pre:
             h, x = pair(a, residual, ln2)
         else:

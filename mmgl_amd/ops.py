@@ -354,7 +354,8 @@ def selfattn_core_prefix(q, k, v, key_valid, num_heads, prefix_len):
 # stores the rows of the live tiles a second time, compact (yc); K | V = yc Wkv^T has 64 x (live tiles) rows, the kernels find a
 # tile's rows through a table.  Every element of Q, K and V is the sum the fused [M, 3d] GEMM forms, so the attention output is bitwise
 # the dense path's; dQ | dK | dV keep the dense [B, T, 3d] layout and the fused dgrad, whose one rounding of dQ Wq' + dKV Wkv two
-# GEMMs cannot reproduce.
+# GEMMs cannot reproduce.  Where the whole pre-LN block runs as one node (frozen_attn_block_tiles) the gradient rows are sorted live
+# tiles first instead, and that one dgrad launch contracts the row tiles behind them over dQ alone: the same sums minus their zero tails.
 KEY_TILE = 64
 
 
@@ -372,10 +373,23 @@ def key_tile_table(attention_mask):
     return table, KEY_TILE * int(live.sum())
 
 
+def grad_tile_table(table, m_live):
+    """(dest, rows) of a key-tile table, on the table's device: the live-first order of the gradient rows.  dest [B, T // 64] int32
+    is a permutation of the batch's tiles -- a live tile goes to its compact index, a dead one to m_live // 64 + its rank among the
+    dead tiles -- and rows [B * T] int32 the row of every dense row under it, 64 dest + (row % 64).  No synchronisation."""
+    t = table.reshape(-1)
+    dead = t < 0
+    rank = torch.cumsum(dead.to(torch.int32), 0, dtype=torch.int32) - 1
+    dest = torch.where(dead, rank + int(m_live) // KEY_TILE, t).to(torch.int32)
+    rows = dest.view(-1, 1) * KEY_TILE + torch.arange(KEY_TILE, dtype=torch.int32, device=table.device)
+    return dest.view(table.shape).contiguous(), rows.reshape(-1).contiguous()
+
+
 class KeyTiles:
     """key_tile_table's result on the device, for one forward / backward pass: table [B, T // 64] int32, rowmap [B * T] int32 (the
-    compact row of every row of a live tile, -1 elsewhere) and m_live, a host integer -- no synchronisation."""
-    __slots__ = ("table", "rowmap", "m_live")
+    compact row of every row of a live tile, -1 elsewhere) and m_live, a host integer -- no synchronisation.  dest / grad_rows: the
+    live-first order of the gradient rows (grad_tile_table)."""
+    __slots__ = ("table", "rowmap", "m_live", "dest", "grad_rows")
 
     def __init__(self, table, m_live, device):
         self.table = table.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
@@ -383,6 +397,7 @@ class KeyTiles:
         t = self.table.view(-1, 1)
         rows = t * KEY_TILE + torch.arange(KEY_TILE, dtype=torch.int32, device=self.table.device)
         self.rowmap = torch.where(t >= 0, rows, torch.full_like(rows, -1)).reshape(-1).contiguous()
+        self.dest, self.grad_rows = grad_tile_table(self.table, self.m_live)
 
     def fits(self, B, T):
         return self.m_live > 0 and tuple(self.table.shape) == (B, T // KEY_TILE) and T % KEY_TILE == 0
@@ -471,6 +486,115 @@ def frozen_selfattn_tiles(y, yc, w, b, key_valid, tiles, num_heads):
     return _FrozenSelfAttnTiles.apply(y, yc, w, b, _key_valid(key_valid), tiles, num_heads)
 
 
+def gemm_nt_rowk(x2, w, K_short, m_full, out=None):
+    """Raw mmgl_gemm_nt_rowk call: x2 [M, K] @ w [N, K]^T where the 256-row tiles from row ceil(m_full / 256) * 256 on contract over
+    the first K_short columns only -- x2 is zero (or uninitialised) behind them there.  One launch without K splits: the sums of
+    gemm_nt(k_splits=False), minus a tail of exact zeros.  No autograd."""
+    require_cuda(x2, w)
+    M, K = x2.shape
+    N = w.shape[0]
+    if x2.stride(1) != 1 or w.stride(1) != 1 or w.shape[1] != K:
+        raise ValueError("gemm_nt_rowk: operands need unit column stride and one K")
+    y = torch.empty(M, N, dtype=x2.dtype, device=x2.device) if out is None else out
+    mlong = min(M, -(-int(m_full) // 256) * 256)
+    _lib.call("mmgl_gemm_nt_rowk", dict(flops=2.0 * N * (mlong * K + (M - mlong) * K_short), bytes=float(M * K + N * K + M * N) * x2.element_size(),
+                                        tag=f"{M}x{N}x{K}|{K_short}@{int(m_full)}"),
+              ptr(x2), x2.stride(0), ptr(w), w.stride(0), ptr(y), y.stride(0), M, N, K, int(K_short), int(m_full), dtype_code(x2), stream_ptr())
+    return y
+
+
+def frozen_attn_block_supported(like, num_heads, tiles, gamma, beta, w):
+    """Whether frozen_attn_block_tiles takes activations `like` [B, T, d]: selfattn_tiles_supported, a frozen LayerNorm affine, and a
+    dense fused dgrad [B T, 3d] -> [B T, d] that runs on the persistent GEMM kernel as whole tiles without K splits -- the one sum
+    per element that the short-K launch reproduces -- within the 2 GiB of the attention kernels' gradient descriptors."""
+    if not selfattn_tiles_supported(like, num_heads, tiles):
+        return False
+    if any(p is not None and p.requires_grad for p in (gamma, beta)) or w.dtype != like.dtype:
+        return False
+    B, T, d = like.shape
+    M = B * T
+    if d % 128 or M * 3 * d * 2 >= 2 ** 31:
+        return False
+    L = lib()
+    return L.mmgl_gemm_nt_fast(M, d, 3 * d, 3 * d, 3 * d, d, _lib.BF16) == 1 and L.mmgl_gemm_nt_workspace(M, d, 3 * d, 3 * d, 3 * d, d, _lib.BF16) == 0
+
+
+class _FrozenAttnBlockTiles(torch.autograd.Function):
+    """The pre-LN attention block of a frozen layer on live key tiles as ONE node: (s, o) with s = x, or res + dropout(x), and
+    o = attention(LayerNorm(s)) -- forward: the calls of _NormPair (with the compact copy) and _FrozenSelfAttnTiles, unchanged.
+    Backward: the attention backward writes dQ | dK | dV with the rows sorted live key tiles first (KeyTiles.dest), so the rows from
+    m_live on have dK = dV = 0 and the fused dgrad contracts their 256-row tiles over dQ alone (gemm_nt_rowk: one launch, one
+    rounding, each sum minus its zero tail: the dense dgrad's bits); the LayerNorm backward reads that result through
+    KeyTiles.grad_rows.  The permuted gradient lives inside this node only: it never reaches autograd as a tensor."""
+
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta, eps, p, seed, tiles, w, b, key_valid, num_heads):
+        require_cuda(x, key_valid)
+        B, T, d = x.shape
+        m = tiles.m_live
+        yc = x.new_empty(m, d)
+        s, y, g, mean, rstd = _norm_fwd(False, x, res, gamma, beta, eps, p, seed, compact=(tiles.rowmap, yc))
+        q = gemm_nt(y, w[:d], None if b is None else b[:d], k_splits=False)
+        kv = gemm_nt(yc, w[d:], None if b is None else b[d:], k_splits=False)
+        out = torch.empty(B, T, d, dtype=x.dtype, device=x.device)
+        lse = torch.empty(B, num_heads, T, dtype=torch.float32, device=x.device)
+        es = x.element_size()
+        work = dict(flops=2.0 * B * T * T * d, bytes=(2.0 * B * T * d + 2.0 * m * d) * es)
+        _lib.call("mmgl_selfattn_tiles_fwd", work, ptr(q), ptr(kv), ptr_off(kv, d * es), ptr(key_valid), ptr(tiles.table), ptr(out), ptr(lse),
+                  B, num_heads, T, d // num_heads, m, d, 2 * d, dtype_code(x), stream_ptr())
+        ctx.save_for_backward(s, g, mean, rstd, q, kv, key_valid, out, lse, w)
+        ctx.set_materialize_grads(False)
+        ctx.cfg = (x.shape, p, seed, res is None, tiles, num_heads)
+        return (x if res is None else s.view(x.shape)), out       # (autograd wraps the returned input as a view, see _NormPair)
+
+    @staticmethod
+    def backward(ctx, ds, dout):
+        s, g, mean, rstd, q, kv, key_valid, out, lse, w = ctx.saved_tensors
+        shape, p, seed, fanout, tiles, H = ctx.cfg
+        nograd = (None,) * 10
+        if dout is None:                                      # only the residual stream was used downstream (see _NormPair)
+            if ds is None or p == 0.0:
+                return (ds, None if fanout else ds) + nograd
+            dres, dx, _, _ = _norm_bwd(False, True, torch.zeros_like(ds), ds, s, g, mean, rstd, (False, False), None, p, seed)
+            return (dx.view(shape), dres.view(shape)) + nograd
+        B, T, d = out.shape
+        m, es = tiles.m_live, out.element_size()
+        M = B * T
+        dkv_rows = min(M, -(-m // 256) * 256)                 # the rows whose dK | dV columns the dgrad reads
+        dout = dout.contiguous()
+        dqkv = torch.empty(M, 3 * d, dtype=out.dtype, device=out.device)
+        nbytes = lib().mmgl_selfattn_bwd_workspace(B, H, T)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
+        work = dict(flops=5.0 * B * T * T * d, bytes=(4.0 * B * T * d + 2.0 * dkv_rows * d + 2.0 * m * d) * es)
+        _lib.call("mmgl_selfattn_tiles_rows_bwd", work, ptr(dout), ptr(q), ptr(kv), ptr_off(kv, d * es), ptr(out), ptr(lse), ptr(key_valid),
+                  ptr(tiles.table), ptr(tiles.dest), ptr(dqkv), ptr_off(dqkv, d * es), ptr_off(dqkv, 2 * d * es), ptr(ws), nbytes, B, H, T,
+                  d // H, m, dkv_rows, d, 2 * d, 3 * d, 3 * d, dtype_code(out), stream_ptr())
+        dy = gemm_nt_rowk(dqkv, _transposed(w), d, m)         # rows in live-first order
+        dres, dx, _, _ = _norm_bwd(False, True, dy, ds, s, g, mean, rstd, (False, False), None, p, seed, dy_rows=tiles.grad_rows)
+        dres = dres.view(shape)
+        if fanout:
+            return (dres, None) + nograd
+        return ((dres if dx is None else dx.view(shape)), dres) + nograd
+
+
+def frozen_attn_block_tiles(x, res, gamma, beta, eps, w, b, key_valid, tiles, num_heads, p_drop=0.0, training=False, seed=None):
+    """(s, o) of a frozen pre-LN layer's attention block: s = x (res None: the fan-out of layer_norm_tiles) or res + dropout(x)
+    (add_layer_norm_tiles), o = frozen_selfattn_tiles(LayerNorm(s), its compact copy, w, b, key_valid, tiles, num_heads) -- the
+    same values, one autograd node whose backward skips the zero dK | dV of the dead key tiles.  Check frozen_attn_block_supported
+    first."""
+    like = x
+    if res is not None and x.shape != res.shape:
+        raise ValueError(f"frozen_attn_block_tiles: shapes differ {tuple(x.shape)} vs {tuple(res.shape)}")
+    if not frozen_attn_block_supported(like, num_heads, tiles, gamma, beta, w):
+        raise ValueError(f"frozen_attn_block_tiles: x{tuple(x.shape)} {x.dtype} with {num_heads} heads does not take the one-node route "
+                         "(frozen_attn_block_supported)")
+    if w.requires_grad or (b is not None and b.requires_grad) or w.shape != (3 * x.shape[2], x.shape[2]):
+        raise ValueError("frozen_attn_block_tiles: w must be the frozen fused [3d, d] projection")
+    _check_mask(key_valid, x.shape[:2])
+    p, seed = (0.0, 0) if res is None else _dropout(p_drop, training, seed)
+    return _FrozenAttnBlockTiles.apply(x, res, gamma, beta, float(eps), p, seed, tiles, w, b, _key_valid(key_valid), num_heads)
+
+
 def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
@@ -527,11 +651,12 @@ def _norm_fwd(rms, x, res, gamma, beta, eps, p=0.0, seed=0, keep_sum=True, keep_
     return s, y, g, mean, rstd
 
 
-def _norm_bwd(rms, fused, dy, dsum, s, g, mean, rstd, pgrad, pdtype, p=0.0, seed=0):
+def _norm_bwd(rms, fused, dy, dsum, s, g, mean, rstd, pgrad, pdtype, p=0.0, seed=0, dy_rows=None):
     """The backward of _norm_fwd in one launch (plus the column reduction when a parameter gradient is wanted).  fused: the
     mmgl_add_* entry points, which add `dsum` (the gradient arriving on s, or None) inside the kernel and with p > 0 also write the
     gradient of the dropped-out x.  pgrad = (gamma, beta) need a gradient: LayerNorm computes both when either does; only the needed
-    ones come back, in the parameters' dtype.  Returns (ds, dx | None, dgamma | None, dbeta | None) with ds, dx [rows, cols]."""
+    ones come back, in the parameters' dtype.  dy_rows [rows] int32 (fused LayerNorm only): row r's gradient is row dy_rows[r] of dy.
+    Returns (ds, dx | None, dgamma | None, dbeta | None) with ds, dx [rows, cols]."""
     rows, cols = s.shape
     dy = dy.contiguous().view(rows, cols)
     dsum = None if dsum is None else dsum.contiguous().view(rows, cols)
@@ -543,7 +668,12 @@ def _norm_bwd(rms, fused, dy, dsum, s, g, mean, rstd, pgrad, pdtype, p=0.0, seed
     nbytes = lib().mmgl_norm_bwd_workspace(rows, cols) if want else 0
     ws = torch.empty(nbytes, dtype=torch.uint8, device=s.device) if want else None
     work = dict(bytes=(3.0 + (dsum is not None) + (dx is not None)) * rows * cols * s.element_size())
-    if not fused:
+    if dy_rows is not None:
+        if rms or not fused or dy_rows.numel() != rows:
+            raise ValueError(f"_norm_bwd: the row map is the fused LayerNorm's, one entry per row ({dy_rows.numel()} for {rows} rows)")
+        _lib.call("mmgl_add_layernorm_rows_bwd", work, ptr(dy), ptr(dy_rows), ptr(dsum), ptr(s), ptr(g), ptr(mean), ptr(rstd), ptr(ds), ptr(dx),
+                  ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, rows, cols, p, seed, dtype_code(s), stream_ptr())
+    elif not fused:
         if rms:
             _lib.call("mmgl_rmsnorm_bwd", work, ptr(dy), ptr(s), ptr(g), ptr(rstd), ptr(ds), ptr(dgamma), ptr(ws), nbytes, rows, cols,
                       dtype_code(s), stream_ptr())
