@@ -176,6 +176,32 @@ int mmgl_attn_general_bwd(const void* dout, const void* q, const void* k, const 
 int mmgl_attn_dropout_mask(uint8_t* mask, int B, int H, int T, int S, float p_drop, uint64_t seed, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * T5 attention (csrc/relbias.hip): unscaled scores plus a learned per-head relative-position bias, on the MFMAs.
+ * replaces: transformers T5Attention.forward (scores + compute_bias(T, S) + mask, softmax in fp32, dropout, matmul with V).
+ *   q [B,T,H*D] rows ldq elements apart; k, v [B,S,H*D] rows ldkv elements apart (pitches: multiples of 8, >= H*D)
+ *   key_valid [B,S] uint8, or NULL for all valid
+ *   table [num_buckets,H] fp32, or NULL for no bias (the decoder-to-encoder cross-attention); bucket_of int32 [T+S-1], the entry of
+ *   the pair (t, s) at s - t + T - 1, values in [0, num_buckets) (clamped into it)
+ *   score = q . k + table[bucket_of[s - t + T - 1], h]  -- no D^-0.5 scale; causal: s <= t only, needs T == S
+ *   p_drop, seed: dropout on the probabilities, the counter hash of (seed, ((b H + h) T + t) S + s) of mmgl_attn_general_*
+ *   out [B,T,H*D] packed; lse [B,H,T] fp32
+ * D = 64 only (every T5 up to t5-large has d_kv = 64), any T, S >= 1; everything else returns MMGL_ERR_UNSUPPORTED before any launch.
+ * A query row without an allowed key is outside the contract (T5's prompts always hold tokens): it writes zeros to out, 0 to lse and
+ * contributes nothing to any gradient (HuggingFace gives such a row the uniform distribution).
+ * Backward: dout, out, dq [B,T,H*D] and dk, dv [B,S,H*D] packed; dtable fp32 [num_buckets,H] (NULL when table is NULL) is written
+ * completely -- a bucket no pair reaches gets 0 -- and reproducibly: no floating-point atomics, per-tile diagonal sums in the workspace
+ * are folded in a fixed order.  `workspace`: mmgl_attn_relbias_bwd_workspace(B, H, T, S) bytes, 16-byte aligned.
+ */
+int mmgl_attn_relbias_fwd(const void* q, const void* k, const void* v, const uint8_t* key_valid, const float* table,
+                          const int32_t* bucket_of, void* out, float* lse, int B, int H, int T, int S, int D, int num_buckets,
+                          int ldq, int ldkv, int causal, float p_drop, uint64_t seed, int dtype, void* stream);
+size_t mmgl_attn_relbias_bwd_workspace(int B, int H, int T, int S);
+int mmgl_attn_relbias_bwd(const void* dout, const void* q, const void* k, const void* v, const void* out, const float* lse,
+                          const uint8_t* key_valid, const float* table, const int32_t* bucket_of, void* dq, void* dk, void* dv,
+                          float* dtable, void* workspace, size_t workspace_bytes, int B, int H, int T, int S, int D,
+                          int num_buckets, int ldq, int ldkv, int causal, float p_drop, uint64_t seed, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * LayerNorm (affine, eps inside the sqrt) over the last dim.
  * replaces: nn.LayerNorm at modelling_cross_attention.py:319-320, 340-341, 349-350, 364-365, 635-636
  *   x,y [rows,cols]; gamma,beta [cols] (same dtype as x; may be NULL = no affine); mean,rstd [rows] fp32

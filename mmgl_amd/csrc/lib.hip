@@ -87,4 +87,6 @@ int mmgl_num_cu() {
 // mmgl_weight_quantize / mmgl_gemm_skinny_w8 (FP8 frozen weights for generate()) were added at 110 the same way.
 // mmgl_selfattn_tiles_rows_bwd / mmgl_gemm_nt_rowk(_item) / mmgl_add_layernorm_rows_bwd (live-first gradient rows of the frozen layers:
 // the fused QKV dgrad skips the zero dK | dV of dead key tiles) were added at 110 the same way.
+// mmgl_attn_relbias_fwd / mmgl_attn_relbias_bwd(_workspace) (T5 attention: relative-position bias, native T5 forward) were added at
+// 110 the same way.
 extern "C" int mmgl_version(void) { return 110; }

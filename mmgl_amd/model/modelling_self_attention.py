@@ -1,7 +1,8 @@
 """Self-attention fusion wrapper: neighbor embeddings are concatenated into the LM's input sequence.
 
 Mirrors reference model/modelling_self_attention.py (constructor, forward kwargs, state-dict names of the
-wrapper-level modules).  T5 (config 1, CPU plumbing) is the stock HuggingFace model; a decoder-only OPT is loaded through
+wrapper-level modules).  T5 (config 1) is the stock HuggingFace model on CPU tensors and runs the native forward of t5_hip.py on the
+GPU (same module, same parameters); a decoder-only OPT is loaded through
 the same HF API and then runs as this build's OPT fork (modelling_cross_attention.MPTForCausalLM without cross-attention
 layers, identical state-dict keys) on the HIP kernels.  What else this build owns here:
   * LoRA injection without `peft` (absent in this image, unpinned in the reference's requirements.txt:8):
@@ -28,6 +29,7 @@ from .encoders import PackedTextEncoder, PackedVisionEncoder
 from .graph import GCN
 from .modelling_cross_attention import TextPooler
 from .sampling import check_processors, check_sampling
+from .t5_hip import T5HipRunner
 
 NUM_VIRTUAL_TOKENS = 20
 
@@ -103,6 +105,8 @@ class SelfAttentionModel(nn.Module):
     """SelfAttentionModel(args, tokenizer): T5 (encoder-decoder) or OPT (decoder-only) with neighbor tokens
     concatenated into the sequence (reference :48-335).  `lm_config`/`text_config`/`visual_config` build random-init
     models instead of from_pretrained (synthetic benchmarks / tests)."""
+
+    t5_native = True         # a T5 on the GPU runs t5_hip.T5HipRunner; False selects the stock HuggingFace call (tools/bench_t5.py)
 
     def __init__(self, args, tokenizer, lm_config=None, text_config=None, visual_config=None):
         super().__init__()
@@ -316,6 +320,15 @@ class SelfAttentionModel(nn.Module):
         if self.prefix_encoder is not None:
             # labels and logits keep the sequence length: the prefix lives in the attention of every layer, not in the sequence
             kw["past_key_values"] = self.prefix_encoder.weight.to(self.input_embeddings.weight.dtype)
+        if self.t5_native and lm_input.is_cuda and labels is not None and not kw and "t5" in self.args.model_name_or_path:
+            # T5 on the GPU: the native forward over the HuggingFace module (t5_hip.py: relative-position-bias attention and every
+            # GEMM on the HIP kernels); a variant it does not cover, CPU tensors and t5_native = False stay the stock call below
+            runner = self.__dict__.get("_t5_runner")
+            if runner is None:               # decided once: the architecture is fixed at construction (False: not covered)
+                runner = self.__dict__["_t5_runner"] = T5HipRunner(self.lm) if T5HipRunner.supports(self.lm) else False
+            if runner:
+                ids, embeds = (None, lm_input) if lm_input.dim() == 3 else (lm_input, None)
+                return runner(input_ids=ids, inputs_embeds=embeds, attention_mask=attention_mask, labels=labels)
         if lm_input.dim() == 3:
             return self.lm(inputs_embeds=lm_input, attention_mask=attention_mask, labels=labels, **kw)
         return self.lm(input_ids=lm_input, attention_mask=attention_mask, labels=labels, **kw)

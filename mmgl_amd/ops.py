@@ -152,6 +152,88 @@ def attn_dropout_mask(B, H, T, S, p_drop, seed, device):
     return m
 
 
+# ------------------------------------------------------------------------------------------ T5 attention (relative-position bias)
+class _AttnRelBias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, key_valid, table, bucket_of, num_heads, causal, p_drop, seed):
+        require_cuda(q, k, v, key_valid, table, bucket_of)
+        B, T, d = q.shape
+        S = k.shape[1]
+        D = d // num_heads
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out = torch.empty_like(q)
+        lse = torch.empty(B, num_heads, T, dtype=torch.float32, device=q.device)
+        tab = None if table is None else table.detach().to(torch.float32).contiguous()
+        nb = 0 if tab is None else tab.shape[0]
+        _lib.call("mmgl_attn_relbias_fwd", dict(flops=4.0 * B * T * S * d), ptr(q), ptr(k), ptr(v), ptr(key_valid), ptr(tab),
+                  ptr(bucket_of), ptr(out), ptr(lse), B, num_heads, T, S, D, nb, d, d, int(causal), float(p_drop), int(seed),
+                  dtype_code(q), stream_ptr())
+        ctx.save_for_backward(q, k, v, key_valid, tab, bucket_of, out, lse)
+        ctx.cfg = (num_heads, int(causal), float(p_drop), int(seed), None if table is None else table.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, key_valid, tab, bucket_of, out, lse = ctx.saved_tensors
+        H, causal, p_drop, seed, table_dtype = ctx.cfg
+        B, T, d = q.shape
+        S = k.shape[1]
+        D = d // H
+        dout = dout.contiguous()
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dtab = None if tab is None else torch.empty_like(tab)
+        nb = 0 if tab is None else tab.shape[0]
+        nbytes = lib().mmgl_attn_relbias_bwd_workspace(B, H, T, S)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+        _lib.call("mmgl_attn_relbias_bwd", dict(flops=10.0 * B * T * S * d), ptr(dout), ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse),
+                  ptr(key_valid), ptr(tab), ptr(bucket_of), ptr(dq), ptr(dk), ptr(dv), ptr(dtab), ptr(ws), nbytes, B, H, T, S, D, nb,
+                  d, d, causal, p_drop, seed, dtype_code(q), stream_ptr())
+        return dq, dk, dv, None, None if dtab is None else dtab.to(table_dtype), None, None, None, None, None
+
+
+def attn_relbias(q, k, v, key_valid, num_heads, table=None, bucket_of=None, causal=False, p_drop=0.0, training=False, seed=None):
+    """T5's attention core (transformers T5Attention.forward): softmax(q k^T + table[bucket_of[s - t + T - 1], h]) v per head, unscaled,
+    over the keys key_valid [B,S] allows (None: all; causal: also s <= t, S == T).  q [B,T,d]; k, v [B,S,d]; `table` [num_buckets, H] is
+    the relative_attention_bias weight in its own dtype (read as fp32, its gradient comes back in its dtype) or None for no bias (the
+    decoder-to-encoder cross-attention); `bucket_of` int32 [T+S-1] from t5_bucket_table.  `p_drop` drops probabilities in training
+    (counter hash of (seed, index), regenerated in backward).  A row without an allowed key gives zeros (HuggingFace: uniform)."""
+    if key_valid is None:
+        key_valid = torch.ones(k.shape[:2], dtype=torch.uint8, device=k.device)
+    _attn_args("attn_relbias", q, k, v, key_valid, num_heads)
+    B, T, _ = q.shape
+    S = k.shape[1]
+    if causal and S != T:
+        raise ValueError(f"attn_relbias: causal attention needs S == T (got {S}, {T})")
+    if table is not None:
+        if table.dim() != 2 or table.shape[1] != num_heads:
+            raise ValueError(f"attn_relbias: table should be of size (num_buckets, {num_heads}), but is {tuple(table.shape)}")
+        if bucket_of is None or bucket_of.dtype != torch.int32 or tuple(bucket_of.shape) != (T + S - 1,):
+            raise ValueError(f"attn_relbias: bucket_of must be int32 of size ({T + S - 1},) (ops.t5_bucket_table)")
+        bucket_of = bucket_of.contiguous()
+    else:
+        bucket_of = None
+    p, seed = _dropout(p_drop, training, seed)
+    return _AttnRelBias.apply(q, k, v, _key_valid(key_valid), table, bucket_of, num_heads, bool(causal), p, seed)
+
+
+_BUCKET_TABLES = {}
+
+
+def t5_bucket_table(T, S, bidirectional, num_buckets, max_distance, device):
+    """bucket_of int32 [T+S-1] for attn_relbias: entry s - t + T - 1 is the bucket of the relative position s - t, computed by
+    transformers' own T5Attention._relative_position_bucket (so the bucket boundaries are HuggingFace's by construction).  Cached per
+    argument tuple."""
+    key = (int(T), int(S), bool(bidirectional), int(num_buckets), int(max_distance), str(torch.device(device)))
+    t = _BUCKET_TABLES.get(key)
+    if t is None:
+        from transformers.models.t5.modeling_t5 import T5Attention
+        rel = torch.arange(-(int(T) - 1), int(S), dtype=torch.long)
+        t = T5Attention._relative_position_bucket(rel, bidirectional=bool(bidirectional), num_buckets=int(num_buckets),
+                                                  max_distance=int(max_distance)).to(torch.int32).to(device)
+        _BUCKET_TABLES[key] = t
+    return t
+
+
 # ------------------------------------------------------------------------------------------ causal self-attention
 # One pair of call helpers for every self-attention op.  q / k / v (and dq / dk / dv) are device pointers.  P is None: the plain entry
 # points mmgl_selfattn_fwd / _bwd, rows `ld` (`ldg` for the gradients) elements apart, 0 = packed.  P >= 0: mmgl_selfattn_prefix_fwd /
