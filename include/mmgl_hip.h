@@ -157,10 +157,15 @@ int mmgl_selfattn_tiles_rows_bwd(const void* dout, const void* q, const void* k,
  *           :246-254 (attn_weights_reshaped: the head-masked probabilities, returned BEFORE dropout), :256 (nn.functional.dropout on
  *           the probabilities); model/modelling_self_attention.py reaches the same class through the OPT decoder.
  *   q [B,T,H*D] already scaled; k, v [B,S,H*D]; key_valid [B,S] uint8; head_mask [H] fp32 or NULL
- *   out [B,T,H*D]; probs [B,H,T,S] (dtype of q) or NULL; lse [B,H,T] fp32 (+inf marks a query row without any allowed key: uniform
- *   over all S keys, as the reference's finfo.min clamp gives)
- *   p_drop in [0, 1): probability of dropping a probability; the keep mask is the counter hash of (seed, ((b H + h) T + t) S + s)
- *   every dropout of this library uses, regenerated by the backward from the same (p_drop, seed) -- nothing is stored.
+ *   out [B,T,H*D]; probs [B,H,T,S] (dtype of q) or NULL; lse [B,H,T] fp32: log-sum-exp of the allowed scores, and exactly +inf on
+ *   a query ROW without any allowed key (per row, not per sample: left padding under the causal mask).  Such a row is uniform
+ *   over all S keys, future and padded ones included -- probs holds dtype(fp32(1 / S) * head_mask[h]) there --, as the reference's
+ *   finfo.min clamp gives; the backward keys off the +inf (dS halved at the tie, zero on keys both future and padded).
+ *   A masked key's probs are exact zeros, and so are its dk, dv unless such a row reaches it.
+ *   p_drop in [0, 1): probability of dropping a probability; the keep mask is the counter hash of (seed, element index) every
+ *   dropout of this library uses, at element index ((b H + h) T + t) S + s (64-bit), kept iff hash >= uint32(min(p 2^32, 2^32 - 1)),
+ *   scaled by fp32(1 / (1 - p)); regenerated by the backward from the same (p_drop, seed) -- nothing is stored.
+ *   workspace: mmgl_attn_general_bwd_workspace(B, H, T) bytes (delta, B H T fp32); a shorter one is refused.
  * Written for exactness, not speed (fp32 VALU arithmetic, two passes over the keys): these options are inert on every BASELINE config
  * (attention_dropout = 0, no head masks); every other call stays on mmgl_xattn_* / mmgl_selfattn_*.  D <= 128, any S.
  * mmgl_attn_dropout_mask writes the keep mask as bytes [B,H,T,S] (1 = kept): a test / debug entry point (the parity tests hand it to
@@ -334,8 +339,13 @@ int mmgl_adamw_step(void* param, float* master, const void* grad, float* exp_avg
  * mmgl_encattn_fwd: bidirectional softmax(QK^T)V over PACKED sequences.  Sequence i owns rows
  *   cu_seqlens[i] .. cu_seqlens[i+1]-1 (int32 device array, nseq+1 entries) of q/k/v [ntok, ld_in] (three column slices
  *   of a fused-QKV GEMM output are fine: ld_in = 3*H*D) and of out [ntok, ld_out]; head h uses columns h*D..h*D+D-1.
- *   q must be pre-scaled by D^-1/2.  max_len = longest sequence (host knows it from the packing); q_rows = number of
- *   leading query rows per sequence to compute (pass max_len for all, 1 for the CLS row only).  No padding token is read.
+ *   q must be pre-scaled by D^-1/2.  max_len = an UPPER BOUND of the longest sequence (host knows it from the packing): it selects
+ *   the kernel (bf16, D 64 / 128: the 32x32 kernel up to 4096, the 16x16 one above) and sizes the grid, nothing else -- a larger
+ *   value gives the same bits inside one kernel; a sequence longer than max_len gets only its first max_len rows written.
+ *   q_rows > 0 = number of leading query rows per sequence to compute (pass max_len for all, 1 for the CLS row only): rows
+ *   cu_seqlens[i] + q_rows and later of a sequence are NOT written (the caller's bytes stay), nor are columns H*D .. ld_out-1.
+ *   ld_in, ld_out >= H*D, multiples of 8 elements.  No padding token is read.  A sequence of no tokens
+ *   (cu_seqlens[i] == cu_seqlens[i+1]) is allowed: both kernels return before any load, nothing is written for it.
  * mmgl_add_layernorm_fwd: s = x + res (rounded to dtype), y = LayerNorm(s); sum_out (may be NULL) receives s; mean, rstd
  *   [rows] fp32 may be NULL (inference).  Also the residual-add + LayerNorm pair of the decoder layers
  *   (modelling_cross_attention.py:334-350: `hidden = residual + h` followed by the next LayerNorm) when they are saved.
