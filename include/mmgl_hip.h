@@ -291,6 +291,9 @@ int mmgl_lora_linear_bwd(const void* dy, const void* x, const void* xa, const vo
  *   text_emb [B,Nt,n_tok*d], vis_emb [B,Ni,n_tok*d] (vis_emb may be NULL with Ni = 0: text_only :1075-1078)
  *   text_loc/img_loc, text_pos/img_pos: int64 [B,Nt] / [B,Ni]
  *   out_emb [B,(Nt+Ni)*n_tok,d] ; out_valid [B,(Nt+Ni)*n_tok] uint8.  Slots nobody writes stay zero/invalid.
+ *   Both directions copy whole 16-byte vectors and refuse, before anything is written, an n_tok*d that is no whole number of
+ *   16-byte chunks (MMGL_ERR_UNSUPPORTED), n_tok > 256 and an unknown dtype (MMGL_ERR_INVALID).  The backward writes every element of
+ *   d_text_emb / d_vis_emb: the gathered slot, or zeros for a neighbor whose location is outside [0, Nt+Ni).
  */
 int mmgl_neighbor_interleave_fwd(const void* text_emb, const void* vis_emb, const int64_t* text_loc,
                                  const int64_t* img_loc, const int64_t* text_pos, const int64_t* img_pos,
@@ -326,7 +329,8 @@ int mmgl_cross_entropy_bwd(const void* logits, const int64_t* labels, const floa
 int mmgl_position_ids(const int64_t* attention_mask, int64_t* pos, int B, int T, void* stream);
 
 /* Fused AdamW step over a flat parameter bucket (torch.optim.AdamW semantics, run_generation.py:327-330).
- * param/grad in `dtype`; exp_avg/exp_avg_sq fp32; master (fp32 copy of param) may be NULL. grad is read * grad_scale. */
+ * param/grad in `dtype`; exp_avg/exp_avg_sq fp32; master (fp32 copy of param) may be NULL. grad is read * grad_scale.
+ * The bias corrections 1 - beta^step are formed in double from the float betas and rounded once (step >= 1). */
 int mmgl_adamw_step(void* param, float* master, const void* grad, float* exp_avg, float* exp_avg_sq, size_t n,
                     float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                     float grad_scale, int dtype, void* stream);

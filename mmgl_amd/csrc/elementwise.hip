@@ -402,6 +402,7 @@ extern "C" int mmgl_neighbor_interleave_fwd(const void* text_emb, const void* vi
     MMGL_CHECK_ARG(out_emb && out_valid && (Nt == 0 || (text_emb && text_loc && text_pos)) &&
                        (Ni == 0 || (vis_emb && img_loc && img_pos)), "mmgl_neighbor_interleave_fwd: null pointer");
     MMGL_CHECK_ARG(n_tok <= 256, "mmgl_neighbor_interleave_fwd: n_tok > 256");
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_neighbor_interleave_fwd: bad dtype %d", dtype);   // before the outputs are cleared
     const size_t esz = dtype == MMGL_BF16 ? 2 : 4;
     if (((size_t)n_tok * d * esz) % 16) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_neighbor_interleave_fwd: n_tok*d must cover whole 16-byte chunks");
     hipStream_t st = (hipStream_t)stream;
@@ -425,6 +426,11 @@ extern "C" int mmgl_neighbor_interleave_bwd(const void* d_out_emb, const int64_t
     MMGL_CHECK_ARG(B > 0 && Nt >= 0 && Ni >= 0 && Nt + Ni > 0 && n_tok > 0 && d > 0, "mmgl_neighbor_interleave_bwd: bad sizes");
     MMGL_CHECK_ARG(d_out_emb && (Nt == 0 || (d_text_emb && text_loc)) && (Ni == 0 || (d_vis_emb && img_loc)),
                    "mmgl_neighbor_interleave_bwd: null pointer");
+    // the forward's size rules: the kernel copies whole 16-byte vectors, a ragged n_tok*d would leave each neighbor's last elements unwritten
+    MMGL_CHECK_ARG(n_tok <= 256, "mmgl_neighbor_interleave_bwd: n_tok > 256");
+    MMGL_CHECK_ARG(dtype == MMGL_BF16 || dtype == MMGL_F32, "mmgl_neighbor_interleave_bwd: bad dtype %d", dtype);
+    const size_t esz = dtype == MMGL_BF16 ? 2 : 4;
+    if (((size_t)n_tok * d * esz) % 16) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_neighbor_interleave_bwd: n_tok*d must cover whole 16-byte chunks");
     hipStream_t st = (hipStream_t)stream;
     const int N = Nt + Ni;
     BY_DTYPE(hipLaunchKernelGGL(interleave_bwd_kernel<bf16>, dim3(B * N), dim3(256), 0, st, (const bf16*)d_out_emb, text_loc,
@@ -478,8 +484,9 @@ extern "C" int mmgl_adamw_step(void* param, float* master, const void* grad, flo
                                float grad_scale, int dtype, void* stream) {
     MMGL_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step >= 1, "mmgl_adamw_step: bad arguments");
     if (n == 0) return MMGL_OK;
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    // in double from the float betas, rounded once: the fp32 1.f - powf(beta, step) cancels (beta2 = 0.999 at step 2: 112 ulp, 6.7e-6)
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     hipStream_t st = (hipStream_t)stream;
     const int blocks = stream_blocks(n);
     BY_DTYPE(hipLaunchKernelGGL(adamw_kernel<bf16>, dim3(blocks), dim3(256), 0, st, (bf16*)param, master, (const bf16*)grad,
