@@ -898,6 +898,25 @@ int mmgl_weight_quantize(const void* w, int ldw, void* codes, int ld_codes, void
 int mmgl_gemm_skinny_w8(const void* x, int ldx, const void* codes, int ld_codes, const void* exps, const void* bias, const void* residual,
                         void* y, int ldy, int M, int N, int K, int act, float scale, int dtype, void* stream);
 
+/* ---- cached decoding of a T5 (model/t5_hip.py: T5HipRunner.generate; csrc/decode.hip) -------------------------------------------------
+ * replaces: HuggingFace generate() behind the reference's test protocol for a T5 (language_modelling/run_generation.py:600), whose
+ *   cached decoder self-attention is T5Attention.forward with past_key_value: scores + position_bias[:, :, -1:, :].  Forward only.
+ *
+ * mmgl_attn_decode_relbias_fwd: out[b, h*D..] = softmax_s(q[b, h] . K[b, s, h] + bias[h, S - 1 - s]) V[b, :, h], one query row per
+ *   (batch, head) over the S cached keys; the query is the newest key s = S - 1, at distance 0.
+ *   q, k, v, out, ldq, ldkv, batch_stride_kv, D, dtype as mmgl_attn_decode_fwd, except that q is the RAW projection: T5 is unscaled
+ *             and no D^-0.5 appears anywhere
+ *   bias      fp32 [H, ld_bias], ld_bias >= S: bias[h, d] = relative_attention_bias[bucket(-d), h], the learned word of distance d
+ *             (ops.t5_decode_bias builds the rows once per generation from transformers' own bucket function)
+ *   There is no key mask: a T5 decoder row starts with the start token and has no padding.
+ *   The kernel is mmgl_attn_decode_fwd's (lane geometry, trip constants, 16-byte buffer loads, fixed-order merges: deterministic, no
+ *   atomics) with the bias word added to the raw score in fp32.  Refusals as mmgl_attn_decode_fwd under this name, the bias rows in
+ *   the mask's place: sizes < 1, a bad dtype, a null pointer, ldq or ldkv < H*D, ld_bias < S: MMGL_ERR_INVALID; D outside
+ *   {16,32,64,128}, strides no multiples of 16 bytes, q / k / v not 16-byte or bias not 4-byte aligned, a sample's key rows spanning
+ *   2 GiB: MMGL_ERR_UNSUPPORTED.  A refused call launches nothing and leaves `out` as it was. */
+int mmgl_attn_decode_relbias_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,
+                                 const float* bias, int ld_bias, void* out, int B, int H, int S, int D, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

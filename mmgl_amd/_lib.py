@@ -120,6 +120,7 @@ SIGNATURES = {
     "mmgl_attn_decode_gqa_q8_fwd": (I, [P, I, P, P, I, P, P, I, Z, P, P, I, Z, I, P, I, P, I, I, I, I, I, I, P]),
     "mmgl_weight_quantize": (I, [P, I, P, I, P, I, I, I, P]),
     "mmgl_gemm_skinny_w8": (I, [P, I, P, I, P, P, P, P, I, I, I, I, I, F, I, P]),
+    "mmgl_attn_decode_relbias_fwd": (I, [P, I, P, P, I, Z, P, I, P, I, I, I, I, I, P]),
 }
 
 _lib = None

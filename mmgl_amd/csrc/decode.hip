@@ -33,6 +33,9 @@
 // in wave order through LDS.  A masked key scores -FLT_MAX: with a valid key in the row it weighs exp(-FLT_MAX - max) = 0, and a row of
 // masked keys only has every weight exp(0) = 1 -- the uniform distribution of the reference's finfo.min clamp.
 //
+// mmgl_attn_decode_relbias_fwd (attn_decode_relbias_kernel).  The same kernel for the T5 decoder's cached self-attention: raw scores, no
+// mask, plus a learned fp32 word per (head, distance to the query) read from bias rows the caller gathered once.
+//
 // mmgl_attn_decode_gqa_fwd (attn_decode_gqa_kernel).  The same kernel over a cache of Hkv <= H key/value heads: one workgroup per (sample,
 // key/value head, block of at most 8 of the G = H / Hkv query heads that read it).  The decode step is a memory-bound read of the cache,
 // so each 16-byte K / V load is issued once and scored against every query head of the block from registers; G > 8 takes further blocks.
@@ -467,6 +470,113 @@ int launch_attn_decode(const AttnPrefix& a, hipStream_t st) {
     hipLaunchKernelGGL((attn_decode_kernel<T, D>), dim3(a.B * a.H), dim3(AD_WAVES * WAVE), 0, st, (const T*)a.q, a.ldq, (const T*)a.k,
                        (const T*)a.v, a.ldkv, a.bs_kv, a.valid, a.ld_valid, (T*)a.out, a.H, a.S);
     MMGL_CHECK_LAUNCH("mmgl_attn_decode_fwd");
+    return MMGL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ single-query attention, T5 bias
+// attn_decode_kernel for the T5 decoder's self-attention: the same lanes, trips, loads and merges, with no key mask (a decoder row
+// has no padding) and no scale, and bias[h][S - 1 - s] -- a learned fp32 word per (head, distance to the query, which is the newest
+// key s = S - 1) -- added to the raw score of key s.  The LPK lanes of a key read the same bias word; past S the index is clamped to
+// distance 0 and the word is not used.
+template <typename T, int D>
+__global__ __launch_bounds__(AD_WAVES * WAVE) void attn_decode_relbias_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k,
+                                                                              const T* __restrict__ v, int ldkv, size_t bs_kv,
+                                                                              const float* __restrict__ bias, int ld_bias,
+                                                                              T* __restrict__ out, int H, int S) {
+    typedef typename Vec16<T>::type V;
+    constexpr int VEC = 16 / sizeof(T);
+    constexpr int LPK = D / VEC;                    // lanes per key
+    constexpr int KPI = WAVE / LPK;                 // keys per wave and load instruction
+    constexpr float NEG = -FLT_MAX;
+    __shared__ float sm_m[AD_WAVES], sm_l[AD_WAVES], sm_o[AD_WAVES][D];
+
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane % LPK, kk = lane / LPK;
+
+    float qf[VEC];
+    {
+        const V qv = *(const V*)(q + (size_t)b * ldq + h * D + c * VEC);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) qf[e] = Elem<T>::to_f(qv[e]);
+    }
+    // branch-free loads: keys past S fall outside the descriptors
+    const uint32_t slab = (uint32_t)(((size_t)(S - 1) * ldkv + D) * sizeof(T)), row_bytes = (uint32_t)(ldkv * sizeof(T));
+    const __amdgpu_buffer_rsrc_t rk = make_rsrc(k + b * bs_kv + h * D, slab);
+    const __amdgpu_buffer_rsrc_t rv = make_rsrc(v + b * bs_kv + h * D, slab);
+    const float* bh = bias + (size_t)h * ld_bias;
+
+    float m = NEG, l = 0.f, acc[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
+
+    for (int base = w * KPI; base < S; base += AD_WAVES * KPI * AD_UNROLL) {          // wave-uniform trip count
+        V kr[AD_UNROLL], vr[AD_UNROLL];
+        float bs[AD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            const int s = base + u * AD_WAVES * KPI + kk;
+            const uint32_t off = s < S ? (uint32_t)s * row_bytes + (uint32_t)(c * 16) : OOB;
+            kr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+            vr[u] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rv, off, 0, 0));
+            bs[u] = bh[S - 1 - min(s, S - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < AD_UNROLL; ++u) {
+            const int s = base + u * AD_WAVES * KPI + kk;
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) dot += qf[e] * Elem<T>::to_f(kr[u][e]);
+#pragma unroll
+            for (int o = 1; o < LPK; o <<= 1) dot += __shfl_xor(dot, o);
+            if (s < S) {
+                const float sc = dot + bs[u];
+                const float mn = fmaxf(m, sc);
+                const float corr = __expf(m - mn), p = __expf(sc - mn);
+                l = l * corr + p;
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) acc[e] = acc[e] * corr + p * Elem<T>::to_f(vr[u][e]);
+                m = mn;
+            }
+        }
+    }
+    // merge the lane groups of the wave (fixed butterfly), then the waves in order
+#pragma unroll
+    for (int o = LPK; o < WAVE; o <<= 1) {
+        const float m2 = __shfl_xor(m, o), l2 = __shfl_xor(l, o);
+        const float mn = fmaxf(m, m2);
+        const float c1 = __expf(m - mn), c2 = __expf(m2 - mn);
+        l = l * c1 + l2 * c2;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] = acc[e] * c1 + __shfl_xor(acc[e], o) * c2;
+        m = mn;
+    }
+    if (lane < LPK) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) sm_o[w][c * VEC + e] = acc[e];
+        if (lane == 0) { sm_m[w] = m; sm_l[w] = l; }
+    }
+    __syncthreads();
+    if (tid < D) {
+        float mm = sm_m[0];
+#pragma unroll
+        for (int i = 1; i < AD_WAVES; ++i) mm = fmaxf(mm, sm_m[i]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int i = 0; i < AD_WAVES; ++i) {
+            const float ci = __expf(sm_m[i] - mm);
+            ll += sm_l[i] * ci;
+            o += sm_o[i][tid] * ci;
+        }
+        out[((size_t)b * H + h) * D + tid] = Elem<T>::from_f(o / ll);
+    }
+}
+
+template <typename T, int D>
+int launch_attn_decode_relbias(const AttnPrefix& a, const float* bias, int ld_bias, hipStream_t st) {
+    hipLaunchKernelGGL((attn_decode_relbias_kernel<T, D>), dim3(a.B * a.H), dim3(AD_WAVES * WAVE), 0, st, (const T*)a.q, a.ldq, (const T*)a.k,
+                       (const T*)a.v, a.ldkv, a.bs_kv, bias, ld_bias, (T*)a.out, a.H, a.S);
+    MMGL_CHECK_LAUNCH("mmgl_attn_decode_relbias_fwd");
     return MMGL_OK;
 }
 
@@ -2082,6 +2192,19 @@ extern "C" int mmgl_attn_decode_fwd(const void* q, int ldq, const void* k, const
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(launch_attn_decode, bf16, D, a, st);
     RETURN_BY_HEAD_DIM(launch_attn_decode, float, D, a, st);
+}
+
+extern "C" int mmgl_attn_decode_relbias_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,
+                                            const float* bias, int ld_bias, void* out, int B, int H, int S, int D, int dtype, void* stream) {
+    MMGL_CHECK_ARG(B >= 1 && H >= 1 && S >= 1, "mmgl_attn_decode_relbias_fwd: bad sizes B=%d H=%d S=%d", B, H, S);
+    // the bias rows stand where the other entry points have their mask: one word per key, non-null, a pitch of at least S
+    const AttnPrefix a{q, k, v, (const uint8_t*)bias, out, ldq, ldkv, ld_bias, B, H, H, S, D, dtype, batch_stride_kv};
+    const int bad = check_attn_prefix(a, __func__);
+    if (bad) return bad;
+    if ((uintptr_t)bias & 3) MMGL_FAIL(MMGL_ERR_UNSUPPORTED, "mmgl_attn_decode_relbias_fwd: bias must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MMGL_BF16) RETURN_BY_HEAD_DIM(launch_attn_decode_relbias, bf16, D, a, bias, ld_bias, st);
+    RETURN_BY_HEAD_DIM(launch_attn_decode_relbias, float, D, a, bias, ld_bias, st);
 }
 
 extern "C" int mmgl_attn_decode_gqa_fwd(const void* q, int ldq, const void* k, const void* v, int ldkv, size_t batch_stride_kv,

@@ -121,6 +121,8 @@ class Arguments:
     weight_dtype: Optional[str] = _f(None, "weights of the frozen layers in the decode steps of the test protocol's generate(): fp8 "
                                            "multiplies e4m3fn codes with one power-of-two scale per weight row (plain projections; the "
                                            "prefill, the gated layers and lm_head keep the model's dtype); default: the model's dtype")
+    generate_seq2seq: bool = _f(False, "test protocol over a T5 the HIP runner covers: generate the captions (cached decoding, 32 new "
+                                       "tokens from the encoder input) instead of the teacher-forced argmax; off = unchanged")
     peft_type: str = _f("none", "peft type: none, prefix, prompt, lora, flamingo")
     lora_r: int = _f(64, "lora row rank")
     lora_alpha: float = _f(1, "lora scaling factor")
@@ -598,7 +600,8 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
     gold summary included) to a generate() its wrappers do not have and has no neighbors to pass.  The loss meter is still the
     teacher-forced one.  Like the forward pass, one generate() call serves the whole fused group of validation batches: its cache
     holds fused_pass_tokens / max_input_length samples (9.6 GB of bf16 K|V at config 3's default).  Every other model keeps the argmax
-    path under "test".
+    path under "test" -- except, with args.generate_seq2seq, a T5 whose can_generate_seq2seq() is true: its captions are generate()'s
+    32 new tokens from the whole encoder input (the reference's :600; labels are separate), without the start token.
     Several validation batches share one forward pass (_eval_groups); meters, gathers and caption order are per batch, as in the
     reference.  `evaluate_loop.last` also carries `samples_per_sec` (this rank's samples / wall time of the loop)."""
     from . import utils
@@ -640,7 +643,12 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                 chunk = [outputs.loss.item()]
             for v in chunk:
                 losses.update(v, mb)
-            if prefix == "test" and hasattr(model, "generate") and getattr(model, "can_generate", lambda: False)():
+            can = prefix == "test" and hasattr(model, "generate") and getattr(model, "can_generate", lambda: False)()
+            # a T5 (opt-in, generate_seq2seq): the encoder reads the whole input -- its labels are separate -- and the decoder row
+            # comes back behind its start token
+            seq2seq = (not can and prefix == "test" and getattr(args, "generate_seq2seq", False) and hasattr(model, "generate")
+                       and getattr(model, "can_generate_seq2seq", lambda: False)())
+            if can or seq2seq:
                 L_in = args.max_input_length
                 named = inspect.signature(getattr(type(model), "generate", model.generate)).parameters     # the class's own signature
                 fields = {key: batch[key] for key in _GENERATE_FIELDS if key in batch and key in named}    # generate()'s named arguments only
@@ -668,10 +676,15 @@ def evaluate_loop(val_loader, model, tokenizer, epoch, args, run=None, prefix="v
                     fields["kv_cache_dtype"] = args.kv_cache_dtype                                   # generate() says what it combines with
                 if getattr(args, "weight_dtype", None) is not None and "weight_dtype" in named:
                     fields["weight_dtype"] = args.weight_dtype
-                generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),
-                                               attention_mask=batch["attention_mask"][:, :L_in].contiguous(), **fields,
-                                               host_meta=extra.get("host_meta"), max_new_tokens=32,
-                                               eos_token_id=getattr(tokenizer, "eos_token_id", None), pad_token_id=pad_id)[:, L_in:]
+                if seq2seq:
+                    generated_ids = model.generate(input_ids=batch["input_ids"], attention_mask=batch["attention_mask"], **fields,
+                                                   max_new_tokens=32, eos_token_id=getattr(tokenizer, "eos_token_id", None),
+                                                   pad_token_id=pad_id)[:, 1:]
+                else:
+                    generated_ids = model.generate(input_ids=batch["input_ids"][:, :L_in].contiguous(),
+                                                   attention_mask=batch["attention_mask"][:, :L_in].contiguous(), **fields,
+                                                   host_meta=extra.get("host_meta"), max_new_tokens=32,
+                                                   eos_token_id=getattr(tokenizer, "eos_token_id", None), pad_token_id=pad_id)[:, L_in:]
             else:
                 generated_ids = torch.argmax(logits, dim=-1)            # the reference's wrappers have no generate() (:600)
             labels = labels.contiguous()

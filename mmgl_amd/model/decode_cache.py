@@ -22,6 +22,7 @@ class DecodeCache:
                   once per generation
       beam, lookup, kv_dtype    what selects the mode of a step, below
       pairs       None, or the pair count B of a guided generation: batch_size is then 2B (the mode `guided`, below)
+      rel_bias    None, or the T5 decoder's fp32 bias rows [H, capacity] (ops.t5_decode_bias; the mode `relbias`, below)
       w8          None, or a StepCodes (generate(weight_dtype="fp8")): the frozen layers' decode_step then multiplies e4m3fn codes of its
                   weights (ops.decode_linear_w8 on what w8.get returns) instead of the weights.  It is only another GEMM: it selects
                   no attention kernel and is no mode below
@@ -48,6 +49,9 @@ class DecodeCache:
                   -- rows [0, B) are the prompts with neighbors, rows [B, 2B) the same prompts prefilled without the gated layers --
                   and every frozen layer runs the plain step on all of them; cross / cross_valid keep B rows and the gated layers run
                   on the leading B rows only (MPTDecoder._decode_rows).  No new branch below: pairs selects no kernel.  OPT fork only.
+      relbias     rel_bias set (T5HipRunner.generate): the plain mode of a T5 decoder -- k|v go into kv[l][:, col] in place, and
+                  ops.attn_decode_relbias reads columns 0..col with the raw q, rel_bias and no mask (a decoder row has no padding).
+                  cross[l] / cross_valid are the encoder's projected keys / values and its mask.  No beams, verify step or FP8 cache.
     The gated layers attend over cross[k] in every mode: ops.attn_decode, or with a BeamState / LookupState ops.attn_decode_beam without a
     tail -- the W rows of a sample read its neighbor tokens once."""
 
@@ -72,6 +76,7 @@ class DecodeCache:
         self.beam = None
         self.lookup = None
         self.pairs = None
+        self.rel_bias = None
         self.w8 = None
 
     def kv_out(self, idx):
@@ -127,6 +132,8 @@ class DecodeCache:
         mode = self._mode()
         kv, mask, col = self.kv[idx], self.mask, self.col
         n = kv.shape[-1] // 2
+        if mode == "plain" and self.rel_bias is not None:
+            return ops.attn_decode_relbias(q, kv[:, :col + 1, :n], kv[:, :col + 1, n:], self.rel_bias, num_heads)
         if mode == "plain":
             return ops.attn_decode(q, kv[:, :col + 1, :n], kv[:, :col + 1, n:], mask[:, :col + 1], num_heads, num_kv_heads=num_kv_heads)
         if mode == "fp8":

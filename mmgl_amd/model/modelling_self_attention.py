@@ -323,9 +323,7 @@ class SelfAttentionModel(nn.Module):
         if self.t5_native and lm_input.is_cuda and labels is not None and not kw and "t5" in self.args.model_name_or_path:
             # T5 on the GPU: the native forward over the HuggingFace module (t5_hip.py: relative-position-bias attention and every
             # GEMM on the HIP kernels); a variant it does not cover, CPU tensors and t5_native = False stay the stock call below
-            runner = self.__dict__.get("_t5_runner")
-            if runner is None:               # decided once: the architecture is fixed at construction (False: not covered)
-                runner = self.__dict__["_t5_runner"] = T5HipRunner(self.lm) if T5HipRunner.supports(self.lm) else False
+            runner = self._t5()
             if runner:
                 ids, embeds = (None, lm_input) if lm_input.dim() == 3 else (lm_input, None)
                 return runner(input_ids=ids, inputs_embeds=embeds, attention_mask=attention_mask, labels=labels)
@@ -364,6 +362,18 @@ class SelfAttentionModel(nn.Module):
         from .modelling_cross_attention import MPTForCausalLM
         return isinstance(self.lm, MPTForCausalLM) and self.args.peft_type in ("none", "lora", "prompt")
 
+    def can_generate_seq2seq(self):
+        """Whether generate() runs the cached T5 decoding of t5_hip.T5HipRunner.generate: the LM is a T5 variant its supports()
+        covers (can_generate() stays False over a T5: the trainer's default test protocol is unchanged).  Decided from the module
+        alone, without touching the device."""
+        return self.prefix_encoder is None and bool(T5HipRunner.supports(self.lm))
+
+    def _t5(self):
+        runner = self.__dict__.get("_t5_runner")
+        if runner is None:                   # decided once: the architecture is fixed at construction (False: not covered)
+            runner = self.__dict__["_t5_runner"] = T5HipRunner(self.lm) if T5HipRunner.supports(self.lm) else False
+        return runner
+
     @torch.no_grad()
     def generate(self, input_ids, attention_mask, images=None, image_positions=None, neighbor_input_ids=None,
                  neighbor_attention_mask=None, neighbor_pos_ids=None, text_locations=None, neighbor_images=None,
@@ -383,11 +393,28 @@ class SelfAttentionModel(nn.Module):
         num_return_sequences > 1 is refused for the same reason as beams.  So are its logits processors repetition_penalty,
         no_repeat_ngram_size, min_new_tokens and suppress_tokens; in either mode their history is the returned row so far, input_ids
         without the masked columns and then the new tokens (embedding mode hands input_ids / attention_mask over as history_ids /
-        history_mask: virtual, image and neighbor tokens are no part of it)."""
+        history_mask: virtual, image and neighbor tokens are no part of it).
+        Over a T5 (can_generate_seq2seq()) the same call runs T5HipRunner.generate on the encoder input _lm_inputs builds and returns
+        [B, 1 + max_new_tokens]: decoder_start_token_id, then the new tokens (transformers' shape for an encoder-decoder; input_ids
+        are the encoder's and are not repeated).  The processors' history is then that decoder row."""
         if int(num_beams) != 1:
             raise ValueError(f"SelfAttentionModel.generate(): num_beams = {num_beams} is not implemented (beam search runs on "
                              "CrossAttentionModel / MPTForCausalLM with input_ids prompts); this path is greedy")
         check_sampling("SelfAttentionModel.generate()", do_sample, temperature, top_k, top_p, seed, sample_u, 1, num_return_sequences)
+        if self.can_generate_seq2seq():
+            # a T5: the encoder input is built as forward builds it (neighbor tokens and their mask included), the decoder row starts
+            # at decoder_start_token_id.  Returns [B, 1 + max_new_tokens] -- the start token, then the new tokens -- as transformers does
+            if not input_ids.is_cuda:
+                raise RuntimeError(f"generate() runs on the GPU only (input_ids is on {input_ids.device}); there is no CPU path")
+            lm_input, lm_mask = self._lm_inputs(input_ids, attention_mask, images, image_positions, neighbor_input_ids,
+                                                neighbor_attention_mask, neighbor_pos_ids, text_locations, neighbor_images,
+                                                neighbor_images_pos_ids, image_locations, lpe, graph)
+            ids, embeds = (None, lm_input) if lm_input.dim() == 3 else (lm_input, None)
+            return self._t5().generate(input_ids=ids, inputs_embeds=embeds, attention_mask=lm_mask, max_new_tokens=max_new_tokens,
+                                       eos_token_id=eos_token_id, pad_token_id=pad_token_id, return_step_logits=return_step_logits,
+                                       do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, sample_u=sample_u,
+                                       repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                       min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens)
         if not self.can_generate():
             raise ValueError(f"generate() is implemented for the decoder-only OPT fork with peft_type none / lora / prompt, not for "
                              f"{type(self.lm).__name__} with peft_type {self.args.peft_type!r}")

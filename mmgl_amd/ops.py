@@ -2012,6 +2012,48 @@ def attn_decode(q, k, v, key_valid, num_heads, out=None, num_kv_heads=None):
     return out
 
 
+def attn_decode_relbias(q, k, v, bias, num_heads, out=None):
+    """The T5 decoder's cached self-attention for one new token: softmax_s(q . k_s + bias[h, S - 1 - s]) v per (sample, head), unscaled
+    and unmasked.  q [B, d] is the RAW query projection; k, v [B, S, d] views with unit column stride and common strides (column slabs
+    of the cache rows [B, capacity, 2d]) whose last row s = S - 1 is the query's own token; bias fp32 [H, >= S] with unit column
+    stride (t5_decode_bias: column = distance to the query).  Returns [B, d] (`out`, a dense [B, d] tensor of q's dtype, when given: a
+    refused call leaves it as it was).  Forward only; GPU only."""
+    require_cuda(q, k, v, bias)
+    _no_grad_inputs("attn_decode_relbias", q, k, v, bias)
+    if (q.dim() != 2 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[1] != k.shape[2] or k.stride() != v.stride()
+            or k.stride(2) != 1 or q.stride(1) != 1 or k.dtype != q.dtype or v.dtype != q.dtype):
+        raise ValueError(f"attn_decode_relbias: incompatible q{tuple(q.shape)} k{tuple(k.shape)}/{k.stride()} v{tuple(v.shape)}/{v.stride()}")
+    B, d = q.shape
+    S = k.shape[1]
+    if d % num_heads:
+        raise ValueError(f"embed_dim must be divisible by num_heads (got `embed_dim`: {d} and `num_heads`: {num_heads}).")
+    if S == 0:
+        raise ValueError("attn_decode_relbias: no keys")
+    if (bias.dim() != 2 or bias.dtype != torch.float32 or bias.shape[0] != num_heads or bias.shape[1] < S
+            or (bias.shape[1] > 1 and bias.stride(1) != 1) or bias.device != q.device):
+        raise ValueError(f"attn_decode_relbias: bias{tuple(bias.shape)}/{bias.stride()} {bias.dtype} must be fp32 [{num_heads}, >= {S}] with unit "
+                         f"column stride on {q.device}")
+    if out is None:
+        out = torch.empty(B, d, dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (B, d) or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError(f"attn_decode_relbias: out{tuple(out.shape)} {out.dtype} must be a dense [{B}, {d}] {q.dtype} tensor on {q.device}")
+    _lib.call("mmgl_attn_decode_relbias_fwd", dict(bytes=2.0 * B * S * d * q.element_size()), ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(1),
+              k.stride(0), ptr(bias), bias.stride(0), ptr(out), B, num_heads, S, d // num_heads, dtype_code(q), stream_ptr())
+    return out
+
+
+def t5_decode_bias(table, capacity, num_buckets, max_distance):
+    """The bias rows of attn_decode_relbias for a cache of `capacity` columns: fp32 [H, capacity], entry [h, d] =
+    table[bucket(-d), h] -- the word a T5 decoder adds to the score of the key d positions behind the query.  table [num_buckets, H] is
+    the decoder's relative_attention_bias weight; the buckets of the relative positions 0, -1, ..., -(capacity - 1) are t5_bucket_table's
+    (transformers' own _relative_position_bucket, bidirectional=False).  One small gather, once per generation."""
+    if table.dim() != 2 or table.shape[0] != int(num_buckets) or int(capacity) < 1:
+        raise ValueError(f"t5_decode_bias: table{tuple(table.shape)} for {num_buckets} buckets, capacity {capacity}")
+    bucket_of = t5_bucket_table(int(capacity), 1, False, num_buckets, max_distance, table.device)       # entry i: position i - (capacity - 1)
+    rows = torch.empty(table.shape[1], int(capacity), dtype=torch.float32, device=table.device)      # strides (capacity, 1), also at capacity 1
+    return rows.copy_(table.detach().float()[bucket_of.flip(0).long()].t())
+
+
 def rope_kv_append(qkv, cos_sin_row, kv_col, num_heads, num_kv_heads):
     """The new token's row of the fused q | k | v projection, qkv [B, (H + 2*Hkv)*D] (unit column stride), at one position:
     rotates the H query heads in place and writes the rotated Hkv key heads and the unrotated Hkv value heads to kv_col
