@@ -1,6 +1,6 @@
 """The cases of tests/test_decode_attn_bounds_gpu.py, built on the CPU so that tests/test_decode_attn_ref_cpu.py can hold the same
 cases' references, deliberately wrong references and fp32 emulation without a GPU.  One class per entry-point family of csrc/decode.hip;
-each holds the storage-rounded operands in the kernel's own layout, expands them for helpers.DecodeAttnRef (`ref(wrong=None, dev)`) and
+each holds the storage-rounded operands in the kernel's own layout, expands them for decode_ref.DecodeAttnRef (`ref(wrong=None, dev)`) and
 calls the kernel through its ops wrapper (`run(dev)`).
 
 A wrong reference is named; `wrongs()` lists the names a case can tell apart from the right one, `blind()` those it cannot BY
@@ -15,11 +15,9 @@ CONSTRUCTION, with the reason -- never by a threshold:
 import torch
 
 import kvq_ref
-from helpers import (DecodeAttnRef, decode_bias_relbias, decode_geometry, decode_rows_beam, decode_rows_block, decode_rows_cache,
-                     decode_rows_q8)
+from bounds import BF16, F32, NAN
+from decode_ref import DecodeAttnRef, decode_bias_relbias, decode_geometry, decode_rows_beam, decode_rows_block, decode_rows_cache, decode_rows_q8
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAN = float("nan")
 HUGE = 1e30                      # tests/test_xattn_bounds_gpu.py group D: what a masked key may hold
 CAP = 0.25                       # the share of the affected elements a wrong reference must push outside the bound
 NAN_CODE, FILL_EXP = 0x7F, 77    # an e4m3fn NaN and an exponent no case produces: the unwritten part of a quantised cache

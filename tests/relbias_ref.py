@@ -2,7 +2,8 @@
 import numpy as np
 import torch
 
-from helpers import SelfAttnRef, _keep_scale, hash_keep
+from attn_ref import SelfAttnRef
+from bounds import U, _keep_scale, check_bounds, first_indices, hash_keep, outside
 
 
 class RelBiasRef:
@@ -15,7 +16,7 @@ class RelBiasRef:
         ds = p (dp - delta)          dq = ds K          dk = ds^T Q          dtable[n, h] = sum of ds over the allowed pairs of bucket n
     A row without an allowed key has p = 0 everywhere, lse = 0 and reaches no gradient (the kernels' documented deviation).
 
-    Bounds, in SelfAttnRef's form and with its constants (helpers.py), every element checked:
+    Bounds, in SelfAttnRef's form and with its constants (attn_ref.py), every element checked:
         |got - want| <= u |want| + (c + n 2^-24 S_i) mag           |lse_got - lse_want| <= n 2^-24 S_i + 2^-20
     S_i = max over the allowed keys of sum_d |q||k| + |bias|; n = 9 + D / kb, one more than SelfAttnRef's for the bias add (the bias
     is the C-input of the first MFMA of the score: one more fp32 rounding in its accumulation chain); mag as there, with
@@ -121,24 +122,13 @@ class RelBiasRef:
         if name == "dtable":
             return (2.0 ** -23 * self.want[name].abs() + (SelfAttnRef.C[dtype] + self.chain() * 2.0 ** -24) * self.mag[name]
                     + n * self.smag[name])
-        return SelfAttnRef.U[dtype] * self.want[name].abs() + SelfAttnRef.C[dtype] * self.mag[name] + n * self.smag[name]
+        return U[dtype] * self.want[name].abs() + SelfAttnRef.C[dtype] * self.mag[name] + n * self.smag[name]
 
     def outside(self, other, name, dtype):
         """The elements at which `other`, a deliberately wrong reference of the same call, leaves this one's bound."""
-        return (other.want[name] - self.want[name]).abs() > self.bound(name, dtype)
+        return outside(self.want[name], other.want[name], self.bound(name, dtype))
 
     def check(self, got, what, dtype):
         """Asserts the bound on every element of got = dict(name -> tensor); prints the largest err / bound of each, returns them."""
-        ratios, failed = {}, []
-        for name, x in got.items():
-            want = self.want[name]
-            assert torch.isfinite(x.float()).all(), f"{what} {name}: non-finite result"
-            err, bound = (x.detach().double().cpu().reshape(want.shape) - want.cpu()).abs(), self.bound(name, dtype).cpu()
-            ratios[name] = (err / bound.clamp_min(1e-300)).max().item()
-            print(f"[bound relbias] {what} {name}: max err/bound {ratios[name]:.3f}")
-            bad = (err > bound).nonzero()
-            if bad.numel():
-                failed.append(f"{what} {name}: {bad.shape[0]} of {err.numel()} elements outside the bound (max err/bound "
-                              f"{ratios[name]:.2f}); first {bad[:6].tolist()}")
-        assert not failed, "\n".join(failed)
-        return ratios
+        return check_bounds(((name, x.cpu(), self.want[name].cpu(), self.bound(name, dtype).cpu(), first_indices, None) for name, x in got.items()),
+                            what, "relbias")

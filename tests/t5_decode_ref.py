@@ -2,7 +2,7 @@
 variants the tests must be able to tell from it, and the operands of the kernel test's cases (CPU tensors: tests/test_generate_t5_cpu.py
 checks the main case without a GPU, tests/test_decode_relbias_gpu.py runs it).
 
-helpers.attn_decode_ref plus the bias, with no mask: the score of key s of (sample b, head h) is q[b, h] . k[b, s, h] + bias[h, S - 1 - s]
+decode_ref.attn_decode_ref plus the bias, with no mask: the score of key s of (sample b, head h) is q[b, h] . k[b, s, h] + bias[h, S - 1 - s]
 -- the query is the newest key s = S - 1, at distance 0 -- with no D^-0.5 anywhere."""
 import torch
 

@@ -1,7 +1,7 @@
 """-m gpu: the general attention core (csrc/attn_general.hip: attention dropout, layer_head_mask, output_attentions) against
-helpers.GeneralAttnRef -- an fp64 reference of the storage-rounded operands -- element by element: out, lse, dq, dk, dv and probs each
+attn_ref.GeneralAttnRef -- an fp64 reference of the storage-rounded operands -- element by element: out, lse, dq, dk, dv and probs each
 within the bound of the class docstring, lse exactly +inf and probs exactly fp32(1 / S) hm on a row without an allowed key, exact
-zeros where the mask kills everything.  The keep mask of the reference is helpers.hash_keep, never mmgl_attn_dropout_mask (which is
+zeros where the mask kills everything.  The keep mask of the reference is bounds.hash_keep, never mmgl_attn_dropout_mask (which is
 held bit for bit against hash_keep on its own).  tests/test_attn_general_ref_cpu.py shows on the CPU that this comparison fails for a
 wrong keep index, scale, head mask, tie factor, causal edge, dropped key or lost row chunk.  mmgl_attn_general_fwd / _bwd are called
 directly, so lse and the workspace are seen; every result buffer holds NaN before the call.
@@ -24,12 +24,11 @@ import ctypes
 import pytest
 import torch
 
-from helpers import ByteSlab, GeneralAttnRef, Slab, XAttnRef, hash_keep
+from attn_ref import GeneralAttnRef, XAttnRef
+from bounds import BF16, F32, NAME, ByteSlab, Slab, code, hash_keep, nan
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0                              # tests/test_attn_general_ref_cpu.py: every wrong reference leaves the bound on >= 40 % at this seed
 DSEED = 0x9E3779B97F4A7C15            # the dropout seed: top bit set
 HM = (1.0, 0.0, 0.5, 2.0)
@@ -77,15 +76,10 @@ def _inputs(c):
     return q, k, v, dout, am.cuda()
 
 
-def _code(dtype):
-    from mmgl_amd import _lib
-    return _lib.dtype_code(torch.empty(0, dtype=dtype))
-
-
 def _fwd(c, q, k, v, am, hm, out, probs, lse, over=None):
     from mmgl_amd import _lib
     a = dict(q=q, k=k, v=v, am=am, hm=hm, out=out, probs=probs, lse=lse, B=c.B, H=c.H, T=c.T, S=c.S, D=c.D, causal=int(c.causal), p=c.p,
-             dtype=_code(c.dtype))
+             dtype=code(c.dtype))
     a.update(over or {})
     p = lambda x: x if (x is None or isinstance(x, ctypes.c_void_p)) else _lib.ptr(x)
     _lib.call("mmgl_attn_general_fwd", None, p(a["q"]), p(a["k"]), p(a["v"]), p(a["am"]), p(a["hm"]), p(a["out"]), p(a["probs"]), p(a["lse"]),
@@ -95,7 +89,7 @@ def _fwd(c, q, k, v, am, hm, out, probs, lse, over=None):
 def _bwd(c, dout, q, k, v, lse, am, hm, dq, dk, dv, ws, nws, over=None):
     from mmgl_amd import _lib
     a = dict(dout=dout, q=q, k=k, v=v, lse=lse, am=am, hm=hm, dq=dq, dk=dk, dv=dv, ws=ws, nws=nws, B=c.B, H=c.H, T=c.T, S=c.S, D=c.D,
-             causal=int(c.causal), p=c.p, dtype=_code(c.dtype))
+             causal=int(c.causal), p=c.p, dtype=code(c.dtype))
     a.update(over or {})
     p = lambda x: x if (x is None or isinstance(x, ctypes.c_void_p)) else _lib.ptr(x)
     _lib.call("mmgl_attn_general_bwd", None, p(a["dout"]), p(a["q"]), p(a["k"]), p(a["v"]), p(a["lse"]), p(a["am"]), p(a["hm"]), p(a["dq"]),
@@ -103,14 +97,10 @@ def _bwd(c, dout, q, k, v, lse, am, hm, dq, dk, dv, ws, nws, over=None):
               a["dtype"], _lib.stream_ptr())
 
 
-def _nan(*shape, dtype):
-    return torch.full(shape, float("nan"), dtype=dtype, device="cuda")
-
-
 def _buffers(c):
-    return dict(out=_nan(c.B, c.T, c.H * c.D, dtype=c.dtype), lse=_nan(c.B, c.H, c.T, dtype=F32),
-                probs=_nan(c.B, c.H, c.T, c.S, dtype=c.dtype) if c.probs else None, dq=_nan(c.B, c.T, c.H * c.D, dtype=c.dtype),
-                dk=_nan(c.B, c.S, c.H * c.D, dtype=c.dtype), dv=_nan(c.B, c.S, c.H * c.D, dtype=c.dtype))
+    return dict(out=nan(c.B, c.T, c.H * c.D, dtype=c.dtype), lse=nan(c.B, c.H, c.T, dtype=F32),
+                probs=nan(c.B, c.H, c.T, c.S, dtype=c.dtype) if c.probs else None, dq=nan(c.B, c.T, c.H * c.D, dtype=c.dtype),
+                dk=nan(c.B, c.S, c.H * c.D, dtype=c.dtype), dv=nan(c.B, c.S, c.H * c.D, dtype=c.dtype))
 
 
 def _call(c, q, k, v, dout, am):
@@ -259,13 +249,13 @@ def test_D_isolation_and_determinism(case):
         _fwd(c, qs.v, ks.v, vs.v, ms.v, hs.v, outs["out"].v, outs["probs"].v, outs["lse"].v)
         _bwd(c, gs.v, qs.v, ks.v, vs.v, outs["lse"].v, ms.v, hs.v, outs["dq"].v, outs["dk"].v, outs["dv"].v, ws.ptr(), nws)
         torch.cuda.synchronize()
-        assert ws.guards_ok(), "bytes next to the workspace were written"
+        assert ws.untouched(), "bytes next to the workspace were written"
         for n, s in outs.items():
-            assert s.guards_ok(), f"bytes next to {n} were written"
+            assert s.untouched(), f"bytes next to {n} were written"
             assert torch.isfinite(s.v.float()).all() or n == "lse", f"{n}: a value from outside the operands reached the result"
             assert torch.equal(s.v, plain[n]), f"{n}: differs from the run on plain tensors"
         for n, s in zip(("q", "k", "v", "dout", "key_valid", "head_mask"), ins):
-            assert s.guards_ok(), f"bytes next to {n} were written"
+            assert s.untouched(), f"bytes next to {n} were written"
     again = _call(c, q, k, v, dout, am)
     for n in plain:
         assert torch.equal(again[n], plain[n]), f"{n}: two launches differ"

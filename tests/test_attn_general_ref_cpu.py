@@ -1,4 +1,4 @@
-"""helpers.GeneralAttnRef and helpers.EncAttnRef, the fp64 references behind tests/test_attn_general_bounds_gpu.py and
+"""attn_ref.GeneralAttnRef and attn_ref.EncAttnRef, the fp64 references behind tests/test_attn_general_bounds_gpu.py and
 tests/test_encattn_bounds_gpu.py, on the CPU (no GPU needed), with the GPU files' inputs and seed:
 
 (a) GeneralAttnRef IS the oracle's attention: oracle.lm_ref.attention_core under autograd in fp64 with expand_mask /
@@ -21,9 +21,10 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import EncAttnRef, GeneralAttnRef, XAttnRef, drop_threshold, hash32_int, hash_keep
+from attn_ref import EncAttnRef, GeneralAttnRef, XAttnRef
+from bounds import BF16, F32, drop_threshold, hash32_int, hash_keep
 
-BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
+F64 = torch.float64
 CAP = 0.40
 SEED = 0
 P_DROP, DSEED = 0.3, 0x9E3779B97F4A7C15          # the GPU files' dropout seed: its top bit is set

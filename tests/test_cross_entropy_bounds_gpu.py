@@ -1,4 +1,4 @@
-"""-m gpu: mmgl_cross_entropy_fwd / bwd (csrc/elementwise.hip) against helpers.CrossEntropyRef -- an fp64 reference of the
+"""-m gpu: mmgl_cross_entropy_fwd / bwd (csrc/elementwise.hip) against row_ref.CrossEntropyRef -- an fp64 reference of the
 storage-rounded logits -- row_lse, row_loss, loss_sum and count, and every element of dlogits (the count of roundings is in
 CrossEntropyRef's docstring; tests/test_row_ref_cpu.py shows on the CPU that the comparison fails for a 16-byte chunk lost from lse, a
 label one column off, a mean over rows instead of live rows, an ignored row treated as live).  The entry points are called directly,
@@ -20,14 +20,12 @@ V - VN, V - 1.  dloss = 1.7 unless said otherwise.
 import pytest
 import torch
 
-from helpers import VEC, CrossEntropyRef, Slab
+from bounds import BF16, CANARY, F32, NAME, VEC, Slab
+from row_ref import CrossEntropyRef
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0                    # tests/test_row_ref_cpu.py's seed
-CANARY = -77.0
 IGNORE = -100
 NVECS = (768, 1023, 1024, 1025, 2056)
 
@@ -51,7 +49,7 @@ def _call(x, lab, dloss, count=None, inplace=False):
     _lib.call("mmgl_cross_entropy_bwd", None, ptr(xs.v), ptr(labs.v), ptr(lse.v), ptr(div.v), ptr(dl.v), ptr(g.v), rows, V, IGNORE, code, st)
     torch.cuda.synchronize()
     for name, s in dict(logits=xs, labels=labs, row_lse=lse, row_loss=loss, loss_sum=lsum, count=cnt, dloss=dl, dlogits=g).items():
-        assert s.guards_ok(), f"written outside {name}"
+        assert s.untouched(), f"written outside {name}"
     if not inplace:
         assert torch.equal(xs.v.view(torch.int16 if x.dtype == BF16 else torch.int32), x.view(torch.int16 if x.dtype == BF16 else torch.int32))
     return dict(row_lse=lse.v, row_loss=loss.v, loss_sum=lsum.v, count=fwd_cnt, dlogits=g.v)

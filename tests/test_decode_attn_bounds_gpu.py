@@ -1,4 +1,4 @@
-"""-m gpu: the eight single-query attention entry points of csrc/decode.hip, every element against helpers.DecodeAttnRef:
+"""-m gpu: the eight single-query attention entry points of csrc/decode.hip, every element against decode_ref.DecodeAttnRef:
 
     |got - want| <= u |want| + (n_s S_i + n_c) 2^-24 mag          u = 2^-8 (bf16), 2^-23 (fp32)
 

@@ -1,6 +1,6 @@
-"""helpers.DecodeAttnRef, the fp64 reference behind tests/test_decode_attn_bounds_gpu.py, on the CPU (no GPU needed):
+"""decode_ref.DecodeAttnRef, the fp64 reference behind tests/test_decode_attn_bounds_gpu.py, on the CPU (no GPU needed):
 
-(a) it IS the four references the decode tests have used so far -- helpers.attn_decode_ref, beam_ref.attn_beam_ref, kvq_ref.attention,
+(a) it IS the four references the decode tests have used so far -- decode_ref.attn_decode_ref, beam_ref.attn_beam_ref, kvq_ref.attention,
     t5_decode_ref.attn_decode_relbias_ref (its three wrong variants included) -- to 1e-12 of the largest magnitude, on cases of
     tests/decode_attn_cases.py: the new reference is the old ones, generalised;
 (b) the comparison it carries can fail: for each of the eight entry points and both dtypes, EVERY deliberately wrong reference the case
@@ -22,7 +22,7 @@ import beam_ref
 import kvq_ref
 import t5_decode_ref
 from decode_attn_cases import BF16, CAP, F32, BeamCase, BlockCase, CacheCase, Q8Case, RelbiasCase, gqa_plan, trip
-from helpers import DecodeAttnRef, attn_decode_ref, decode_geometry
+from decode_ref import DecodeAttnRef, attn_decode_ref, decode_geometry
 
 DTYPES = [pytest.param(BF16, id="bf16"), pytest.param(F32, id="fp32")]
 

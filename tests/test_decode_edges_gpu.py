@@ -1,7 +1,7 @@
 """-m gpu: the kernels of csrc/decode.hip at the states and addresses tests/test_decode_kernels_gpu.py and tests/test_decode_lora_gpu.py
-do not visit, against fp64 references of the same storage-rounded operands computed on the GPU (helpers.SkinnyRef, helpers.attn_decode_ref).
+do not visit, against fp64 references of the same storage-rounded operands computed on the GPU (decode_ref.SkinnyRef, decode_ref.attn_decode_ref).
 
-GEMM groups -- every element within  u |want| + 2^-16 mag  (helpers.SkinnyRef: the half ulp of the one rounding store plus 256 fp32
+GEMM groups -- every element within  u |want| + 2^-16 mag  (decode_ref.SkinnyRef: the half ulp of the one rounding store plus 256 fp32
 roundings on the magnitude sum), after asserting from the reference alone that a dropped 64-wide K unit, and a dropped rank-r term, leave
 that bound on >= 25 % of the elements:
   B  the MFMA kernel's K loop: a W ring of 4 units per lane, 4 (16-row workgroups) or 8 (8-row) K slots -- fewer units than slots, a ragged
@@ -22,7 +22,7 @@ per sample.  I = 1024 VEC / D keys per workgroup loop trip, KPI = 64 VEC / D key
 import pytest
 import torch
 
-from helpers import SkinnyRef, attn_decode_ref
+from decode_ref import SkinnyRef, attn_decode_ref
 
 pytestmark = pytest.mark.gpu
 

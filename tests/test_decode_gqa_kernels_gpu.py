@@ -1,7 +1,7 @@
 """-m gpu: the two kernels of the Llama-family decode step (csrc/decode.hip): mmgl_attn_decode_gqa_fwd through ops.attn_decode(...,
 num_kv_heads) and mmgl_rope_kv_append through ops.rope_kv_append.
 
-Attention -- the fp64 reference is helpers.attn_decode_ref on K / V expanded to H heads (repeat_interleave(G) over the head axis:
+Attention -- the fp64 reference is decode_ref.attn_decode_ref on K / V expanded to H heads (repeat_interleave(G) over the head axis:
 transformers' repeat_kv), the bounds are those of tests/test_decode_edges_gpu.py: per sample 1e-3 (fp32) / 2e-2 (bf16) of the sample's
 largest reference magnitude.  The kernel keeps attn_decode_kernel's lane layout: I = 1024 VEC / D keys per workgroup loop trip, KPI =
 64 VEC / D keys per wave and load (VEC = 8 bf16, 4 fp32); a workgroup serves up to 8 query heads of one key/value head, G = 12 takes
@@ -14,7 +14,7 @@ rounding to bf16 is 2^-9 relative of |want| <= a; the fp32 arithmetic in front o
 import pytest
 import torch
 
-from helpers import attn_decode_ref
+from decode_ref import attn_decode_ref
 
 pytestmark = pytest.mark.gpu
 

@@ -2,7 +2,7 @@
   * mmgl_gemm_skinny against an fp32 torch GEMM of the same (bf16-rounded) operands, bound as in tests/test_gemm_nt_gpu.py
     (2e-2 * max|want| + 1e-2 on the largest absolute error); every epilogue option; a strided output inside a larger buffer whose
     other bytes must stay untouched; two runs bitwise equal (the K partials are folded in a fixed order).  Every comparison also
-    holds element by element against the fp64 reference, within helpers.SkinnyRef's bound (half an ulp of the store plus 256 fp32
+    holds element by element against the fp64 reference, within decode_ref.SkinnyRef's bound (half an ulp of the store plus 256 fp32
     roundings on the magnitude sum), which a dropped 64-wide K unit leaves on a quarter of the elements or more.
   * mmgl_attn_decode_fwd against oracle.lm_ref.attention_core with one query row: random key masks, a sample without any valid key
     (uniform over its keys), K and V addressed in place as column slabs of wider cache rows.  Tolerances of tests/test_xattn_gpu.py:
@@ -10,7 +10,8 @@
 import pytest
 import torch
 
-from helpers import SkinnyRef, rel_err
+from decode_ref import SkinnyRef
+from helpers import rel_err
 
 pytestmark = pytest.mark.gpu
 

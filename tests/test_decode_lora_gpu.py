@@ -3,14 +3,15 @@
 against an fp32 torch reference on the same (bf16-rounded) operands, with the bound of tests/test_decode_kernels_gpu.py::_check
 (2e-2 * max|want| + 1e-2 on the largest absolute error).  B is scaled so that the rank-r term is of the size of the base product: every
 comparison first asserts, from the reference alone, that dropping the term would miss the bound tenfold, and then holds element by
-element against the fp64 reference within helpers.SkinnyRef's bound (which the reference without the term, or without its last 64 K
+element against the fp64 reference within decode_ref.SkinnyRef's bound (which the reference without the term, or without its last 64 K
 columns, leaves on a quarter of the elements or more).  Also: the epilogue options
 one by one and together; a strided output inside a larger buffer whose other bytes stay untouched; two runs bitwise equal; agreement
 with the training forward ops.lora_linear on the same operands (2e-2 bf16, 1e-3 fp32, max-norm relative: DESIGN.md 2)."""
 import pytest
 import torch
 
-from helpers import SkinnyRef, rel_err
+from decode_ref import SkinnyRef
+from helpers import rel_err
 
 pytestmark = pytest.mark.gpu
 

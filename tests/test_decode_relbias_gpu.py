@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import t5_decode_ref as R
-from helpers import Slab
+from bounds import Slab
 
 pytestmark = pytest.mark.gpu
 
@@ -120,7 +120,7 @@ def test_nothing_past_the_keys_or_outside_the_slabs(dtype, D):
         out = Slab((B, d), dtype, NAN)
         assert ops.attn_decode_relbias(q, k, v, bias, H, out=out.v) is out.v
         _check(out.v, want, dtype, f"{dtype} D={D} S={S}, NaN outside", "c")
-        assert out.guards_ok(), f"{dtype} D={D} S={S}: bytes around the output changed"
+        assert out.untouched(), f"{dtype} D={D} S={S}: bytes around the output changed"
 
 
 def test_refused_calls_leave_the_output_alone():

@@ -1,5 +1,5 @@
 """-m gpu: the packed bidirectional encoder attention mmgl_encattn_fwd (encattn_fwd_kernel of csrc/selfattn.hip, sa32_enc_fwd of
-csrc/selfattn32.hip) against helpers.EncAttnRef -- per sequence an fp64 all-valid attention of the storage-rounded operands --
+csrc/selfattn32.hip) against attn_ref.EncAttnRef -- per sequence an fp64 all-valid attention of the storage-rounded operands --
 element by element, within u |want| + (c + n 2^-24 (S_i + ln len)) mag (XAttnRef's count).  tests/test_attn_general_ref_cpu.py shows
 on the CPU that this comparison fails for a key leaking in from the next sequence, a dropped last key and a shifted head mapping.
 The raw entry point is called (ld_out is free there); `out` holds a canary before every call.
@@ -27,16 +27,14 @@ import functools
 import pytest
 import torch
 
-from helpers import EncAttnRef, Slab
+from attn_ref import EncAttnRef
+from bounds import BF16, CANARY, F32, NAME, NAN, Slab
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0
 LENS = (1, 129, 15, 64, 17, 63, 16, 128, 65, 257, 127)
 H = 3
-CANARY = 1536.0              # exact in bf16
 R32, R16, R16BIG = "R32", "R16", "R16big"
 ROUTES = ([(R32, BF16, D, 257) for D in (64, 128)] + [(R16, F32, D, 257) for D in (16, 32, 64, 128)] + [(R16, BF16, D, 257) for D in (16, 32)]
           + [(R16BIG, BF16, D, 4097) for D in (64, 128)])
@@ -79,10 +77,10 @@ def _run(dtype, D, max_len, q_rows=None, lens=LENS, heads=H, qkv=None):
     q, k, v, cu, ref = _batch(dtype, D, lens, heads)
     if qkv is not None:
         q, k, v = qkv
-    out = torch.full((q.shape[0], heads * D), CANARY, dtype=dtype, device="cuda")
-    _enc(q, k, v, cu, out, len(lens), heads, D, q.stride(0), heads * D, max_len, max_len if q_rows is None else q_rows, dtype)
+    so = Slab((q.shape[0], heads * D), dtype, CANARY)
+    _enc(q, k, v, cu, so.v, len(lens), heads, D, q.stride(0), heads * D, max_len, max_len if q_rows is None else q_rows, dtype)
     torch.cuda.synchronize()
-    return out, ref
+    return so.v, ref
 
 
 # ------------------------------------------------------------------------------------------ A: lengths
@@ -168,17 +166,14 @@ def test_D_layouts(route):
     out, _ = _run(dtype, D, max_len, qkv=(fused[:, :hd], fused[:, hd:2 * hd], fused[:, 2 * hd:]))
     assert torch.equal(out, plain), "column slices of a fused [ntok, 3 H D] buffer"
     pitch = hd + 8
-    bufs = [torch.full((n, pitch), float("nan"), dtype=dtype, device="cuda") for _ in range(3)]
-    for b, t in zip(bufs, (q, k, v)):
-        b[:, :hd] = t
-    out, _ = _run(dtype, D, max_len, qkv=tuple(b[:, :hd] for b in bufs))
+    out, _ = _run(dtype, D, max_len, qkv=tuple(Slab((n, hd), dtype, NAN, t, ld=pitch).v for t in (q, k, v)))
     assert torch.equal(out, plain), "three buffers of a padded pitch (NaN in the pad columns)"
-    wide = torch.full((n, hd + 16), CANARY, dtype=dtype, device="cuda")
-    _enc(q, k, v, cu, wide, len(LENS), H, D, hd, hd + 16, max_len, max_len, dtype)
+    wide = Slab((n, hd), dtype, CANARY, ld=hd + 16)
+    _enc(q, k, v, cu, wide.v, len(LENS), H, D, hd, hd + 16, max_len, max_len, dtype)
     torch.cuda.synchronize()
-    assert bool((wide[:, hd:] == CANARY).all()), "ld_out > H D: a pad column was written"
-    assert torch.equal(wide[:, :hd], plain)
-    ref.check(wide[:, :hd].contiguous(), _rid(route) + " ld_out", f"D {r} {NAME[dtype]}")
+    assert wide.untouched(), "ld_out > H D: a pad column was written"
+    assert torch.equal(wide.v, plain)
+    ref.check(wide.v, _rid(route) + " ld_out", f"D {r} {NAME[dtype]}")
 
 
 # ------------------------------------------------------------------------------------------ E: memory
@@ -187,11 +182,11 @@ def test_E_isolation_and_determinism(route):
     r, dtype, D, max_len = route
     q, k, v, cu, ref = _batch(dtype, D)
     plain, _ = _run(dtype, D, max_len)
-    slabs = [Slab(t.shape, dtype, float("nan"), t) for t in (q, k, v)]
+    slabs = [Slab(t.shape, dtype, NAN, t) for t in (q, k, v)]
     so = Slab(plain.shape, dtype, CANARY)
     _enc(slabs[0].v, slabs[1].v, slabs[2].v, cu, so.v, len(LENS), H, D, H * D, H * D, max_len, max_len, dtype)
     torch.cuda.synchronize()
-    assert so.guards_ok() and all(s.guards_ok() for s in slabs), "bytes next to a buffer were written"
+    assert so.untouched() and all(s.untouched() for s in slabs), "bytes next to a buffer were written"
     assert torch.isfinite(so.v.float()).all() and torch.equal(so.v, plain), "the guards reached the result"
     again, _ = _run(dtype, D, max_len)
     assert torch.equal(again, plain), "two launches differ"
@@ -221,13 +216,13 @@ BAD = [("q_rows-0", dict(q_rows=0)), ("ld_in-below-HD", dict(ld_in=H * 64 - 8)),
 def test_F_refusals(dtype, what, over):
     D = 64
     q, k, v, cu, _ = _batch(dtype, D)
-    out = torch.full((q.shape[0], H * D), CANARY, dtype=dtype, device="cuda")
-    a = dict(q=q, k=k, v=v, cu=cu, out=out, nseq=len(LENS), heads=H, D=D, ld_in=H * D, ld_out=H * D, max_len=257, q_rows=257, dtype=dtype)
+    so = Slab((q.shape[0], H * D), dtype, CANARY)
+    a = dict(q=q, k=k, v=v, cu=cu, out=so.v, nseq=len(LENS), heads=H, D=D, ld_in=H * D, ld_out=H * D, max_len=257, q_rows=257, dtype=dtype)
     a.update(over)
     with pytest.raises(ValueError):
         _enc(**a)
     torch.cuda.synchronize()
-    assert bool((out == CANARY).all()), "written by a refused call"
+    assert so.unwritten(), "written by a refused call"
 
 
 # ------------------------------------------------------------------------------------------ Z: a sequence without tokens
@@ -243,4 +238,4 @@ def test_Z_zero_length_sequence(route):
     so = Slab(without.shape, dtype, CANARY)
     _enc(q, k, v, cu, so.v, len(lens_z), H, D, H * D, H * D, max_len, max_len, dtype)
     torch.cuda.synchronize()
-    assert so.guards_ok() and torch.equal(so.v, without)
+    assert so.untouched() and torch.equal(so.v, without)

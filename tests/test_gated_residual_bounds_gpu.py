@@ -1,5 +1,5 @@
-"""-m gpu: mmgl_gated_residual_fwd / bwd (csrc/elementwise.hip) against helpers.GatedRef -- an fp64 reference of the storage-rounded
-operands -- element by element, with the dropout mask taken from helpers.hash_keep, an independent restatement of mmgl_hash32 (the
+"""-m gpu: mmgl_gated_residual_fwd / bwd (csrc/elementwise.hip) against row_ref.GatedRef -- an fp64 reference of the storage-rounded
+operands -- element by element, with the dropout mask taken from bounds.hash_keep, an independent restatement of mmgl_hash32 (the
 existing tests compare the kernels' masks with each other only; tests/test_row_ref_cpu.py holds hash_keep against a big-integer
 restatement and shows that a mask one element off leaves the bound on 42 % of the elements).  The entry points are called directly.
 
@@ -11,15 +11,13 @@ restatement and shows that a mask one element off leaves the bound on 42 % of th
 import pytest
 import torch
 
-from helpers import VEC, ByteSlab, GatedRef, Slab
+from bounds import BF16, CANARY, F32, NAME, VEC, ByteSlab, Slab
+from row_ref import GatedRef
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0
 DROP_SEED = 0x9E3779B97F4A7C15          # a seed with its top bit set: the hash's 64-bit wrap-around
-CANARY = -77.0
 BIG = 256 * 8 * 2048 + 3
 WS_BYTES = 2048 * 4
 
@@ -68,12 +66,12 @@ def test_gated_residual_bounds(dtype, n, gated, p):
     if gated:
         ref.check(dgate.v, "dgate", what, group)
     else:
-        assert dgate.untouched()
+        assert dgate.unwritten()
     if p > 0:
         assert bool((dx.v[~ref.keep] == 0).all()), f"{what}: a dropped element has a gradient"
         assert n < 100 or 0.69 < ref.keep.double().mean().item() < 0.71
     for name, s in dict(res=rs, x=xs, dy=dys, y=y, dx=dx, dgate=dgate, ws=ws).items():
-        assert s.guards_ok(), f"{what}: written outside {name}"
+        assert s.untouched(), f"{what}: written outside {name}"
 
 
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=NAME.get)
@@ -99,4 +97,4 @@ def test_refusals(dtype):
         _bwd(dys, xs, gate, dx, dgate, ws, WS_BYTES - 1, n, 0.0)
     torch.cuda.synchronize()
     for s in (y, dx, dgate, ws):
-        assert s.untouched()
+        assert s.unwritten()

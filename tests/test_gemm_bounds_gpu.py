@@ -1,12 +1,12 @@
-"""-m gpu: mmgl_gemm_nt and the mask-bits pair (csrc/gemm8p.hip, gemm_mid.hip, gemm.hip) against helpers.GemmRef -- an fp64 reference of
+"""-m gpu: mmgl_gemm_nt and the mask-bits pair (csrc/gemm8p.hip, gemm_mid.hip, gemm.hip) against gemm_ref.GemmRef -- an fp64 reference of
 the storage-rounded operands -- element by element: |got - want| <= u |want| + L c mag + E + staged (the count is in GemmRef's
 docstring; tests/test_gemm_ref_cpu.py shows on the CPU that this comparison fails for a lost or doubled K unit or K split, a bias line
 of another tile, a tail-row offset, a scale on the wrong side of the activation, a transposed operand).  The entry points are called
 directly, with a workspace of exactly mmgl_gemm_nt_workspace bytes.
 
-The plans of csrc/gemm.hip and csrc/gemm8p.hip are restated here (nt_route, gemm8p_plan, gemm8p_row_split, gemm8p_use_splits,
-gemm8p_supported, gemm_mid_supported; the CU count from the device properties) and every case holds the restated route and scratch
-size against mmgl_gemm_nt_fast, mmgl_gemm_nt_workspace and mmgl_gemm_nt_relu_bits_bytes, so a change to the plans fails loudly instead
+The plans of csrc/gemm.hip and csrc/gemm8p.hip are restated in tests/gemm_ref.py (nt_route, gemm8p_plan, gemm8p_row_split,
+gemm8p_use_splits, gemm8p_supported, gemm_mid_supported; the CU count from the device properties) and every case holds the restated
+route and scratch size against mmgl_gemm_nt_fast, mmgl_gemm_nt_workspace and mmgl_gemm_nt_relu_bits_bytes, so a change to the plans fails loudly instead
 of quietly moving the cases off the routes they were chosen for.  The shapes are the smallest that reach each route on 256 CUs:
 
   A  whole 256x256 tiles on the persistent kernel: two and three K units, ragged last tile row / column (240 and 16 columns), every
@@ -35,99 +35,13 @@ of quietly moving the cases off the routes they were chosen for.  The shapes are
 import pytest
 import torch
 
-from helpers import GemmRef
+from bounds import BF16, CANARY_BYTE, F32, NAME, NAN, NAN_BYTE, Slab
+from gemm_ref import (FAST, MID, P8, P8_FEW, P8_REM, P8_ROWS, TILE128, GemmRef, bits_bytes, cdiv, detail, gemm8p_plan, gemm8p_row_split, nt_route,
+                      num_cu, workspace_bytes)
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0                    # tests/test_gemm_ref_cpu.py: every wrong reference leaves the bound on >= 25 % at this seed
-P8, P8_ROWS, P8_REM, P8_FEW, MID, TILE128 = "P8", "P8+rows", "P8+rem", "P8+few", "MID", "TILE128"
-FAST = {P8: 1, P8_ROWS: 1, P8_REM: 1, P8_FEW: 1, MID: 2, TILE128: 0}        # mmgl_gemm_nt_fast
-MIN_TILES = 160             # GEMM8P_MIN_TILES
-
-
-# ------------------------------------------------------------------------------------------ the plans, restated
-def cdiv(a, b):
-    return (a + b - 1) // b
-
-
-def num_cu():
-    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-
-
-def gemm8p_supported(M, N, K, ldx, ldw, ldy):
-    return (M > 0 and N > 0 and K >= 256 and K % 128 == 0 and N % 16 == 0 and ldx % 8 == 0 and ldw % 8 == 0 and ldy % 8 == 0
-            and M * ldx * 2 < 0xffffffff and N * ldw * 2 < 0xffffffff)
-
-
-def gemm_mid_supported(M, N, K, ldx, ldw, ldy):
-    return (M > 0 and N > 0 and K >= 64 and K % 64 == 0 and N % 8 == 0 and ldx % 8 == 0 and ldw % 8 == 0 and ldy % 8 == 0
-            and ldx + 127 >= K and ldw >= K and ldy >= N and max(ldx, ldw, ldy) * 2 * 128 < 0x7fffffff)
-
-
-def gemm8p_plan(M, N, K, G):
-    """(direct, nsplit): tiles [0, direct) whole, the rest as nsplit K-split work items each (0: none)."""
-    tiles, units = cdiv(M, 256) * cdiv(N, 256), K // 128
-    if tiles < MIN_TILES:
-        if units < 24 or (units < 32 and tiles >= 64):
-            return tiles, 0
-        s = min(cdiv(224, tiles), 8, units // 2)
-        return (0, s) if s >= 2 else (tiles, 0)
-    rounds, r = tiles // G, tiles % G
-    if rounds < 1 or rounds > 12 or r == 0:
-        return tiles, 0
-    s = min(G // r, 8, units // 4)
-    return (tiles - r, s) if s >= 3 else (tiles, 0)
-
-
-def gemm8p_split_bytes(M, N, K, G):
-    d, s = gemm8p_plan(M, N, K, G)
-    return (cdiv(M, 256) * cdiv(N, 256) - d) * s * 256 * 256 * 4 if s else 0
-
-
-def gemm8p_use_splits(M, N, K, G):
-    return cdiv(M, 256) * cdiv(N, 256) >= 24 and gemm8p_plan(M, N, K, G)[1] > 0
-
-
-def gemm8p_row_split(M, N, K, ldx, ldw, ldy, G):
-    tm, tn = cdiv(M, 256), cdiv(N, 256)
-    rounds, rem = tm * tn // G, tm * tn % G
-    if rounds < 1 or rounds > 3 or rem == 0 or rem > G // 4 or (rounds * G) % tn:
-        return 0
-    m1 = rounds * G // tn * 256
-    return m1 if 0 < m1 < M and gemm_mid_supported(M - m1, N, K, ldx, ldw, ldy) else 0
-
-
-def nt_route(M, N, K, ldx, ldw, ldy, dtype, k_splits, G):
-    if dtype != BF16:
-        return TILE128
-    if gemm8p_supported(M, N, K, ldx, ldw, ldy) and (cdiv(M, 256) * cdiv(N, 256) >= MIN_TILES or (k_splits and gemm8p_use_splits(M, N, K, G))):
-        return P8
-    return MID if gemm_mid_supported(M, N, K, ldx, ldw, ldy) else TILE128
-
-
-def workspace_bytes(M, N, K, ldx, ldw, ldy, dtype, G):
-    if nt_route(M, N, K, ldx, ldw, ldy, dtype, True, G) != P8 or not gemm8p_use_splits(M, N, K, G):
-        return 0
-    return cdiv(gemm8p_split_bytes(M, N, K, G), 256) * 256
-
-
-def bits_bytes(M, N, K, ldx, ldw, ldy, dtype, G):
-    return cdiv(M, 256) * cdiv(N, 256) * 8192 if nt_route(M, N, K, ldx, ldw, ldy, dtype, False, G) == P8 else 0
-
-
-def detail(M, N, K, ldx, ldw, ldy, dtype, scratch, G):
-    """(what launch_nt does, K splits folded): the route of nt_route with the persistent kernel's three plans told apart."""
-    r = nt_route(M, N, K, ldx, ldw, ldy, dtype, True, G)
-    if r != P8:
-        return r, 0
-    if gemm8p_row_split(M, N, K, ldx, ldw, ldy, G):
-        return P8_ROWS, 0
-    d, s = gemm8p_plan(M, N, K, G)
-    if s and scratch:
-        return (P8_FEW if d == 0 else P8_REM), s
-    return P8, 0
 
 
 # ------------------------------------------------------------------------------------------ cases
@@ -423,34 +337,6 @@ def test_H_mask_bits_are_refused_for_a_few_tile_shape():
 
 
 # ------------------------------------------------------------------------------------------ I: isolation and determinism
-PAD = 512                   # bytes on either side of a carved tensor (keeps the 16-byte alignment)
-CANARY = 0xA5
-
-
-class Carved:
-    """A [rows, cols] tensor with row stride ld, PAD bytes into a uint8 slab filled with the byte `fill`: the margins, the columns
-    past `cols` of every row and the rows past `rows` (`extra` of them) hold `fill`."""
-
-    def __init__(self, rows, cols, ld, dtype, fill, src=None, extra=0):
-        self.esz = torch.empty((), dtype=dtype).element_size()
-        self.shape, self.ld, self.dtype, self.fill = (rows, cols), ld, dtype, fill
-        self.slab = torch.full(((rows + extra) * ld * self.esz + 2 * PAD,), fill, dtype=torch.uint8, device="cuda")
-        self.view = self.of(self.slab)
-        if src is not None:
-            self.view.copy_(src)
-
-    def of(self, slab):
-        rows, cols = self.shape
-        return slab[PAD:PAD + rows * self.ld * self.esz].view(self.dtype).view(rows, self.ld)[:, :cols]
-
-    def untouched(self):
-        """Nothing but the view's own elements differs from the fill."""
-        rows, cols = self.shape
-        s = self.slab.clone()
-        s[PAD:PAD + rows * self.ld * self.esz].view(rows, self.ld * self.esz)[:, :cols * self.esz].fill_(self.fill)
-        return bool((s == self.fill).all())
-
-
 CASES_I = [
     C("I", P8, 2500, 4080, 256, act=1, pad=(64, 8, 16), **ALL), C("I", P8_ROWS, 2400, 8176, 256, act=3, pad=(8, 64, 16), **ALL),
     C("I", P8_REM, 5400, 3072, 1536, act=0, pad=(8, 8, 8), **ALL), C("I", P8_FEW, 2500, 2064, 4096, act=1, scale=0.125, pad=(8, 8, 48), **ALL),
@@ -465,22 +351,22 @@ def test_I_isolation_and_determinism(case):
     route, s, nws = _plan_checks(c)
     t = GemmRef.inputs(c.dtype, c.M, c.N, c.K, seed=SEED, device="cuda")
     ldx, ldw, ldy = c.ld
-    x, w = Carved(c.M, c.K, ldx, c.dtype, 0xFF, t["x"]), Carved(c.N, c.K, ldw, c.dtype, 0xFF, t["w"])
-    b = Carved(1, c.N, c.N, c.dtype, 0xFF, t["bias"][None])
-    r, z = Carved(c.M, c.N, ldy, c.dtype, 0xFF, t["residual"]), Carved(c.M, c.N, ldy, c.dtype, 0xFF, t["zmask"])
-    ys = [Carved(c.M, c.N, ldy, c.dtype, CANARY, extra=3) for _ in range(2)]
-    ws = Carved(1, max(nws, 1), max(nws, 1), torch.uint8, CANARY)
+    x, w = Slab((c.M, c.K), c.dtype, NAN_BYTE, t["x"], ld=ldx), Slab((c.N, c.K), c.dtype, NAN_BYTE, t["w"], ld=ldw)
+    b = Slab((c.N,), c.dtype, NAN_BYTE, t["bias"])
+    r, z = Slab((c.M, c.N), c.dtype, NAN_BYTE, t["residual"], ld=ldy), Slab((c.M, c.N), c.dtype, NAN_BYTE, t["zmask"], ld=ldy)
+    ys = [Slab((c.M, c.N), c.dtype, CANARY_BYTE, ld=ldy, extra=3) for _ in range(2)]
+    ws = Slab((max(nws, 1),), torch.uint8, CANARY_BYTE)
     for y in ys:
-        y.view.fill_(float("nan"))
-        ws.view.fill_(0xFF)
-        _gemm(c, x.view, w.view, b.view[0], r.view, z.view, y.view, ws.view if nws else None, nws)
+        y.v.fill_(NAN)
+        ws.v.fill_(NAN_BYTE)
+        _gemm(c, x.v, w.v, b.v, r.v, z.v, y.v, ws.v if nws else None, nws)
         torch.cuda.synchronize()
         assert y.untouched(), "bytes next to the output (rows past M, columns past N) were written"
         assert ws.untouched(), "bytes past the workspace were written"
     assert all(o.untouched() for o in (x, w, b, r, z))
-    ref = GemmRef.forward(x.view, w.view, b.view[0], c.act, c.scale, r.view, z.view)
-    ref.check(ys[0].view, c.id, f"I {route} {NAME[c.dtype]}", **_bound_kw(c, route, s))
-    assert torch.equal(ys[0].view, ys[1].view), "two launches differ"
+    ref = GemmRef.forward(x.v, w.v, b.v, c.act, c.scale, r.v, z.v)
+    ref.check(ys[0].v, c.id, f"I {route} {NAME[c.dtype]}", **_bound_kw(c, route, s))
+    assert torch.equal(ys[0].v, ys[1].v), "two launches differ"
 
 
 # ------------------------------------------------------------------------------------------ J: dynamic tile schedule

@@ -1,4 +1,4 @@
-"""CPU: the comparison of tests/test_gemm_bounds_gpu.py and tests/test_linear_bwd_bounds_gpu.py can fail.  From helpers.GemmRef alone
+"""CPU: the comparison of tests/test_gemm_bounds_gpu.py and tests/test_linear_bwd_bounds_gpu.py can fail.  From gemm_ref.GemmRef alone
 (fp64, no kernel): a deliberately wrong reference of each defect the GEMM family could have -- a K unit or a K split lost or folded
 twice, a bias line of another tile, a residual or zmask row offset lost in the tail rows of a row split, the scale on the wrong side
 of the activation, a transposed operand, contraction rows lost from a weight gradient, `accumulate` ignored or applied twice, a row
@@ -8,9 +8,9 @@ statistics depend on the contraction length only).  The bound is taken in bf16, 
 import pytest
 import torch
 
-from helpers import GemmRef
+from bounds import BF16
+from gemm_ref import GemmRef
 
-BF16 = torch.bfloat16
 SEED = 0                                    # the GPU files' seed
 KS = (256, 384, 1536, 3072, 4096)           # contraction lengths of the forward GPU cases on the fused routes
 M, N, M1 = 384, 512, 256                    # two tile rows (the second one the "tail" of a row split), two 256-column tiles

@@ -4,7 +4,7 @@ mmgl_weight_quantize -- codes and exponents bitwise equal to the restatement tes
 edge rows of the exponent rule, K at the 16-element vector width's edges (8, 64, 72; 16, 1024 = one trip of a wave, 1040, 2064) and
 N = 1 and 9 (4 rows per workgroup); source and destination as windows of buffers that hold NaN / a marker everywhere else.
 
-mmgl_gemm_skinny_w8 -- every element within helpers.SkinnyRef's bound  u |want| + 2^-16 mag  of fp64 on the dequantised weight, with
+mmgl_gemm_skinny_w8 -- every element within decode_ref.SkinnyRef's bound  u |want| + 2^-16 mag  of fp64 on the dequantised weight, with
 bias, residual, ReLU and scale together, two runs bitwise equal.  tests/test_weight_fp8_ref_cpu.py shows from the references alone that
 the mistakes such a kernel can make leave that bound; here SkinnyRef.assert_can_fail repeats it for the dropped K columns.  The codes
 come from the restatement, not from the kernel under test, and the weight rows span exponents from negative to large, so the
@@ -20,7 +20,7 @@ import pytest
 import torch
 
 import w8_ref
-from helpers import SkinnyRef
+from decode_ref import SkinnyRef
 
 pytestmark = pytest.mark.gpu
 

@@ -5,7 +5,7 @@ one autograd node that strings them together, each against the call it replaces.
 import pytest
 import torch
 
-from helpers import GemmRef
+from gemm_ref import GemmRef
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16

@@ -247,7 +247,7 @@ def test_restatement_attention_matches_softmax():
     ok[1] = False
     out = kvq_ref.attention(q, kc, vc, ok, kn, vn, H)
     assert torch.allclose(out[1], vn[1].double())                  # every cached key masked: the new value row
-    from helpers import attn_decode_ref
+    from decode_ref import attn_decode_ref
     full_k, full_v = torch.cat([kc, kn[:, None]], 1), torch.cat([vc, vn[:, None]], 1)
     ref = attn_decode_ref(q, full_k, full_v, torch.cat([ok, torch.ones(B, 1, dtype=torch.bool)], 1), H)
     assert torch.allclose(out, ref.double(), atol=1e-5)

@@ -1,11 +1,11 @@
-"""-m gpu: mmgl_linear_fwd / mmgl_linear_bwd through the C ABI against helpers.GemmRef, element by element (the bound's count is in
+"""-m gpu: mmgl_linear_fwd / mmgl_linear_bwd through the C ABI against gemm_ref.GemmRef, element by element (the bound's count is in
 GemmRef's docstring; tests/test_gemm_ref_cpu.py shows on the CPU that the comparison fails for contraction rows lost from a weight
 gradient, `accumulate` ignored or applied twice, a row split lost from a bias gradient and mask_dx taken from x >= 0).  The backward
 is called directly, so y, `accumulate`, mask_dx and the NULL-able outputs are the test's to choose; the workspace has exactly
 mmgl_linear_bwd_workspace bytes and sits, like every output, in a canary slab that must come back untouched.
 
-gemm8p_tt_splits, colsum_splits, big_tile_shape and the workspace layout of csrc/gemm.hip are restated here (the NT plans in
-tests/test_gemm_bounds_gpu.py); the restated size is held against mmgl_linear_bwd_workspace for every case and the case list asserts
+gemm8p_tt_splits, colsum_splits, big_tile_shape and the workspace layout of csrc/gemm.hip are restated in tests/gemm_ref.py, beside
+the NT plans; the restated size is held against mmgl_linear_bwd_workspace for every case and the case list asserts
 the route of every case.
 
   dgrad   NT against W^T on the 128x128 kernel (300 x 128 x 192), NT on the persistent kernel with K splits (1536 x 1024, N = 3072),
@@ -22,65 +22,13 @@ the route of every case.
 import pytest
 import torch
 
-from helpers import GemmRef
-from test_gemm_bounds_gpu import (BF16, F32, MID, NAME, P8, P8_FEW, SEED, TILE128, Carved, CANARY, cdiv, detail, gemm8p_split_bytes, nt_route,
-                                  num_cu)
+from bounds import BF16, CANARY_BYTE, F32, NAME, NAN, NAN_BYTE, Slab
+from gemm_ref import (MID, NT_FEW, NT_MID, P8, TILE128, TRANSPOSE, TT1, TT4, TX, TX_GLDS, GemmRef, bwd_workspace, cdiv, colsum_splits, dgrad_route,
+                      gemm8p_tt_splits, nt_route, num_cu, wgrad_route)
 
 pytestmark = pytest.mark.gpu
 
-NT_MID, NT_FEW, TX_GLDS, TX, TT1, TT4, TRANSPOSE = "nt-" + MID, "nt-" + P8_FEW, "tx-glds", "tx", "tt1", "tt4", "transpose"
-COLSUM_SPLITS = 64
-
-
-# ------------------------------------------------------------------------------------------ the plans, restated
-def gemm8p_tt_splits(RA, RB, M, G):
-    if M % 128:
-        return 0
-    if RA % 256 or RB % 256:
-        return 1 if RA % 8 == 0 and RB % 8 == 0 and M >= 256 and cdiv(RA, 256) * cdiv(RB, 256) >= 192 else 0
-    tiles, units = (RA // 256) * (RB // 256), M // 128
-    best = best_cost = 0
-    for s in range(1, 33):
-        if units % s or M // s < 256:
-            continue
-        cost = cdiv(tiles * s, G) * (units // s + 3) + (3 + tiles * s * 6 // 100 if s > 1 else 0)
-        if not best or cost < best_cost:
-            best, best_cost = s, cost
-    return best if best and tiles * best >= 64 else 0
-
-
-def colsum_splits(M, N, vn):
-    s = min(max(cdiv(1024, cdiv(N, 16 * vn)), 16), COLSUM_SPLITS)
-    return min(s, max(M // 128, 1))
-
-
-def big_tile_shape(M, N, K):
-    return K % 64 == 0 and cdiv(M, 256) * cdiv(N, 256) >= 512
-
-
-def dgrad_route(M, N, K, G):
-    """(route, K splits folded) of the bf16 dx[M, K] = dyp[M, N] W[N, K]."""
-    route, s = detail(M, K, N, N, N, K, BF16, True, G)
-    if big_tile_shape(M, K, N) or (N % 128 == 0 and nt_route(M, K, N, N, N, K, BF16, True, G) != TILE128):
-        return "nt-" + route, s
-    return (TX_GLDS if N % 64 == 0 and K % 128 == 0 else TX), 0
-
-
-def wgrad_route(M, N, K, G):
-    """(route, K splits folded) of the bf16 dW[N, K] = dyp[M, N]^T x[M, K]."""
-    s = gemm8p_tt_splits(K, N, M, G)
-    if s:
-        return f"tt{s}", s if s > 1 else 0
-    return (TX_GLDS if M % 64 == 0 and K % 128 == 0 and N % 128 == 0 else TX), 0
-
-
-def bwd_workspace(M, N, K, act, dtype, G):
-    al = lambda n: cdiv(n, 256) * 256
-    if dtype == BF16:         # [dyp] [bias column-sum partials] [W^T] [fp32 split partials of the dgrad / the weight gradient]
-        s = gemm8p_tt_splits(K, N, M, G)
-        return al(M * N * 2) + al(COLSUM_SPLITS * N * 4) + al(K * N * 2) + max(al(s * K * N * 4) if s > 1 else 0, al(gemm8p_split_bytes(M, K, N, G)))
-    Mp, Np = cdiv(M, 8) * 8, cdiv(N, 8) * 8
-    return max(al(K * Np * 4) + (al(M * N * 4) if act else 0), al(N * Mp * 4) + al(K * Mp * 4))
+SEED = 0                    # tests/test_gemm_ref_cpu.py: every wrong reference leaves the bound on >= 25 % at this seed
 
 
 # ------------------------------------------------------------------------------------------ cases
@@ -141,11 +89,6 @@ def test_case_list_reaches_every_route():
     assert [c.scale for c in EVERY if c.scale != 0.125] == [0.3]
 
 
-def _nan(shape, dtype):
-    rows, cols = (1, shape[0]) if len(shape) == 1 else shape
-    return Carved(rows, cols, cols, dtype, CANARY)
-
-
 def _bwd(c, dy, y, x, w, dx, dw, db, ws, nws):
     from mmgl_amd import _lib
     from mmgl_amd._lib import ptr
@@ -162,16 +105,16 @@ def _run(c):
     nws = bwd_workspace(c.M, c.N, c.K, c.act, c.dtype, G)
     assert _lib.lib().mmgl_linear_bwd_workspace(c.M, c.N, c.K, c.act, _lib.BF16 if c.dtype == BF16 else _lib.F32) == nws, \
         f"{c.id}: mmgl_linear_bwd_workspace is not the restated layout's"
-    ws = Carved(1, nws, nws, torch.uint8, CANARY)
-    ws.view.fill_(0xFF)
-    dx = _nan((c.M, c.K), c.dtype) if c.dx else None
-    dw = _nan((c.N, c.K), c.dtype) if c.dw else None
-    db = _nan((c.N,), c.dtype) if c.db else None
+    ws = Slab((nws,), torch.uint8, CANARY_BYTE)
+    ws.v.fill_(NAN_BYTE)
+    dx = Slab((c.M, c.K), c.dtype, CANARY_BYTE) if c.dx else None
+    dw = Slab((c.N, c.K), c.dtype, CANARY_BYTE) if c.dw else None
+    db = Slab((c.N,), c.dtype, CANARY_BYTE) if c.db else None
     for o, fill in ((dx, None), (dw, t["prior_w"]), (db, t["prior_b"])):
         if o is not None:
-            o.view.copy_(fill.reshape(o.view.shape)) if (fill is not None and c.accumulate) else o.view.fill_(float("nan"))
-    v = lambda o: None if o is None else o.view
-    _bwd(c, t["dy"], y, x, t["w"], v(dx), v(dw), v(db), ws.view, nws)
+            o.v.copy_(fill) if (fill is not None and c.accumulate) else o.v.fill_(NAN)
+    v = lambda o: None if o is None else o.v
+    _bwd(c, t["dy"], y, x, t["w"], v(dx), v(dw), v(db), ws.v, nws)
     torch.cuda.synchronize()
     for name, o in (("dx", dx), ("dW", dw), ("dbias", db), ("workspace", ws)):
         assert o is None or o.untouched(), f"{c.id}: bytes next to {name} were written"
@@ -181,14 +124,14 @@ def _run(c):
     if dx is not None:
         route, s = dgrad_route(c.M, c.N, c.K, G) if bf else (TRANSPOSE, 0)
         ref = GemmRef.dgrad(t["dy"], t["w"], y, c.scale, x_mask=x if c.mask_dx else None)
-        ref.check(dx.view, f"{c.id} dx", f"{group} dgrad {route}", n=GemmRef.chain(c.dtype, c.N, s), dyp_rounded=rounded)
+        ref.check(dx.v, f"{c.id} dx", f"{group} dgrad {route}", n=GemmRef.chain(c.dtype, c.N, s), dyp_rounded=rounded)
         if c.mask_dx:
-            assert bool((dx.view[x <= 0] == 0).all()) and 0.3 < (x <= 0).float().mean().item() < 0.7
+            assert bool((dx.v[x <= 0] == 0).all()) and 0.3 < (x <= 0).float().mean().item() < 0.7
     prior = c.accumulate == 1
     if dw is not None:
         route, s = wgrad_route(c.M, c.N, c.K, G) if bf else (TRANSPOSE, 0)
         ref = GemmRef.wgrad(t["dy"], x, y, c.scale, prior=t["prior_w"] if prior else None)
-        ref.check(dw.view, f"{c.id} dW", f"{group} wgrad {route}", n=GemmRef.chain(c.dtype, c.M, s), dyp_rounded=rounded)
+        ref.check(dw.v, f"{c.id} dW", f"{group} wgrad {route}", n=GemmRef.chain(c.dtype, c.M, s), dyp_rounded=rounded)
     if db is not None:
         if bf:      # colsum_kernel: rows of a split in 16 strides, the 16-slot LDS fold, colsum_finish_kernel's fold of the splits
             sp = colsum_splits(c.M, c.N, 8)
@@ -196,7 +139,7 @@ def _run(c):
         else:       # transpose_kernel: one thread adds every fourth row of its column, four partial sums
             n, route = cdiv(c.M, 4) + 4 + 8, TRANSPOSE
         ref = GemmRef.dbias(t["dy"], y, c.scale, prior=t["prior_b"] if prior else None)
-        ref.check(db.view, f"{c.id} dbias", f"{group} dbias {route}", n=n, dyp_rounded=rounded)
+        ref.check(db.v, f"{c.id} dbias", f"{group} dbias {route}", n=n, dyp_rounded=rounded)
     return t, (v(dx), v(dw), v(db))
 
 
@@ -260,11 +203,11 @@ def test_linear_fwd(dtype, M, N, K, route, act, bias, scale):
     if (M, N, K) == (1536, 1024, 3072):
         assert nt_route(M, N, K, K, K, N, dtype, True, G) == P8
     t = GemmRef.inputs(dtype, M, N, K, seed=SEED, device="cuda")
-    y = Carved(M, N, N, dtype, CANARY, extra=1)
-    y.view.fill_(float("nan"))
+    y = Slab((M, N), dtype, CANARY_BYTE, extra=1)
+    y.v.fill_(NAN)
     b = t["bias"] if bias else None
-    _lib.call("mmgl_linear_fwd", None, ptr(t["x"]), ptr(t["w"]), ptr(b), ptr(y.view), M, N, K, act, float(scale), _lib.dtype_code(t["x"]), _lib.stream_ptr())
+    _lib.call("mmgl_linear_fwd", None, ptr(t["x"]), ptr(t["w"]), ptr(b), ptr(y.v), M, N, K, act, float(scale), _lib.dtype_code(t["x"]), _lib.stream_ptr())
     torch.cuda.synchronize()
     assert y.untouched(), "bytes next to the output were written"
-    GemmRef.forward(t["x"], t["w"], b, act, scale).check(y.view, f"{NAME[dtype]}-{M}x{N}x{K}-a{act}{'b' if bias else ''}-s{scale}", f"fwd {route} {NAME[dtype]}",
+    GemmRef.forward(t["x"], t["w"], b, act, scale).check(y.v, f"{NAME[dtype]}-{M}x{N}x{K}-a{act}{'b' if bias else ''}-s{scale}", f"fwd {route} {NAME[dtype]}",
                                                         n=GemmRef.chain(dtype, K), composed=route == TILE128)

@@ -1,4 +1,4 @@
-"""-m gpu: mmgl_rope_inplace / mmgl_rope and mmgl_swiglu_fwd / mmgl_swiglu_bwd (csrc/llama_ops.hip) against helpers.RopeRef and
+"""-m gpu: mmgl_rope_inplace / mmgl_rope and mmgl_swiglu_fwd / mmgl_swiglu_bwd (csrc/llama_ops.hip) against stream_ref.RopeRef and
 SwigluRef -- fp64 references of the storage-rounded operands -- element by element (tests/test_stream_ref_cpu.py shows that the
 comparisons can fail and that torch's fp32 arithmetic stays inside).  The entry points are called directly; operands in NaN slabs,
 outputs in canary slabs with intact guards, two launches bit-equal, both dtypes (VN = 8 elements of a 16-byte vector in bf16, 4 in fp32).
@@ -15,25 +15,14 @@ outputs in canary slabs with intact guards, two launches bit-equal, both dtypes 
 import pytest
 import torch
 
-from helpers import VEC, RopeRef, Slab, SwigluRef
+from bounds import BF16, CANARY, F32, NAME, NAN, VEC, Slab, same
+from stream_ref import RopeRef, SwigluRef
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0
-CANARY = -77.0
-NAN = float("nan")
 BIG_ROWS = 349531                                       # 49,933 x 7: with 3 work items per row 17 past 4096 x 256
 LAYOUTS = [(2, 3), (5, 6)]                              # (nblk, nall)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.dtype == BF16 else torch.int32)
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _rope(src, dst, cs, rows, T, unit, D, ld, nblk, nall, backward, code=None):
@@ -60,13 +49,13 @@ def _rope_case(dtype, rows, T, H, D, nblk, nall, pad, what, group):
     first = buf.v.clone()
     ref = RopeRef(x, cs.v, T, H, D, nblk, nblk)
     ref.check(buf.v, f"{what} inplace", group)
-    assert _same(buf.v[:, ref.width:], x[:, ref.width:]), f"{what}: in place changed a column past the rotated blocks"
-    assert buf.guards_ok() and cs.guards_ok()
+    assert same(buf.v[:, ref.width:], x[:, ref.width:]), f"{what}: in place changed a column past the rotated blocks"
+    assert buf.untouched() and cs.untouched()
     buf.v.copy_(x)
     _rope(buf.v, None, cs.v, rows, T, H, D, ld, nblk, nall, False)
-    assert _same(buf.v, first), f"{what}: two in-place launches differ"
+    assert same(buf.v, first), f"{what}: two in-place launches differ"
     if T == 1:
-        assert _same(buf.v, x), f"{what}: the angle 0 changed a value"
+        assert same(buf.v, x), f"{what}: the angle 0 changed a value"
     # out of place, forward and backward
     src = Slab((rows, ld), dtype, NAN, x)
     for backward in (False, True):
@@ -75,12 +64,12 @@ def _rope_case(dtype, rows, T, H, D, nblk, nall, pad, what, group):
         _rope(src.v, dst2.v, cs.v, rows, T, H, D, ld, nblk, nall, backward)
         ref = RopeRef(x, cs.v, T, H, D, nblk, nall, backward=backward)
         ref.check(dst.v, f"{what} {'bwd' if backward else 'fwd'}", group)
-        assert _same(dst.v[:, :width][:, ~ref.rotated], x[:, :width][:, ~ref.rotated]), f"{what}: the unrotated block is no bit-for-bit copy"
+        assert same(dst.v[:, :width][:, ~ref.rotated], x[:, :width][:, ~ref.rotated]), f"{what}: the unrotated block is no bit-for-bit copy"
         assert bool((dst.v[:, width:] == CANARY).all()), f"{what}: the padding columns were written"
-        assert _same(dst.v, dst2.v), f"{what}: two launches differ"
-        assert _same(src.v, x) and src.guards_ok() and dst.guards_ok() and cs.guards_ok(), f"{what}: the source or a guard changed"
+        assert same(dst.v, dst2.v), f"{what}: two launches differ"
+        assert same(src.v, x) and src.untouched() and dst.untouched() and cs.untouched(), f"{what}: the source or a guard changed"
         if T == 1:
-            assert _same(dst.v[:, :width], x[:, :width]), f"{what}: the angle 0 changed a value"
+            assert same(dst.v[:, :width], x[:, :width]), f"{what}: the angle 0 changed a value"
 
 
 @pytest.mark.parametrize("layout", LAYOUTS, ids=lambda l: f"{l[0]}of{l[1]}")
@@ -153,7 +142,7 @@ def test_rope_refusals(dtype):
     _rope(src.v, dst.v, **dict(ok, rows=0))                                     # rows = 0: OK, nothing written
     _rope(buf.v, None, **dict(ok, rows=0))
     torch.cuda.synchronize()
-    assert buf.untouched() and dst.untouched() and src.guards_ok()
+    assert buf.unwritten() and dst.unwritten() and src.untouched()
 
 
 # ------------------------------------------------------------------------------------------ SwiGLU
@@ -193,10 +182,10 @@ def test_swiglu_bounds(dtype, case):
     ref.check(y.v, "y", what, group)
     ref.check(dgu.v[:, :F], "dg", what, group)
     ref.check(dgu.v[:, F:], "du", what, group)
-    assert _same(y.v, y2.v) and _same(dgu.v, dgu2.v), f"{what}: two launches differ"
-    assert _same(gus.v, gu) and _same(dys.v, dy), f"{what}: an operand changed"
+    assert same(y.v, y2.v) and same(dgu.v, dgu2.v), f"{what}: two launches differ"
+    assert same(gus.v, gu) and same(dys.v, dy), f"{what}: an operand changed"
     for name, s in dict(gu=gus, dy=dys, y=y, dgu=dgu).items():
-        assert s.guards_ok(), f"{what}: written outside {name}"
+        assert s.untouched(), f"{what}: written outside {name}"
 
 
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=NAME.get)
@@ -239,4 +228,4 @@ def test_swiglu_refusals(dtype):
     _swiglu_fwd(gus.v, y.v, 0, F)                                               # M = 0: OK, nothing written
     _swiglu_bwd(dys.v, gus.v, dgu.v, 0, F)
     torch.cuda.synchronize()
-    assert y.untouched() and dgu.untouched() and gus.guards_ok() and dys.guards_ok()
+    assert y.unwritten() and dgu.unwritten() and gus.untouched() and dys.untouched()

@@ -1,6 +1,6 @@
-"""-m gpu: the ten norm entry points of csrc/rownorm.hip against helpers.NormRef -- an fp64 reference of the storage-rounded operands --
+"""-m gpu: the ten norm entry points of csrc/rownorm.hip against row_ref.NormRef -- an fp64 reference of the storage-rounded operands --
 element by element: y and dx within u |want| + 2^-16 mag, the saved mean and rstd within 2^-18 A and 2^-17 rs, dgamma and dbeta within
-2^-24 |want| + max(2^-16, 2 n 2^-24) mag, the stored sum and the dropout mask bit for bit against helpers.hash_keep (the count is in
+2^-24 |want| + max(2^-16, 2 n 2^-24) mag, the stored sum and the dropout mask bit for bit against bounds.hash_keep (the count is in
 NormRef's docstring; tests/test_row_ref_cpu.py shows on the CPU that this comparison fails for a chunk lost from the statistics, a row
 lost from the parameter gradients, dres left out, a mask index one row off).  The entry points are called directly.
 
@@ -27,16 +27,14 @@ one byte less is refused (F), so a change to the dispatch fails loudly instead o
 import pytest
 import torch
 
-from helpers import VEC, ByteSlab, NormRef, Slab
+from bounds import BF16, CANARY, F32, NAME, VEC, ByteSlab, Slab
+from row_ref import NormRef
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0                    # tests/test_row_ref_cpu.py: every wrong reference leaves the bound on >= 25 % at this seed
 DROP_SEED = 11
 EPS = 1e-5
-CANARY = -77.0
 MAXBLK, FWD_MAXBLK, NVMAX = 512, 8192, 4
 
 
@@ -181,9 +179,9 @@ def _run(c, check=True):
             for name in ("dx", "dx_drop", "dgamma", "dbeta"):
                 if outs[name] is not None:
                     ref.check(outs[name].v, name, c.id, grp, tpr)
-        assert ws is None or ws.guards_ok(), f"{c.id}: written past the workspace"
+        assert ws is None or ws.untouched(), f"{c.id}: written past the workspace"
     for k, sl in list(o.items()) + list(outs.items()):
-        assert sl is None or sl.guards_ok(), f"{c.id}: written outside {k}"
+        assert sl is None or sl.untouched(), f"{c.id}: written outside {k}"
     return outs, ref
 
 
@@ -273,7 +271,7 @@ def test_C_element_index_past_2_31():
     _lib.call("mmgl_add_layernorm_fwd", None, ptr(x), ptr(res), ptr(gamma), ptr(beta), ptr(s), ptr(y), P(mean), P(rstd), rows, cols, EPS, 0.3, DROP_SEED,
               _lib.dtype_code(x), _lib.stream_ptr())
     torch.cuda.synchronize()
-    assert mean.guards_ok() and rstd.guards_ok()
+    assert mean.untouched() and rstd.untouched()
     for r0, r1 in ((0, 3), (8191, 8194), (262143, 262147)):
         ref = NormRef(x[r0:r1], gamma, beta, eps=EPS, res=res[r0:r1], p=0.3, seed=DROP_SEED, mask_row_shift=r0)
         what = f"C-ln+add-p0.3-bf16-{rows}x{cols}-rows{r0}:{r1}"
@@ -308,7 +306,7 @@ def test_D_compact_copy(dtype, cols, fused, p):
     if fused:
         ref.check_sum(s.v, what)
     else:
-        assert s.untouched()
+        assert s.unwritten()
     for name, got in (("y", y), ("mean", mean), ("rstd", rstd)):
         ref.check(got.v, name, what, f"D tpr{tpr} nv{nv} {NAME[dtype]}")
     named = {}
@@ -322,7 +320,7 @@ def test_D_compact_copy(dtype, cols, fused, p):
         else:
             assert bool((yc.v[cr] == CANARY).all()), f"{what}: compact row {cr} is named by no map entry and was written"
     for sl in list(o.values()) + [y, yc, s, mean, rstd]:
-        assert sl.guards_ok(), what
+        assert sl.untouched(), what
 
 
 # ------------------------------------------------------------------------------------------ E: determinism
@@ -335,8 +333,7 @@ def test_E_two_launches_bit_equal(case):
     for k in a:
         assert (a[k] is None) == (b[k] is None)
         if a[k] is not None:
-            assert torch.equal(a[k].buf.view(torch.int16 if a[k].buf.dtype == BF16 else torch.int32),
-                               b[k].buf.view(torch.int16 if b[k].buf.dtype == BF16 else torch.int32)), f"{case.id}: {k} differs between two launches"
+            assert torch.equal(a[k].buf, b[k].buf), f"{case.id}: {k} differs between two launches"
 
 
 # ------------------------------------------------------------------------------------------ F: refusals
@@ -359,8 +356,8 @@ def _refused(c, match, forward=True, backward=True, nbytes=None, p=None):
                       ws.nbytes if nbytes is None else nbytes)
     torch.cuda.synchronize()
     for name, sl in dict(y=y, s=s, dx=dx, dd=dd, dg=dg, db=db, ws=ws).items():
-        assert sl.untouched(), f"{c.id}: {name} written by a refused call"
-    assert mean.guards_ok() and rstd.guards_ok()
+        assert sl.unwritten(), f"{c.id}: {name} written by a refused call"
+    assert mean.untouched() and rstd.untouched()
 
 
 @pytest.mark.parametrize("kind,fused", [("ln", False), ("rms", False), ("ln", True), ("rms", True)])
@@ -396,4 +393,4 @@ def test_F_p_drop_1_and_crows_past_rows():
                   _lib.ptr(rowmap), P(mean), P(rstd), rows, cols, rows + 1, EPS, 0.0, DROP_SEED, code, st)
     torch.cuda.synchronize()
     for sl in (y, yc, s, mean, rstd):
-        assert sl.untouched()
+        assert sl.unwritten()

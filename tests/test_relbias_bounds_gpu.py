@@ -12,15 +12,12 @@ import ctypes
 import pytest
 import torch
 
-from helpers import ByteSlab, Slab
+from bounds import BF16, F32, NAME, NAN, ByteSlab, Slab
 from relbias_ref import RelBiasRef
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 B, H, D, NB = 2, 3, 64, 32
-NAN = float("nan")
 BIDIR = [(1, 1), (17, 40), (64, 64), (65, 129), (130, 70)]
 CAUSAL = [1, 63, 65, 129]
 
@@ -60,7 +57,7 @@ def _run(dtype, cpu, key_valid, table, bucket_of, causal, p_drop=0.0, seed=0, ba
             got["dtable"] = dtab.v
     torch.cuda.synchronize()
     for s in slabs:
-        assert s.guards_ok(), "a canary next to a result or the workspace was overwritten"
+        assert s.untouched(), "a canary next to a result or the workspace was overwritten"
     return got, slabs
 
 
@@ -99,7 +96,7 @@ def test_causal_bounds(dtype, T):
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
 @pytest.mark.parametrize("T,S,causal", [(65, 129, False), (65, 65, True)])
 def test_dropout_follows_the_counter_hash(dtype, T, S, causal):
-    """p_drop = 0.3 with a fixed seed: the reference drops the probabilities helpers.hash_keep names; a kernel with another index
+    """p_drop = 0.3 with a fixed seed: the reference drops the probabilities bounds.hash_keep names; a kernel with another index
     order, threshold or scale leaves the bound everywhere."""
     cpu = RelBiasRef.inputs(dtype, B, T, S, H, D, seed=11)
     key_valid, table, bucket_of = RelBiasRef.mask(B, S, "M1"), _table(), _bucket(T, S, causal)
@@ -155,7 +152,7 @@ def test_unsupported_arguments_launch_nothing():
                                      ptr(dv.v), None, ws.ptr(), nbytes, B, H, T, S, d, 0, H * d, H * d, causal, 0.0, 0, _lib.BF16, None)
         assert rc == _lib._ERR_UNSUPPORTED
         torch.cuda.synchronize()
-        assert all(s.untouched() for s in (out, lse, dq, dk, dv, ws))
+        assert all(s.unwritten() for s in (out, lse, dq, dk, dv, ws))
 
 
 def test_op_under_autograd_matches_the_reference():

@@ -1,5 +1,5 @@
 """CPU: the comparisons of tests/test_norm_bounds_gpu.py, tests/test_cross_entropy_bounds_gpu.py and
-tests/test_gated_residual_bounds_gpu.py can fail, and do not fail an honest kernel.  From helpers.NormRef, CrossEntropyRef, GatedRef and
+tests/test_gated_residual_bounds_gpu.py can fail, and do not fail an honest kernel.  From row_ref.NormRef, CrossEntropyRef, GatedRef and
 hash_keep alone (fp64, no kernel), at the inputs and the seed of the GPU files:
 
   * a deliberately wrong reference of each defect the row kernels could have -- a 16-byte chunk lost from the norm statistics or from
@@ -15,10 +15,9 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import VEC, CrossEntropyRef, GatedRef, NormRef, drop_threshold, hash32_int, hash_keep
+from bounds import BF16, F32, NAME, VEC, drop_threshold, hash32_int, hash_keep
+from row_ref import CrossEntropyRef, GatedRef, NormRef
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0                                    # the GPU files' seed
 NORM_SHAPES = [(BF16, 5, 512), (BF16, 5, 1032), (BF16, 5, 4104), (BF16, 5, 8192), (BF16, 125, 2056), (F32, 5, 260), (F32, 5, 4096), (F32, 125, 1028)]
 CE_V = [(BF16, 1001), (BF16, 8192), (BF16, 16448), (F32, 1001), (F32, 4096), (F32, 8224)]

@@ -1,4 +1,4 @@
-"""-m gpu: the causal self-attention kernels (csrc/selfattn32.hip, csrc/selfattn.hip) against helpers.SelfAttnRef -- an fp64 reference of
+"""-m gpu: the causal self-attention kernels (csrc/selfattn32.hip, csrc/selfattn.hip) against attn_ref.SelfAttnRef -- an fp64 reference of
 the storage-rounded operands -- element by element: out, lse, dq, dk, dv each within u |want| + (c + n 2^-24 S) mag (the count is in
 SelfAttnRef's docstring; tests/test_selfattn_ref_cpu.py shows on the CPU that this comparison fails for a mask or head mapping that is
 off by one).  Every case uses the recency-ramp inputs (the newest allowed key carries ~40 % of a row), and the forward also a plain
@@ -20,13 +20,12 @@ WikiWeb2M layout prompt | pad | summary | pad with hole edges at 70 and T - T //
 import pytest
 import torch
 
-from helpers import SelfAttnRef
+from attn_ref import SelfAttnRef
+from bounds import BF16, F32, NAME, NAN, Slab
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
 SEED = 2                    # tests/test_selfattn_ref_cpu.py: the seed at which every wrong reference leaves the bound on >= 40 %
-NAME = {BF16: "bf16", F32: "f32"}
 
 
 def _case(group, dtype, D, T, layout="M0", L=None, B=2, H=3, Hkv=None, P=0):
@@ -158,7 +157,8 @@ SENTINEL = 777.0
 def _windowed(c, fill):
     """The call through mmgl_selfattn_prefix_fwd / _bwd (P = 0: they take separate row strides for q and k / v) with every operand a
     window of a larger buffer: TAIL rows behind the last sample and the pad columns of the free row strides hold `fill` on the
-    inputs and SENTINEL on the outputs; the key mask has TAIL more bytes, all 1.  Returns the payloads and the output buffers."""
+    inputs and SENTINEL on the outputs, as do the guards of each Slab; the key mask has TAIL more bytes, all 1.  Returns the payloads
+    and the output slabs."""
     from mmgl_amd import _lib
     from mmgl_amd._lib import ptr
     group, dtype, D, T, layout, L, B, H, Hkv, P = c
@@ -167,20 +167,18 @@ def _windowed(c, fill):
     q, k, v, dout, am = _inputs(c)
 
     def window(x, ld):
-        buf = torch.full((rows + TAIL, ld), fill, dtype=dtype, device="cuda")
-        buf[:rows, :HD] = x.reshape(rows, HD)
-        return buf
+        return Slab((rows, HD), dtype, fill, x.reshape(rows, HD), ld=ld, extra=TAIL).v
 
     def target(ld):
-        buf = torch.full((rows + TAIL, ld), SENTINEL, dtype=dtype, device="cuda")
-        buf[:rows, :HD] = float("nan")
-        return buf
+        s = Slab((rows, HD), dtype, SENTINEL, ld=ld, extra=TAIL)
+        s.v.fill_(NAN)
+        return s
 
     qb, kb, vb, gb = window(q, ldq), window(k, ldk), window(v, ldk), window(dout, HD)
     amb = torch.ones(rows + TAIL, dtype=torch.uint8, device="cuda")
     amb[:rows] = am.reshape(-1)
-    outb, dqb, dkb, dvb = target(HD), target(ldgq), target(ldgk), target(ldgk)
-    lseb = torch.full((B * H * T + TAIL,), SENTINEL, dtype=torch.float32, device="cuda")
+    outs = dict(out=target(HD), lse=Slab((B * H * T,), F32, SENTINEL), dq=target(ldgq), dk=target(ldgk), dv=target(ldgk))
+    outb, lseb, dqb, dkb, dvb = (outs[n].v for n in SelfAttnRef.NAMES)
     code, st = _lib.dtype_code(qb), _lib.stream_ptr()
     _lib.call("mmgl_selfattn_prefix_fwd", None, ptr(qb), ptr(kb), ptr(vb), ptr(amb), ptr(outb), ptr(lseb), B, H, T, 0, D, ldq, ldk, code, st)
     nbytes = _lib.lib().mmgl_selfattn_bwd_workspace(B, H, T)
@@ -188,29 +186,23 @@ def _windowed(c, fill):
     _lib.call("mmgl_selfattn_prefix_bwd", None, ptr(gb), ptr(qb), ptr(kb), ptr(vb), ptr(outb), ptr(lseb), ptr(amb), ptr(dqb), ptr(dkb),
               ptr(dvb), ptr(ws), nbytes, B, H, T, 0, D, ldq, ldk, ldgq, ldgk, code, st)
     torch.cuda.synchronize()
-    payload = tuple(b[:rows, :HD].reshape(B, T, HD) for b in (outb, dqb, dkb, dvb))
-    got = (payload[0], lseb[:B * H * T].view(B, H, T)) + payload[1:]
-    return (q, k, v, dout, am), got, dict(out=outb, lse=lseb, dq=dqb, dk=dkb, dv=dvb)
+    payload = tuple(b.reshape(B, T, HD) for b in (outb, dqb, dkb, dvb))
+    got = (payload[0], lseb.view(B, H, T)) + payload[1:]
+    return (q, k, v, dout, am), got, outs
 
 
 @pytest.mark.parametrize("case", CASES_F, ids=_id)
 def test_F_nothing_outside_the_tensors(case):
     group, dtype, D, T, layout, L, B, H, Hkv, P = case
-    HD, rows = H * D, B * T
     (q, k, v, dout, am), clean, _ = _windowed(case, 0.0)
     SelfAttnRef(q, k, v, am, dout, H).check(clean, _id(case), "F")
     for fill in (float("nan"), float("inf")):
-        _, got, bufs = _windowed(case, fill)
+        _, got, outs = _windowed(case, fill)
         for name, a, b in zip(SelfAttnRef.NAMES, got, clean):
             assert torch.isfinite(a.float()).all(), f"{name}: {fill} behind the last sample or in a pad column reached the result"
             assert torch.equal(a, b), f"{name}: differs from the run with zeros outside the tensors (fill {fill})"
-        for name, buf in bufs.items():
-            sent = torch.full_like(buf, SENTINEL)
-            if name == "lse":
-                assert torch.equal(buf[B * H * T:], sent[B * H * T:]), "lse: written behind the last row"
-            else:
-                assert torch.equal(buf[rows:], sent[rows:]), f"{name}: rows behind the last sample were written"
-                assert torch.equal(buf[:rows, HD:], sent[:rows, HD:]), f"{name}: a pad column was written"
+        for name, s in outs.items():
+            assert s.untouched(), f"{name}: rows behind the last sample (lse: the last row) or a pad column were written"
 
 
 # ------------------------------------------------------------------------------------------ G: determinism

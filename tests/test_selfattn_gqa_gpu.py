@@ -21,7 +21,7 @@ GENERIC_CASES = [(dt, D, H, Hkv, 70) for (dt, D) in ((F32, 16), (F32, 32), (BF16
 CASES = SA32_CASES + GENERIC_CASES
 B = 2
 ORACLE_TOL = {F32: 1e-3, BF16: 2e-2}           # tests/test_selfattn_gpu.py
-U = {F32: 2.0 ** -23, BF16: 2.0 ** -8}         # helpers.SkinnyRef
+U = {F32: 2.0 ** -23, BF16: 2.0 ** -8}         # decode_ref.SkinnyRef
 
 
 def _id(c):

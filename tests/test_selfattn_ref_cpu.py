@@ -1,4 +1,4 @@
-"""helpers.SelfAttnRef, the fp64 reference behind tests/test_selfattn_bounds_gpu.py, on the CPU (no GPU needed):
+"""attn_ref.SelfAttnRef, the fp64 reference behind tests/test_selfattn_bounds_gpu.py, on the CPU (no GPU needed):
 
 (a) it IS the oracle's attention: oracle.lm_ref.decoder_self_mask + attention_core under autograd in fp64, to 1e-12;
 (b) the comparison it carries can fail: for every mask layout of the GPU file, deliberately wrong references (a key leaking across
@@ -25,9 +25,9 @@ import functools
 import pytest
 import torch
 
-from helpers import SelfAttnRef
+from attn_ref import SelfAttnRef
+from bounds import BF16
 
-BF16 = torch.bfloat16
 CAP = 0.40
 B = 2
 SEED = 2            # seeds 0, 1 and 3 leave one to three key-dropped references at 37-39 %; the cap stays, the seed moved

@@ -2,11 +2,11 @@
 (tests/test_stream_ref_cpu.py shows that the comparisons can fail and that torch's fp32 arithmetic stays inside).  Called directly;
 operands in NaN slabs, outputs in canary slabs with intact guards; VN = 8 elements of a 16-byte vector in bf16, 4 in fp32.
 
-  activation  mmgl_activation_fwd against helpers.ActRef: 4 activations x 2 dtypes, n in {1, VN - 1, VN, VN + 1, 65 VN + 3,
+  activation  mmgl_activation_fwd against stream_ref.ActRef: 4 activations x 2 dtypes, n in {1, VN - 1, VN, VN + 1, 65 VN + 3,
               2048 * 256 VN + 3 VN + (VN - 1)} (nothing but the tail loop, one vector, vectors and a tail, past the 2048-block cap with a
               tail); randn * 3 with +-{0, 1e-30, 5, 9, 30, 100, 1e13, 1e20} planted; finite in, finite out; in place bit-equal.
   scale       mmgl_scale, the same n, s in {1/3, 0, 1, -2^-20}: bit-equal to torch's fp32 product, in place and out of place.
-  AdamW       mmgl_adamw_step against helpers.AdamWRef, one step from the state handed in: n in {1, 255, 257, 10007, 2048 * 256 + 259},
+  AdamW       mmgl_adamw_step against stream_ref.AdamWRef, one step from the state handed in: n in {1, 255, 257, 10007, 2048 * 256 + 259},
               an fp32 parameter / bf16 + fp32 master / bf16 alone, betas (0.9, 0.95) and (0.9, 0.999), step in {1, 2, 3, 1000},
               wd in {0, 0.01}, grad_scale in {1, 1/8, 1/3}, p = 0 and p = randn, gradients 0, 1e-20, 1e4 planted.
   interleave  mmgl_neighbor_interleave_fwd / bwd, bit-exact against torch indexing: B = 2, Nt in {1, 3}, Ni in {0, 2}, one 16-byte
@@ -17,24 +17,13 @@ operands in NaN slabs, outputs in canary slabs with intact guards; VN = 8 elemen
 import pytest
 import torch
 
-from helpers import VEC, ActRef, AdamWRef, Slab, _report
+from bounds import BF16, CANARY, F32, NAME, NAN, VEC, Slab, bits, check_bound, code, same
+from stream_ref import ActRef, AdamWRef
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0
-CANARY = -77.0
-NAN = float("nan")
 ACTS = {1: "relu", 2: "gelu", 3: "quick_gelu", 4: "gelu_tanh"}
-
-
-def _bits(t):
-    return t.contiguous().view({BF16: torch.int16, F32: torch.int32}.get(t.dtype, t.dtype))
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _sizes(dtype):
@@ -52,11 +41,6 @@ def _call(name, *args):
     _lib.call(name, None, *[_lib.ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args], _lib.stream_ptr())
 
 
-def _code(dtype):
-    from mmgl_amd import _lib
-    return _lib.BF16 if dtype == BF16 else _lib.F32
-
-
 # ------------------------------------------------------------------------------------------ activation
 @pytest.mark.parametrize("act", list(ACTS), ids=ACTS.get)
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=NAME.get)
@@ -65,12 +49,12 @@ def test_activation_bounds(dtype, act):
         x = ActRef.inputs(dtype, n, seed=SEED).cuda()
         assert torch.isfinite(x.float()).all()
         xs, y, z = Slab((n,), dtype, NAN, x), Slab((n,), dtype, CANARY), Slab((n,), dtype, CANARY, x)
-        _call("mmgl_activation_fwd", xs.v, y.v, n, act, _code(dtype))
-        _call("mmgl_activation_fwd", z.v, z.v, n, act, _code(dtype))            # in place, as ops.activation_ calls it
+        _call("mmgl_activation_fwd", xs.v, y.v, n, act, code(dtype))
+        _call("mmgl_activation_fwd", z.v, z.v, n, act, code(dtype))            # in place, as ops.activation_ calls it
         what = f"{NAME[dtype]}-{ACTS[act]}-n{n}"
         ActRef(x, act).check(y.v, what, _group(dtype, n))
-        assert _same(y.v, z.v), f"{what}: in place differs from out of place"
-        assert _same(xs.v, x) and xs.guards_ok() and y.guards_ok() and z.guards_ok(), f"{what}: the operand or a guard changed"
+        assert same(y.v, z.v), f"{what}: in place differs from out of place"
+        assert same(xs.v, x) and xs.untouched() and y.untouched() and z.untouched(), f"{what}: the operand or a guard changed"
 
 
 def test_activation_ops_route_and_refusals():
@@ -84,7 +68,7 @@ def test_activation_ops_route_and_refusals():
             _call("mmgl_activation_fwd", *args)
     _call("mmgl_activation_fwd", xs.v, y.v, 0, 2, 0)                            # n = 0: OK, nothing written
     torch.cuda.synchronize()
-    assert y.untouched() and xs.guards_ok()
+    assert y.unwritten() and xs.untouched()
 
 
 # ------------------------------------------------------------------------------------------ scale
@@ -95,23 +79,23 @@ def test_scale_is_torchs_fp32_product(dtype):
         for s in (1 / 3, 0.0, 1.0, -2.0 ** -20):
             st = Slab((1,), F32, NAN, torch.tensor([s], device="cuda"))
             xs, y, z = Slab((n,), dtype, NAN, x), Slab((n,), dtype, CANARY), Slab((n,), dtype, CANARY, x)
-            _call("mmgl_scale", xs.v, st.v, y.v, n, _code(dtype))
-            _call("mmgl_scale", z.v, st.v, z.v, n, _code(dtype))
+            _call("mmgl_scale", xs.v, st.v, y.v, n, code(dtype))
+            _call("mmgl_scale", z.v, st.v, z.v, n, code(dtype))
             want = (x.float() * st.v[0]).to(dtype)
             what = f"{NAME[dtype]}-n{n}-s{s:.3g}"
-            bad = int((_bits(y.v) != _bits(want)).sum())
+            bad = int((bits(y.v) != bits(want)).sum())
             print(f"[bound {_group(dtype, n)}] scale {what}: {bad} of {n} elements differ from torch's fp32 product")
-            assert bad == 0 and _same(z.v, want), f"{what}: {bad} elements differ, or in place differs"
-            assert _same(xs.v, x) and all(t.guards_ok() for t in (xs, y, z, st))
+            assert bad == 0 and same(z.v, want), f"{what}: {bad} elements differ, or in place differs"
+            assert same(xs.v, x) and all(t.untouched() for t in (xs, y, z, st))
     xs, y = Slab((9,), dtype, NAN, torch.ones(9, dtype=dtype, device="cuda")), Slab((9,), dtype, CANARY)
     st = torch.ones(1, device="cuda")
-    for args, msg in [((None, st, y.v, 9, _code(dtype)), "null pointer"), ((xs.v, None, y.v, 9, _code(dtype)), "null pointer"),
-                      ((xs.v, st, None, 9, _code(dtype)), "null pointer"), ((xs.v, st, y.v, 9, 7), "bad dtype")]:
+    for args, msg in [((None, st, y.v, 9, code(dtype)), "null pointer"), ((xs.v, None, y.v, 9, code(dtype)), "null pointer"),
+                      ((xs.v, st, None, 9, code(dtype)), "null pointer"), ((xs.v, st, y.v, 9, 7), "bad dtype")]:
         with pytest.raises(ValueError, match=msg):
             _call("mmgl_scale", *args)
-    _call("mmgl_scale", xs.v, st, y.v, 0, _code(dtype))
+    _call("mmgl_scale", xs.v, st, y.v, 0, code(dtype))
     torch.cuda.synchronize()
-    assert y.untouched()
+    assert y.unwritten()
 
 
 # ------------------------------------------------------------------------------------------ AdamW
@@ -131,7 +115,7 @@ def _adam_state(layout, n, step, p_zero):
 
 
 def _adam_call(param, master, grad, m, v, n, b1, b2, wd, step, gs, dtype):
-    _call("mmgl_adamw_step", param, master, grad, m, v, n, LR, b1, b2, EPS, wd, step, gs, _code(dtype))
+    _call("mmgl_adamw_step", param, master, grad, m, v, n, LR, b1, b2, EPS, wd, step, gs, code(dtype))
 
 
 @pytest.mark.parametrize("step", [1, 2, 3, 1000])
@@ -150,12 +134,12 @@ def test_adamw_one_step(layout, n, betas, step):
             errs[k].append(ref.err(got, k))
             bounds[k].append(ref.bound(k))
         if ms is not None:
-            assert _same(ps.v, ms.v.to(BF16)), f"wd={wd} gs={gs} p0={pz}: the bf16 parameter is not the rounded master"
-        assert _same(gsl.v, g) and all(s.guards_ok() for s in (ps, m_, v_, gsl) + (() if ms is None else (ms,))), "an operand or a guard changed"
+            assert same(ps.v, ms.v.to(BF16)), f"wd={wd} gs={gs} p0={pz}: the bf16 parameter is not the rounded master"
+        assert same(gsl.v, g) and all(s.untouched() for s in (ps, m_, v_, gsl) + (() if ms is None else (ms,))), "an operand or a guard changed"
     what = f"{layout}-n{n}-betas{betas[1]}-step{step}"
     group = f"{'one block' if n <= 256 else 'capped, second trip' if n > 2048 * 256 else 'blocks'} {layout}"
     for k in "mvp":
-        _report(torch.stack(errs[k]), torch.stack(bounds[k]), f"adamw {what} {k}", group)
+        check_bound(torch.stack(errs[k]), None, torch.stack(bounds[k]), f"adamw {what} {k}", group)
 
 
 def test_adamw_refusals():
@@ -225,16 +209,16 @@ def test_interleave_is_exact(dtype, Nt, Ni, kind):
         ts, vs, ds = Slab(text.shape, dtype, NAN, text), (Slab(vis.shape, dtype, NAN, vis) if Ni else None), Slab(dout.shape, dtype, NAN, dout)
         out, valid = Slab((B, N, n_tok, d), dtype, CANARY), Slab((B, N, n_tok), torch.uint8, 0xA5)
         dtext, dvis = Slab(text.shape, dtype, CANARY), (Slab(vis.shape, dtype, CANARY) if Ni else None)
-        _call("mmgl_neighbor_interleave_fwd", ts.v, vs.v if Ni else None, tl, il, tp, ip, out.v, valid.v, B, Nt, Ni, n_tok, d, _code(dtype))
-        _call("mmgl_neighbor_interleave_bwd", ds.v, tl, il, dtext.v, dvis.v if Ni else None, B, Nt, Ni, n_tok, d, _code(dtype))
+        _call("mmgl_neighbor_interleave_fwd", ts.v, vs.v if Ni else None, tl, il, tp, ip, out.v, valid.v, B, Nt, Ni, n_tok, d, code(dtype))
+        _call("mmgl_neighbor_interleave_bwd", ds.v, tl, il, dtext.v, dvis.v if Ni else None, B, Nt, Ni, n_tok, d, code(dtype))
         w_out, w_valid, w_dt, w_dv = _interleave_want(text, vis, tl, il, tp, ip, dout)
         what = f"{NAME[dtype]}-Nt{Nt}-Ni{Ni}-{kind}-{n_tok}x{d}"
-        bad = [int((_bits(a) != _bits(b)).sum()) for a, b in ((out.v, w_out), (valid.v, w_valid), (dtext.v, w_dt))] + ([int((_bits(dvis.v) != _bits(w_dv)).sum())] if Ni else [])
+        bad = [int((bits(a) != bits(b)).sum()) for a, b in ((out.v, w_out), (valid.v, w_valid), (dtext.v, w_dt))] + ([int((bits(dvis.v) != bits(w_dv)).sum())] if Ni else [])
         print(f"[bound {seam} {NAME[dtype]}] interleave {what}: elements that differ (out, valid, dtext, dvis) {bad}")
         assert not any(bad), f"{what}: elements that differ from plain indexing (out, valid, dtext, dvis): {bad}"
         slabs = [ts, ds, out, valid, dtext] + ([vs, dvis] if Ni else [])
-        assert all(s.guards_ok() for s in slabs), f"{what}: a guard changed"
-        assert _same(ts.v, text) and _same(ds.v, dout)
+        assert all(s.untouched() for s in slabs), f"{what}: a guard changed"
+        assert same(ts.v, text) and same(ds.v, dout)
 
 
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=NAME.get)
@@ -245,11 +229,11 @@ def test_interleave_refusals(dtype):
         size = (B, Nt, max(n_tok, 1), max(d, 1))
         text, out, valid, dtext = Slab(size, dtype, NAN), Slab(size, dtype, CANARY), Slab(size[:3], torch.uint8, 0xA5), Slab(size, dtype, CANARY)
         with pytest.raises(ValueError, match=msg):
-            _call("mmgl_neighbor_interleave_fwd", text.v, None, tl, None, tp, None, out.v, valid.v, B, Nt, Ni, n_tok, d, _code(dtype))
+            _call("mmgl_neighbor_interleave_fwd", text.v, None, tl, None, tp, None, out.v, valid.v, B, Nt, Ni, n_tok, d, code(dtype))
         with pytest.raises(ValueError, match=msg):
-            _call("mmgl_neighbor_interleave_bwd", out.v, tl, None, dtext.v, None, B, Nt, Ni, n_tok, d, _code(dtype))
+            _call("mmgl_neighbor_interleave_bwd", out.v, tl, None, dtext.v, None, B, Nt, Ni, n_tok, d, code(dtype))
         torch.cuda.synchronize()
-        assert out.untouched() and valid.untouched() and dtext.untouched(), f"a refused call ({n_tok} x {d}) wrote"
+        assert out.unwritten() and valid.unwritten() and dtext.unwritten(), f"a refused call ({n_tok} x {d}) wrote"
     size = (B, Nt, 1, vn)
     text, out, valid, dtext = Slab(size, dtype, NAN), Slab(size, dtype, CANARY), Slab(size[:3], torch.uint8, 0xA5), Slab(size, dtype, CANARY)
     with pytest.raises(ValueError, match="bad dtype"):                          # refused before the forward clears its outputs
@@ -257,11 +241,11 @@ def test_interleave_refusals(dtype):
     with pytest.raises(ValueError, match="bad dtype"):
         _call("mmgl_neighbor_interleave_bwd", out.v, tl, None, dtext.v, None, B, Nt, Ni, 1, vn, 7)
     with pytest.raises(ValueError, match="null pointer"):
-        _call("mmgl_neighbor_interleave_fwd", text.v, None, tl, None, tp, None, None, valid.v, B, Nt, Ni, 1, vn, _code(dtype))
+        _call("mmgl_neighbor_interleave_fwd", text.v, None, tl, None, tp, None, None, valid.v, B, Nt, Ni, 1, vn, code(dtype))
     with pytest.raises(ValueError, match="null pointer"):
-        _call("mmgl_neighbor_interleave_bwd", out.v, tl, None, None, None, B, Nt, Ni, 1, vn, _code(dtype))
+        _call("mmgl_neighbor_interleave_bwd", out.v, tl, None, None, None, B, Nt, Ni, 1, vn, code(dtype))
     torch.cuda.synchronize()
-    assert out.untouched() and valid.untouched() and dtext.untouched()
+    assert out.unwritten() and valid.unwritten() and dtext.unwritten()
 
 
 # ------------------------------------------------------------------------------------------ position ids
@@ -289,7 +273,7 @@ def test_position_ids_are_the_cumsum(T):
             bad = [int((out.v != want).sum()), int((ops.position_ids(m) != want).sum()), int((ops.position_ids(m.bool()) != want).sum())]
             print(f"[bound {seam}] position_ids T{T}-B{B}-{'all rows' if B == 5 else ['ones', 'zeros', 'left', 'right', 'holes'][k]}: elements that differ (direct, int64, bool) {bad}")
             assert not any(bad), f"T={T} B={B}: elements that differ from cumsum (direct, int64 mask, bool mask): {bad}"
-            assert ms.guards_ok() and out.guards_ok() and torch.equal(ms.v, m)
+            assert ms.untouched() and out.untouched() and torch.equal(ms.v, m)
 
 
 def test_position_ids_refusals():
@@ -298,4 +282,4 @@ def test_position_ids_refusals():
         with pytest.raises(ValueError, match="bad arguments"):
             _call("mmgl_position_ids", *args)
     torch.cuda.synchronize()
-    assert out.untouched()
+    assert out.unwritten()

@@ -1,5 +1,5 @@
 """CPU: the comparisons of tests/test_llama_ops_bounds_gpu.py and tests/test_stream_bounds_gpu.py can fail, and do not fail an honest
-kernel.  From helpers.RopeRef, SwigluRef, ActRef and AdamWRef alone (fp64, no kernel), at the small cases of the GPU files, their
+kernel.  From stream_ref.RopeRef, SwigluRef, ActRef and AdamWRef alone (fp64, no kernel), at the small cases of the GPU files, their
 inputs and their seed:
 
   * the same operations in torch's fp32 arithmetic, in the kernels' operation order (the exponential as an exact 2^x of the argument
@@ -16,10 +16,10 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import VEC, ActRef, AdamWRef, GemmRef, RopeRef, SwigluRef, _report
+from bounds import BF16, F32, NAME, VEC, check_bound
+from gemm_ref import GemmRef
+from stream_ref import ActRef, AdamWRef, RopeRef, SwigluRef
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0
 LOG2E = np.float32(1.4426950408889634)
 ROPE_LAYOUTS = [(2, 3), (5, 6)]                         # (nblk, nall): multi-head / G = 1, and grouped-query with G = 4
@@ -199,7 +199,7 @@ def test_adamw(n, layout):
                 pn = pn.to(BF16)
             what = f"torch fp32 {layout} n={n} betas=({b1},{b2}) step={step} wd={wd} gs={gsc:.3f} {'p=0' if p_zero else 'p~1'}"
             for name, got in dict(m=mn, v=vn, p=pn).items():
-                assert _report(ref.err(got, name)[:, None], ref.bound(name)[:, None], f"{what} {name}", "cpu") <= 1.0
+                assert check_bound(ref.err(got, name)[:, None], None, ref.bound(name)[:, None], f"{what} {name}", "cpu") <= 1.0
             if n < 255 or layout == "bf16":                                       # the wrong references: the fp32 layouts at a few hundred elements
                 continue
             live = 1 - AdamWRef.f32(b2) ** (step - 1) < 0.999                       # (0.95 at step 1000: both corrections are 1 to 1e-22, nothing to tell apart)

@@ -1,4 +1,4 @@
-"""CPU: the comparison tests/test_gemm_skinny_w8_gpu.py makes can fail.  From the references alone (helpers.SkinnyRef on the dequantised
+"""CPU: the comparison tests/test_gemm_skinny_w8_gpu.py makes can fail.  From the references alone (decode_ref.SkinnyRef on the dequantised
 weight against the same reference of a wrong kernel), each of the mistakes a kernel on FP8 codes can make moves at least 25 % of the
 elements out of the per-element bound  u |want| + 2^-16 mag:
   a dropped K unit (the last 128 codes of every row), an exponent off by one, codes read as e5m2, the two halves of a 32-bit code word
@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import w8_ref
-from helpers import SkinnyRef
+from decode_ref import SkinnyRef
 
 SHAPES = [(17, 768, 1152), (33, 24, 640), (8, 5, 200)]
 

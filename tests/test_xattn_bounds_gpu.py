@@ -1,4 +1,4 @@
-"""-m gpu: the masked cross-attention core (csrc/xattn.hip) against helpers.XAttnRef -- an fp64 reference of the storage-rounded
+"""-m gpu: the masked cross-attention core (csrc/xattn.hip) against attn_ref.XAttnRef -- an fp64 reference of the storage-rounded
 operands -- element by element: out, lse, dq, dk, dv each within u |want| + (c + n 2^-24 (S_i + ln S)) mag (the count is in the
 docstrings of XAttnRef and SelfAttnRef; tests/test_xattn_ref_cpu.py shows on the CPU that this comparison fails for a dropped key, a
 shifted mask, a wrong head, a lost query row or the wrong rule for a sample without a valid key).  mmgl_xattn_fwd / mmgl_xattn_bwd are
@@ -21,22 +21,17 @@ paths they were chosen for.
 import pytest
 import torch
 
-from helpers import XAttnRef
+from attn_ref import XAttnRef
+from bounds import BF16, CANARY_BYTE, F32, NAME, NAN, NAN_BYTE, ByteSlab, Slab, esz, nan
 
 pytestmark = pytest.mark.gpu
 
-BF16, F32 = torch.bfloat16, torch.float32
-NAME = {BF16: "bf16", F32: "f32"}
 SEED = 0                    # tests/test_xattn_ref_cpu.py: every wrong reference leaves the bound on >= 25 % at this seed
 ONE_WAVE, MULTI_WAVE, TWO_KERNEL = "one-wave", "multi-wave", "two-kernel"
 MAX_LDS = 160 * 1024        # mmgl_set_lds
 
 
 # ------------------------------------------------------------------------------------------ csrc/xattn.hip's plans, restated
-def _esz(dtype):
-    return 2 if dtype == BF16 else 4
-
-
 def _nsb(S):
     """DISPATCH_NSB: 16-key blocks of the instantiation that serves S keys."""
     return 2 if S <= 32 else 4 if S <= 64 else 8 if S <= 128 else 16
@@ -44,7 +39,7 @@ def _nsb(S):
 
 def _qt(dtype, D, S, work=1):
     """XC::QT: 16-row query tiles per iteration (work = 1 forward, 2 dQ)."""
-    return 2 if work * _nsb(S) * (D // 16) * (_esz(dtype) // 2) <= 32 else 1
+    return 2 if work * _nsb(S) * (D // 16) * (esz(dtype) // 2) <= 32 else 1
 
 
 def _route(dtype, D, S):
@@ -91,7 +86,7 @@ def _workspace(B, H, T, S, D):
 def _lds_fwd(dtype, D, S):
     """launch_fwd / the dQ kernel: XC::KV_BYTES + SPAD."""
     spad, dpad = 16 * _nsb(S), (D + 31) // 32 * 32
-    return _esz(dtype) * (spad * dpad + (spad * (dpad + 16) if dtype == BF16 else spad * dpad)) + spad
+    return esz(dtype) * (spad * dpad + (spad * (dpad + 16) if dtype == BF16 else spad * dpad)) + spad
 
 
 # ------------------------------------------------------------------------------------------ cases
@@ -148,20 +143,16 @@ def _bwd(c, q, k, v, dout, am, lse, dq, dk, dv, ws):
               B, H, T, S, D, _lib.dtype_code(q), _lib.stream_ptr())
 
 
-def _nan(*shape, dtype):
-    return torch.full(shape, float("nan"), dtype=dtype, device="cuda")
-
-
 def _call(c, q, k, v, dout, am):
     """out, lse, dq, dk, dv of the raw entry points; every result buffer holds NaN before the call, the workspace NaN bit patterns."""
     from mmgl_amd import _lib
     group, dtype, D, S, T, B, H, first = c
-    out, lse = _nan(B, T, H * D, dtype=dtype), _nan(B, H, T, dtype=F32)
+    out, lse = nan(B, T, H * D, dtype=dtype), nan(B, H, T, dtype=F32)
     _fwd(c, q, k, v, am, out, lse)
     nws = _lib.lib().mmgl_xattn_bwd_workspace(B, H, T, S, D)
     assert nws == _workspace(B, H, T, S, D), "mmgl_xattn_bwd_workspace is not the restated plan's: the cases may have left their paths"
     ws = torch.full((nws,), 0xFF, dtype=torch.uint8, device="cuda")
-    dq, dk, dv = _nan(B, T, H * D, dtype=dtype), _nan(B, S, H * D, dtype=dtype), _nan(B, S, H * D, dtype=dtype)
+    dq, dk, dv = nan(B, T, H * D, dtype=dtype), nan(B, S, H * D, dtype=dtype), nan(B, S, H * D, dtype=dtype)
     _bwd(c, q, k, v, dout, am, lse, dq, dk, dv, ws)
     torch.cuda.synchronize()
     return out, lse, dq, dk, dv
@@ -202,12 +193,12 @@ def test_A_refused_before_any_launch(dtype, D, S):
     c = _case("A", dtype, D, S)
     group, dtype, D, S, T, B, H, first = c
     q, k, v, dout, am = _inputs(c)
-    out, lse = _nan(B, T, H * D, dtype=dtype), _nan(B, H, T, dtype=F32)
+    out, lse = nan(B, T, H * D, dtype=dtype), nan(B, H, T, dtype=F32)
     with pytest.raises(ValueError, match="LDS"):
         _fwd(c, q, k, v, am, out, lse)
     from mmgl_amd import _lib
     ws = torch.full((_lib.lib().mmgl_xattn_bwd_workspace(B, H, T, S, D),), 0xFF, dtype=torch.uint8, device="cuda")
-    dq, dk, dv = _nan(B, T, H * D, dtype=dtype), _nan(B, S, H * D, dtype=dtype), _nan(B, S, H * D, dtype=dtype)
+    dq, dk, dv = nan(B, T, H * D, dtype=dtype), nan(B, S, H * D, dtype=dtype), nan(B, S, H * D, dtype=dtype)
     with pytest.raises(ValueError, match="LDS"):
         _bwd(c, q, k, v, dout, am, torch.zeros_like(lse), dq, dk, dv, ws)
     torch.cuda.synchronize()
@@ -279,45 +270,24 @@ def test_C_chunk_plans(case):
 
 
 # ------------------------------------------------------------------------------------------ D: isolation and determinism
-PAD = 512                   # bytes on either side of a carved tensor (keeps the 16-byte alignment)
-CANARY = 0xA5
-
-
-def _carve(shape, dtype, fill, inner=None):
-    """(slab, view): `view` is a tensor of `shape` / `dtype` PAD bytes into a uint8 slab filled with the byte `fill`; it holds
-    `inner` (a tensor, copied) or NaN."""
-    n = torch.empty(shape, dtype=dtype).numel() * torch.empty((), dtype=dtype).element_size()
-    slab = torch.full((n + 2 * PAD,), fill, dtype=torch.uint8, device="cuda")
-    view = slab[PAD:PAD + n].view(dtype).view(shape)
-    if inner is not None:
-        view.copy_(inner)
-    elif dtype != torch.uint8:
-        view.fill_(float("nan"))
-    return slab, view
-
-
-def _untouched(slab, fill):
-    return bool((slab[:PAD] == fill).all()) and bool((slab[-PAD:] == fill).all())
-
-
 def _carved_call(c, q, k, v, dout, am):
     """The two calls with every operand carved out of a slab of 0xFF bytes (NaN in either dtype, 255 in the mask) and every result,
     and a workspace of exactly mmgl_xattn_bwd_workspace bytes, out of canary slabs.  lse is a result of the forward and an operand of
     the backward: its slab is 0xFF.  Returns the results and the names of the slabs whose margins changed."""
     from mmgl_amd import _lib
     group, dtype, D, S, T, B, H, first = c
-    ins = [_carve(t.shape, t.dtype, 0xFF, t) for t in (q, k, v, dout, am)]
-    (_, qc), (_, kc), (_, vc), (_, gc), (_, ac) = ins
+    ins = dict(zip(("q", "k", "v", "dout", "key_valid"), (Slab(t.shape, t.dtype, NAN_BYTE, t) for t in (q, k, v, dout, am))))
+    qc, kc, vc, gc, ac = (s.v for s in ins.values())
     nws = _lib.lib().mmgl_xattn_bwd_workspace(B, H, T, S, D)
-    outs = dict(out=_carve((B, T, H * D), dtype, CANARY), lse=_carve((B, H, T), F32, 0xFF), dq=_carve((B, T, H * D), dtype, CANARY),
-                dk=_carve((B, S, H * D), dtype, CANARY), dv=_carve((B, S, H * D), dtype, CANARY), workspace=_carve((nws,), torch.uint8, CANARY))
-    outs["workspace"][1].fill_(0xFF)
-    _fwd(c, qc, kc, vc, ac, outs["out"][1], outs["lse"][1])
-    _bwd(c, qc, kc, vc, gc, ac, outs["lse"][1], outs["dq"][1], outs["dk"][1], outs["dv"][1], outs["workspace"][1])
+    outs = dict(out=Slab((B, T, H * D), dtype, CANARY_BYTE), lse=Slab((B, H, T), F32, NAN_BYTE), dq=Slab((B, T, H * D), dtype, CANARY_BYTE),
+                dk=Slab((B, S, H * D), dtype, CANARY_BYTE), dv=Slab((B, S, H * D), dtype, CANARY_BYTE), workspace=ByteSlab(nws))
+    for name in ("out", "dq", "dk", "dv"):
+        outs[name].v.fill_(NAN)
+    _fwd(c, qc, kc, vc, ac, outs["out"].v, outs["lse"].v)
+    _bwd(c, qc, kc, vc, gc, ac, outs["lse"].v, outs["dq"].v, outs["dk"].v, outs["dv"].v, outs["workspace"].v)
     torch.cuda.synchronize()
-    touched = [name for name, (slab, _) in outs.items() if not _untouched(slab, 0xFF if name == "lse" else CANARY)]
-    touched += [name for name, (slab, _) in zip(("q", "k", "v", "dout", "key_valid"), ins) if not _untouched(slab, 0xFF)]
-    return tuple(outs[n][1] for n in XAttnRef.NAMES), touched
+    touched = [name for name, s in list(outs.items()) + list(ins.items()) if not s.untouched()]
+    return tuple(outs[n].v for n in XAttnRef.NAMES), touched
 
 
 @pytest.mark.parametrize("case", CASES_D, ids=_id)

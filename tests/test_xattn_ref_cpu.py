@@ -1,4 +1,4 @@
-"""helpers.XAttnRef, the fp64 reference behind tests/test_xattn_bounds_gpu.py, on the CPU (no GPU needed):
+"""attn_ref.XAttnRef, the fp64 reference behind tests/test_xattn_bounds_gpu.py, on the CPU (no GPU needed):
 
 (a) it IS the oracle's attention: oracle.lm_ref.expand_mask + attention_core under autograd in fp64, to 1e-12, on out, lse, dq, dk, dv
     (lse of a sample without a valid key excepted: the kernel's convention is log S, the oracle's finfo.min + log S);
@@ -23,9 +23,9 @@ import functools
 import pytest
 import torch
 
-from helpers import XAttnRef
+from attn_ref import XAttnRef
+from bounds import BF16
 
-BF16 = torch.bfloat16
 CAP = 0.25
 B, H, T = 3, 3, 130
 SEED = 0
