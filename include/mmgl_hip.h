@@ -335,6 +335,31 @@ int mmgl_adamw_step(void* param, float* master, const void* grad, float* exp_avg
                     float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                     float grad_scale, int dtype, void* stream);
 
+/* Fused Adafactor step over the flat buffers of a data-parallel engine: transformers.optimization.Adafactor.step with beta1 = None,
+ * relative_step = scale_parameter = warmup_init = False (run_generation.py:321-324), every tensor of the table in four launches.
+ * With g = grad * grad_scale in fp32 and beta2t = 1 - step^decay_rate (formed in double, rounded once, as is its complement):
+ *   2-D [R, C]: row_i = beta2t row_i + (1 - beta2t) mean_j(g^2 + eps1); col_j likewise over i;
+ *               u = (rsqrt(row_i / mean(row)) * rsqrt(col_j)) * g
+ *   1-D:        v = beta2t v + (1 - beta2t)(g^2 + eps1); u = g * rsqrt(v)
+ *   both:       u /= max(1, sqrt(mean(u^2)) / clip_threshold); p = p + (-lr weight_decay) p - lr u
+ *
+ * mmgl_adafactor_workspace: the host-side plan.  segs [n, 4] int64 (host): per tensor its offset in the flat buffers (a multiple of 128,
+ *   ascending, no overlap), R, C (C = 0: a 1-D tensor of R elements) and its offset in `state` (row[R] | col[C], or v[R]; ascending, no
+ *   overlap).  Returns the workspace bytes of a step and, with table_out != NULL ([n + 1, 8] int64, host), writes the table the kernels
+ *   read: the caller copies it to the device once and keeps the host copy.  0 with mmgl_last_error() set: an invalid segment.
+ * mmgl_adafactor_step:
+ *   param, grad   the flat buffers in `dtype`; master: fp32 copy of param or NULL (param is then stored as its rounding)
+ *   state         fp32; table: the planned table on the device, table_host: the same words on the host (the totals are read from it)
+ *   workspace     mmgl_adafactor_workspace bytes, 8-byte aligned (the partial sums are doubles); every word a step reads it has written before
+ *   No host synchronisation, no allocation, no atomics: reductions in a fixed order, two runs give the same bits.  Elements of the
+ *   flat buffers outside the table's tensors are neither read nor written.  The device table is the caller's contract.
+ *   step < 1, n < 1, a null pointer, a bad dtype, clip_threshold <= 0, eps1 < 0, decay_rate >= 0, a table that was not planned or a
+ *   workspace too small: MMGL_ERR_INVALID, nothing launched. */
+size_t mmgl_adafactor_workspace(const int64_t* segs, int n, int64_t* table_out);
+int mmgl_adafactor_step(void* param, float* master, const void* grad, float* state, const int64_t* table, const int64_t* table_host,
+                        int n, void* workspace, size_t workspace_bytes, float lr, float eps1, float clip_threshold, double decay_rate,
+                        float weight_decay, int step, float grad_scale, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Frozen neighbor encoders, forward only (padding-free RoBERTa / CLIP-ViT passes).
  * replaces: the HF encoder calls in get_text_embs / get_visual_embs, modelling_cross_attention.py:978-1027

@@ -19,6 +19,7 @@ _ERR_INVALID, _ERR_UNSUPPORTED, _ERR_HIP = 1, 2, 3
 c_void_p, c_int, c_float, c_size_t, c_u64, c_i64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t,
                                                     ctypes.c_uint64, ctypes.c_int64)
 P, I, F, Z, U, L = c_void_p, c_int, c_float, c_size_t, c_u64, c_i64
+D = ctypes.c_double
 
 # name -> (restype, argtypes); every symbol include/mmgl_hip.h declares
 SIGNATURES = {
@@ -121,6 +122,8 @@ SIGNATURES = {
     "mmgl_weight_quantize": (I, [P, I, P, I, P, I, I, I, P]),
     "mmgl_gemm_skinny_w8": (I, [P, I, P, I, P, P, P, P, I, I, I, I, I, F, I, P]),
     "mmgl_attn_decode_relbias_fwd": (I, [P, I, P, P, I, Z, P, I, P, I, I, I, I, I, P]),
+    "mmgl_adafactor_workspace": (Z, [P, I, P]),
+    "mmgl_adafactor_step": (I, [P, P, P, P, P, P, I, P, Z, F, F, F, D, F, I, F, I, P]),
 }
 
 _lib = None

@@ -89,4 +89,5 @@ int mmgl_num_cu() {
 // the fused QKV dgrad skips the zero dK | dV of dead key tiles) were added at 110 the same way.
 // mmgl_attn_relbias_fwd / mmgl_attn_relbias_bwd(_workspace) (T5 attention: relative-position bias, native T5 forward) were added at
 // 110 the same way.
+// mmgl_adafactor_workspace / mmgl_adafactor_step (fused Adafactor for T5 training) were added at 110 the same way.
 extern "C" int mmgl_version(void) { return 110; }

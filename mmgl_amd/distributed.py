@@ -43,7 +43,8 @@ def _grad_ready_order(named_params):
 class DataParallelEngine:
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, betas=(0.9, 0.95), eps: float = 1e-8,
                  weight_decay: float = 0.01, bucket_mb: Optional[float] = None, tail_mb: Optional[float] = None, process_group=None, master_weights: Optional[bool] = None,
-                 fused: Optional[bool] = None, broadcast: bool = True, optimizer: str = "adamw", force_exchange: Optional[bool] = None):
+                 fused: Optional[bool] = None, broadcast: bool = True, optimizer: str = "adamw", force_exchange: Optional[bool] = None,
+                 adafactor: Optional[dict] = None):
         import os
         self.model = model
         self.pg = process_group
@@ -95,14 +96,22 @@ class DataParallelEngine:
             self.flat_param[o:o + p.numel()].copy_(p.data.reshape(-1))
             p.data = self.flat_param[o:o + p.numel()].view(p.shape)
             p.grad = self.flat_grad[o:o + p.numel()].view(p.shape)
-        self.exp_avg = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.master = self.flat_param.float() if master_weights else None
         self.torch_optimizer = None
+        if optimizer == "adafactor_fused":
+            # Adafactor on the project's kernel (mmgl_adafactor_step): one flat fp32 state of R + C floats per 2-D tensor and numel per
+            # 1-D tensor, no AdamW moments.  The table is planned and validated here, once; a step builds nothing.
+            self._init_adafactor(adafactor or {})
+            self.master = self.flat_param.float() if master_weights else None
+        else:
+            if adafactor:
+                raise ValueError("DataParallelEngine: `adafactor` options belong to optimizer='adafactor_fused'")
+            self.exp_avg = torch.zeros(off, dtype=torch.float32, device=self.device)
+            self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=self.device)
+            self.master = self.flat_param.float() if master_weights else None
         if optimizer == "adafactor":          # the reference trains T5 with Adafactor (run_generation.py:321-324)
             from transformers.optimization import Adafactor
             self.torch_optimizer = Adafactor(self.params, scale_parameter=False, relative_step=False, warmup_init=False, lr=lr)
-        elif optimizer != "adamw":
+        elif optimizer not in ("adamw", "adafactor_fused"):
             raise ValueError(f"unknown optimizer {optimizer!r}")
 
         # ---- buckets = contiguous ranges of the flat gradient, closed in grad-ready order
@@ -168,6 +177,70 @@ class DataParallelEngine:
                 dist.broadcast(t.data, src=0, group=self.pg)      # frozen LM / encoders: one-off, ~3 GB at OPT-1.3B
             if self.master is not None:
                 self.master.copy_(self.flat_param)
+
+    _ADAFACTOR_DEFAULTS = dict(eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, weight_decay=0.0)
+    _ADAFACTOR_REFUSED = dict(beta1=None, scale_parameter=False, relative_step=False, warmup_init=False)
+
+    @classmethod
+    def _check_adafactor_options(cls, opts, where):
+        """The fused kind is Adafactor as the reference configures it; anything else is the stock kind's."""
+        for k, v in cls._ADAFACTOR_REFUSED.items():
+            if opts.get(k, v) not in (v, None if v is None else 0):
+                raise ValueError(f"{where}: {k}={opts[k]!r} is not supported by optimizer='adafactor_fused' (beta1, relative_step, "
+                                 "scale_parameter and warmup_init are out of its scope); use optimizer='adafactor'")
+        unknown = set(opts) - set(cls._ADAFACTOR_DEFAULTS) - set(cls._ADAFACTOR_REFUSED) - {"lr", "params"}
+        if unknown:
+            raise ValueError(f"{where}: unknown Adafactor option(s) {sorted(unknown)}")
+
+    def _init_adafactor(self, opts):
+        from . import ops
+        self._check_adafactor_options(opts, "DataParallelEngine")
+        o = dict(self._ADAFACTOR_DEFAULTS, **{k: v for k, v in opts.items() if k in self._ADAFACTOR_DEFAULTS})
+        self.adafactor_eps, self.clip_threshold, self.decay_rate, self.weight_decay = tuple(o["eps"]), o["clip_threshold"], o["decay_rate"], o["weight_decay"]
+        for n, p in zip(self.names, self.params):
+            if p.dim() > 2 or p.dim() == 0:
+                raise ValueError(f"optimizer='adafactor_fused': trainable tensor {n!r} has shape {tuple(p.shape)}; only 1-D and 2-D tensors are "
+                                 "supported (transformers factors the last two dimensions of a larger one per leading index); use "
+                                 "optimizer='adafactor'")
+        self.adafactor_table = ops.AdafactorTable([(o_, p.shape) for o_, p in zip(self.offsets, self.params)])
+        if self.fused:
+            self.adafactor_table.to(self.device)
+        self.adafactor_state = torch.zeros(self.adafactor_table.state_numel, dtype=torch.float32, device=self.device)
+
+    def _adafactor_views(self, i):
+        """(row, col) or (v,) of trainable tensor i: views into the flat state."""
+        p, so = self.params[i], self.adafactor_table.state_offsets[i]
+        if p.dim() == 2:
+            R, C = p.shape
+            return self.adafactor_state[so:so + R], self.adafactor_state[so + R:so + R + C]
+        return (self.adafactor_state[so:so + p.numel()],)
+
+    def _adafactor_torch_step(self, lr, scale):
+        """transformers' Adafactor.step restated over the flat buffers in plain torch (CPU tests of state and checkpoints only)."""
+        pw = float(self.step_count) ** self.decay_rate
+        b2, eps1 = 1.0 - pw, self.adafactor_eps[0]
+        for i, (p, o) in enumerate(zip(self.params, self.offsets)):
+            k = p.numel()
+            g = self.flat_grad[o:o + k].float().view(p.shape) * scale
+            tgt = (self.master if self.master is not None else self.flat_param)[o:o + k].view(p.shape)
+            x = g * g + eps1
+            if p.dim() == 2:
+                row, col = self._adafactor_views(i)
+                row.mul_(b2).add_(x.mean(dim=-1), alpha=pw)
+                col.mul_(b2).add_(x.mean(dim=-2), alpha=pw)
+                u = torch.mul((row / row.mean(dim=-1, keepdim=True)).rsqrt_().unsqueeze(-1), col.unsqueeze(-2).rsqrt()).mul_(g)
+            else:
+                (v,) = self._adafactor_views(i)
+                v.mul_(b2).add_(x, alpha=pw)
+                u = v.rsqrt().mul_(g)
+            u.div_((u.norm(2) / k ** 0.5 / self.clip_threshold).clamp_(min=1.0)).mul_(lr)
+            pf = tgt.float()
+            if self.weight_decay != 0:
+                pf.add_(pf, alpha=-self.weight_decay * lr)
+            pf.add_(-u)
+            tgt.copy_(pf)
+        if self.master is not None:
+            self.flat_param.copy_(self.master)
 
     # ---------------------------------------------------------------------------------- gradient exchange
     def _make_hook(self, i):
@@ -236,6 +309,14 @@ class DataParallelEngine:
         self.step_count += 1
         scale = 1.0 / self.world
         b1, b2 = self.betas
+        if self.optimizer_kind == "adafactor_fused":          # 1 / world goes in as grad_scale: no pass over the gradients
+            if self.fused:
+                from . import ops
+                ops.adafactor_step_(self.flat_param, self.master, self.flat_grad, self.adafactor_state, self.adafactor_table, lr,
+                                    self.step_count, scale, self.weight_decay, self.adafactor_eps[0], self.clip_threshold, self.decay_rate)
+            else:
+                self._adafactor_torch_step(lr, scale)
+            return
         if self.torch_optimizer is not None:
             if self.world > 1:
                 self.flat_grad.mul_(scale)
@@ -275,6 +356,8 @@ class DataParallelEngine:
         :411): `state` holds the entries of the trainable parameters at their model index (frozen parameters never get state
         in torch either), `param_groups[0]['params']` lists every index, so `torch.optim.AdamW(model.parameters())
         .load_state_dict()` on the reference side accepts it.  `param_names` (index -> name) is an extra key torch ignores."""
+        if self.optimizer_kind == "adafactor_fused":
+            return self._adafactor_state_dict()
         names = self._model_param_names()
         index = {n: i for i, n in enumerate(names)}
         state = {}
@@ -291,6 +374,8 @@ class DataParallelEngine:
         matched BY PARAMETER NAME -- through the checkpoint's own `param_names` when present, else through this model's
         named_parameters() order, which is the order the reference's optimizer indexed.  A checkpoint that carries state but
         matches none of the trainable parameters is an error, never a silent cold start."""
+        if self.optimizer_kind == "adafactor_fused":
+            return self._adafactor_load_state_dict(sd)
         names = sd.get("param_names") or self._model_param_names()
         index = {n: i for i, n in enumerate(names)}
         state = sd.get("state", {})
@@ -316,6 +401,63 @@ class DataParallelEngine:
                           "their Adam moments start from zero")
         g = sd["param_groups"][0]
         self.lr, self.betas, self.eps, self.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
+        if self.master is not None:
+            self.master.copy_(self.flat_param.float())
+
+    def _adafactor_state_dict(self):
+        """transformers.optimization.Adafactor.state_dict() layout over ALL of model.parameters() in model order, so that a stock
+        `Adafactor(model.parameters(), scale_parameter=False, relative_step=False, warmup_init=False, lr=...)` loads it: per trainable
+        index `step`, `exp_avg_sq_row` [R] and `exp_avg_sq_col` [C] (2-D) or `exp_avg_sq` (1-D), and `RMS` -- the root mean square of the
+        parameter as it stands (stock: as it stood before its last step; only scale_parameter reads it, which this kind refuses).  No
+        state before the first step, as in torch.  `param_names` (index -> name) is an extra key torch ignores."""
+        names = self._model_param_names()
+        index = {n: i for i, n in enumerate(names)}
+        state = {}
+        if self.step_count:
+            for i, (n, p) in enumerate(zip(self.names, self.params)):
+                views = [v.clone() for v in self._adafactor_views(i)]
+                moments = dict(exp_avg_sq_row=views[0], exp_avg_sq_col=views[1]) if p.dim() == 2 else dict(exp_avg_sq=views[0].view(p.shape))
+                state[index[n]] = dict(step=self.step_count, **moments, RMS=p.detach().float().norm(2) / p.numel() ** 0.5)
+        group = dict(lr=self.lr, eps=tuple(self.adafactor_eps), clip_threshold=self.clip_threshold, decay_rate=self.decay_rate, beta1=None,
+                     weight_decay=self.weight_decay, scale_parameter=False, relative_step=False, warmup_init=False,
+                     params=list(range(len(names))))
+        return dict(state=state, param_groups=[group], param_names=names)
+
+    def _adafactor_load_state_dict(self, sd):
+        """Accepts this kind's checkpoints and a stock Adafactor's over model.parameters(), matched by parameter name as the AdamW kind
+        matches.  An AdamW-layout checkpoint (exp_avg / betas) is refused: its moments mean nothing here, and starting the second-moment
+        estimates from zero without saying so is what the stock kind did."""
+        g = sd["param_groups"][0]
+        state = sd.get("state", {})
+        if "betas" in g or any("exp_avg" in st for st in state.values()):
+            raise ValueError("optimizer='adafactor_fused': the checkpoint holds AdamW state (exp_avg / betas), not Adafactor's "
+                             "(exp_avg_sq_row / exp_avg_sq_col / exp_avg_sq); it was written by another optimizer kind")
+        self._check_adafactor_options({k: v for k, v in g.items() if k in self._ADAFACTOR_REFUSED}, "optimizer checkpoint")
+        names = sd.get("param_names") or self._model_param_names()
+        index = {n: i for i, n in enumerate(names)}
+        matched, missing = 0, []
+        for i, (n, p) in enumerate(zip(self.names, self.params)):
+            st = state.get(index[n]) if n in index else None
+            if st is None:
+                missing.append(n)
+                continue
+            keys = ("exp_avg_sq_row", "exp_avg_sq_col") if p.dim() == 2 else ("exp_avg_sq",)
+            for key, view in zip(keys, self._adafactor_views(i)):
+                if key not in st or st[key].numel() != view.numel():
+                    raise ValueError(f"optimizer state of {n!r} ({tuple(p.shape)}): {key} is missing or has "
+                                     f"{st[key].numel() if key in st else 0} elements, expected {view.numel()}")
+                view.copy_(st[key].reshape(-1))
+            self.step_count = int(st["step"])
+            matched += 1
+        if state and not matched:
+            raise ValueError("optimizer checkpoint carries state for none of the trainable parameters (index space mismatch): "
+                             f"checkpoint indices {sorted(state)[:5]}..., trainable names {self.names[:3]}...")
+        if missing and matched:
+            import warnings
+            warnings.warn(f"optimizer checkpoint has no state for {len(missing)} trainable parameter(s), e.g. {missing[:3]}: "
+                          "their second-moment estimates start from zero")
+        self.lr, self.adafactor_eps, self.clip_threshold = g["lr"], tuple(g["eps"]), g["clip_threshold"]
+        self.decay_rate, self.weight_decay = g["decay_rate"], g["weight_decay"]
         if self.master is not None:
             self.master.copy_(self.flat_param.float())
 

@@ -77,6 +77,9 @@ class Arguments:
     adam_beta1: Optional[float] = _f(0.9, "beta1 for Adam.")
     adam_beta2: Optional[float] = _f(0.95, "beta2 for AdamDecay.")
     weight_decay: Optional[float] = _f(0.01, "Weight decay parameter.")
+    fused_adafactor: Optional[bool] = _f(False, "T5 models: run Adafactor as one fused HIP step over the flat buffers "
+                                                "(DataParallelEngine optimizer='adafactor_fused') instead of transformers' per-tensor "
+                                                "loop; same formula, and the Adafactor state is checkpointed.  No effect on other models")
     grad_accumulation_steps: Optional[int] = _f(4, "number of gradient accumulation steps.")
     grad_clip: Optional[float] = _f(1.0, "gradient clipping amount.")
     lr_warmup_steps: Optional[int] = _f(2000, "Number of steps to warm up lr.")
@@ -817,7 +820,7 @@ def main_worker(gpu, world_size, args, log_dir, run=None, tokenizer=None, offlin
         _, ntrain, nfrozen = utils.get_params_count(model)
         print(f"total_params {ntrain + nfrozen}  trainable_params {ntrain}  non_trainable_params {nfrozen}")
     engine = DataParallelEngine(model, lr=args.learning_rate, betas=(args.adam_beta1, args.adam_beta2), eps=1e-8,
-                                weight_decay=args.weight_decay, optimizer="adafactor" if "t5" in args.model_name_or_path else "adamw",
+                                weight_decay=args.weight_decay, optimizer=("adafactor_fused" if args.fused_adafactor else "adafactor") if "t5" in args.model_name_or_path else "adamw",
                                 master_weights=False if "t5" in args.model_name_or_path else None)
     scheduler = None
     if "t5" not in args.model_name_or_path:

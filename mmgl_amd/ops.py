@@ -1335,6 +1335,57 @@ def adamw_step_(param, master, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
                                 eps, weight_decay, step, grad_scale, dtype_code(param), stream_ptr())
 
 
+class AdafactorTable:
+    """The segment table of mmgl_adafactor_step, planned and validated once on the host (mmgl_adafactor_workspace; no GPU needed for
+    that): per tensor its offset in the flat buffers, R, C (0 for a 1-D tensor of R elements) and its offset in the flat fp32 state
+    (row[R] | col[C], or v[R]).  `segments` gives (flat offset, shape) per tensor, in ascending offsets that are multiples of 128;
+    state segments start on 32-float boundaries.  `.state_offsets[i]`, `.state_numel`, `.workspace_bytes` describe the layout; the
+    device copy of the table and the workspace are made by `.to(device)` (the engine calls it in its constructor, never in a step)."""
+
+    def __init__(self, segments):
+        import ctypes
+        self.shapes, self.offsets, self.state_offsets = [], [], []
+        rows, st = [], 0
+        for off, shape in segments:
+            shape = tuple(int(s) for s in shape)
+            if not 1 <= len(shape) <= 2:
+                raise ValueError(f"fused Adafactor takes 1-D and 2-D tensors, got shape {shape}: transformers factors a tensor of more "
+                                 "dimensions over its last two with the leading ones as a batch, which this kernel does not do")
+            R, C = (shape[0], 0) if len(shape) == 1 else shape
+            if C == 0 and len(shape) == 2 or R == 0:
+                raise ValueError(f"fused Adafactor: empty tensor of shape {shape}")
+            self.shapes.append(shape), self.offsets.append(int(off)), self.state_offsets.append(st)
+            rows += [int(off), R, C, st]
+            st += (R + C + 31) // 32 * 32
+        self.n, self.state_numel = len(self.shapes), st
+        if not self.n:
+            raise ValueError("fused Adafactor: no tensors")
+        segs = (ctypes.c_int64 * len(rows))(*rows)
+        self.host = (ctypes.c_int64 * (8 * (self.n + 1)))()
+        self.workspace_bytes = lib().mmgl_adafactor_workspace(segs, self.n, self.host)
+        if not self.workspace_bytes:
+            raise ValueError(lib().mmgl_last_error().decode("utf-8", "replace"))
+        self.n_tiles, self.n_folds = int(self.host[8 * self.n + 4]), int(self.host[8 * self.n + 5])
+        self.device = self.workspace = None
+
+    def to(self, device):
+        self.device = torch.tensor(list(self.host), dtype=torch.int64).to(device)
+        self.workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=device)
+        return self
+
+
+def adafactor_step_(param, master, grad, state, table, lr, step, grad_scale=1.0, weight_decay=0.0, eps1=1e-30, clip_threshold=1.0,
+                    decay_rate=-0.8):
+    """In-place fused Adafactor over flat buffers (transformers' Adafactor.step with beta1 None, no relative step, no parameter
+    scaling): one C-ABI call, four launches, for every tensor of `table` (an AdafactorTable moved to the device)."""
+    require_cuda(param, grad, state, table.device, table.workspace)
+    if grad.dtype != param.dtype or state.dtype != torch.float32 or (master is not None and master.dtype != torch.float32):
+        raise ValueError("adafactor_step_: grad in the parameter's dtype, state and master in float32")
+    _lib.call("mmgl_adafactor_step", None, ptr(param), ptr(master), ptr(grad), ptr(state), ptr(table.device), table.host, table.n,
+              ptr(table.workspace), table.workspace_bytes, lr, eps1, clip_threshold, decay_rate, weight_decay, step, grad_scale,
+              dtype_code(param), stream_ptr())
+
+
 # ------------------------------------------------------------------------------------------ frozen linears
 # The frozen decoder layers, lm_head and the encoders only ever need y = act(x W^T + b) and dx = dy W.  Both run on
 # mmgl_gemm_nt (the persistent ping-pong MFMA kernel of csrc/gemm8p.hip for large bf16 shapes): forward with the bias /
